@@ -32,6 +32,8 @@ import torch.distributed as dist  # noqa: E402
 
 PEAK_BF16_TFLOPS = 2500.0   # dense bf16 MFMA, MI355X_MICROARCH.md chip table
 S_VIEWS, IMG = 8, 518
+DUMP_BYTES = 60 * 10**6     # --dump-outputs: payload of all arrays together (the .npy headers stay well under 64 MB)
+DUMP_SEED = 0               # --dump-outputs: seed of the element sample of an array over its share
 
 
 def vggt_flops_per_step(S, track=True):
@@ -64,7 +66,15 @@ def main():
                          "load_and_preprocess_images (vggt/load.py:38-183; vggt/vggt/infer.py:77 does both per call) inside the timed "
                          "region.  The default keeps the inputs resident in HBM (the contract's `value`); with this flag the line is "
                          "the PCIe-inclusive rate and says so in config.inputs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path computed in its last step to DIR/<name>.npy "
+                         "(float32): rank 0's time steps of the step -- the model's outputs of its every batch and their "
+                         "joints and cameras (under N ranks: rank 0's shard only, not the gathered joints).  An array over "
+                         "its share of the 60 MB budget is written as a fixed, seeded sample of its flattened elements "
+                         "(dump_outputs).  Inputs are seeded: the same arguments give the same inputs")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # `python bench.py --gpus N`: start the N ranks ourselves, as fresh child processes, before
@@ -156,8 +166,12 @@ def main():
             out["joints3d"], out["E"], out["K"] = out["joints3d_local"], out["E_local"], out["K_local"]
         return out
 
+    last_outs = []   # the model outputs of every batch of the latest step (--dump-outputs)
+
     def step():
-        return gather(step_on(images, kps), world * B)
+        out = step_on(images, kps)
+        last_outs[:] = [out]
+        return gather(out, world * B)
 
     def step_multi(n_streams):
         """one step = n_streams independent batches, each on its own stream from its own host thread: the
@@ -182,6 +196,7 @@ def main():
             t_.join()
         for s_ in side:
             main.wait_stream(s_)
+        last_outs[:] = outs
         out = outs[0]
         for key in ("joints3d_local", "E_local", "K_local"):
             out[key] = torch.cat([o[key] for o in outs])
@@ -229,6 +244,9 @@ def main():
     from skiing_analysis_pytorch_amd import fuse
     smoothed = fuse.temporal_smooth_ema(out["joints3d"].cpu().numpy().astype("float64"))
     assert smoothed.shape == tuple(out["joints3d"].shape)
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before any later leg runs a model again
+        dumped = dump_outputs(args.dump_outputs, step_outputs(last_outs, out))
 
     frames = world * args.steps * B * NS
     value = frames / elapsed
@@ -260,6 +278,8 @@ def main():
         "whole_path_tflops": vggt_flops_per_step(S_VIEWS, track) * B * NS * args.steps * world / elapsed / 1e12,
         "tflop_per_step": vggt_flops_per_step(S_VIEWS, track) / 1e12,
     }
+    if dumped is not None:
+        line["dump_outputs"] = dumped
     if n.value > 0:
         avg_s = ms.value * 1e-3 / n.value
         flops_per_launch = fl.value / n.value
@@ -418,6 +438,54 @@ def launch_ranks(n: int) -> int:
         print("bench.py: the ranks exited without a result line", file=sys.stderr)
         return 1
     return rc
+
+
+def step_outputs(batch_outs, out):
+    """What a caller of the timed path receives from one step on this rank: the model's outputs of every batch of the
+    step (concatenated along the time-step dimension in stream order; pose_enc_list stacked to [iters, steps, S, 9]) and
+    the joints and cameras of the same time steps (this rank's *_local ones: under N ranks the gathered joints3d / E / K
+    also hold the other ranks' shards).  The input images the model hands back are left out."""
+    arrays = {}
+    for k, v in batch_outs[0].items():
+        if k == "images" or k.endswith("_local") or k in ("joints3d", "E", "K"):
+            continue
+        if isinstance(v, list):
+            arrays[k] = torch.cat([torch.stack(o[k]) for o in batch_outs], dim=1)
+        else:
+            arrays[k] = torch.cat([o[k] for o in batch_outs])
+    for k in ("joints3d", "E", "K"):
+        arrays[k] = out[k + "_local"]
+    return arrays
+
+
+def dump_outputs(out_dir, arrays):
+    """Write every array to out_dir/<name>.npy, float64 kept and everything else as float32.  Each array gets an equal
+    share of DUMP_BYTES.  One that fits is written whole in its own shape; a larger one is written as the 1-D sample
+    flat[idx], idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, numel, share // itemsize)), so the same
+    shapes give the same elements in every run.  Returns a description for the result line."""
+    import numpy as np
+
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    desc = {"dir": str(out_dir), "seed": DUMP_SEED, "arrays": {}}
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        dtype = torch.float64 if t.dtype == torch.float64 else torch.float32
+        itemsize = torch.finfo(dtype).bits // 8
+        entry = {"shape": list(t.shape), "dtype": str(dtype).replace("torch.", ""), "sampled_elements": None}
+        if t.numel() * itemsize > share:
+            idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), size=share // itemsize))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            entry["sampled_elements"] = int(idx.size)
+        a = t.to(dtype).cpu().numpy()
+        np.save(out_dir / f"{name}.npy", a)
+        total += a.nbytes
+        desc["arrays"][name] = entry
+    assert total <= DUMP_BYTES, total
+    desc["bytes"] = total
+    return desc
 
 
 def cpu_threads():
