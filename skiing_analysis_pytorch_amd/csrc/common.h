@@ -101,6 +101,16 @@ __device__ __forceinline__ f32x16 mfma_32x32x16(bf16x8 a, bf16x8 b, f32x16 c) {
     else
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
+// one k-step of a 16x16 output tile (32 deep): lane l holds A row / B column l & 15, k = 8 (l >> 4) .. + 7, and
+// accumulator rows 4 (l >> 4) + r (r = 0..3) of column l & 15.  Same cycles per FLOP as 32x32x16, but on random data
+// the chip holds a higher clock on this shape (tools/peaks.hip, profiles/r04_peaks.json)
+template <bool F16>
+__device__ __forceinline__ f32x4 mfma_16x16x32(bf16x8 a, bf16x8 b, f32x4 c) {
+    if constexpr (F16)
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    else
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+}
 // MXFP8 (gemm_fp8.hip): E8M0 byte of a 32-element block = smallest power of two with amax / scale <= 448 (0: all zero),
 // and its inverse as an exact power of two
 __device__ __forceinline__ unsigned mx_scale_byte(float amax) {

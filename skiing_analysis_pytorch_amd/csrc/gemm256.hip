@@ -14,7 +14,10 @@
 //     see gemm256pp_kernel); gemm256_launch picks by the CU-rounds a shape wastes;
 //   * tiles are walked in 8 x 4 patches per XCD (tile_coords256);
 //   * compile-time epilogues through per-wave LDS slabs -> row-contiguous 16-B stores, branch-free
-//     on interior tiles (epilogue256).
+//     on interior tiles (epilogue256);
+//   * the single-stream and ping-pong loops run on either MFMA shape (M16: v_mfma_f32_16x16x32, the
+//     default, or v_mfma_f32_32x32x16; SKIMI_GEMM256_MFMA=16|32): the same cycles per FLOP, but on
+//     random data the chip holds a higher clock on the 16x16 shape (profiles/r04_peaks.json).
 #include <stdlib.h>
 
 #include "common.h"
@@ -70,14 +73,36 @@ __device__ __forceinline__ bf16x4 pack4_16(float y0, float y1, float y2, float y
     return hb;
 }
 
-template <int MT, int EPI, int PF = 2, bool H16 = false>
-__device__ __forceinline__ void epilogue256(const GemmArgs& p, f32x16 (&acc)[MT][2], char* smem, int wave, int lane,
-                                            int wr, int wc, int m0, int n0) {
+// Slab writers: pass i of a wave's (32 MT) x 64 accumulator strip -> its 32 x 64 fp32 slab (row-major, 64 columns).
+// 32x32 tiles acc[i][j] (columns 32 j): lane l holds column l & 31, rows 8 (r >> 2) + 4 (l >> 5) + (r & 3)
+template <int MT>
+__device__ __forceinline__ void acc_to_slab(float* stg, const f32x16 (&acc)[MT][2], int i, int lane) {
     const int l31 = lane & 31, lh = lane >> 5;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) stg[((r & 3) + 8 * (r >> 2) + 4 * lh) * 64 + j * 32 + l31] = acc[i][j][r];
+}
+// 16x16 tiles acc[b][c] (rows 16 b, columns 16 c): lane l holds column l & 15, rows 4 (l >> 4) + r
+template <int MT>
+__device__ __forceinline__ void acc_to_slab(float* stg, const f32x4 (&acc)[2 * MT][4], int i, int lane) {
+    const int l15 = lane & 15, lq = lane >> 4;
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) stg[(16 * b + 4 * lq + r) * 64 + 16 * c + l15] = acc[2 * i + b][c][r];
+}
+
+// ACC: f32x16[MT][2] (32x32 tiles) or f32x4[2 MT][4] (16x16 tiles); everything after the slab is layout-free
+template <int MT, int EPI, int PF = 2, bool H16 = false, typename ACC>
+__device__ __forceinline__ void epilogue256(const GemmArgs& p, ACC& acc, char* smem, int wave, int lane,
+                                            int wr, int wc, int m0, int n0) {
     float* stg = reinterpret_cast<float*>(smem) + wave * (32 * 64);
     const int n = n0 + wc * 64 + 4 * (lane & 15);
     if (p.dbg & 8) {   // timing ablation: no epilogue (keeps the accumulators alive through one store)
-        if (acc[0][0][0] == 123.456f) ((float*)p.out)[0] = acc[MT - 1][1][15];
+        if (acc[0][0][0] == 123.456f) ((float*)p.out)[0] = acc[MT - 1][1][sizeof(acc[0][0]) / 4 - 1];
         return;
     }
     const bool interior = (m0 + 64 * MT <= p.M) && (n0 + 256 <= p.N) && !(p.dbg & 4);   // block-uniform
@@ -90,8 +115,7 @@ __device__ __forceinline__ void epilogue256(const GemmArgs& p, f32x16 (&acc)[MT]
     // wave execute in order; the compiler only needs to keep them in program order.
 #define SKIMI_ACC_TO_SLAB(i)                                                                                   \
     do {                                                                                                        \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) _Pragma("unroll") for (int r = 0; r < 16; ++r)            \
-            stg[((r & 3) + 8 * (r >> 2) + 4 * lh) * 64 + j * 32 + l31] = acc[i][j][r];                         \
+        acc_to_slab<MT>(stg, acc, i, lane);                                                                     \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                  \
         __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0) */                                                    \
     } while (0)
@@ -336,6 +360,8 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
 // everything but the two quarters just issued has landed, i.e. all of K-tile kt+1.
 // WAR distance: HA[0](kt) is last read in P1 and overwritten from P3 (4+ barriers later), HW[1]
 // P2 -> P4, HA[1] P3 -> next P1, HW[0] P1 -> next P2.
+// M16: a quadrant is 4 x 2 tiles of 16x16 in 2 k-steps of 32 (16 v_mfma_f32_16x16x32 instead of 8 of 32x32x16: the
+// same MFMA cycles), with the same 8 + 4 fragment reads per phase (rows l & 15, 16-B chunk 4 s + (l >> 4)).
 #define SKIMI_BAR()                           \
     do {                                      \
         __builtin_amdgcn_sched_barrier(0);    \
@@ -345,7 +371,7 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
 // s_waitcnt vmcnt(N) only (expcnt / lgkmcnt fields at their maxima)
 #define SKIMI_VMCNT(N) __builtin_amdgcn_s_waitcnt(0x0F70 | ((N) & 15) | (((N) >> 4) << 14))
 
-template <int EPI, int DEEP, bool F16 = false>
+template <int EPI, int DEEP, bool F16 = false, bool M16 = false>
 __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
     constexpr int MT = 4, BM = 256, BN = 256, BK = 64;
     constexpr int RB = 128;
@@ -356,6 +382,7 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave >> 2, wc = wave & 3;
     const int l31 = lane & 31, lh = lane >> 5;
+    const int l15 = lane & 15, lq = lane >> 4;
 
     int tm, tn;
     tile_coords256(p, tm, tn);
@@ -401,13 +428,18 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
                                              0, 0);
     };
 
-    f32x16 acc[MT][2];
+    f32x16 acc[MT][2];           // 32x32 tiles
+    f32x4 acc16[2 * MT][4];      // M16: 16x16 tiles [16-row block][16-column block]
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2 * MT; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // prologue: all of K-tile 0, then the two quarters of K-tile 1 that the loop does not issue
     issue_a(0, 0); issue_w(0, 0); issue_w(1, 0); issue_a(1, 0);
@@ -423,17 +455,28 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
     if (wr == 1) SKIMI_BAR();   // wave row 1 runs one barrier behind wave row 0
 
     bf16x8 af[2][4], wf[2][4];   // A: [row block within the quadrant][k-step]; W: [jh][k-step]
+    bf16x8 af16[4][2], wf16[2][2][2];   // M16: A [16-row block][k-step]; W [jh][16-column block][k-step]
     if (no_rd) {
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int s = 0; s < 4; ++s) af[i][s] = wf[i][s] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+            for (int s = 0; s < 4; ++s) af[i][s] = wf[i][s] = af16[s][i] = wf16[i][s >> 1][s & 1] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
     }
     for (int kt = 0; kt < nkt; ++kt) {
         const char* ab = smem + (kt & 1) * BUF;
         const char* wb = ab + A_TILE;
         auto read_a = [&](int ih) {
             if (no_rd) return;
+            if constexpr (M16) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        const int row = wr * 128 + ih * 64 + i * 16 + l15;
+                        af16[i][s] = *reinterpret_cast<const bf16x8*>(ab + row * RB + (((4 * s + lq) ^ ((row >> 1) & 7)) << 4));
+                    }
+                return;
+            }
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -444,6 +487,16 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
         };
         auto read_w = [&](int jh) {
             if (no_rd) return;
+            if constexpr (M16) {
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        const int row = wc * 64 + jh * 32 + c * 16 + l15;
+                        wf16[jh][c][s] = *reinterpret_cast<const bf16x8*>(wb + row * RB + (((4 * s + lq) ^ ((row >> 1) & 7)) << 4));
+                    }
+                return;
+            }
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const int row = wc * 64 + jh * 32 + l31;
@@ -454,9 +507,16 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
     do {                                                                                                         \
         SKIMI_BAR();                                                                                             \
         __builtin_amdgcn_s_setprio(1);                                                                           \
-        if (!no_mfma) _Pragma("unroll") for (int s = 0; s < 4; ++s) {                                                          \
-            acc[2 * IH][JH] = mfma_32x32x16<F16>(af[0][s], wf[JH][s], acc[2 * IH][JH]);                           \
-            acc[2 * IH + 1][JH] = mfma_32x32x16<F16>(af[1][s], wf[JH][s], acc[2 * IH + 1][JH]);                   \
+        if (no_mfma) {                                                                                           \
+        } else if constexpr (M16) {                                                                              \
+            _Pragma("unroll") for (int s = 0; s < 2; ++s) _Pragma("unroll") for (int i = 0; i < 4; ++i)          \
+                _Pragma("unroll") for (int c = 0; c < 2; ++c) acc16[4 * IH + i][2 * JH + c] =                    \
+                    mfma_16x16x32<F16>(af16[i][s], wf16[JH][c][s], acc16[4 * IH + i][2 * JH + c]);               \
+        } else {                                                                                                 \
+            _Pragma("unroll") for (int s = 0; s < 4; ++s) {                                                      \
+                acc[2 * IH][JH] = mfma_32x32x16<F16>(af[0][s], wf[JH][s], acc[2 * IH][JH]);                       \
+                acc[2 * IH + 1][JH] = mfma_32x32x16<F16>(af[1][s], wf[JH][s], acc[2 * IH + 1][JH]);               \
+            }                                                                                                    \
         }                                                                                                        \
         __builtin_amdgcn_s_setprio(0);                                                                           \
         SKIMI_BAR();                                                                                             \
@@ -490,7 +550,8 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
     }
     if (wr == 0) SKIMI_BAR();   // re-align the two wave rows: nobody reads operand tiles any more
 
-    epilogue256<MT, EPI, 2, F16 && EPI == 3>(p, acc, smem, wave, lane, wr, wc, m0, n0);
+    if constexpr (M16) epilogue256<MT, EPI, 2, F16 && EPI == 3>(p, acc16, smem, wave, lane, wr, wc, m0, n0);
+    else epilogue256<MT, EPI, 2, F16 && EPI == 3>(p, acc, smem, wave, lane, wr, wc, m0, n0);
 }
 
 
@@ -508,7 +569,13 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
 //   k-step 1, 2 of kt : issue (kt+2; q = 0), (kt+2; q = 1)      -> the slots K-tile kt-1's W left
 //   k-step 3 of kt    : lgkmcnt(0), vmcnt(8) = all of kt+1 landed, barrier (= K-tile kt released),
 //                       read (kt+1, k-step 0), issue (kt+2; q = 2, 3) -> K-tile kt's A slots
-template <int EPI, bool F16 = false>
+// M16: the quadrant is 8 x 8 tiles of 16x16 (256 accumulator registers again) and a K-tile is 2 k-steps of 32, each
+// with 8 + 8 fragment reads (rows l & 15, 16-B chunk 4 s + (l >> 4)) and 64 v_mfma_f32_16x16x32: the same reads, bytes
+// and MFMA cycles per K-tile.  Each k-step stands for two of the 32x32x16 loop's, so the DMA and barrier plan keeps
+// its meaning:
+//   k-step 0 of kt    : read (kt, k-step 1), issue (kt+2; q = 0, 1)
+//   k-step 1 of kt    : lgkmcnt(0), vmcnt(8), barrier, read (kt+1, k-step 0), issue (kt+2; q = 2, 3)
+template <int EPI, bool F16 = false, bool M16 = false>
 __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
     constexpr int RB = 128, BK = 64, PIECE = 128 * RB, NSLOT = 10;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -540,6 +607,135 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
             __builtin_amdgcn_global_load_lds((gbl_void*)(src[q][j] + kt * BK), (lds_void*)(base + j * 8 * RB), 16, 0, 0);
     };
 
+    if constexpr (M16) {
+    // fragment reads: 16-row block i of this wave's A piece (n = i) / W piece (n = 8 + i), k-step s
+    const int l15 = lane & 15;
+    const int t = (lane >> 4) ^ ((l15 >> 1) & 7);
+    const int lane_off = l15 * RB;
+    bf16x8 fa0[8], fb0[8], fa1[8], fb1[8];
+    auto read_one = [&](int sb, int s, int n, bf16x8 (&fa)[8], bf16x8 (&fb)[8]) {
+        int sa = sb + wr, sw = sb + 2 + wc;
+        sa = sa >= NSLOT ? sa - NSLOT : sa;
+        sw = sw >= NSLOT ? sw - NSLOT : sw;
+        const int off = lane_off + (((4 * s) ^ t) << 4) + (n & 7) * 16 * RB;
+        if (n < 8) fa[n] = *reinterpret_cast<const bf16x8*>(smem + sa * PIECE + off);
+        else fb[n - 8] = *reinterpret_cast<const bf16x8*>(smem + sw * PIECE + off);
+    };
+    auto issue_one = [&](int q, int j, int kt, int slot) {
+        __builtin_amdgcn_global_load_lds((gbl_void*)(src[q][j] + kt * BK), (lds_void*)(smem + slot * PIECE + (4 * wave + j) * 8 * RB),
+                                         16, 0, 0);
+    };
+
+    // [column half h][16-row block i][16-column block c]: columns 64 h + 16 c.  The MFMAs are inline asm on accumulators
+    // pinned in AGPRs: with the builtin, hipcc shuttles ~590 of these 256 registers per K-tile through
+    // v_accvgpr_mov / read / write.  hipcc pads nothing around an asm statement, so the wait states the MFMAs need are
+    // written out: s_nop 1 between the accumulators' v_accvgpr_write and the first MFMA, 12 states between the last
+    // MFMA and the epilogue's reads (8-pass XDL).
+    f32x4 acc[2][8][4];
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                acc[h][i][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+                asm volatile("" : "+a"(acc[h][i][c]));
+            }
+    asm volatile("s_nop 1");
+    auto mfma = [&](f32x4& c, const bf16x8& a, const bf16x8& b) {
+        if constexpr (F16) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+        else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(c) : "v"(a), "v"(b));
+    };
+    // one k-step: 64 MFMAs, extra(g) placed after MFMA g (source order = issue order: asm volatile + sched_barrier)
+    auto kstep = [&](bf16x8 (&fa)[8], bf16x8 (&fb)[8], auto&& extra) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                mfma(acc[j >> 2][i][j & 3], fa[i], fb[j]);
+                extra(8 * j + i);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+    };
+
+    // prologue: K-tiles 0 and 1 whole
+#pragma unroll
+    for (int q = 0; q < 4; ++q) issue(q, 0, q);
+    if (nkt > 1) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) issue(q, 1, 4 + q);
+        SKIMI_VMCNT(16);
+    } else {
+        SKIMI_VMCNT(0);
+    }
+    SKIMI_BAR();
+    int sb = 0;   // slot of piece 0 of K-tile kt
+#pragma unroll
+    for (int n = 0; n < 16; ++n) read_one(sb, 0, n, fa0, fb0);
+    // One k-step: lgkmcnt(0) in front (its fragments were requested a whole k-step ago); the next k-step's 16 fragment
+    // reads go one behind each of the first 16 MFMAs, this k-step's 8 DMA issues one behind every second of the next 16
+    // (an MFMA holds the SIMD for 16 cycles here instead of 32); the rest run back to back.
+#define SKIMI_W4_HEAD()                       \
+    do {                                      \
+        __builtin_amdgcn_s_waitcnt(0xC07F);   \
+        __builtin_amdgcn_sched_barrier(0);    \
+    } while (0)
+#define SKIMI_W4_KTILE(N1, N2)                                                                       \
+    do {                                                                                             \
+        int s8 = sb + 8, s9 = sb + 9, s1 = sb + 1, nsb = sb + 4;                                     \
+        s8 = s8 >= NSLOT ? s8 - NSLOT : s8;                                                          \
+        s9 = s9 >= NSLOT ? s9 - NSLOT : s9;                                                          \
+        s1 = s1 >= NSLOT ? s1 - NSLOT : s1;                                                          \
+        nsb = nsb >= NSLOT ? nsb - NSLOT : nsb;                                                      \
+        /* k-step 0: read (kt, k-step 1), issue (kt+2; q = 0, 1) */                                  \
+        SKIMI_W4_HEAD();                                                                             \
+        kstep(fa0, fb0, [&](int g) {                                                                 \
+            if (g < 16) read_one(sb, 1, g, fa1, fb1);                                                \
+            else if (N2 && g < 32 && (g & 1)) {                                              \
+                const int d = (g - 16) >> 1;                                                         \
+                issue_one(d >> 2, d & 3, kt + 2, (d >> 2) ? s9 : s8);                                \
+            }                                                                                        \
+        });                                                                                          \
+        /* k-step 1: vmcnt(8) = all of kt+1 landed, barrier (= K-tile kt released),                  \
+           read (kt+1, k-step 0), issue (kt+2; q = 2, 3) into K-tile kt's A slots */                 \
+        SKIMI_W4_HEAD();                                                                             \
+        if (N1) {                                                                                    \
+            if (N2) SKIMI_VMCNT(8); else SKIMI_VMCNT(0);                                             \
+            SKIMI_BAR();                                                                             \
+        }                                                                                            \
+        kstep(fa1, fb1, [&](int g) {                                                                 \
+            if (N1 && g < 16) read_one(nsb, 0, g, fa0, fb0);                                         \
+            else if (N2 && g < 32 && (g & 1)) {                                              \
+                const int d = (g - 16) >> 1;                                                         \
+                issue_one(2 + (d >> 2), d & 3, kt + 2, (d >> 2) ? s1 : sb);                          \
+            }                                                                                        \
+        });                                                                                          \
+        sb = nsb;                                                                                    \
+    } while (0)
+    int kt = 0;
+    for (; kt + 2 < nkt; ++kt) SKIMI_W4_KTILE(true, true);
+    if (kt + 1 < nkt) {
+        SKIMI_W4_KTILE(true, false);
+        ++kt;
+    }
+    SKIMI_W4_KTILE(false, false);
+#undef SKIMI_W4_KTILE
+#undef SKIMI_W4_HEAD
+    // 12 states: last MFMA's D -> the epilogue's v_accvgpr_read; the pins make every accumulator a value of THIS point,
+    // so that hipcc reads none of them out between the MFMAs
+    asm volatile("s_nop 7\n\ts_nop 4");
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+#pragma unroll
+            for (int c = 0; c < 4; ++c) asm volatile("" : "+a"(acc[h][i][c]));
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    SKIMI_BAR();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0 and 1
+
+    epilogue256<4, EPI, 4, F16 && EPI == 3>(p, acc[0], smem, wave, lane, wr, 2 * wc, m0, n0);
+    epilogue256<4, EPI, 4, F16 && EPI == 3>(p, acc[1], smem, wave, lane, wr, 2 * wc + 1, m0, n0);
+    } else {
     // fragment reads: row block i of this wave's A piece / W piece, k-step s
     const int t = lh ^ ((l31 >> 1) & 7);
     const int lane_off = l31 * RB;
@@ -660,6 +856,7 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
 
     epilogue256<4, EPI, 4, F16 && EPI == 3>(p, acc[0], smem, wave, lane, wr, 2 * wc, m0, n0);
     epilogue256<4, EPI, 4, F16 && EPI == 3>(p, acc[1], smem, wave, lane, wr, 2 * wc + 1, m0, n0);
+    }
 }
 
 
@@ -908,57 +1105,61 @@ static int launch256(GemmArgs& a, hipStream_t st) {
     return SKIMI_OK;
 }
 
-template <int EPI, int DEEP, bool F16 = false>
+template <int EPI, int DEEP, bool F16, bool M16>
 static int launch256pp_(GemmArgs& a, hipStream_t st) {
     constexpr size_t lds = 2ull * (256 + 256) * 128;
-    SKIMI_LDS_OPT_IN((gemm256pp_kernel<EPI, DEEP, F16>), lds, "gemm256pp");
+    SKIMI_LDS_OPT_IN((gemm256pp_kernel<EPI, DEEP, F16, M16>), lds, "gemm256pp");
     a.ntm = (int)cdiv(a.M, 256);
     a.ntn = (int)cdiv(a.N, 256);
     a.splitk = 1;
-    hipLaunchKernelGGL((gemm256pp_kernel<EPI, DEEP, F16>), dim3(a.ntm * a.ntn), dim3(512), lds, st, a);
+    hipLaunchKernelGGL((gemm256pp_kernel<EPI, DEEP, F16, M16>), dim3(a.ntm * a.ntn), dim3(512), lds, st, a);
     SKIMI_LAUNCH_CHECK();
     return SKIMI_OK;
 }
 
-template <int EPI, bool F16 = false>
+template <int EPI, bool F16, bool M16>
 static int launch256pp(GemmArgs& a, hipStream_t st) {
-    if constexpr (F16) return launch256pp_<EPI, 1, true>(a, st);
+    if constexpr (F16) return launch256pp_<EPI, 1, true, M16>(a, st);
     const int deep = SKIMI_ENV_INT("SKIMI_GEMM256_DEEP", 1);
-    return deep ? launch256pp_<EPI, 1>(a, st) : launch256pp_<EPI, 0>(a, st);
+    return deep ? launch256pp_<EPI, 1, false, M16>(a, st) : launch256pp_<EPI, 0, false, M16>(a, st);
 }
 
-template <int EPI, bool F16 = false>
+template <int EPI, bool F16, bool M16>
 static int launch256w4(GemmArgs& a, hipStream_t st) {
     constexpr size_t lds = 10ull * 128 * 128;
-    SKIMI_LDS_OPT_IN((gemm256w4_kernel<EPI, F16>), lds, "gemm256w4");
+    SKIMI_LDS_OPT_IN((gemm256w4_kernel<EPI, F16, M16>), lds, "gemm256w4");
     a.ntm = (int)cdiv(a.M, 256);
     a.ntn = (int)cdiv(a.N, 256);
     a.splitk = 1;
-    hipLaunchKernelGGL((gemm256w4_kernel<EPI, F16>), dim3(a.ntm * a.ntn), dim3(256), lds, st, a);
+    hipLaunchKernelGGL((gemm256w4_kernel<EPI, F16, M16>), dim3(a.ntm * a.ntn), dim3(256), lds, st, a);
     SKIMI_LAUNCH_CHECK();
     return SKIMI_OK;
+}
+
+template <bool F16, bool M16>
+static int gemm256_pick_loop(GemmArgs& a, hipStream_t st, int epi, bool w4) {
+    if (w4) {
+        if (epi == 1) return launch256w4<1, F16, M16>(a, st);
+        if (epi == 2) return launch256w4<2, F16, M16>(a, st);
+        if (epi == 3) return launch256w4<3, F16, M16>(a, st);
+        return launch256w4<0, F16, M16>(a, st);
+    }
+    if (epi == 1) return launch256pp<1, F16, M16>(a, st);
+    if (epi == 2) return launch256pp<2, F16, M16>(a, st);
+    if (epi == 3) return launch256pp<3, F16, M16>(a, st);
+    return launch256pp<0, F16, M16>(a, st);
 }
 
 template <bool F16>
-static int gemm256_pick(GemmArgs& a, hipStream_t st, int epi, bool mt3, bool w4, int use_pp) {
+static int gemm256_pick(GemmArgs& a, hipStream_t st, int epi, bool mt3, bool w4, int use_pp, bool m16) {
     if (mt3) {
         if (epi == 1) return launch256<3, 1, F16>(a, st);
         if (epi == 2) return launch256<3, 2, F16>(a, st);
         if (epi == 3) return launch256<3, 3, F16>(a, st);
         return launch256<3, 0, F16>(a, st);
     }
-    if (w4) {
-        if (epi == 1) return launch256w4<1, F16>(a, st);
-        if (epi == 2) return launch256w4<2, F16>(a, st);
-        if (epi == 3) return launch256w4<3, F16>(a, st);
-        return launch256w4<0, F16>(a, st);
-    }
-    if (use_pp || F16) {   // the fp16 build carries the two loops the dispatch picks (single-stream, ping-pong) + the 192-row one
-        if (epi == 1) return launch256pp<1, F16>(a, st);
-        if (epi == 2) return launch256pp<2, F16>(a, st);
-        if (epi == 3) return launch256pp<3, F16>(a, st);
-        return launch256pp<0, F16>(a, st);
-    }
+    // the fp16 build carries the two loops the dispatch picks (single-stream, ping-pong) + the 192-row one
+    if (w4 || use_pp || F16) return m16 ? gemm256_pick_loop<F16, true>(a, st, epi, w4) : gemm256_pick_loop<F16, false>(a, st, epi, w4);
     if constexpr (!F16) {
         if (epi == 1) return launch256<4, 1>(a, st);
         if (epi == 2) return launch256<4, 2>(a, st);
@@ -988,12 +1189,15 @@ int gemm256_launch(GemmArgs& a, hipStream_t st) {
     //     loop (8 waves) where the epilogue does (K <= 1024 with the residual epilogue, or GELU: its
     //     chain of LDS / VALU / global round trips runs on twice the waves there).
     // SKIMI_GEMM256_MT3 / _W4 / _PP = 0 / 1 force a choice (A/B timing).
+    // MFMA shape of the single-stream and ping-pong loops (SKIMI_GEMM256_MFMA = 16 | 32): v_mfma_f32_16x16x32 by
+    // default, measured against 32x32x16 interleaved on one box
+    const bool m16 = SKIMI_ENV_INT("SKIMI_GEMM256_MFMA", 16) != 32;
     const int use_pp = SKIMI_ENV_INT("SKIMI_GEMM256_PP", 1);
     const int use_mt3 = SKIMI_ENV_INT("SKIMI_GEMM256_MT3", -1);
     const int use_w4 = SKIMI_ENV_INT("SKIMI_GEMM256_W4", -1);
     const bool mt3 = use_mt3 == 1 || (use_mt3 < 0 && cost(192) < 0.8 * cost(256));
     const bool w4 = use_w4 >= 0 ? use_w4 != 0 : (epi == 1 || (epi == 2 && a.K > 1024));
-    return a.f16 ? gemm256_pick<true>(a, st, epi, mt3, w4, use_pp) : gemm256_pick<false>(a, st, epi, mt3, w4, use_pp);
+    return a.f16 ? gemm256_pick<true>(a, st, epi, mt3, w4, use_pp, m16) : gemm256_pick<false>(a, st, epi, mt3, w4, use_pp, m16);
 }
 
 template <int EPI>
