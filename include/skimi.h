@@ -268,6 +268,33 @@ int skimi_attention(const void* qkv, void* out, int32_t dtype, int32_t batch, in
 int skimi_attention_out(const void* qkv, void* out, int32_t dtype, int32_t out_dtype, int32_t batch, int32_t seq,
                         int32_t heads, int32_t head_dim, void* stream);
 
+/* The attention and qk-norm launches exactly as the VGGT block forward makes them (vggt.hip), for the tests:
+ *
+ * skimi_qknorm_rope_scaled: skimi_qknorm_rope, and where it takes the fast bf16 kernel (bf16 qkv 16-byte aligned,
+ * qn_w, kn_w and pos given) q is multiplied by q_scale before its one rounding to bf16; *q_scaled (host) says whether
+ * it was.  The forward passes q_scale = log2(e) / sqrt(64), the form skimi_attention_ex's q_prescaled expects.
+ *
+ * skimi_attention_ex: skimi_attention_out (same out_dtype rules and layouts) plus
+ *   q_prescaled  bf16 q / k / v: q already carries 1/sqrt(head_dim) * log2(e) (*q_scaled of the call above);
+ *                ignored for f32;
+ *   x3_scratch   f32 with head_dim 64: dev scratch of at least skimi_attention_x3_scratch_bytes(batch*seq,
+ *                3*heads*head_dim) bytes selects the bf16x3 kernel (hi + lo operands, three MFMAs per product);
+ *                NULL or a smaller one the exact-fp32 kernel;
+ *   out_records  host, may be NULL.  In: non-zero asks the bf16x3 kernel for bf16x3 records instead of f32 rows;
+ *                out: whether they were written.  Records are [batch*seq][heads*head_dim/32][hi 32 | lo 32] bf16
+ *                (the a_dtype SKIMI_BF16X3_REC operand of skimi_gemm) followed by a 256-byte zero page, so `out`
+ *                needs batch*seq*heads*head_dim*4 + 256 bytes and 128-byte alignment; when it is not aligned the
+ *                call writes f32 rows and reports 0. */
+int skimi_qknorm_rope_scaled(void* qkv, int32_t dtype, int64_t tokens, int32_t heads,
+                             const float* qn_w, const float* qn_b, const float* kn_w, const float* kn_b,
+                             float eps, const int32_t* pos, const float* rope_cos, const float* rope_sin,
+                             int32_t rope_npos, float q_scale, int32_t* q_scaled, void* stream);
+int skimi_attention_ex(const void* qkv, void* out, int32_t dtype, int32_t out_dtype, int32_t batch, int32_t seq,
+                       int32_t heads, int32_t head_dim, int32_t q_prescaled, void* x3_scratch,
+                       uint64_t x3_scratch_bytes, int32_t* out_records, void* stream);
+/* bytes of x3_scratch the bf16x3 attention kernel needs for `tokens` packed qkv rows of `row_elems` f32 each */
+uint64_t skimi_attention_x3_scratch_bytes(int64_t tokens, int64_t row_elems);
+
 /* ------------------------------------------------------------------------- */
 /* VideoPose3D TemporalModel lifter  (VideoPose3D/common/model.py:79-138)     */
 /* ------------------------------------------------------------------------- */

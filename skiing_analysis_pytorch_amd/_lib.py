@@ -86,6 +86,11 @@ _SIGNATURES = {
                                     _vp, _vp, _vp, C.c_int32, _vp]),
     "skimi_attention": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "skimi_attention_out": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "skimi_qknorm_rope_scaled": (C.c_int, [_vp, C.c_int32, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, C.c_float,
+                                           _vp, _vp, _vp, C.c_int32, C.c_float, C.POINTER(C.c_int32), _vp]),
+    "skimi_attention_ex": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     _vp, C.c_uint64, C.POINTER(C.c_int32), _vp]),
+    "skimi_attention_x3_scratch_bytes": (C.c_uint64, [C.c_int64, C.c_int64]),
     "skimi_vp3d_create": (_vp, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                 C.c_int32, C.c_int32]),
     "skimi_vp3d_destroy": (None, [_vp]),

@@ -210,4 +210,34 @@ int skimi_attention_out(const void* qkv, void* out, int32_t dtype, int32_t out_d
                             out_dtype == SKIMI_F16 && dtype == SKIMI_BF16);
 }
 
+// the two calls of the block forward (vggt.hip), with its arguments, for kernel-level tests
+int skimi_qknorm_rope_scaled(void* qkv, int32_t dtype, int64_t tokens, int32_t heads, const float* qn_w,
+                             const float* qn_b, const float* kn_w, const float* kn_b, float eps,
+                             const int32_t* pos, const float* rope_cos, const float* rope_sin,
+                             int32_t rope_npos, float q_scale, int32_t* q_scaled, void* stream) {
+    return qknorm_rope_launch(qkv, dtype, tokens, heads, qn_w, qn_b, kn_w, kn_b, eps, pos, rope_cos,
+                              rope_sin, rope_npos, (hipStream_t)stream, q_scale, q_scaled);
+}
+
+int skimi_attention_ex(const void* qkv, void* out, int32_t dtype, int32_t out_dtype, int32_t batch, int32_t seq,
+                       int32_t heads, int32_t head_dim, int32_t q_prescaled, void* x3_scratch,
+                       uint64_t x3_scratch_bytes, int32_t* out_records, void* stream) {
+    if (out_dtype == SKIMI_FP8MX) {   // the layout of skimi_attention_out
+        if (out_records) *out_records = 0;
+        SKIMI_CHECK_ARG(out && batch > 0 && seq > 0 && attention_mx_output_ok(dtype, heads, head_dim),
+                        "skimi_attention_ex: MXFP8 rows need bf16 q / k / v, head_dim 64 and an even number of heads");
+        const size_t Kp = align_up((size_t)heads * head_dim, 128);
+        return attention_launch(qkv, nullptr, dtype, batch, seq, heads, head_dim, (hipStream_t)stream, q_prescaled, nullptr, 0,
+                                nullptr, 0, out, (char*)out + (size_t)batch * seq * Kp);
+    }
+    SKIMI_CHECK_ARG(out_dtype == dtype || (dtype == SKIMI_BF16 && out_dtype == SKIMI_F16),
+                    "skimi_attention_ex: out_dtype is dtype, SKIMI_F16 or SKIMI_FP8MX for bf16 q / k / v (got %d -> %d)", dtype, out_dtype);
+    return attention_launch(qkv, out, dtype, batch, seq, heads, head_dim, (hipStream_t)stream, q_prescaled, x3_scratch,
+                            (size_t)x3_scratch_bytes, out_records, out_dtype == SKIMI_F16 && dtype == SKIMI_BF16);
+}
+
+uint64_t skimi_attention_x3_scratch_bytes(int64_t tokens, int64_t row_elems) {
+    return (uint64_t)attention_x3_scratch_bytes((long)tokens, (long)row_elems);
+}
+
 }  // extern "C"

@@ -242,6 +242,8 @@ int attention_bf16_launch(const AttnArgs& a, hipStream_t st) {
                     a.q_head % 8 == 0 && a.k_head % 8 == 0 && a.v_head % 8 == 0 && a.o_head % 4 == 0 &&
                     a.q_batch % 8 == 0 && a.k_batch % 8 == 0 && a.v_batch % 8 == 0 && a.o_batch % 4 == 0,
                     "skimi_attention: bf16 strides must keep 16-B alignment");
+    SKIMI_CHECK_ARG((((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) & 15) == 0,
+                    "skimi_attention: bf16 q / k / v are loaded in 16-B pieces: the buffer must be 16-B aligned");
     const int nqb = (int)cdiv(a.seq_q, 128);
     const long nblk = (long)nqb * a.heads * a.batch;
     SKIMI_CHECK_ARG(nblk < (1l << 31), "skimi_attention: grid too large");

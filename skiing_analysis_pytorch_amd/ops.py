@@ -117,22 +117,42 @@ def layernorm(x, gamma=None, beta=None, eps=1e-5, *, x2=None, out_dtype=torch.fl
 
 
 def qknorm_rope_(qkv, heads, qn_w=None, qn_b=None, kn_w=None, kn_b=None, eps=1e-5, pos=None, rope_cos=None,
-                 rope_sin=None):
-    """in place on qkv [tokens, 3*heads*64]"""
+                 rope_sin=None, *, q_scale=None):
+    """in place on qkv [tokens, 3*heads*64].  q_scale: the block forward's call -- where the fast bf16 kernel runs, q is
+    multiplied by q_scale before its one rounding to bf16; returns (qkv, q_scaled: bool) then"""
     _require_cuda(qkv, pos, rope_cos, rope_sin)
     tokens = qkv.numel() // (3 * heads * 64)
     npos = rope_cos.shape[0] if rope_cos is not None else 0
+    if q_scale is not None:
+        flag = C.c_int32(0)
+        check(lib().skimi_qknorm_rope_scaled(ptr(qkv), _dt(qkv), tokens, heads, ptr(qn_w), ptr(qn_b), ptr(kn_w), ptr(kn_b),
+                                             eps, ptr(pos), ptr(rope_cos), ptr(rope_sin), npos, q_scale, C.byref(flag),
+                                             _lib.current_stream()), "skimi_qknorm_rope_scaled")
+        return qkv, bool(flag.value)
     check(lib().skimi_qknorm_rope(ptr(qkv), _dt(qkv), tokens, heads, ptr(qn_w), ptr(qn_b), ptr(kn_w), ptr(kn_b),
                                   eps, ptr(pos), ptr(rope_cos), ptr(rope_sin), npos, _lib.current_stream()),
           "skimi_qknorm_rope")
     return qkv
 
 
-def attention(qkv, batch, seq, heads, head_dim, out_dtype=None):
+def attention_x3_scratch_bytes(tokens, row_elems):
+    """bytes of `x3_scratch` that selects the bf16x3 kernel for `tokens` packed fp32 qkv rows of `row_elems`"""
+    return int(lib().skimi_attention_x3_scratch_bytes(tokens, row_elems))
+
+
+def attention(qkv, batch, seq, heads, head_dim, out_dtype=None, *, q_prescaled=0, x3_scratch=None, out_records=False,
+              out=None):
     """qkv: [batch*seq, 3*heads*head_dim] -> [batch*seq, heads*head_dim] (same dtype; out_dtype=torch.float16 with
     bf16 qkv: the result rows as fp16, PREC_F16's proj operand; out_dtype="fp8mx" with bf16 qkv, head_dim 64: the result
-    rows as MXFP8 -> (payload uint8 [rows, Kp], scales uint8 [rows, Kp/32]), PREC_FP8's proj operand)"""
+    rows as MXFP8 -> (payload uint8 [rows, Kp], scales uint8 [rows, Kp/32]), PREC_FP8's proj operand)
+
+    The keyword arguments make the block forward's launch (skimi_attention_ex): q_prescaled=1 for q that
+    qknorm_rope_(q_scale=...) scaled; x3_scratch (a device tensor of >= attention_x3_scratch_bytes) selects the bf16x3
+    kernel for fp32 qkv; out_records=True asks it for bf16x3 records in `out` (default: a `records_buffer`) and returns
+    (out, written: bool) -- when not written, `out` holds the fp32 rows; out: the destination (any dtype, enough bytes)."""
     _require_cuda(qkv)
+    if q_prescaled or x3_scratch is not None or out_records or out is not None:
+        return _attention_ex(qkv, batch, seq, heads, head_dim, out_dtype, q_prescaled, x3_scratch, out_records, out)
     if isinstance(out_dtype, str):
         assert out_dtype == "fp8mx", out_dtype
         rows, Kp = batch * seq, (heads * head_dim + 127) // 128 * 128
@@ -148,6 +168,33 @@ def attention(qkv, batch, seq, heads, head_dim, out_dtype=None):
         check(lib().skimi_attention_out(ptr(qkv), ptr(out), _dt(qkv), _dt(out), batch, seq, heads, head_dim,
                                         _lib.current_stream()), "skimi_attention_out")
     return out
+
+
+def _attention_ex(qkv, batch, seq, heads, head_dim, out_dtype, q_prescaled, x3_scratch, out_records, out):
+    _require_cuda(x3_scratch, out)
+    rows, Cc = batch * seq, heads * head_dim
+    flag = C.c_int32(1 if out_records else 0)
+    sc_bytes = x3_scratch.numel() * x3_scratch.element_size() if x3_scratch is not None else 0
+    mx = isinstance(out_dtype, str)
+    if mx:
+        assert out_dtype == "fp8mx", out_dtype
+        odt, Kp = _lib.FP8MX, (Cc + 127) // 128 * 128
+        need = rows * (Kp + Kp // 32)
+        if out is None:
+            out = torch.zeros(need, dtype=torch.uint8, device=qkv.device)
+    else:
+        odt = {torch.float32: F32, torch.bfloat16: BF16, torch.float16: F16}[out_dtype or qkv.dtype]
+        need = rows * Cc * (4 if odt == F32 else 2) + (256 if out_records else 0)
+        if out is None:
+            out = records_buffer(rows, Cc, qkv.device) if out_records else \
+                torch.empty((rows, Cc), dtype=out_dtype or qkv.dtype, device=qkv.device)
+    assert out.numel() * out.element_size() >= need, "attention: `out` is too small"
+    check(lib().skimi_attention_ex(ptr(qkv), ptr(out), _dt(qkv), odt, batch, seq, heads, head_dim, int(q_prescaled),
+                                   ptr(x3_scratch), sc_bytes, C.byref(flag), _lib.current_stream()), "skimi_attention_ex")
+    if mx:
+        buf = out.view(torch.uint8).reshape(-1)
+        return buf[:rows * Kp].view(rows, Kp), buf[rows * Kp:need].view(rows, Kp // 32)
+    return (out, bool(flag.value)) if out_records else out
 
 
 def conv3x3_n32(x, w, bias=None, relu=False):
