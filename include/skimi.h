@@ -184,6 +184,24 @@ int skimi_split_records(const float* x, int64_t ld, int64_t rows, int32_t C, voi
 
 int skimi_gemm(const skimi_gemm_desc* d, void* stream);
 
+/* Which kernel the calling thread's last skimi_gemm dispatch chose (a host-side record written before the
+ * launch; tests pin their cases to a kernel with it).  0 before any dispatch and after an argument error.
+ *   bits  0- 3  family: SKIMI_GEMM_PATH_*
+ *   bits  4- 7  generic: tile (1 = 64x64, 2 = 128x64, 3 = 128x128);
+ *               gemm256: main loop (1 = two-phase 256 rows, 2 = two-phase 192 rows, 3 = ping-pong, 4 = single-stream)
+ *   bits  8-11  gemm256: MFMA shape (1 = v_mfma_f32_16x16x32, 2 = v_mfma_f32_32x32x16); 0 elsewhere
+ *   bits 12-15  gemm256: compile-time epilogue (0 = shared epilogue, 1 bias -> 16-bit, 2 LayerScale + residual,
+ *               3 bias + GELU -> 16-bit); 0 elsewhere
+ *   bits 16-23  K splits (1 = no split-K) */
+#define SKIMI_GEMM_PATH_GENERIC 1
+#define SKIMI_GEMM_PATH_SPLITK_ORDERED 2
+#define SKIMI_GEMM_PATH_SPLITK_ATOMIC 3
+#define SKIMI_GEMM_PATH_X3DMA_WIDE 4
+#define SKIMI_GEMM_PATH_X3DMA_NARROW 5
+#define SKIMI_GEMM_PATH_GEMM256 6
+#define SKIMI_GEMM_PATH_CONV_WIN 7
+int32_t skimi_gemm_last_path(void);
+
 /* OCP microscaling FP8 (MXFP8) operands of skimi_gemm_fp8: x [rows, K] (bf16 or fp32, row stride ldx elements,
  * 16-byte aligned rows) -> payload [rows][Kp] e4m3 bytes (Kp = K rounded up to 128, tail zero) and scales
  * [rows][Kp / 32] E8M0 bytes (value 2^(byte - 127); per 32-element block the smallest power of two with

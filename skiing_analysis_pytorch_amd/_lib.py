@@ -17,7 +17,10 @@ BF16X3_REC = 2   # skimi_gemm_desc.a_dtype: A already split into bf16x3 records
 FP8MX = 3        # skimi_gemm_fp8 out_dtype: the result as MXFP8 payload + scales
 PREC_BF16, PREC_BF16X3, PREC_FP8 = 0, 1, 2   # PREC_FP8: VGGT aggregator only (MXFP8 qkv / proj / fc1 / fc2)
 PREC_F16 = 3     # fp16 operands on the f16 MFMA (Linears of the aggregator blocks + patch embed; skimi_gemm with fp16 / fp32 operands)
-ACT_NONE, ACT_RELU, ACT_GELU, ACT_SILU = 0, 1, 2, 3
+ACT_NONE, ACT_RELU, ACT_GELU, ACT_SILU, ACT_SIGMOID = 0, 1, 2, 3, 4
+# skimi_gemm_last_path families (include/skimi.h)
+GEMM_PATH_GENERIC, GEMM_PATH_SPLITK_ORDERED, GEMM_PATH_SPLITK_ATOMIC = 1, 2, 3
+GEMM_PATH_X3DMA_WIDE, GEMM_PATH_X3DMA_NARROW, GEMM_PATH_GEMM256, GEMM_PATH_CONV_WIN = 4, 5, 6, 7
 
 
 class SkimiError(RuntimeError):
@@ -69,6 +72,7 @@ _SIGNATURES = {
     "skimi_profile_stop": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                     C.POINTER(C.c_double)]),
     "skimi_gemm": (C.c_int, [C.POINTER(GemmDesc), _vp]),
+    "skimi_gemm_last_path": (C.c_int32, []),
     "skimi_quant_mx": (C.c_int, [_vp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp]),
     "skimi_layernorm_mx": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, C.c_float, _vp, _vp, _vp]),
     "skimi_gemm_fp8": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_int64,

@@ -118,8 +118,11 @@ int skimi_profile_stop(double* total_ms, int64_t* launches, double* flops, doubl
     return SKIMI_OK;
 }
 
+int32_t skimi_gemm_last_path(void) { return gemm_last_path(); }
+
 int skimi_gemm(const skimi_gemm_desc* d, void* stream) {
     if (!d) {
+        set_gemm_path(0, 0, 0, 0, 0);
         set_error("skimi_gemm: null descriptor");
         return SKIMI_ERR_ARG;
     }

@@ -418,9 +418,16 @@ static int launch_cfg(const GemmArgs& a, hipStream_t st) {
     return SKIMI_OK;
 }
 
+static thread_local int tl_gemm_path = 0;
+void set_gemm_path(int family, int tile, int mfma, int epi, int splitk) {
+    tl_gemm_path = family | (tile << 4) | (mfma << 8) | (epi << 12) | (splitk << 16);
+}
+int gemm_last_path() { return tl_gemm_path; }
+
 // scratch: caller-owned fp32 slab [M, N] for split-K partials (NULL => split-K is not used)
 int gemm_dispatch(const skimi_gemm_desc* d, hipStream_t st, void* scratch, size_t scratch_bytes,
                   int force_splitk) {
+    tl_gemm_path = 0;
     SKIMI_CHECK_ARG(d != nullptr, "skimi_gemm: null descriptor");
     SKIMI_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "skimi_gemm: empty shape M=%d N=%d K=%d", d->M, d->N, d->K);
     SKIMI_CHECK_ARG(d->K % 8 == 0, "skimi_gemm: K=%d must be a multiple of 8", d->K);
@@ -523,6 +530,7 @@ int gemm_dispatch(const skimi_gemm_desc* d, hipStream_t st, void* scratch, size_
 
     // 3 x 3 convolutions to 128 channels on 16-bit operands (the track head's feature extractor): halo window in LDS
     if (force_splitk <= 0 && conv_win_eligible(d)) {
+        set_gemm_path(SKIMI_GEMM_PATH_CONV_WIN, 0, 0, 0, 1);
         const bool profw = prof_armed(PROF_GEMM, (long)d->M);
         if (profw) prof_before(st);
         const int rcw = conv_win_launch(a, st);
@@ -573,6 +581,8 @@ int gemm_dispatch(const skimi_gemm_desc* d, hipStream_t st, void* scratch, size_
         // (splitk_scratch_zeroed) pays no memset per launch
         if (!d->splitk_scratch_zeroed) SKIMI_HIP(hipMemsetAsync(scratch, 0, need, st));
     }
+    set_gemm_path(splitk == 1 ? SKIMI_GEMM_PATH_GENERIC : a.splitk_ordered ? SKIMI_GEMM_PATH_SPLITK_ORDERED : SKIMI_GEMM_PATH_SPLITK_ATOMIC,
+                  BM == 64 ? 1 : BN == 64 ? 2 : 3, 0, 0, splitk);
 
     int rc;
     const bool prof = prof_armed(PROF_GEMM, (long)d->M);

@@ -1197,6 +1197,9 @@ int gemm256_launch(GemmArgs& a, hipStream_t st) {
     const int use_w4 = SKIMI_ENV_INT("SKIMI_GEMM256_W4", -1);
     const bool mt3 = use_mt3 == 1 || (use_mt3 < 0 && cost(192) < 0.8 * cost(256));
     const bool w4 = use_w4 >= 0 ? use_w4 != 0 : (epi == 1 || (epi == 2 && a.K > 1024));
+    // the loop gemm256_pick takes (the fp16 build has no two-phase 256-row loop: ping-pong in its place)
+    const int loop = mt3 ? 2 : w4 ? 4 : (use_pp || a.f16) ? 3 : 1;
+    set_gemm_path(SKIMI_GEMM_PATH_GEMM256, loop, (loop >= 3 && m16) ? 1 : 2, epi, 1);
     return a.f16 ? gemm256_pick<true>(a, st, epi, mt3, w4, use_pp, m16) : gemm256_pick<false>(a, st, epi, mt3, w4, use_pp, m16);
 }
 

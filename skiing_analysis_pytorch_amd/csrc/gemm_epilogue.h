@@ -260,6 +260,10 @@ __device__ __forceinline__ void store_four(const GemmArgs& p, const RowMap& rm, 
     }
 }
 
+// the calling thread's record of its last skimi_gemm dispatch (skimi_gemm_last_path: field layout in skimi.h)
+void set_gemm_path(int family, int tile, int mfma, int epi, int splitk);
+int gemm_last_path();
+
 bool gemm256_eligible(const skimi_gemm_desc* d);
 bool gemm_x3dma_eligible(const skimi_gemm_desc* d);
 int gemm_x3dma_launch(GemmArgs& a, const skimi_gemm_desc* d, hipStream_t st);

@@ -822,6 +822,7 @@ int gemm_x3dma_launch(GemmArgs& a, const skimi_gemm_desc* d, hipStream_t st) {
     pl.w_row_bytes = ((long)d->K + 31) / 32 * 32 * 4;
     pl.a_bias = d->a_mode == 0 ? 0 : ((long)d->pad * d->cW + d->pad) * pl.a_row_bytes;
     a.dbg = 0;
+    set_gemm_path(d->N <= 128 ? SKIMI_GEMM_PATH_X3DMA_NARROW : SKIMI_GEMM_PATH_X3DMA_WIDE, 0, 0, 0, 1);
     if (d->N <= 128) {
         if (a.a_mode == 0) return launch_x3w4n<0>(a, pl, st);
         if (a.a_mode == 1) return launch_x3w4n<1>(a, pl, st);

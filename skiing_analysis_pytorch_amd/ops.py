@@ -4,6 +4,7 @@ arithmetic happens in libskimi.so.  Used by the parity tests and by the Python h
 from __future__ import annotations
 
 import ctypes as C
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -30,7 +31,7 @@ def _require_cuda(*ts):
 def gemm(a, w, *, prec=PREC_BF16X3, bias=None, gamma=None, resid=None, act=ACT_NONE, out=None,
          out_dtype=torch.float32, conv=None, resid_map=None, pixel_shuffle=None, splitk_scratch=None,
          force_splitk=0, M=None, lda=None, w_split=None, x3_scratch=None, a_records=None, out_records=None,
-         records_only=False, post_act=ACT_NONE):
+         records_only=False, post_act=ACT_NONE, resid2=None, out2=None, out_map=None, splitk_zeroed=False):
     """out = epilogue(gather(a) @ w.T).  a: [rows, lda] (f32|bf16), w: [N, K].
 
     conv = dict(N,H,W,C,KH,KW,stride,pad,dil,OH,OW) selects the implicit-im2col gather;
@@ -38,8 +39,16 @@ def gemm(a, w, *, prec=PREC_BF16X3, bias=None, gamma=None, resid=None, act=ACT_N
     out_records = a `records_buffer(M, N)`: the result also as bf16x3 records (+ zero page) for a
     following `gemm(None, ..., a_records=that buffer)` (its [rows, C] shape comes through `conv`, or
     `M` and `lda` for plain rows); records_only: no fp32 result at all (returns None).
-    post_act: activation applied after the residual add."""
-    _require_cuda(w, bias, gamma, resid, out)
+    post_act: activation applied after the residual adds.
+    resid2: second residual, plain row m, the same dtype as resid; out2: the result again in the other
+    dtype (bf16 next to an fp32 out, fp32 next to a 16-bit out), same indexing with its own row stride;
+    out_map = (rows_per_batch, batch_stride, row_off): the output row remap (needs `out`: the rows it
+    skips cannot be sized here); splitk_zeroed: the caller vouches that splitk_scratch is all zero (no memset)."""
+    _require_cuda(w, bias, gamma, resid, out, resid2, out2)
+    if out_map is not None and out is None:
+        raise _lib.SkimiError("gemm: out_map needs a caller-owned out (the remapped rows cannot be sized here)")
+    if resid is not None and resid2 is not None and resid.dtype != resid2.dtype:
+        raise _lib.SkimiError("gemm: resid and resid2 share one dtype (resid_dtype)")
     d = GemmDesc()
     N, K = w.shape
     d.N, d.K = N, K
@@ -79,10 +88,20 @@ def gemm(a, w, *, prec=PREC_BF16X3, bias=None, gamma=None, resid=None, act=ACT_N
         d.ldo = out.stride(-2)
     if not records_only:
         d.out, d.out_dtype = ptr(out), _dt(out)
+    if out2 is not None:
+        if out is None or (out2.dtype == torch.float32) == (out.dtype == torch.float32) or \
+                (out.dtype == torch.float32 and out2.dtype != torch.bfloat16):
+            raise _lib.SkimiError("gemm: out2 is the other dtype of out (bf16 next to fp32, fp32 next to 16-bit)")
+        d.out2, d.ldo2 = ptr(out2), out2.stride(-2)
+    if out_map is not None:
+        d.out_rows_per_batch, d.out_batch_stride, d.out_row_off = out_map
     d.bias, d.gamma, d.resid = ptr(bias), ptr(gamma), ptr(resid)
     if resid is not None:
         d.ldr = resid.stride(-2)
         d.resid_dtype = _dt(resid)
+    if resid2 is not None:
+        d.resid2, d.ldr2 = ptr(resid2), resid2.stride(-2)
+        d.resid_dtype = _dt(resid2)
     if resid_map is not None:
         d.resid_rows_per_batch, d.resid_batch_stride, d.resid_row_off = resid_map
     d.act = act
@@ -91,6 +110,7 @@ def gemm(a, w, *, prec=PREC_BF16X3, bias=None, gamma=None, resid=None, act=ACT_N
         d.splitk_scratch = ptr(splitk_scratch)
         d.splitk_scratch_bytes = splitk_scratch.numel() * splitk_scratch.element_size()
     d.force_splitk = force_splitk
+    d.splitk_scratch_zeroed = int(splitk_zeroed)
     if w_split is not None:
         d.W_split = ptr(w_split)
         if a_records is not None:   # the zero page behind the records
@@ -104,6 +124,34 @@ def gemm(a, w, *, prec=PREC_BF16X3, bias=None, gamma=None, resid=None, act=ACT_N
         d.out_records = ptr(out_records)
     check(lib().skimi_gemm(C.byref(d), _lib.current_stream()), "skimi_gemm")
     return out
+
+
+class GemmPath(NamedTuple):
+    """skimi_gemm_last_path decoded (field layout in include/skimi.h)"""
+    family: Optional[str]   # generic | splitk_ordered | splitk_atomic | x3dma_wide | x3dma_narrow | gemm256 | conv_win
+    tile: Optional[str]     # generic kernel: 64x64 | 128x64 | 128x128
+    loop: Optional[str]     # gemm256: two_phase_256 | two_phase_192 | ping_pong | single_stream
+    mfma: Optional[int]     # gemm256: 16 (v_mfma_f32_16x16x32) | 32 (v_mfma_f32_32x32x16)
+    epi: int                # gemm256: compile-time epilogue 0..3
+    splitk: int             # K splits (1 = none)
+    raw: int
+
+
+_PATH_FAMILY = {1: "generic", 2: "splitk_ordered", 3: "splitk_atomic", 4: "x3dma_wide", 5: "x3dma_narrow",
+                6: "gemm256", 7: "conv_win"}
+_PATH_TILE = {1: "64x64", 2: "128x64", 3: "128x128"}
+_PATH_LOOP = {1: "two_phase_256", 2: "two_phase_192", 3: "ping_pong", 4: "single_stream"}
+
+
+def gemm_last_path() -> GemmPath:
+    """which kernel the calling thread's last skimi_gemm dispatched to"""
+    v = int(lib().skimi_gemm_last_path())
+    fam = _PATH_FAMILY.get(v & 15)
+    sub = (v >> 4) & 15
+    generic = fam in ("generic", "splitk_ordered", "splitk_atomic")
+    return GemmPath(family=fam, tile=_PATH_TILE.get(sub) if generic else None,
+                    loop=_PATH_LOOP.get(sub) if fam == "gemm256" else None,
+                    mfma={1: 16, 2: 32}.get((v >> 8) & 15), epi=(v >> 12) & 15, splitk=(v >> 16) & 255, raw=v)
 
 
 def layernorm(x, gamma=None, beta=None, eps=1e-5, *, x2=None, out_dtype=torch.float32):
