@@ -433,6 +433,37 @@ int skimi_unproject_depth(const float* depth, const float* extrinsic, const floa
 int skimi_triangulate_dlt(const float* K, const float* R, const float* t, const float* keypoints,
                           float* joints3d, int64_t steps, int32_t views, int32_t joints, void* stream);
 
+/* Point-to-plane ICP of two dense point maps (replaces ICP_with_bbox, vggt/multi_view_process.py:427-520, which
+ * calls Open3D's estimate_normals and registration_icp on the host).  Clouds are raw dev f32 [n, 3]; the validity
+ * filter runs inside: a point is kept iff its coordinates are finite and x^2 + y^2 + z^2 > 1e-12 (the reference keeps
+ * ||p|| > 1e-6; the two differ only on non-finite input).  Neighbours and correspondences lie at d^2 < r^2 (float64).
+ * Every sum has a fixed order: results are bitwise reproducible.  ws: device scratch of at least
+ * skimi_icp_workspace_bytes(n_src, n_tgt) bytes (skimi_estimate_normals: (0, n)); nothing is allocated in a call.
+ * Each call synchronises `stream` (it reads valid-point counts back; ICP reads a 6x6 system per iteration). */
+size_t skimi_icp_workspace_bytes(int64_t n_src, int64_t n_tgt);
+/* Radius normals of the valid points (estimate_normals(KDTreeSearchParamRadius(radius)), :487-496): neighbours of a
+ * point are the valid points at d < radius, itself included; with >= 3 of them the normal is the unit eigenvector of
+ * the smallest eigenvalue of their float64 covariance (cumulant form), else (0, 0, 1).  The sign is arbitrary.
+ * normals_out: dev f64 [n, 3], neighbour_count_out: dev i32 [n]; an invalid point gets (0, 0, 0) and 0. */
+int skimi_estimate_normals(const float* points, int64_t n, double radius, double* normals_out,
+                           int32_t* neighbour_count_out, void* ws, size_t ws_bytes, void* stream);
+/* For tests: the correspondence of every source point under T4x4 (host f64, row-major): the nearest valid target
+ * point at d < max_dist, d^2 computed in float64 from T s (ties -> the smaller target index) -> tgt_index_out
+ * (dev i32 [n_src], original target indices; -1 = none or invalid source point). */
+int skimi_icp_correspondences(const float* src, int64_t n_src, const float* tgt, int64_t n_tgt, const double* T4x4,
+                              double max_dist, int32_t* tgt_index_out, void* ws, size_t ws_bytes, void* stream);
+/* registration_icp with TransformationEstimationPointToPlane (:498-505), target normals at normal_radius:
+ * evaluate(T) -> for each iteration: solve JtJ x = -Jtr (LDLT, r = (T s - t).n, J = [T s x n ; n]), update =
+ * Rz(x2) Ry(x1) Rx(x0) | x3..5 (identity without correspondences or on a non-finite solution), T = update T,
+ * evaluate(T), stop when |d fitness| < rel_fitness and |d rmse| < rel_rmse.  The source is always the original
+ * float32 cloud transformed by T in float64.  init4x4 (host f64, NULL = identity); T_out (host f64 [16]),
+ * fitness = correspondences / valid source points, rmse = sqrt(sum d^2 / correspondences) of the last evaluation,
+ * iterations = updates applied.  Fewer than 50 valid points in either cloud: identity, 0, 0, 0 iterations (:471-474). */
+int skimi_icp_point_to_plane(const float* src, int64_t n_src, const float* tgt, int64_t n_tgt, double max_corr_dist,
+                             double normal_radius, int32_t max_iteration, double rel_fitness, double rel_rmse,
+                             const double* init4x4, double* T_out, double* fitness_out, double* rmse_out,
+                             int32_t* iterations_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -193,6 +193,7 @@ class CameraHead:
         preds = self.vggt(imgs.view(B, S, 3, oh, ow), want={"camera", "depth"})
         E, K = geometry.pose_encoding_to_extri_intri(preds["pose_enc"], (oh, ow))
         wp = torch.stack([geometry.unproject_depth_map_to_point_map(preds["depth"][b], E[b], K[b]) for b in range(B)])
+        self.last_world_points = wp   # the device copy of the returned maps [B, S, H, W, 3] (the ICP of process_multi_view_video)
         En, Kn, wpn, pen = E.cpu().numpy(), K.cpu().numpy(), wp.cpu().numpy(), preds["pose_enc"].cpu().numpy()
         out = []
         for b in range(B):

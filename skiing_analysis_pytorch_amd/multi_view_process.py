@@ -10,10 +10,16 @@ detector boxes (`extract_person_points`, :356-395) -> the right camera's 180-deg
 -> DLT triangulation of the 17 joints (`triangulate_one_frame`, vggt/triangulate.py:38-71), and at the
 end the camera / joints NPZ of `save_camera_info` (vggt/save.py:84-110, called at :312-319).
 
+With `cfg.infer.icp` true it also runs the reference's refinement of the right camera (:263-291): point-to-plane
+ICP of the step's two world-point maps (`ICP_with_bbox`, :427-520; HIP kernels instead of Open3D,
+geometry.icp_point_to_plane), the update of R[1] / t[1] (`apply_icp_update`) and a second triangulation; the NPZ
+then holds the refined R, t and x3d, as the reference's does, with icp_refined=True.  The flag is off by default:
+the arrays are then the pre-ICP quantities under the same keys, with icp_refined=False.  Parity with Open3D
+itself is "unpinned" (DESIGN §2 "ICP": tie, eigensolver and non-finite-point rules of this build).
+
 What it leaves out (out of scope): video decode (frames come from the `.pt` files, which
-`prepare_dataset` can embed; the video paths only name the subject), PNG / GLB / matplotlib output, the
-Open3D ICP refinement (:285-296; Open3D is not part of this build, "parity unpinned") and the commented-out
-bundle adjustment.  The time steps are independent: they go through the HIP model `steps_per_call` at a
+`prepare_dataset` can embed; the video paths only name the subject), PNG / GLB / matplotlib output and the
+commented-out bundle adjustment.  The time steps are independent: they go through the HIP model `steps_per_call` at a
 time, sharded over ranks under torch.distributed, and the per-step joints are re-assembled with one
 all-gather (parallel.py).
 """
@@ -74,6 +80,35 @@ def recenter_and_align(R: np.ndarray, t: np.ndarray, origin: np.ndarray):
     return R, t
 
 
+def ICP_with_bbox(source_points, target_points, source_bbox, target_bbox):
+    """multi_view_process.py:427-520: point-to-plane ICP of the whole source map onto the whole target map
+    (the boxes are ignored: the reference's crop is commented out, :453-456) -> (aligned source [N, 3] =
+    R_T p + t_T for every source point, float64 4x4 T).  Maps [H, W, 3] or [N, 3], device tensors or arrays;
+    the ICP runs on the device (geometry.icp_point_to_plane with the reference's parameters: 0.05, 0.05, 200).
+    Fewer than 50 valid points in either map: the unchanged source and eye(4) (:471-474)."""
+    del source_bbox, target_bbox
+    dev = torch.device("cuda", torch.cuda.current_device())
+    src = source_points if isinstance(source_points, torch.Tensor) else torch.from_numpy(np.asarray(source_points, np.float32))
+    tgt = target_points if isinstance(target_points, torch.Tensor) else torch.from_numpy(np.asarray(target_points, np.float32))
+    src = src.to(dev).reshape(-1, 3)
+    tgt = tgt.to(dev).reshape(-1, 3)
+    T = geometry.icp_point_to_plane(src, tgt, 0.05, 0.05, 200).transformation
+    P = src.cpu().numpy().astype(np.float64)
+    return (T[:3, :3] @ P.T).T + T[:3, 3], T
+
+
+def apply_icp_update(R: np.ndarray, t: np.ndarray, T: np.ndarray):
+    """multi_view_process.py:271-275 on copies: R[1] = R_T R[1], t[1] = R_T t[1] + t_T.
+    As in the reference, T is estimated between the world-point maps in VGGT's frame but applied to the camera
+    AFTER the person recentring and the 180-degree turn of recenter_and_align (:196-217); that mismatch is the
+    reference's and is reproduced, not fixed."""
+    R, t = np.array(R, dtype=np.float64), np.array(t, dtype=np.float64)
+    R_u, t_u = T[:3, :3], T[:3, 3]
+    R[1] = R_u @ R[1]
+    t[1] = R_u @ t[1] + t_u
+    return R, t
+
+
 def _bbox_of(bboxes: np.ndarray, idx: int):
     b = bboxes[idx]
     return b if b.ndim == 1 else b[0]
@@ -113,6 +148,7 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
     T = min(len(lf), len(rf))
     lo, hi, _T_pad = parallel.shard_range(T)
     source_size = tuple(lf.shape[1:3])
+    icp = bool(cfg_get(cfg, "infer.icp", False))
     x3d_l, K_l, R_l, t_l, C_l = [], [], [], [], []
     for a in range(lo, hi, steps_per_call):
         idx = [min(i, T - 1) for i in range(a, min(a + steps_per_call, hi))]     # padded steps repeat the last one
@@ -121,11 +157,15 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
         write = [i < T for i in range(a, min(a + steps_per_call, hi))]
         recs = head.reconstruct_batch(idx, [[lf[i], rf[i]] for i in idx], write=write)
         Ks, Rs, ts = [], [], []
-        for i, (_E, K_res, R, t, C, wp) in zip(idx, recs):
+        for b, (i, (_E, K_res, R, t, C, wp)) in enumerate(zip(idx, recs)):
             pl = extract_person_points(wp[0], _bbox_of(lb, i), source_size)
             pr = extract_person_points(wp[1], _bbox_of(rb, i), source_size)
             origin = 0.5 * (pl.mean(axis=0) + pr.mean(axis=0)) if len(pl) and len(pr) else np.zeros(3)
             R2, t2 = recenter_and_align(R, t, origin)
+            if icp:   # :263-275: ICP of view 0's map onto view 1's (the device copy of wp), then R[1], t[1] updated
+                wpd = head.last_world_points[b]
+                T_icp = geometry.icp_point_to_plane(wpd[0].reshape(-1, 3), wpd[1].reshape(-1, 3), 0.05, 0.05, 200).transformation
+                R2, t2 = apply_icp_update(R2, t2, T_icp)
             Ks.append(np.stack(K_res[:2]))
             Rs.append(R2)
             ts.append(t2)
@@ -147,12 +187,12 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
     # fuse/'s temporal smoothing of the gathered joints (BASELINE config 4; fuse/fuse.py:329-412)
     x3d_smoothed = fuse.temporal_smooth_ema(x3d.astype(np.float64)) if cfg_get(cfg, "infer.smooth", True) else None
     if parallel.world()[0] == 0:
-        # icp_refined = False: the reference stores R, t and the joints AFTER its Open3D ICP update
-        # (multi_view_process.py:285-319); this build has no ICP (out of scope, "parity unpinned"), the arrays are
-        # the pre-ICP quantities under the same keys
-        logger.warning("[Run-MV] cameras / joints are written without the reference's Open3D ICP refinement (icp_refined=False)")
+        # the reference stores R, t and the joints AFTER its ICP update (multi_view_process.py:285-319); with
+        # infer.icp off (the default) the arrays are the pre-ICP quantities under the same keys, icp_refined = False
+        if not icp:
+            logger.warning("[Run-MV] cameras / joints are written without the reference's Open3D ICP refinement (icp_refined=False)")
         save_camera_info(out_pt_path=inference_output_path / f"{subject}_multi_view_3d_info.npz",
                          all_frame_x3d=list(x3d), all_frame_camera_intrinsics=list(Ka), all_frame_R=list(Ra),
                          all_frame_t=list(ta), all_frame_C=list(Ca),
-                         extra={"icp_refined": np.array(False)} | ({"x3d_smoothed": x3d_smoothed} if x3d_smoothed is not None else {}))
+                         extra={"icp_refined": np.array(icp)} | ({"x3d_smoothed": x3d_smoothed} if x3d_smoothed is not None else {}))
     return out_dir
