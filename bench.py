@@ -13,6 +13,12 @@ timed region starts.  Launched by the driver as
 One rank per GPU; time steps are independent, so ranks shard them with no data-path collective
 (weak scaling); the barrier + MAX-over-ranks timing is the only communication.
 Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: set up, warm up, time the steps (with the
+roofline hook on their global-attention launches), write --dump-outputs, print.  `--full` adds every
+other leg after the timed region: the one-stream roofline, the other 16-bit format, MXFP8, the
+bf16x3 parity mode, the VideoPose3D lifter, the fp32 CPU oracle and the joints-vs-oracle bar, and
+config 4's smoothing of the gathered joints.
 """
 from __future__ import annotations
 
@@ -51,16 +57,20 @@ def main():
     ap.add_argument("--streams", type=int, default=2,
                     help="independent batches of --batch time steps per step, each issued from its own host thread on "
                          "its own HIP stream (infer.process_multi_view_clip(streams=N)); 1 = one batch per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-vp3d", action="store_true", help="skip the VideoPose3D lifter leg (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, run every leg beside the headline (one-stream roofline, other 16-bit format, "
+                         "MXFP8, bf16x3 parity mode, VideoPose3D lifter, fp32 CPU oracle + joints bar, EMA of the joints); "
+                         "the --no-* options below trim them.  Off: only what the headline needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the fp32 CPU oracle leg and the joints bar")
+    ap.add_argument("--no-vp3d", action="store_true", help="--full: skip the VideoPose3D lifter leg (profiling runs)")
     ap.add_argument("--no-track", action="store_true", help="leave the track head out of the step (39.6 instead of 40.6 TFLOP)")
-    ap.add_argument("--no-parity-mode", action="store_true", help="skip the timing of the fp32-accurate (bf16x3) mode")
-    ap.add_argument("--no-fp8", action="store_true", help="skip the MXFP8 leg (BASELINE config 5)")
+    ap.add_argument("--no-parity-mode", action="store_true", help="--full: skip the timing of the fp32-accurate (bf16x3) mode")
+    ap.add_argument("--no-fp8", action="store_true", help="--full: skip the MXFP8 leg (BASELINE config 5)")
     ap.add_argument("--prec", choices=["f16", "bf16"], default="f16",
                     help="operand format of the aggregator's Linears in the timed region: f16 (default: the cheapest mode whose 3D "
                          "joints stay within north_star's 1e-3 of the fp32 CPU path) or bf16 (the reference's autocast format, which "
-                         "does not); the other one is timed as a leg of the same line")
-    ap.add_argument("--no-other-prec", action="store_true", help="skip the leg that times the other of f16 / bf16")
+                         "does not); with --full the other one is timed as a leg of the same line")
+    ap.add_argument("--no-other-prec", action="store_true", help="--full: skip the leg that times the other of f16 / bf16")
     ap.add_argument("--with-upload", action="store_true",
                     help="start every step from uint8 HWC frames in pinned HOST memory: PCIe upload + the device preprocessing of "
                          "load_and_preprocess_images (vggt/load.py:38-183; vggt/vggt/infer.py:77 does both per call) inside the timed "
@@ -110,8 +120,9 @@ def main():
     model = vggt.VGGT(config=cfg, prec=agg_prec, head_prec=PREC_BF16X3)
     sd = W.make_vggt_state_dict(cfg, seed=0, device=dev)      # random-init weights of that architecture
     model.load_state_dict(sd)
+    legs = args.full and rank == 0 and world == 1   # the legs beside the headline: --full, rank 0 at N = 1 only
     cpu_sd = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:   # CPU legs: rank 0 at N = 1 only
+    if legs and not args.no_cpu_baseline:
         cpu_sd = {k: v.cpu() for k, v in sd.items()}
     del sd
     torch.cuda.empty_cache()
@@ -240,10 +251,11 @@ def main():
         assert torch.equal(sums, blocks), "all-gather: a rank's block is missing from the gathered joints"
         assert torch.isfinite(out["joints3d"]).all()
         assert out["E"].shape == (world * nloc, S_VIEWS, 3, 4) and torch.equal(out["E"][rank * nloc:(rank + 1) * nloc], out["E_local"])
-    # BASELINE config 4's last stage on the gathered joints (outside the timed region: it runs once per clip on the host)
-    from skiing_analysis_pytorch_amd import fuse
-    smoothed = fuse.temporal_smooth_ema(out["joints3d"].cpu().numpy().astype("float64"))
-    assert smoothed.shape == tuple(out["joints3d"].shape)
+    if args.full:
+        # BASELINE config 4's last stage on the gathered joints (outside the timed region: it runs once per clip on the host)
+        from skiing_analysis_pytorch_amd import fuse
+        smoothed = fuse.temporal_smooth_ema(out["joints3d"].cpu().numpy().astype("float64"))
+        assert smoothed.shape == tuple(out["joints3d"].shape)
     dumped = None
     if args.dump_outputs and rank == 0:   # before any later leg runs a model again
         dumped = dump_outputs(args.dump_outputs, step_outputs(last_outs, out))
@@ -296,7 +308,7 @@ def main():
             line["roofline"]["peak_measured"] = {"unit": "TFLOP/s", "random_operands": pk["random_operands"], "zero_operands": pk["zero_operands"],
                                                  "frac_of_random_operand_peak": ach / pk["random_operands"],
                                                  "source": "static: profiles/r03_peaks.json (tools/peaks.hip, register-only v_mfma_f32_32x32x16_bf16 loop)"}
-    if rank == 0 and world == 1 and NS > 1 and "roofline" in line:
+    if legs and NS > 1 and "roofline" in line:
         # outside the timed region: the same kernel with the chip to itself (one batch, one stream)
         _lib.check(lib.skimi_profile_start(1, seq_global), "profile_start")
         step()
@@ -307,7 +319,7 @@ def main():
             line["roofline"]["one_stream"] = {"achieved": a1, "frac": a1 / PEAK_BF16_TFLOPS,
                                               "avg_launch_us": ms.value * 1e3 / n.value, "launches": int(n.value)}
     other_model, other_name = None, ("bf16" if args.prec == "f16" else "f16")
-    if rank == 0 and world == 1 and not args.no_other_prec:
+    if legs and not args.no_other_prec:
         # the same step with the other 16-bit operand format (bf16 = the reference's own autocast precision): same
         # inputs, same step code, its own timed region; not part of `value`
         mo = vggt.VGGT(config=cfg, prec=PREC_BF16 if other_name == "bf16" else PREC_F16, head_prec=PREC_BF16X3)
@@ -331,7 +343,7 @@ def main():
                                       "pose_enc_max_abs_diff_vs_timed_mode": (outo["pose_enc"] - out["pose_enc"]).abs().max().item()}
         active["model"] = model
         other_model = mo
-    if rank == 0 and world == 1 and not args.no_fp8:
+    if legs and not args.no_fp8:
         # BASELINE config 5: the same step with the four Linears (qkv / proj / fc1 / fc2) of every block on the MXFP8 MFMA
         # (SKIMI_PREC_FP8); not part of `value`.  Same inputs, same step code, its own timed region.
         from skiing_analysis_pytorch_amd._lib import PREC_FP8
@@ -359,7 +371,7 @@ def main():
         fp8_model = m8
     else:
         fp8_model = None
-    if rank == 0 and world == 1 and not args.no_vp3d:
+    if legs and not args.no_vp3d:
         line["vp3d"] = vp3d_leg(dev, cpu=not args.no_cpu_baseline)
     if rank == 0 and cpu_sd is not None:
         line["cpu_baseline"], line["mpjpe_vs_cpu_oracle"], m3 = cpu_baseline(
@@ -401,10 +413,10 @@ def main():
         else:
             line["value_within_bar"], line["mode_within_bar"] = None, None
     if rank == 0:
-        if "within_bar" not in line:   # no CPU-oracle leg in this run (N > 1 or --no-cpu-baseline): the bar is judged by the N = 1 run
+        if "within_bar" not in line:   # no CPU-oracle leg in this run (no --full, N > 1 or --no-cpu-baseline): the bar is judged by a --full N = 1 run
             line["within_bar"] = None
-            line["within_bar_note"] = ("not measured in this run: the joints-vs-CPU-oracle leg runs on rank 0 at N = 1 only; the same mode measured "
-                                       "4.7e-4 ring-rig MPJPE there (profiles/r03_bench_line.json)")
+            line["within_bar_note"] = ("not measured in this run: the joints-vs-CPU-oracle leg runs with --full, on rank 0 at N = 1 only; the same "
+                                       "mode measured 4.7e-4 ring-rig MPJPE there (profiles/r03_bench_line.json)")
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.destroy_process_group()

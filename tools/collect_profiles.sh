@@ -8,7 +8,7 @@ tag=${1:-r03}
 out=gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-vp3d --no-fp8 --no-parity-mode --no-other-prec > $out/bench.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-vp3d --no-fp8 --no-parity-mode --no-other-prec > $out/bench.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/vp3d -- python3 tools/prof_vp3d.py 1 2 64 > $out/vp3d.log 2>&1
 for c in FETCH_SIZE WRITE_SIZE; do
   rocprofv3 --kernel-trace --output-format csv --pmc $c -d $out/attn_$c -- python3 tools/pmc_attn.py > $out/attn_$c.log 2>&1

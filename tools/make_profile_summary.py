@@ -27,14 +27,14 @@ for name, gx, wx, d in load_rows(trace):
     g[k][0] += d; g[k][1] += 1; byk[n][0] += d; byk[n][1] += 1; tot += d
 line = json.load(open(linef))
 out = []
-out.append(f"# Round {int(TAG[1:])} — rocprofv3 --kernel-trace --stats of `python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-vp3d --no-fp8 --no-parity-mode --no-other-prec` (timed mode: {line['dtype']})\n")
+out.append(f"# Round {int(TAG[1:])} — rocprofv3 --kernel-trace --stats of `python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-vp3d --no-fp8 --no-parity-mode --no-other-prec` (timed mode: {line['dtype']})\n")
 out.append(f"MI355X (gfx950); {NS} batch forwards in the trace (1 one-stream preparation, then 1 warm-up and 2 timed steps of 2 concurrent batches each, `--streams 2`); one batch = 4 time steps x 8 views x 518x518 (`--batch 4`), all four heads (17 query points per step).")
 out.append(f"Total kernel time {tot/1e6:.1f} ms = {tot/NS/1e6:.1f} ms per batch (summed kernel durations: with two batches in flight kernels of the two streams share the chip, so this is more than the wall time; includes the one-off weight upload / synthetic-weight kernels of the first forward).\n")
 out.append("| kernel | ms / batch | % | calls / batch | avg us |\n|---|---:|---:|---:|---:|")
 for n, v in sorted(byk.items(), key=lambda kv: -kv[1][0])[:24]:
     out.append(f"| `{n[:90]}` | {v[0]/NS/1e6:.2f} | {100*v[0]/tot:.1f} | {v[1]/NS:.0f} | {v[0]/v[1]/1e3:.1f} |")
 rf = line['roofline']
-out.append("\nUn-profiled bench line of the same build (`profiles/" + TAG + "_bench_line.json`, full default run incl. the CPU legs):")
+out.append("\nUn-profiled bench line of the same build (`profiles/" + TAG + "_bench_line.json`, a `bench.py --full` run incl. the CPU legs):")
 out.append(f"- value {line['value']:.2f} frames/s, {line['ms_per_step']:.1f} ms/step (one step = {line['config'].get('streams', 1)} concurrent batches of 4 time steps), whole path {line['whole_path_tflops']:.0f} TFLOP/s")
 one = rf.get('one_stream')
 if one:
