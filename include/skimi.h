@@ -464,6 +464,32 @@ int skimi_icp_point_to_plane(const float* src, int64_t n_src, const float* tgt, 
                              const double* init4x4, double* T_out, double* fitness_out, double* rmse_out,
                              int32_t* iterations_out, void* ws, size_t ws_bytes, void* stream);
 
+/* Bundle adjustment of one clip (run_local_ba, called at vggt/multi_view_process.py:553-564 and defined nowhere in the
+ * reference): Adam (torch defaults) on the sum of the five losses of bundle_adjustment/loss.py, all in float64.
+ * Inputs (dev f64): K [C,3,3], R0 [T,C,3,3], t0 [T,C,3] (world -> camera), X0 [T,J,3], x2d [T,C,J,2] pixels,
+ * conf [T,C,J]; 1 <= C <= 8, 1 <= J <= 32, 1 <= T <= 2^20.  modes (host i32 [n_modes], 1..8 problems over the same
+ * clip, one workgroup each): SKIMI_BA_POSE_ONLY optimises X, SKIMI_BA_POSE_CAM_T X and t, SKIMI_BA_FULL X, t and
+ * w [T,C,3] with R = Exp(w) R0, w = 0 at the start.  Weights: reprojection, camera smoothness, baseline, bone length,
+ * pose temporal.  Outputs (dev f64, problem-major): R_out [n_modes,T,C,3,3], t_out [n_modes,T,C,3],
+ * X_out [n_modes,T,J,3]; a block a mode does not optimise is its input, bitwise.  history_out (NULL allowed):
+ * [n_modes, num_iters, 6] = total, then the five weighted terms, row i at the iterate before step i+1.
+ * placement: SKIMI_BA_AUTO keeps each problem's state and scratch in LDS when it fits, else in ws; _LDS / _WORKSPACE
+ * force one (results are bitwise the same).  ws: at least skimi_ba_workspace_bytes(T, C, J, n_modes) bytes (unused
+ * when the state is in LDS).  One launch, no synchronisation, no allocation; sums have a fixed order, so results are
+ * bitwise reproducible.  Rules: DESIGN §2 "BA". */
+#define SKIMI_BA_POSE_ONLY 0
+#define SKIMI_BA_POSE_CAM_T 1
+#define SKIMI_BA_FULL 2
+#define SKIMI_BA_AUTO 0
+#define SKIMI_BA_LDS 1
+#define SKIMI_BA_WORKSPACE 2
+size_t skimi_ba_workspace_bytes(int64_t T, int32_t C, int32_t J, int32_t modes);
+int skimi_bundle_adjust(const double* K, const double* R0, const double* t0, const double* X0, const double* x2d,
+                        const double* conf, int64_t T, int32_t C, int32_t J, const int32_t* modes, int32_t n_modes,
+                        int32_t num_iters, double lr, double w_reproj, double w_smooth, double w_baseline,
+                        double w_bone_length, double w_pose_temporal, int32_t placement, double* R_out, double* t_out,
+                        double* X_out, double* history_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

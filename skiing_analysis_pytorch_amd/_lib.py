@@ -113,6 +113,10 @@ _SIGNATURES = {
     "skimi_icp_point_to_plane": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_double,
                                            C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                            C.POINTER(C.c_double), C.POINTER(C.c_int32), _vp, C.c_size_t, _vp]),
+    "skimi_ba_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "skimi_bundle_adjust": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                      C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                      C.c_double, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "skimi_vggt_create": (_vp, [_vp]),
     "skimi_vggt_destroy": (None, [_vp]),
     "skimi_vggt_set_weight": (C.c_int, [_vp, C.c_char_p, _vp, C.c_int64, C.c_int32]),

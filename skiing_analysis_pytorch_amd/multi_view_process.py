@@ -17,9 +17,18 @@ then holds the refined R, t and x3d, as the reference's does, with icp_refined=T
 the arrays are then the pre-ICP quantities under the same keys, with icp_refined=False.  Parity with Open3D
 itself is "unpinned" (DESIGN §2 "ICP": tie, eigensolver and non-finite-point rules of this build).
 
+With `cfg.infer.ba` true it also runs the clip-level bundle adjustment that the reference defines but leaves
+commented out (:321-353): after the all-gather, on rank 0, the gathered joints / R / t (after ICP when that is on),
+the time-mean K (:543), the keypoints and their scores go through geometry.bundle_adjust (one HIP launch for every
+mode of cfg.bundle_adjustment.mode, all three when it is absent, as the commented loop at :338 does) and the NPZ
+gains ba_<mode>_x3d / _R / _t / _history.  `run_local_ba` is the function its caller names (:553-564), which the
+reference never defines; its parity is unpinned beyond bundle_adjustment/loss.py (DESIGN §2 "BA").  The reference's
+own `run_ba` key is not read: it ships true while the reference never runs BA.  Flag off (the default): the NPZ is
+unchanged.
+
 What it leaves out (out of scope): video decode (frames come from the `.pt` files, which
 `prepare_dataset` can embed; the video paths only name the subject), PNG / GLB / matplotlib output and the
-commented-out bundle adjustment.  The time steps are independent: they go through the HIP model `steps_per_call` at a
+bundle adjustment's images (:566-627).  The time steps are independent: they go through the HIP model `steps_per_call` at a
 time, sharded over ranks under torch.distributed, and the per-step joints are re-assembled with one
 all-gather (parallel.py).
 """
@@ -109,6 +118,44 @@ def apply_icp_update(R: np.ndarray, t: np.ndarray, T: np.ndarray):
     return R, t
 
 
+def ba_settings(cfg):
+    """cfg.bundle_adjustment -> (modes, num_iters, lr, weights) as the reference's caller reads them (:338, :560-561):
+    `mode` a string or a list (absent: all three modes), num_iters 200 and lr 1e-3 when absent, and the ba_weight_*
+    keys that are present (an absent one takes its loss.py default in geometry.bundle_adjust)."""
+    mode = cfg_get(cfg, "bundle_adjustment.mode", None)
+    if mode is None:
+        modes = list(geometry.BA_MODES)
+    elif isinstance(mode, str):
+        modes = [mode]
+    else:
+        modes = [str(m) for m in mode]
+    bad = [m for m in modes if m not in geometry.BA_MODES]
+    if bad or not modes:
+        raise ValueError(f"cfg.bundle_adjustment.mode: unknown modes {bad or modes}; known: {list(geometry.BA_MODES)}")
+    num_iters = int(cfg_get(cfg, "bundle_adjustment.num_iters", 200))
+    lr = float(cfg_get(cfg, "bundle_adjustment.lr", 1e-3))
+    weights = {}
+    for key in geometry.BA_WEIGHT_KEYS:
+        v = cfg_get(cfg, f"bundle_adjustment.{key}", None)
+        if v is not None:
+            weights[key] = float(v)
+    return modes, num_iters, lr, weights
+
+
+def run_local_ba(K_torch, R_init_torch, t_init_torch, X3d_init_torch, x2d_torch, conf2d_torch, num_iters: int = 200,
+                 lr: float = 1e-3, device="cuda", mode: str = "pose_only", weights=None):
+    """The function the reference's bundle_adjustment() calls (:553-564) and never defines: K (C,3,3), R (T,C,3,3),
+    t (T,C,3), X (T,J,3), x2d (T,C,J,2), conf (T,C,J) -> (R_opt, t_opt, X_opt, history) as float64 tensors on `device`
+    (history [num_iters, 6]: total, then the five weighted terms).  One HIP launch (geometry.bundle_adjust)."""
+    dev = torch.device(device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    with torch.cuda.device(dev):
+        r = geometry.bundle_adjust(K_torch, R_init_torch, t_init_torch, X3d_init_torch, x2d_torch, conf2d_torch, modes=(mode,),
+                                   num_iters=num_iters, lr=lr, weights=weights)[0]
+    return r.R, r.t, r.X, r.history
+
+
 def _bbox_of(bboxes: np.ndarray, idx: int):
     b = bboxes[idx]
     return b if b.ndim == 1 else b[0]
@@ -128,8 +175,8 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
     inference_output_path.mkdir(parents=True, exist_ok=True)
     logger.info(f"[Run-MV] {left_video_path} & {right_video_path} -> {out_dir} | ")
 
-    lk, _ls, lb, _lbs, lf = formats.load_info(left_pt_path, video_file_path=left_video_path, assume_normalized=False)
-    rk, _rs, rb, _rbs, rf = formats.load_info(right_pt_path, video_file_path=right_video_path, assume_normalized=False)
+    lk, ls, lb, _lbs, lf = formats.load_info(left_pt_path, video_file_path=left_video_path, assume_normalized=False)
+    rk, rs, rb, _rbs, rf = formats.load_info(right_pt_path, video_file_path=right_video_path, assume_normalized=False)
     for frames_, pt_, vid_ in ((lf, left_pt_path, left_video_path), (rf, right_pt_path, right_video_path)):
         if frames_ is None:
             raise RuntimeError(f"{pt_} embeds no frames and {vid_} cannot be decoded here (formats.read_video_frames)")
@@ -149,6 +196,7 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
     lo, hi, _T_pad = parallel.shard_range(T)
     source_size = tuple(lf.shape[1:3])
     icp = bool(cfg_get(cfg, "infer.icp", False))
+    ba = bool(cfg_get(cfg, "infer.ba", False))
     x3d_l, K_l, R_l, t_l, C_l = [], [], [], [], []
     for a in range(lo, hi, steps_per_call):
         idx = [min(i, T - 1) for i in range(a, min(a + steps_per_call, hi))]     # padded steps repeat the last one
@@ -191,8 +239,20 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
         # infer.icp off (the default) the arrays are the pre-ICP quantities under the same keys, icp_refined = False
         if not icp:
             logger.warning("[Run-MV] cameras / joints are written without the reference's Open3D ICP refinement (icp_refined=False)")
+        extra = {"icp_refined": np.array(icp)} | ({"x3d_smoothed": x3d_smoothed} if x3d_smoothed is not None else {})
+        if ba:   # the reference's commented-out stage (:321-353), every mode in one launch
+            modes, num_iters, lr, weights = ba_settings(cfg)
+            x2d = np.stack([np.stack([lk[i], rk[i]]) for i in range(T)]).astype(np.float64)     # (T,C,J,2)
+            conf = np.stack([np.stack([ls[i], rs[i]]) for i in range(T)]).astype(np.float64)    # (T,C,J)
+            with torch.cuda.device(dev):
+                res = geometry.bundle_adjust(Ka.astype(np.float64).mean(0), Ra, ta, x3d, x2d, conf, modes=modes,
+                                             num_iters=num_iters, lr=lr, weights=weights)
+            for r in res:
+                extra[f"ba_{r.mode}_x3d"] = r.X.cpu().numpy()
+                extra[f"ba_{r.mode}_R"] = r.R.cpu().numpy()
+                extra[f"ba_{r.mode}_t"] = r.t.cpu().numpy()
+                extra[f"ba_{r.mode}_history"] = r.history.cpu().numpy()
         save_camera_info(out_pt_path=inference_output_path / f"{subject}_multi_view_3d_info.npz",
                          all_frame_x3d=list(x3d), all_frame_camera_intrinsics=list(Ka), all_frame_R=list(Ra),
-                         all_frame_t=list(ta), all_frame_C=list(Ca),
-                         extra={"icp_refined": np.array(icp)} | ({"x3d_smoothed": x3d_smoothed} if x3d_smoothed is not None else {}))
+                         all_frame_t=list(ta), all_frame_C=list(Ca), extra=extra)
     return out_dir

@@ -382,6 +382,116 @@ def gen_formats():
 GENERATORS["formats"] = gen_formats
 
 
+def _ba_clip(T, C, J, seed):
+    """A synthetic clip: C cameras on a ring looking at a person near the origin, keypoints = projections + noise."""
+    rng = np.random.default_rng(seed)
+    K = np.zeros((C, 3, 3))
+    K[:, 0, 0], K[:, 1, 1] = rng.uniform(900, 1100, C), rng.uniform(900, 1100, C)
+    K[:, 0, 2], K[:, 1, 2], K[:, 2, 2] = 960 + rng.normal(0, 5, C), 540 + rng.normal(0, 5, C), 1.0
+    R, t = np.zeros((T, C, 3, 3)), np.zeros((T, C, 3))
+    for c in range(C):
+        a = 2 * np.pi * c / C + 0.3
+        ctr = np.array([4 * np.sin(a), -0.3, -4 * np.cos(a)])      # camera centre on the ring
+        z = -ctr / np.linalg.norm(ctr)
+        x = np.cross([0.0, 1.0, 0.0], z)
+        x /= np.linalg.norm(x)
+        Rc = np.stack([x, np.cross(z, x), z])
+        for s in range(T):
+            ang = rng.normal(0, 0.01, 3)
+            th = np.linalg.norm(ang)
+            Kx = np.array([[0, -ang[2], ang[1]], [ang[2], 0, -ang[0]], [-ang[1], ang[0], 0]])
+            dR = np.eye(3) + np.sin(th) / th * Kx + (1 - np.cos(th)) / th**2 * Kx @ Kx
+            R[s, c] = dR @ Rc
+            t[s, c] = -R[s, c] @ (ctr + rng.normal(0, 0.02, 3))
+    X = rng.normal(0, 0.4, (J, 3)) + np.cumsum(rng.normal(0, 0.01, (T, J, 3)), 0)
+    Xc = np.einsum("tcij,tkj->tcki", R, X) + t[:, :, None]
+    x2d = np.einsum("cij,tckj->tcki", K, Xc / Xc[..., 2:3])[..., :2] + rng.normal(0, 2.0, (T, C, J, 2))
+    conf = rng.uniform(0.3, 1.0, (T, C, J))
+    Xn = X + rng.normal(0, 0.02, X.shape)
+    return K, R, t, Xn, x2d, conf
+
+
+def _ba_rodrigues(w):
+    s = (w * w).sum(-1)[..., None, None]
+    small = s < 1e-8
+    s_safe = torch.where(small, torch.ones_like(s), s)
+    th = torch.sqrt(s_safe)
+    A = torch.where(small, 1.0 - s / 6.0 + s * s / 120.0, torch.sin(th) / th)
+    B = torch.where(small, 0.5 - s / 24.0 + s * s / 720.0, (1.0 - torch.cos(th)) / s_safe)
+    z = torch.zeros_like(w[..., 0])
+    Kx = torch.stack([torch.stack([z, -w[..., 2], w[..., 1]], -1), torch.stack([w[..., 2], z, -w[..., 0]], -1),
+                      torch.stack([-w[..., 1], w[..., 0], z], -1)], -2)
+    return torch.eye(3, dtype=w.dtype) + A * Kx + B * (Kx @ Kx)
+
+
+def gen_ba():
+    """DESIGN §2 "BA": the reference's OWN losses (bundle_adjustment/loss.py, imported by file spec: it needs only
+    torch) on two synthetic clips -- each term's value and the autograd gradients of their sum w.r.t. X, R (the matrix)
+    and t -- and a 50-step trajectory per mode: those losses, the w wrapper of mode full (R = Exp(w) R0) and
+    torch.optim.Adam, as run_local_ba (called at vggt/multi_view_process.py:553-564, defined nowhere) would run them."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("ref_ba_loss", os.path.join(REF, "bundle_adjustment", "loss.py"))
+    L = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(L)
+
+    def terms(X, R, t, K, x2d, conf, w=None):
+        w = w or {}
+        return [L.reprojection_loss(X, R, t, K, x2d, conf, **({"w": w["ba_weight_reproj"]} if w else {})),
+                L.camera_smooth_loss(R, t, **({"w": w["ba_weight_smooth"]} if w else {})),
+                L.baseline_reg_loss(R, t, **({"w": w["ba_weight_baseline"]} if w else {})),
+                L.bone_length_loss(X, **({"w": w["ba_weight_bone_length"]} if w else {})),
+                L.pose_temporal_loss(X, **({"w": w["ba_weight_pose_temporal"]} if w else {}))]
+
+    out = {}
+    with torch.enable_grad():
+        for name, (T, C, J, seed) in {"a": (8, 2, 17, 41), "b": (2, 3, 12, 42)}.items():
+            K, R, t, X, x2d, conf = _ba_clip(T, C, J, seed)
+            if name == "b":
+                X[1, 3] = -(R[1, 2].T @ t[1, 2]) - 0.1 * R[1, 2][2]    # joint 3 of step 1 behind camera 2 (Z clamp)
+                conf[:, :, 4] = 0.0                                      # joint 4: conf 0 in every view
+            Xt, Rt, tt = (torch.tensor(a, requires_grad=True) for a in (X, R, t))
+            tm = terms(Xt, Rt, tt, torch.tensor(K), torch.tensor(x2d), torch.tensor(conf))
+            total = tm[0] + tm[1] + tm[2] + tm[3] + tm[4]
+            gX, gR, gt = torch.autograd.grad(total, (Xt, Rt, tt))
+            for k, v in dict(K=K, R=R, t=t, X=X, x2d=x2d, conf=conf).items():
+                out[f"{name}_{k}"] = v
+            out[f"{name}_terms"] = np.array([float(v.detach()) for v in tm])
+            out[f"{name}_gX"], out[f"{name}_gR"], out[f"{name}_gt"] = gX.numpy(), gR.numpy(), gt.numpy()
+        # trajectories on clip a with the configured weights of configs/vggt.yaml:43-51 and lr 1e-2
+        wcfg = {"ba_weight_reproj": 1.0, "ba_weight_smooth": 0.1, "ba_weight_baseline": 0.01,
+                "ba_weight_bone_length": 0.1, "ba_weight_pose_temporal": 0.1}
+        out["traj_weights"] = np.array(list(wcfg.values()))
+        out["traj_lr"], out["traj_steps"] = np.array(1e-2), np.array(50)
+        Kt, x2dt, conft = (torch.tensor(out[f"a_{k}"]) for k in ("K", "x2d", "conf"))
+        R0 = torch.tensor(out["a_R"])
+        for mode in ("pose_only", "pose_cam_t", "full"):
+            X = torch.tensor(out["a_X"], requires_grad=True)
+            t = torch.tensor(out["a_t"], requires_grad=mode != "pose_only")
+            w = torch.zeros_like(t, requires_grad=mode == "full")
+            params = [X] + ([t] if mode != "pose_only" else []) + ([w] if mode == "full" else [])
+            opt = torch.optim.Adam(params, lr=1e-2)
+            hist = []
+            for _ in range(50):
+                opt.zero_grad()
+                R = _ba_rodrigues(w) @ R0 if mode == "full" else R0
+                tm = terms(X, R, t, Kt, x2dt, conft, wcfg)
+                loss = tm[0] + tm[1] + tm[2] + tm[3] + tm[4]
+                hist.append([float(loss.detach())] + [float(v.detach()) for v in tm])
+                loss.backward()
+                opt.step()
+            with torch.no_grad():
+                R = _ba_rodrigues(w) @ R0 if mode == "full" else R0
+            out[f"traj_{mode}_X"], out[f"traj_{mode}_t"] = X.detach().numpy(), t.detach().numpy()
+            out[f"traj_{mode}_R"], out[f"traj_{mode}_history"] = R.detach().numpy(), np.array(hist)
+    path = GOLD / "ba_losses.npz"
+    np.savez_compressed(path, **out)
+    print("wrote", path.name, path.stat().st_size, "bytes")
+
+
+GENERATORS["ba"] = gen_ba
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GENERATORS)
     for w in which:
