@@ -189,7 +189,7 @@ int skimi_gemm(const skimi_gemm_desc* d, void* stream);
  *   bits  0- 3  family: SKIMI_GEMM_PATH_*
  *   bits  4- 7  generic: tile (1 = 64x64, 2 = 128x64, 3 = 128x128);
  *               gemm256: main loop (1 = two-phase 256 rows, 2 = two-phase 192 rows, 3 = ping-pong, 4 = single-stream)
- *   bits  8-11  gemm256: MFMA shape (1 = v_mfma_f32_16x16x32, 2 = v_mfma_f32_32x32x16); 0 elsewhere
+ *   bits  8-11  gemm256, x3dma: MFMA shape (1 = v_mfma_f32_16x16x32, 2 = v_mfma_f32_32x32x16); 0 elsewhere
  *   bits 12-15  gemm256: compile-time epilogue (0 = shared epilogue, 1 bias -> 16-bit, 2 LayerScale + residual,
  *               3 bias + GELU -> 16-bit); 0 elsewhere
  *   bits 16-23  K splits (1 = no split-K) */

@@ -128,9 +128,24 @@ struct X3Rec {
     } while (0)
 #define SKIMI_X3_VMCNT(N) __builtin_amdgcn_s_waitcnt(0x0F70 | ((N) & 15) | (((N) >> 4) << 14))
 
-template <int AMODE, int ABL = 0>   // a_mode of the launch (0 plain rows, 1 tap-major, 2 slice-major gather), compile-time:
-                      // the K-tile body must stay one straight-line scheduling region.  ABL: timing
-                      // ablations (bit 0 no staging, bit 1 no fragment reads, bit 2 no MFMAs)
+//
+// M16 (SKIMI_X3_MFMA=16, the default): the quadrant is 8 x 8 tiles of 16x16 (256 accumulator registers again) and a
+// K-tile is ONE k-step of 32 = 192 v_mfma_f32_16x16x32_bf16, the same MFMA cycles: on this shape the chip holds a
+// higher clock (profiles/r04_peaks.json).  Operand map: row l & 15, 16-B chunk l >> 4 of the 64-B hi half (the
+// records' K-slice is exactly one k-step), lo chunk = hi ^ 64; the source swizzle is unchanged (16 consecutive rows
+// see chunk ^ 0..7 twice each: conflict-free).  Double-buffering a k-step's 32 fragments (128 VGPRs) next to 256
+// accumulators does not fit, so the K-tile runs as three 64-MFMA phases, term by term, and a fragment group (8
+// fragments = 32 VGPRs) is re-read as soon as its last phase is done:
+//   phase 1  AL.WH : lgkmcnt(0); read AH, WL of kt;  issue A pieces of kt+2   -> the slots K-tile kt-1's W left
+//   phase 2  AH.WH : lgkmcnt(0), vmcnt(8) = all of kt+1 landed, barrier (= K-tile kt released);
+//                    read AL of kt+1; issue W pieces of kt+2 -> K-tile kt's A slots
+//   phase 3  AH.WL : read WH of kt+1
+// so at most four groups (128 VGPRs) are live, and every accumulator sees its three MFMAs 64 instructions apart.  The
+// MFMAs are inline asm on AGPR-pinned accumulators, as in gemm256w4_kernel<.., M16> (gemm256.hip): the builtin makes
+// hipcc shuttle accumulators between the register files.
+template <int AMODE, int ABL = 0, bool M16 = false>   // a_mode of the launch (0 plain rows, 1 tap-major, 2 slice-major
+                      // gather), compile-time: the K-tile body must stay one straight-line scheduling region.  ABL:
+                      // timing ablations (bit 0 no staging, bit 1 no fragment reads, bit 2 no MFMAs)
 __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, const X3Rec pl) {
     constexpr int BM = 256, BN = 256, BK = 32, RB = 128, PIECE = 128 * RB, NSLOT = 10;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -188,7 +203,13 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
     // K-tiles are requested in order, so the (tap, channel slice) of the next one is kept as scalar
     // counters: no integer division in the loop
     int cur_tap = 0, cur_ky = 0, cur_kx = 0, cur_cs = 0;
-    auto issue_a = [&](int kt, int slot0, int slot1) {
+    // wave-uniform: base of the next K-tile's A records, the zero page seen from it, and its tap
+    struct ATile {
+        const char* base;
+        unsigned z;
+        int tap;
+    };
+    auto a_tile = [&](int kt) {
         const int tap = cur_tap, tap_dy = cur_ky * p.dil, tap_dx = cur_kx * p.dil;
         const int cs = AMODE == 0 ? kt : cur_cs;
         if (AMODE == 2) {          // slice-major K: the taps of a 32-channel slice are consecutive K-tiles
@@ -202,34 +223,158 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
                 if (++cur_kx == p.KW) { cur_kx = 0; ++cur_ky; }
             }
         }
-        // wave-uniform: base of this K-tile's records, and the zero page seen from it
-        if (ABL & 1) return;
         const long kbytes = ((long)tap_dy * p.cW + tap_dx) * pl.a_row_bytes + (long)cs * 128 - (AMODE != 0 ? pl.a_bias : 0);
         const char* base = pl.a + kbytes;
-        const unsigned z = (unsigned)(pl.zero - base);
+        return ATile{base, (unsigned)(pl.zero - base), tap};
+    };
+    // one staging instruction: rows 8 (4 wave + j) .. + 7 of A piece q (wave row q) / W piece q (wave column q)
+    auto dma_a = [&](const ATile& at, int q, int j, int slot) {
+        if (ABL & 1) return;
+        const bool ok = AMODE == 0 || ((a_ok[q][j] >> at.tap) & 1u) != 0;
+        const unsigned o = ok ? a_off[q][j] : at.z + ((lane & 7) << 4);
+        __builtin_amdgcn_global_load_lds((gbl_void*)(at.base + (size_t)o),
+                                         (lds_void*)(smem + slot * PIECE + (4 * wave + j) * 8 * RB), 16, 0, 0);
+    };
+    auto dma_w = [&](int kt, int q, int j, int slot) {
+        if (ABL & 1) return;
+        __builtin_amdgcn_global_load_lds((gbl_void*)(pl.w + (long)kt * 128 + (size_t)w_off[q][j]),
+                                         (lds_void*)(smem + slot * PIECE + (4 * wave + j) * 8 * RB), 16, 0, 0);
+    };
+    auto issue_a = [&](int kt, int slot0, int slot1) {
+        const ATile at = a_tile(kt);
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            char* dst = smem + (q == 0 ? slot0 : slot1) * PIECE + (4 * wave) * 8 * RB;
+        for (int q = 0; q < 2; ++q)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool ok = AMODE == 0 || ((a_ok[q][j] >> tap) & 1u) != 0;
-                const unsigned o = ok ? a_off[q][j] : z + ((lane & 7) << 4);
-                __builtin_amdgcn_global_load_lds((gbl_void*)(base + (size_t)o), (lds_void*)(dst + j * 8 * RB), 16, 0, 0);
-            }
-        }
+            for (int j = 0; j < 4; ++j) dma_a(at, q, j, q == 0 ? slot0 : slot1);
     };
     auto issue_w = [&](int kt, int slot0, int slot1) {
-        if (ABL & 1) return;
-        const char* base = pl.w + (long)kt * 128;
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            char* dst = smem + (q == 0 ? slot0 : slot1) * PIECE + (4 * wave) * 8 * RB;
+        for (int q = 0; q < 2; ++q)
 #pragma unroll
-            for (int j = 0; j < 4; ++j)
-                __builtin_amdgcn_global_load_lds((gbl_void*)(base + (size_t)w_off[q][j]), (lds_void*)(dst + j * 8 * RB), 16, 0, 0);
-        }
+            for (int j = 0; j < 4; ++j) dma_w(kt, q, j, q == 0 ? slot0 : slot1);
     };
     auto slot = [&](int x) { return x >= NSLOT ? x - NSLOT : x; };
+    // accumulators of this wave's quadrant: 32x32 tiles [row block i][column block j], or (M16) 16x16 tiles
+    // [16-column block j][16-row block i]
+    f32x16 acc[4][4];
+    f32x4 acc16[8][8];
+    // the epilogue's slab row pitch in floats: the 16x16 layout writes rows 4 (l >> 4) + r, four 16-lane groups 4 rows
+    // apart, which a 128-float pitch puts on the same banks; 132 moves them 16 banks apart
+    constexpr int SP = M16 ? 132 : 128;
+
+    if constexpr (M16) {
+    const int l15 = lane & 15;
+    const int off16 = l15 * RB + (((lane >> 4) ^ ((l15 >> 1) & 7)) << 4);   // hi chunk; the lo chunk is at ^ 64
+    bf16x8 ah[8], al[8], wh[8], wl[8];
+    if (ABL & 2) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const bf16x8 c = {(short)lane, 1, 2, 3, 4, 5, 6, 7};
+            ah[i] = al[i] = wh[i] = wl[i] = c;
+        }
+    }
+    // 16-row block i of this wave's A piece (W = false) or W piece (W = true) of the K-tile at slot sb, hi or lo half
+    auto rd = [&](int sb, bool W, bool lo, int i, bf16x8& f) {
+        if (ABL & 2) return;
+        const char* base = smem + slot(sb + (W ? 2 + wc : wr)) * PIECE + (off16 ^ (lo ? 64 : 0));
+        f = *reinterpret_cast<const bf16x8*>(base + i * 16 * RB);
+    };
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            acc16[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            asm volatile("" : "+a"(acc16[j][i]));
+        }
+    asm volatile("s_nop 1");   // v_accvgpr_write -> first MFMA reading it as C
+    // one phase: 64 MFMAs (column block outer), extra(g) placed after MFMA g (asm volatile + sched_barrier: source
+    // order = issue order)
+    auto phase = [&](const bf16x8 (&fa)[8], const bf16x8 (&fw)[8], auto&& extra) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                if (!(ABL & 4)) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc16[j][i]) : "v"(fa[i]), "v"(fw[j]));
+                extra(8 * j + i);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+    };
+
+    // prologue: K-tiles 0 and 1 whole, then AL and WH of K-tile 0
+    issue_a(0, 0, 1);
+    issue_w(0, 2, 3);
+    if (nkt > 1) {
+        issue_a(1, 4, 5);
+        issue_w(1, 6, 7);
+        SKIMI_X3_VMCNT(16);
+    } else {
+        SKIMI_X3_VMCNT(0);
+    }
+    SKIMI_X3_BAR();
+    int sb = 0;   // slot of piece 0 of K-tile kt
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        rd(sb, false, true, i, al[i]);
+        rd(sb, true, false, i, wh[i]);
+    }
+#define SKIMI_X3_HEAD()                       \
+    do {                                      \
+        __builtin_amdgcn_s_waitcnt(0xC07F);   \
+        __builtin_amdgcn_sched_barrier(0);    \
+    } while (0)
+    // one K-tile: the fragment reads go one behind each of a phase's first MFMAs, the 8 staging instructions one behind
+    // every second of the next 16.  N1 / N2: K-tiles kt+1 / kt+2 exist (literals; the last two K-tiles are peeled)
+#define SKIMI_X3_KTILE16(N1, N2)                                                                   \
+    do {                                                                                           \
+        const int nsb = slot(sb + 4), s8 = slot(sb + 8), s9 = slot(sb + 9), s1 = slot(sb + 1);     \
+        /* phase 1: AL.WH; read AH, WL of kt; A pieces of kt+2 */                                  \
+        SKIMI_X3_HEAD();                                                                           \
+        ATile at{};                                                                                \
+        if (N2) at = a_tile(kt + 2);                                                               \
+        phase(al, wh, [&](int g) {                                                                 \
+            if (g < 8) rd(sb, false, false, g, ah[g]);                                             \
+            else if (g < 16) rd(sb, true, true, g - 8, wl[g - 8]);                                 \
+            else if (N2 && g < 32 && (g & 1)) {                                                    \
+                const int d = (g - 16) >> 1;                                                       \
+                dma_a(at, d >> 2, d & 3, (d >> 2) ? s9 : s8);                                      \
+            }                                                                                      \
+        });                                                                                        \
+        /* phase 2: AH.WH; kt+1 landed, barrier; read AL of kt+1; W pieces of kt+2 */              \
+        SKIMI_X3_HEAD();                                                                           \
+        if (N1) {                                                                                  \
+            if (N2) SKIMI_X3_VMCNT(8); else SKIMI_X3_VMCNT(0);                                     \
+            SKIMI_X3_BAR();                                                                        \
+        }                                                                                          \
+        phase(ah, wh, [&](int g) {                                                                 \
+            if (N1 && g < 8) rd(nsb, false, true, g, al[g]);                                       \
+            else if (N2 && g >= 8 && g < 24 && (g & 1)) {                                          \
+                const int d = (g - 8) >> 1;                                                        \
+                dma_w(kt + 2, d >> 2, d & 3, (d >> 2) ? s1 : sb);                                  \
+            }                                                                                      \
+        });                                                                                        \
+        /* phase 3: AH.WL; read WH of kt+1 */                                                      \
+        phase(ah, wl, [&](int g) {                                                                 \
+            if (N1 && g < 8) rd(nsb, true, false, g, wh[g]);                                       \
+        });                                                                                        \
+        sb = nsb;                                                                                  \
+    } while (0)
+    int kt = 0;
+    for (; kt + 2 < nkt; ++kt) SKIMI_X3_KTILE16(true, true);
+    if (kt + 1 < nkt) {
+        SKIMI_X3_KTILE16(true, false);
+        ++kt;
+    }
+    SKIMI_X3_KTILE16(false, false);
+#undef SKIMI_X3_KTILE16
+#undef SKIMI_X3_HEAD
+    // 12 states: last MFMA's D -> the epilogue's v_accvgpr_read; the pins make every accumulator a value of THIS
+    // point, so that hipcc reads none of them out between the MFMAs
+    asm volatile("s_nop 7\n\ts_nop 4");
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) asm volatile("" : "+a"(acc16[j][i]));
+    } else {
 
     // ---- fragment reads: row block i of this wave's A piece / W piece, k-step s ----
     const int t = lh ^ ((l31 >> 1) & 7);
@@ -259,7 +404,6 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
         }
     };
 
-    f32x16 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -341,11 +485,36 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
 #undef SKIMI_X3_TAIL
 #undef SKIMI_X3_HEAD
 #undef SKIMI_X3_MFMA
+    }
     __builtin_amdgcn_s_waitcnt(0xC07F);
-    SKIMI_X3_BAR();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0..3
+    SKIMI_X3_BAR();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0..4
 
-    // ---- epilogue: per-wave 32-row x 128-column passes through a private 16-KiB LDS slab ----
-    float* stg = reinterpret_cast<float*>(smem) + wave * (32 * 128);
+    // ---- epilogue: per-wave 32-row x 128-column passes through a private LDS slab (row pitch SP) ----
+    float* stg = reinterpret_cast<float*>(smem) + wave * (32 * SP);
+    // pass i: the accumulators of rows 32 i .. + 31 of the quadrant -> the slab.  32x32: lane l holds column l & 31,
+    // rows 8 (r >> 2) + 4 (l >> 5) + (r & 3); 16x16: column l & 15, rows 4 (l >> 4) + r
+    auto to_slab = [&](int i) {
+        if constexpr (M16) {
+            const int l15 = lane & 15, lq = lane >> 4;
+            // pinned here, in each epilogue variant: otherwise hipcc reads all 256 accumulators out into VGPRs ahead of
+            // the variant switch, and spills
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int j = 0; j < 8; ++j) asm volatile("" : "+a"(acc16[j][2 * i + b]));
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int j = 0; j < 8; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) stg[(16 * b + 4 * lq + r) * SP + 16 * j + l15] = acc16[j][2 * i + b][r];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) stg[((r & 3) + 8 * (r >> 2) + 4 * lh) * SP + j * 32 + l31] = acc[i][j][r];
+        }
+    };
     const int n = n0 + wc * 128 + 4 * (lane & 31);
     // Interior tiles of the common case (fp32 rows, bias, ReLU before / after one fp32 residual): a
     // straight-line path, 8 rows of loads and stores in flight per lane (the checked loop below
@@ -373,15 +542,14 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
         };
 #define SKIMI_X3_EPI_PASS(HAS_RES, HAS_OUT, HAS_REC)                                                                                 \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                \
-        _Pragma("unroll") for (int j = 0; j < 4; ++j) _Pragma("unroll") for (int r = 0; r < 16; ++r)               \
-            stg[((r & 3) + 8 * (r >> 2) + 4 * lh) * 128 + j * 32 + l31] = acc[i][j][r];                           \
+        to_slab(i);                                                                                                \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                     \
         __builtin_amdgcn_s_waitcnt(0xC07F);                                                                        \
         _Pragma("unroll") for (int half = 0; half < 2; ++half) {                                                   \
             const long mrow = m0 + wr * 128 + i * 32 + half * 16 + lh;                                             \
             float4 v[8], rr[8], r2[8];                                                                             \
             _Pragma("unroll") for (int it = 0; it < 8; ++it)                                                       \
-                v[it] = *reinterpret_cast<const float4*>(&stg[(half * 16 + it * 2 + lh) * 128 + 4 * (lane & 31)]); \
+                v[it] = *reinterpret_cast<const float4*>(&stg[(half * 16 + it * 2 + lh) * SP + 4 * (lane & 31)]);  \
             if (HAS_RES) _Pragma("unroll") for (int it = 0; it < 8; ++it)                                          \
                 rr[it] = *reinterpret_cast<const float4*>(rs + res_row(mrow + it * 2) + n);                       \
             if (HAS_RES == 2) _Pragma("unroll") for (int it = 0; it < 8; ++it)                                     \
@@ -417,10 +585,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) stg[((r & 3) + 8 * (r >> 2) + 4 * lh) * 128 + j * 32 + l31] = acc[i][j][r];
+        to_slab(i);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_s_waitcnt(0xC07F);
 #pragma unroll 1
@@ -428,7 +593,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
             const int row_l = it * 2 + lh;
             const int m = m0 + wr * 128 + i * 32 + row_l;
             if (m >= p.M || n >= p.N) continue;
-            const float4 v = *reinterpret_cast<const float4*>(&stg[row_l * 128 + 4 * (lane & 31)]);
+            const float4 v = *reinterpret_cast<const float4*>(&stg[row_l * SP + 4 * (lane & 31)]);
             const RowMap rm = row_map(p, m);
             if (p.vec4) {
                 store_four(p, rm, n, v);
@@ -447,8 +612,9 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
 // owns 128 rows x 64 columns (4 x 2 MFMA tiles, 24 MFMAs and 12 fragment reads per k-step); a
 // K-tile is three pieces (A rows of wave row 0 / 1, the 128 W rows), the ring holds nine slots =
 // three whole K-tiles: K-tile kt+3 is requested into K-tile kt's slots right after the barrier that
-// releases them, so two K-tiles (96 KiB) are in flight while one is multiplied.
-template <int AMODE>
+// releases them, so two K-tiles (96 KiB) are in flight while one is multiplied.  M16: the three-phase K-tile of
+// gemm_x3w4_kernel on 8 x 4 tiles of 16x16.
+template <int AMODE, bool M16 = false>
 __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, const X3Rec pl) {
     constexpr int BM = 256, BN = 128, BK = 32, RB = 128, PIECE = 128 * RB, NSLOT = 9;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -505,8 +671,12 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
         w_off[j] = (unsigned)((long)min(n0 + row, p.N - 1) * pl.w_row_bytes + c * 16);
     }
     int cur_tap = 0, cur_ky = 0, cur_kx = 0, cur_cs = 0;
-    // all three pieces of K-tile kt -> slots s0 (A rows 0..127), s1 (A rows 128..255), s2 (W rows)
-    auto issue = [&](int kt, int s0, int s1, int s2) {
+    struct ATile {
+        const char* base;
+        unsigned z;
+        int tap;
+    };
+    auto a_tile = [&](int kt) {
         const int tap = cur_tap, tap_dy = cur_ky * p.dil, tap_dx = cur_kx * p.dil;
         const int cs = AMODE == 0 ? kt : cur_cs;
         if (AMODE == 2) {
@@ -522,24 +692,132 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
         }
         const long kbytes = ((long)tap_dy * p.cW + tap_dx) * pl.a_row_bytes + (long)cs * 128 - (AMODE != 0 ? pl.a_bias : 0);
         const char* base = pl.a + kbytes;
-        const unsigned z = (unsigned)(pl.zero - base);
+        return ATile{base, (unsigned)(pl.zero - base), tap};
+    };
+    auto dma_a = [&](const ATile& at, int q, int j, int slot) {
+        const bool ok = AMODE == 0 || ((a_ok[q][j] >> at.tap) & 1u) != 0;
+        const unsigned o = ok ? a_off[q][j] : at.z + ((lane & 7) << 4);
+        __builtin_amdgcn_global_load_lds((gbl_void*)(at.base + (size_t)o),
+                                         (lds_void*)(smem + slot * PIECE + (4 * wave + j) * 8 * RB), 16, 0, 0);
+    };
+    auto dma_w = [&](int kt, int j, int slot) {
+        __builtin_amdgcn_global_load_lds((gbl_void*)(pl.w + (long)kt * 128 + (size_t)w_off[j]),
+                                         (lds_void*)(smem + slot * PIECE + (4 * wave + j) * 8 * RB), 16, 0, 0);
+    };
+    // all three pieces of K-tile kt -> slots s0 (A rows 0..127), s1 (A rows 128..255), s2 (W rows)
+    auto issue = [&](int kt, int s0, int s1, int s2) {
+        const ATile at = a_tile(kt);
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            char* dst = smem + (q == 0 ? s0 : s1) * PIECE + (4 * wave) * 8 * RB;
+        for (int q = 0; q < 2; ++q)
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const bool ok = AMODE == 0 || ((a_ok[q][j] >> tap) & 1u) != 0;
-                const unsigned o = ok ? a_off[q][j] : z + ((lane & 7) << 4);
-                __builtin_amdgcn_global_load_lds((gbl_void*)(base + (size_t)o), (lds_void*)(dst + j * 8 * RB), 16, 0, 0);
-            }
-        }
-        const char* wbase = pl.w + (long)kt * 128;
-        char* dst = smem + s2 * PIECE + (4 * wave) * 8 * RB;
+            for (int j = 0; j < 4; ++j) dma_a(at, q, j, q == 0 ? s0 : s1);
 #pragma unroll
-        for (int j = 0; j < 4; ++j)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(wbase + (size_t)w_off[j]), (lds_void*)(dst + j * 8 * RB), 16, 0, 0);
+        for (int j = 0; j < 4; ++j) dma_w(kt, j, s2);
     };
     auto slot = [&](int x) { return x >= NSLOT ? x - NSLOT : x; };
+    // accumulators of this wave's 128 x 64: 32x32 tiles [row block i][column block j], or (M16) 16x16 tiles
+    // [16-column block j][16-row block i]
+    f32x16 acc[4][2];
+    f32x4 acc16[4][8];
+    constexpr int SP = M16 ? 68 : 64;   // slab row pitch in floats (see gemm_x3w4_kernel)
+
+    if constexpr (M16) {
+    // M16: the three-phase K-tile of gemm_x3w4_kernel on 8 x 4 tiles of 16x16 (96 MFMAs per K-tile, 12 + 8 + 4
+    // fragment reads); K-tile kt+3 goes out in phase 2, right after the barrier that releases K-tile kt's slots
+    const int l15 = lane & 15;
+    const int off16 = l15 * RB + (((lane >> 4) ^ ((l15 >> 1) & 7)) << 4);
+    bf16x8 ah[8], al[8], wh[4], wl[4];
+    auto rd_a = [&](int sb, bool lo, int i, bf16x8& f) {
+        f = *reinterpret_cast<const bf16x8*>(smem + slot(sb + wr) * PIECE + (off16 ^ (lo ? 64 : 0)) + i * 16 * RB);
+    };
+    auto rd_w = [&](int sb, bool lo, int j, bf16x8& f) {
+        f = *reinterpret_cast<const bf16x8*>(smem + slot(sb + 2) * PIECE + (off16 ^ (lo ? 64 : 0)) + (wc * 64 + j * 16) * RB);
+    };
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            acc16[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            asm volatile("" : "+a"(acc16[j][i]));
+        }
+    asm volatile("s_nop 1");
+    auto phase = [&](const bf16x8 (&fa)[8], const bf16x8 (&fw)[4], auto&& extra) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc16[j][i]) : "v"(fa[i]), "v"(fw[j]));
+                extra(8 * j + i);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+    };
+
+    issue(0, 0, 1, 2);
+    if (nkt > 1) issue(1, 3, 4, 5);
+    if (nkt > 2) issue(2, 6, 7, 8);
+    if (nkt > 2) SKIMI_X3_VMCNT(24); else if (nkt > 1) SKIMI_X3_VMCNT(12); else SKIMI_X3_VMCNT(0);
+    SKIMI_X3_BAR();
+    int sb = 0;   // slot of piece 0 of K-tile kt
+#pragma unroll
+    for (int i = 0; i < 8; ++i) rd_a(sb, true, i, al[i]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) rd_w(sb, false, j, wh[j]);
+#define SKIMI_X3N_HEAD()                      \
+    do {                                      \
+        __builtin_amdgcn_s_waitcnt(0xC07F);   \
+        __builtin_amdgcn_sched_barrier(0);    \
+    } while (0)
+    // N1 / N2 / N3: K-tiles kt+1 / kt+2 / kt+3 exist (literals; the last three K-tiles are peeled)
+#define SKIMI_X3N_KTILE16(N1, N2, N3)                                                              \
+    do {                                                                                           \
+        const int nsb = slot(sb + 3), s1 = slot(sb + 1), s2 = slot(sb + 2);                        \
+        /* phase 1: AL.WH; read AH, WL of kt */                                                    \
+        SKIMI_X3N_HEAD();                                                                          \
+        phase(al, wh, [&](int g) {                                                                 \
+            if (g < 8) rd_a(sb, false, g, ah[g]);                                                  \
+            else if (g < 12) rd_w(sb, true, g - 8, wl[g - 8]);                                     \
+        });                                                                                        \
+        /* phase 2: AH.WH; kt+1 landed, barrier; read AL of kt+1; K-tile kt+3 -> kt's slots */     \
+        SKIMI_X3N_HEAD();                                                                          \
+        ATile at{};                                                                                \
+        if (N1) {                                                                                  \
+            if (N2) SKIMI_X3_VMCNT(12); else SKIMI_X3_VMCNT(0);                                    \
+            SKIMI_X3_BAR();                                                                        \
+            if (N3) at = a_tile(kt + 3);                                                           \
+        }                                                                                          \
+        phase(ah, wh, [&](int g) {                                                                 \
+            if (N1 && g < 8) rd_a(nsb, true, g, al[g]);                                            \
+            else if (N3 && g >= 8 && (g & 1)) {                                                    \
+                const int d = (g - 8) >> 1;                                                        \
+                if (d < 8) dma_a(at, d >> 2, d & 3, (d >> 2) ? s1 : sb);                           \
+                else dma_w(kt + 3, d - 8, s2);                                                     \
+            }                                                                                      \
+        });                                                                                        \
+        /* phase 3: AH.WL; read WH of kt+1 */                                                      \
+        phase(ah, wl, [&](int g) {                                                                 \
+            if (N1 && g < 4) rd_w(nsb, false, g, wh[g]);                                           \
+        });                                                                                        \
+        sb = nsb;                                                                                  \
+    } while (0)
+    int kt = 0;
+    for (; kt + 3 < nkt; ++kt) SKIMI_X3N_KTILE16(true, true, true);
+    if (kt + 2 < nkt) {
+        SKIMI_X3N_KTILE16(true, true, false);
+        ++kt;
+    }
+    if (kt + 1 < nkt) {
+        SKIMI_X3N_KTILE16(true, false, false);
+        ++kt;
+    }
+    SKIMI_X3N_KTILE16(false, false, false);
+#undef SKIMI_X3N_KTILE16
+#undef SKIMI_X3N_HEAD
+    asm volatile("s_nop 7\n\ts_nop 4");
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) asm volatile("" : "+a"(acc16[j][i]));
+    } else {
 
     // ---- fragment reads ----
     const int t = lh ^ ((l31 >> 1) & 7);
@@ -561,7 +839,6 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
         }
     };
 
-    f32x16 acc[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -641,11 +918,32 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
 #undef SKIMI_X3N_TAIL
 #undef SKIMI_X3N_HEAD
 #undef SKIMI_X3N_MFMA
+    }
     __builtin_amdgcn_s_waitcnt(0xC07F);
-    SKIMI_X3_BAR();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0, 1
+    SKIMI_X3_BAR();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0..2
 
-    // ---- epilogue: per-wave 32-row x 64-column passes through a private 8-KiB LDS slab ----
-    float* stg = reinterpret_cast<float*>(smem) + wave * (32 * 64);
+    // ---- epilogue: per-wave 32-row x 64-column passes through a private LDS slab (row pitch SP) ----
+    float* stg = reinterpret_cast<float*>(smem) + wave * (32 * SP);
+    auto to_slab = [&](int i) {
+        if constexpr (M16) {
+            const int l15 = lane & 15, lq = lane >> 4;
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) asm volatile("" : "+a"(acc16[j][2 * i + b]));
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) stg[(16 * b + 4 * lq + r) * SP + 16 * j + l15] = acc16[j][2 * i + b][r];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) stg[((r & 3) + 8 * (r >> 2) + 4 * lh) * SP + j * 32 + l31] = acc[i][j][r];
+        }
+    };
     const int n = n0 + wc * 64 + 4 * (lane & 15);
     const bool relu_ok = (p.act == SKIMI_ACT_NONE || p.act == SKIMI_ACT_RELU) &&
                          (p.post_act == SKIMI_ACT_NONE || p.post_act == SKIMI_ACT_RELU);
@@ -669,14 +967,13 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
         };
 #define SKIMI_X3N_EPI_PASS(HAS_RES, HAS_OUT, HAS_REC)                                                                                \
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                \
-        _Pragma("unroll") for (int j = 0; j < 2; ++j) _Pragma("unroll") for (int r = 0; r < 16; ++r)               \
-            stg[((r & 3) + 8 * (r >> 2) + 4 * lh) * 64 + j * 32 + l31] = acc[i][j][r];                            \
+        to_slab(i);                                                                                                \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                     \
         __builtin_amdgcn_s_waitcnt(0xC07F);                                                                        \
         const long mrow = m0 + wr * 128 + i * 32 + (lane >> 4);                                                    \
         float4 v[8], rr[8], r2[8];                                                                                 \
         _Pragma("unroll") for (int it = 0; it < 8; ++it)                                                           \
-            v[it] = *reinterpret_cast<const float4*>(&stg[(it * 4 + (lane >> 4)) * 64 + 4 * (lane & 15)]);         \
+            v[it] = *reinterpret_cast<const float4*>(&stg[(it * 4 + (lane >> 4)) * SP + 4 * (lane & 15)]);         \
         if (HAS_RES) _Pragma("unroll") for (int it = 0; it < 8; ++it)                                              \
             rr[it] = *reinterpret_cast<const float4*>(rs + res_row(mrow + it * 4) + n);                           \
         if (HAS_RES == 2) _Pragma("unroll") for (int it = 0; it < 8; ++it)                                         \
@@ -710,10 +1007,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) stg[((r & 3) + 8 * (r >> 2) + 4 * lh) * 64 + j * 32 + l31] = acc[i][j][r];
+        to_slab(i);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_s_waitcnt(0xC07F);
 #pragma unroll 1
@@ -721,7 +1015,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
             const int row_l = it * 4 + (lane >> 4);
             const int m = m0 + wr * 128 + i * 32 + row_l;
             if (m >= p.M || n >= p.N) continue;
-            const float4 v = *reinterpret_cast<const float4*>(&stg[row_l * 64 + 4 * (lane & 15)]);
+            const float4 v = *reinterpret_cast<const float4*>(&stg[row_l * SP + 4 * (lane & 15)]);
             const RowMap rm = row_map(p, m);
             if (p.vec4) {
                 store_four(p, rm, n, v);
@@ -777,28 +1071,47 @@ bool gemm_x3dma_eligible(const skimi_gemm_desc* d) {
     return d->M >= (min_tiles <= 1 ? 256 : 4096) && d->N >= 96 && tiles >= min_tiles;
 }
 
-template <int AMODE, int ABL = 0>
-static int launch_x3w4(GemmArgs& a, const X3Rec& pl, hipStream_t st) {
+template <int AMODE, int ABL = 0, bool M16 = false>
+static int launch_x3w4_(GemmArgs& a, const X3Rec& pl, hipStream_t st) {
     constexpr size_t lds = 10ull * 128 * 128;
-    SKIMI_LDS_OPT_IN((gemm_x3w4_kernel<AMODE, ABL>), lds, "gemm_x3w4");
+    SKIMI_LDS_OPT_IN((gemm_x3w4_kernel<AMODE, ABL, M16>), lds, "gemm_x3w4");
     a.ntm = (int)cdiv(a.M, 256);
     a.ntn = (int)cdiv(a.N, 256);
     a.splitk = 1;
-    hipLaunchKernelGGL((gemm_x3w4_kernel<AMODE, ABL>), dim3(a.ntm * a.ntn), dim3(256), lds, st, a, pl);
+    hipLaunchKernelGGL((gemm_x3w4_kernel<AMODE, ABL, M16>), dim3(a.ntm * a.ntn), dim3(256), lds, st, a, pl);
     SKIMI_LAUNCH_CHECK();
     return SKIMI_OK;
 }
 
-template <int AMODE>
-static int launch_x3w4n(GemmArgs& a, const X3Rec& pl, hipStream_t st) {
+template <int AMODE, bool M16 = false>
+static int launch_x3w4n_(GemmArgs& a, const X3Rec& pl, hipStream_t st) {
     constexpr size_t lds = 9ull * 128 * 128;
-    SKIMI_LDS_OPT_IN(gemm_x3w4n_kernel<AMODE>, lds, "gemm_x3w4n");
+    SKIMI_LDS_OPT_IN((gemm_x3w4n_kernel<AMODE, M16>), lds, "gemm_x3w4n");
     a.ntm = (int)cdiv(a.M, 256);
     a.ntn = (int)cdiv(a.N, 128);
     a.splitk = 1;
-    hipLaunchKernelGGL(gemm_x3w4n_kernel<AMODE>, dim3(a.ntm * a.ntn), dim3(256), lds, st, a, pl);
+    hipLaunchKernelGGL((gemm_x3w4n_kernel<AMODE, M16>), dim3(a.ntm * a.ntn), dim3(256), lds, st, a, pl);
     SKIMI_LAUNCH_CHECK();
     return SKIMI_OK;
+}
+
+// MFMA shape of both loops (SKIMI_X3_MFMA = 16 | 32): v_mfma_f32_16x16x32_bf16 by default; read once, or per launch
+// under SKIMI_ENV_DYNAMIC=1 (interleaved A/B timing in one process)
+static bool x3_m16() {
+    static const bool dyn = getenv("SKIMI_ENV_DYNAMIC") && atoi(getenv("SKIMI_ENV_DYNAMIC"));
+    static int shape = -1;
+    if (shape < 0 || dyn) shape = getenv("SKIMI_X3_MFMA") ? atoi(getenv("SKIMI_X3_MFMA")) : 16;
+    return shape != 32;
+}
+
+template <int AMODE, int ABL = 0>
+static int launch_x3w4(GemmArgs& a, const X3Rec& pl, hipStream_t st) {
+    return x3_m16() ? launch_x3w4_<AMODE, ABL, true>(a, pl, st) : launch_x3w4_<AMODE, ABL, false>(a, pl, st);
+}
+
+template <int AMODE>
+static int launch_x3w4n(GemmArgs& a, const X3Rec& pl, hipStream_t st) {
+    return x3_m16() ? launch_x3w4n_<AMODE, true>(a, pl, st) : launch_x3w4n_<AMODE, false>(a, pl, st);
 }
 
 // d->x3_scratch: the A records (4 bytes per element of the A buffer, rows padded to 32) + 256 zero bytes
@@ -822,7 +1135,7 @@ int gemm_x3dma_launch(GemmArgs& a, const skimi_gemm_desc* d, hipStream_t st) {
     pl.w_row_bytes = ((long)d->K + 31) / 32 * 32 * 4;
     pl.a_bias = d->a_mode == 0 ? 0 : ((long)d->pad * d->cW + d->pad) * pl.a_row_bytes;
     a.dbg = 0;
-    set_gemm_path(d->N <= 128 ? SKIMI_GEMM_PATH_X3DMA_NARROW : SKIMI_GEMM_PATH_X3DMA_WIDE, 0, 0, 0, 1);
+    set_gemm_path(d->N <= 128 ? SKIMI_GEMM_PATH_X3DMA_NARROW : SKIMI_GEMM_PATH_X3DMA_WIDE, 0, x3_m16() ? 1 : 2, 0, 1);
     if (d->N <= 128) {
         if (a.a_mode == 0) return launch_x3w4n<0>(a, pl, st);
         if (a.a_mode == 1) return launch_x3w4n<1>(a, pl, st);

@@ -131,7 +131,7 @@ class GemmPath(NamedTuple):
     family: Optional[str]   # generic | splitk_ordered | splitk_atomic | x3dma_wide | x3dma_narrow | gemm256 | conv_win
     tile: Optional[str]     # generic kernel: 64x64 | 128x64 | 128x128
     loop: Optional[str]     # gemm256: two_phase_256 | two_phase_192 | ping_pong | single_stream
-    mfma: Optional[int]     # gemm256: 16 (v_mfma_f32_16x16x32) | 32 (v_mfma_f32_32x32x16)
+    mfma: Optional[int]     # gemm256, x3dma: 16 (v_mfma_f32_16x16x32) | 32 (v_mfma_f32_32x32x16)
     epi: int                # gemm256: compile-time epilogue 0..3
     splitk: int             # K splits (1 = none)
     raw: int
