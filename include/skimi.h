@@ -318,10 +318,18 @@ uint64_t skimi_attention_x3_scratch_bytes(int64_t tokens, int64_t row_elems);
 /* ------------------------------------------------------------------------- */
 typedef struct skimi_vp3d skimi_vp3d;
 
-/* filter_widths: e.g. {3,3,3}; causal as TemporalModel(causal=...) */
+/* filter_widths: e.g. {3,3,3}; causal as TemporalModel(causal=...).  Same as
+ * skimi_vp3d_create_ex(..., dense = 0). */
 skimi_vp3d* skimi_vp3d_create(int32_t joints_in, int32_t in_features, int32_t joints_out,
                               const int32_t* filter_widths, int32_t n_widths,
                               int32_t channels, int32_t causal);
+/* dense as TemporalModel(dense=...) (model.py:113-116): block i's first conv has 2*pad_i + 1
+ * taps at dilation 1 instead of filter_widths[i] taps at dilation filter_widths[0]*..*[i-1];
+ * pad, causal shift, receptive field and output lengths are those of the dilated model, and
+ * "layers_conv.{2(i-1)}.weight" is [channels, channels, 2*pad_i + 1]. */
+skimi_vp3d* skimi_vp3d_create_ex(int32_t joints_in, int32_t in_features, int32_t joints_out,
+                                 const int32_t* filter_widths, int32_t n_widths,
+                                 int32_t channels, int32_t causal, int32_t dense);
 void skimi_vp3d_destroy(skimi_vp3d*);
 /* one state_dict entry, by its reference key name ("expand_conv.weight",
  * "layers_bn.0.running_var", "shrink.bias", ...; VideoPose3D/run.py:288-289).

@@ -97,6 +97,8 @@ _SIGNATURES = {
     "skimi_attention_x3_scratch_bytes": (C.c_uint64, [C.c_int64, C.c_int64]),
     "skimi_vp3d_create": (_vp, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                 C.c_int32, C.c_int32]),
+    "skimi_vp3d_create_ex": (_vp, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                   C.c_int32, C.c_int32, C.c_int32]),
     "skimi_vp3d_destroy": (None, [_vp]),
     "skimi_vp3d_set_weight": (C.c_int, [_vp, C.c_char_p, _vp, C.c_int64]),
     "skimi_vp3d_finalize": (C.c_int, [_vp, C.c_int32]),

@@ -89,5 +89,9 @@ int vp3d_expand_mfma_launch(const float* x, const void* wfrag, int Kpad, const f
 int vp3d_mm_launch(const void* wrec, int Npad, const void* xrec, const float* bias, const float* resid, int resid_L,
                    int resid_off, float* out_f32, int ldo, void* out_rec, int B, int Lin, int C, int taps, int dil, int N,
                    int relu, hipStream_t st);
+// vp3d_dense.hip: TemporalModel(dense=True)'s wide dilation-1 convs at small batch (the tap-reuse window kernel)
+bool vp3d_window_enabled();
+int vp3d_win_launch(const void* wrec, int Npad, const void* xrec, const float* bias, float* out_f32, int ldo, void* out_rec,
+                    int B, int Lin, int C, int taps, int N, hipStream_t st);
 
 }  // namespace skimi

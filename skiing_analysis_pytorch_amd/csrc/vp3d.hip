@@ -2,6 +2,7 @@
 // MFMA contractions on channels-last activations [B, L, C]:
 //   expand_conv(k) -> BN -> ReLU                    one GEMM over zero-padded windows (im2col of 34 ch)
 //   per block i: conv(k, dilation 3^i) -> BN -> ReLU  implicit-gather GEMM, K = k*C (tap-major)
+//                (dense=True, model.py:113-116: 2*pad_i + 1 taps at dilation 1 instead)
 //                conv1x1 -> BN -> ReLU, + res         GEMM with the residual slice fused in the epilogue
 //   shrink (1x1, bias)                              GEMM N = joints_out*3
 // Eval-mode BatchNorm is affine, so it is folded into the conv weight and bias once at finalize
@@ -29,6 +30,8 @@ struct skimi_vp3d {
     std::vector<int> pad;         // model.py:31,106
     std::vector<int> causal_shift;
     std::vector<int> dilation;    // dilation of block i's first conv (i >= 1)
+    std::vector<int> taps;        // taps of block i's first conv: fw[i], or 2 * pad[i] + 1 when dense (model.py:114-116)
+    int dense = 0;
     std::map<std::string, std::vector<float>> host;
     bool finalized = false;
     int prec = SKIMI_PREC_BF16X3;
@@ -75,9 +78,9 @@ static int upload(skimi_vp3d* h, const std::vector<float>& src, bool as_bf16, vo
 
 extern "C" {
 
-skimi_vp3d* skimi_vp3d_create(int32_t joints_in, int32_t in_features, int32_t joints_out,
-                              const int32_t* filter_widths, int32_t n_widths, int32_t channels,
-                              int32_t causal) {
+skimi_vp3d* skimi_vp3d_create_ex(int32_t joints_in, int32_t in_features, int32_t joints_out,
+                                 const int32_t* filter_widths, int32_t n_widths, int32_t channels,
+                                 int32_t causal, int32_t dense) {
     if (joints_in <= 0 || in_features <= 0 || joints_out <= 0 || !filter_widths || n_widths <= 0 ||
         channels <= 0 || channels % 64 != 0) {
         set_error("skimi_vp3d_create: bad arguments (channels must be a multiple of 64)");
@@ -100,14 +103,24 @@ skimi_vp3d* skimi_vp3d_create(int32_t joints_in, int32_t in_features, int32_t jo
     h->pad.push_back(h->fw[0] / 2);
     h->causal_shift.push_back(causal ? h->fw[0] / 2 : 0);
     h->dilation.push_back(1);
+    h->taps.push_back(h->fw[0]);
+    h->dense = dense ? 1 : 0;
     int next_dilation = h->fw[0];
     for (int i = 1; i < n_widths; ++i) {
         h->pad.push_back((h->fw[i] - 1) * next_dilation / 2);
         h->causal_shift.push_back(causal ? (h->fw[i] / 2) * next_dilation : 0);
-        h->dilation.push_back(next_dilation);
+        // dense: the same pad, shift and receptive field from 2 * pad + 1 taps at dilation 1
+        h->dilation.push_back(dense ? 1 : next_dilation);
+        h->taps.push_back(dense ? 2 * h->pad.back() + 1 : h->fw[i]);
         next_dilation *= h->fw[i];
     }
     return h;
+}
+
+skimi_vp3d* skimi_vp3d_create(int32_t joints_in, int32_t in_features, int32_t joints_out,
+                              const int32_t* filter_widths, int32_t n_widths, int32_t channels,
+                              int32_t causal) {
+    return skimi_vp3d_create_ex(joints_in, in_features, joints_out, filter_widths, n_widths, channels, causal, 0);
 }
 
 void skimi_vp3d_destroy(skimi_vp3d* h) {
@@ -246,15 +259,16 @@ int skimi_vp3d_finalize(skimi_vp3d* h, int32_t prec) {
         float* db;
         snprintf(cn, sizeof cn, "layers_conv.%zu", 2 * (i - 1));
         snprintf(bn, sizeof bn, "layers_bn.%zu", 2 * (i - 1));
-        if ((rc = fold(h, cn, bn, C, C, h->fw[i], h->fw[i] * C, &w, &b))) return rc;
+        const int k = h->taps[i];
+        if ((rc = fold(h, cn, bn, C, C, k, k * C, &w, &b))) return rc;
         if ((rc = upload(h, w, bf, &dw))) return rc;
         if ((rc = upload(h, b, false, (void**)&db))) return rc;
         h->w_conv.push_back(dw);
         h->b_conv.push_back(db);
-        if ((rc = add_records(h, dw, C, h->fw[i] * C, bf))) return rc;
+        if ((rc = add_records(h, dw, C, k * C, bf))) return rc;
         if (!bf && C % 32 == 0) {
             void* fr;
-            if ((rc = upload_frag(h, w, C, C, h->fw[i] * C, &fr))) return rc;
+            if ((rc = upload_frag(h, w, C, C, k * C, &fr))) return rc;
             h->w_frag.push_back(fr);
         }
         snprintf(cn, sizeof cn, "layers_conv.%zu", 2 * (i - 1) + 1);
@@ -356,12 +370,18 @@ int skimi_vp3d_forward(skimi_vp3d* h, const float* x, float* out, int32_t batch,
 #define SKIMI_VP3D_COUNT()
 #endif
             for (size_t i = 1; i < h->fw.size(); ++i) {
-                const int k = h->fw[i], dil = h->dilation[i];
+                const int k = h->taps[i], dil = h->dilation[i];
                 const int Lo = L - (k - 1) * dil;
                 SKIMI_CHECK_ARG(Lo > 0, "skimi_vp3d_forward: sequence too short");
-                // conv k, dilated (+ BN + ReLU): records in, records out
-                if ((rc = vp3d_mm_launch(h->w_frag[2 * (i - 1)], C, recX, h->b_conv[2 * (i - 1)], nullptr, 0, 0, nullptr, C, recY,
-                                         batch, L, C, k, dil, C, 1, st))) return rc;
+                // conv k, dilated (+ BN + ReLU): records in, records out.  A dense block's wide dilation-1 conv runs on
+                // the window kernel (vp3d_dense.hip; SKIMI_VP3D_WINDOW=0: the per-tap kernel, for A/B timing)
+                if (h->dense && k > 1 && vp3d_window_enabled())
+                    rc = vp3d_win_launch(h->w_frag[2 * (i - 1)], C, recX, h->b_conv[2 * (i - 1)], nullptr, C, recY, batch, L, C, k,
+                                         C, st);
+                else
+                    rc = vp3d_mm_launch(h->w_frag[2 * (i - 1)], C, recX, h->b_conv[2 * (i - 1)], nullptr, 0, 0, nullptr, C, recY,
+                                        batch, L, C, k, dil, C, 1, st);
+                if (rc) return rc;
                 SKIMI_VP3D_COUNT();
                 // conv 1x1 (+ BN + ReLU) + res = x[:, pad+shift : L-pad+shift] (model.py:129-135): the block's
                 // output as fp32 (residual of the next block) and as records (operand of the next layer)
@@ -399,7 +419,7 @@ int skimi_vp3d_forward(skimi_vp3d* h, const float* x, float* out, int32_t batch,
     if (chain) {
         int Lc = L0;
         for (size_t i = 1; i < h->fw.size() && chain; ++i) {
-            const int k = h->fw[i], dil = h->dilation[i];
+            const int k = h->taps[i], dil = h->dilation[i];
             const int Lo = Lc - (k - 1) * dil;
             skimi_gemm_desc q = d;
             char* fake = (char*)(uintptr_t)0x10000000;
@@ -428,7 +448,7 @@ int skimi_vp3d_forward(skimi_vp3d* h, const float* x, float* out, int32_t batch,
 
     int L = L0;   // frames held by bufX, per batch element
     for (size_t i = 1; i < h->fw.size(); ++i) {
-        const int k = h->fw[i], dil = h->dilation[i];
+        const int k = h->taps[i], dil = h->dilation[i];
         const int Lo = L - (k - 1) * dil;
         SKIMI_CHECK_ARG(Lo > 0, "skimi_vp3d_forward: sequence too short");
         // conv k, dilated: gather over the [B, 1, L, C] "image"

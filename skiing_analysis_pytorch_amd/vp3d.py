@@ -35,18 +35,17 @@ class TemporalModel:
                  channels=1024, dense=False, prec=PREC_BF16X3):
         for fw in filter_widths:
             assert fw % 2 != 0, "Only odd filter widths are supported"  # model.py:20-21
-        if dense:
-            raise NotImplementedError("dense=True (ablation, model.py:114-116) is not on the hot path")
         self.num_joints_in = num_joints_in
         self.in_features = in_features
         self.num_joints_out = num_joints_out
         self.filter_widths = list(filter_widths)
         self.causal = bool(causal)
+        self.dense = bool(dense)   # model.py:113-116: block i's first conv has 2 * pad_i + 1 taps at dilation 1
         self.channels = channels
         self.prec = prec
         fw = (C.c_int32 * len(filter_widths))(*filter_widths)
-        self._h = lib().skimi_vp3d_create(num_joints_in, in_features, num_joints_out, fw, len(filter_widths),
-                                          channels, int(causal))
+        self._h = lib().skimi_vp3d_create_ex(num_joints_in, in_features, num_joints_out, fw, len(filter_widths),
+                                             channels, int(causal), int(self.dense))
         if not self._h:
             raise _lib.SkimiError(lib().skimi_last_error().decode())
         # model.py:31,105-110 — kept on the host too: callers read .pad / .causal_shift
@@ -94,7 +93,7 @@ class TemporalModel:
         from .weights import vp3d_spec
 
         spec = vp3d_spec(self.num_joints_in, self.in_features, self.num_joints_out, self.filter_widths,
-                         self.channels)
+                         self.channels, dense=self.dense)
         missing = [k for k in spec if k not in state_dict]
         unexpected = [k for k in state_dict if k not in spec]
         if strict and (missing or unexpected):

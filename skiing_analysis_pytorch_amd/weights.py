@@ -33,7 +33,8 @@ def _uniform(key, seed, shape, lo, hi):
 # --------------------------------------------------------------------------------------
 # VideoPose3D TemporalModel (keys: VideoPose3D/common/model.py:32-33,103,112-122)
 # --------------------------------------------------------------------------------------
-def vp3d_spec(joints_in=17, in_features=2, joints_out=17, filter_widths=(3, 3, 3), channels=1024):
+def vp3d_spec(joints_in=17, in_features=2, joints_out=17, filter_widths=(3, 3, 3), channels=1024, dense=False):
+    """dense: TemporalModel(dense=True) (model.py:113-116): block i's first conv has 2 * pad_i + 1 taps."""
     spec = OrderedDict()
     cin = joints_in * in_features
 
@@ -48,8 +49,11 @@ def vp3d_spec(joints_in=17, in_features=2, joints_out=17, filter_widths=(3, 3, 3
     spec["shrink.weight"] = ((joints_out * 3, channels, 1), "conv")
     spec["shrink.bias"] = ((joints_out * 3,), "bias")
     spec["expand_conv.weight"] = ((channels, cin, filter_widths[0]), "conv")
+    next_dilation = filter_widths[0]
     for i in range(1, len(filter_widths)):
-        spec[f"layers_conv.{2 * (i - 1)}.weight"] = ((channels, channels, filter_widths[i]), "conv")
+        taps = (filter_widths[i] - 1) * next_dilation + 1 if dense else filter_widths[i]   # 2 * pad_i + 1
+        next_dilation *= filter_widths[i]
+        spec[f"layers_conv.{2 * (i - 1)}.weight"] = ((channels, channels, taps), "conv")
         spec[f"layers_conv.{2 * (i - 1) + 1}.weight"] = ((channels, channels, 1), "conv")
     for i in range(1, len(filter_widths)):
         bn(f"layers_bn.{2 * (i - 1)}")

@@ -7,7 +7,7 @@ Fixtures hold data only: seeds/config, inputs, and the reference's outputs.  Wei
 rebuilt from (spec, seed) by skiing_analysis_pytorch_amd.weights on whichever machine runs
 the tests, so they are not stored.
 
-    PYTHONPATH=/root/reference PYTHONDONTWRITEBYTECODE=1 python tools/make_goldens.py [vp3d|vggt_tiny|...]
+    PYTHONPATH=/root/reference PYTHONDONTWRITEBYTECODE=1 python tools/make_goldens.py [vp3d|vp3d_dense|vggt_tiny|...]
 """
 from __future__ import annotations
 
@@ -74,6 +74,55 @@ def gen_vp3d():
                             seed=np.array(0), kp_seed=np.array(1), frames=np.array(frames), w=np.array(W_),
                             h=np.array(H_), keypoints_px=kp, receptive_field=np.array(rf), **out)
         print("wrote", f"vp3d_{name}.npz", {k: v.shape for k, v in out.items()})
+
+
+def gen_vp3d_dense():
+    """TemporalModel(dense=True) (VideoPose3D/common/model.py:113-116): the same fields as gen_vp3d, plus the shapes
+    of the conv weights (data only; the weights themselves are rebuilt from the seed)."""
+    from VideoPose3D.common.camera import normalize_screen_coordinates
+    from VideoPose3D.common.generators import UnchunkedGenerator
+    from VideoPose3D.common.model import TemporalModel
+
+    kps_left, kps_right = [1, 3, 5, 7, 9, 11, 13, 15], [2, 4, 6, 8, 10, 12, 14, 16]
+    joints_left, joints_right = [4, 5, 6, 11, 12, 13], [1, 2, 3, 14, 15, 16]
+    W_, H_ = 1920, 1080
+    for name, fw, causal, frames in (
+        ("rf27_dense", [3, 3, 3], False, 243),
+        ("rf27_dense_causal", [3, 3, 3], True, 60),
+        ("rf243_dense", [3, 3, 3, 3, 3], False, 243),
+        ("w535_dense", [3, 5, 3], False, 40),     # 13 and 31 taps
+    ):
+        sd = W.make_vp3d_state_dict(seed=0, filter_widths=fw, dense=True)
+        m = TemporalModel(17, 2, 17, filter_widths=fw, causal=causal, channels=1024, dense=True).eval()
+        m.load_state_dict(sd, strict=True)
+        conv_keys = [k for k, v in m.state_dict().items() if v.dim() == 3]
+        conv_shapes = np.array([list(m.state_dict()[k].shape) for k in conv_keys], dtype=np.int64)
+        kp = W.make_keypoints_2d(frames=frames, seed=1).numpy()
+        kps_n = normalize_screen_coordinates(kp.astype(np.float64), w=W_, h=H_)
+        rf = m.receptive_field()
+        pad = (rf - 1) // 2
+        shift = pad if causal else 0
+        out = {}
+        for aug in (False, True):
+            gen = UnchunkedGenerator(None, None, [kps_n], pad=pad, causal_shift=shift, augment=aug,
+                                     kps_left=kps_left, kps_right=kps_right, joints_left=joints_left,
+                                     joints_right=joints_right)
+            for _, _, batch_2d in gen.next_epoch():
+                x = torch.from_numpy(batch_2d.astype("float32"))
+                pred = m(x)
+                out[f"batch2d_aug{int(aug)}"] = batch_2d.astype(np.float32)
+                out[f"raw_aug{int(aug)}"] = pred.numpy().copy()
+                if aug:  # VideoPose3D/run.py:979-986
+                    pred[1, :, :, 0] *= -1
+                    pred[1, :, joints_left + joints_right] = pred[1, :, joints_right + joints_left]
+                    pred = torch.mean(pred, dim=0, keepdim=True)
+                out[f"pred_aug{int(aug)}"] = pred.squeeze(0).numpy()
+        path = GOLD / f"vp3d_{name}.npz"
+        np.savez_compressed(path, filter_widths=np.array(fw), causal=np.array(causal), dense=np.array(True),
+                            seed=np.array(0), kp_seed=np.array(1), frames=np.array(frames), w=np.array(W_),
+                            h=np.array(H_), keypoints_px=kp, receptive_field=np.array(rf),
+                            conv_weight_keys=np.array(conv_keys), conv_weight_shapes=conv_shapes, **out)
+        print("wrote", path.name, path.stat().st_size, "bytes", dict(zip(conv_keys, conv_shapes.tolist())))
 
 
 TINY_CONFIGS = {
@@ -180,7 +229,7 @@ def gen_vggt_tiny():
         print("wrote", f"vggt_{name}.npz", {k: getattr(v, "shape", None) for k, v in out.items()})
 
 
-GENERATORS = {"vp3d": gen_vp3d, "vggt_tiny": gen_vggt_tiny}
+GENERATORS = {"vp3d": gen_vp3d, "vp3d_dense": gen_vp3d_dense, "vggt_tiny": gen_vggt_tiny}
 
 
 
