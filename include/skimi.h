@@ -112,7 +112,11 @@ typedef struct skimi_gemm_desc {
      * [cN, cH, cW, cC] with a KH x KW window (tap-major K: k = (ky*KW+kx)*cC + c),
      * M = cN*OH*OW, K = KH*KW*cC, cC % BK == 0 (BK = 64 for BF16, 32 for BF16X3);
      * 2 = the same gather with slice-major K (BF16X3 only, cC % 32 == 0):
-     * k = ((c / 32) * KH*KW + ky*KW + kx) * 32 + c % 32, i.e. weights [N][cC/32][KH][KW][32] */
+     * k = ((c / 32) * KH*KW + ky*KW + kx) * 32 + c % 32, i.e. weights [N][cC/32][KH][KW][32];
+     * 3 = (with store_mode 2, BF16X3 fast path only) ConvTranspose2d(kernel == stride == ps_s) followed by a
+     * bias-free 3x3 / pad 1 conv, folded into ps_s x ps_s small convs on the coarse image [cN, cH, cW, cC], one per
+     * output phase (y mod ps_s, x mod ps_s): W_split and bias as written by skimi_dpt_fold_pack, M = cN*cH*cW,
+     * N = ps_C output channels, K = 4*cC (the longest phase), KH / KW / stride / pad / dil / OH / OW unused */
     int32_t a_mode;
     int32_t cN, cH, cW, cC, KH, KW, stride, pad, dil, OH, OW;
     /* epilogue: v = acc + bias[n]; v = act(v); v *= gamma[n]; v += resid[m', n];
@@ -138,7 +142,10 @@ typedef struct skimi_gemm_desc {
     int64_t out_row_off;
     /* store: store_mode 0 = out[row*ldo + n]; 1 = ConvTranspose2d with kernel == stride
      * (ps_s): m = (img, iy, ix) over [cN, cH, cW], n = (a*ps_s + b)*ps_C + co,
-     * out[((img*cH*ps_s + iy*ps_s + a)*cW*ps_s + ix*ps_s + b)*ldo + co] */
+     * out[((img*cH*ps_s + iy*ps_s + a)*cW*ps_s + ix*ps_s + b)*ldo + co];
+     * 2 = (with a_mode 3) the same scatter with the phase (a, b) chosen per column tile by the kernel and n = co:
+     * out is [cN, cH*ps_s, cW*ps_s, ldo], out_records (allowed here) holds cN*cH*ps_s*cW*ps_s pixel rows, bias is the
+     * [9][ps_C] border-class table; fp32 out, act SKIMI_ACT_NONE / SKIMI_ACT_RELU, no gamma / residuals / out2 */
     void* out;                /* dev; f32, bf16 or fp16 */
     void* out2;               /* dev or NULL: second copy in the other dtype (same indexing, ldo2) */
     int32_t out_dtype;
@@ -181,6 +188,18 @@ int skimi_split_planes(const float* x, int64_t ld, int64_t rows, int32_t C, void
  * (4 * rows * ceil(C/32) * 32 bytes; a ragged last slice is zero-filled): the hi and lo halves of
  * a 32-element K-slice share one 128-byte line (operand form of skimi_gemm_desc.W_split) */
 int skimi_split_records(const float* x, int64_t ld, int64_t rows, int32_t C, void* records, void* stream);
+
+/* Operands of skimi_gemm_desc.a_mode 3: ConvTranspose2d(C_in, C_mid, kernel = stride = s) (weight w_T [C_in, C_mid, s, s],
+ * bias b_T [C_mid] or NULL) followed by Conv2d(C_mid, C_out, 3, padding = 1, bias = False) (w_rn [C_out, C_mid, 3, 3]),
+ * the pair of dpt_head.py:218-221, 273-274 (resize_layers[i], then scratch.layer{i+1}_rn), folded per output phase
+ * (p, q) = (y mod s, x mod s).  Along an axis phase 0 reads coarse offsets {-1, 0}, phase s-1 {0, +1}, the others {0}:
+ * (s + 2)^2 phase taps in all.  w_records: (s + 2)^2 * C_out * C_in * 4 bytes, the phases row-major, each a
+ * [C_out][taps * C_in] matrix with slice-major K as bf16 records (skimi_split_records' form); beta: fp32 [9][C_out],
+ * b_T seen through the 3x3 taps that stay inside the fine map, class = 3 * yc + xc with yc / xc = 0 inside, 1 first
+ * row / column, 2 last.  All dev; sums in float64, rounded once to fp32.  A pack-time call: it allocates its staging
+ * buffer and synchronises the stream.  C_in % 32 == 0, s >= 2. */
+int skimi_dpt_fold_pack(const float* w_T, const float* b_T, const float* w_rn, int32_t C_in, int32_t C_mid, int32_t C_out,
+                        int32_t s, void* w_records, float* beta, void* stream);
 
 int skimi_gemm(const skimi_gemm_desc* d, void* stream);
 

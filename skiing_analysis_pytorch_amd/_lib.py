@@ -73,6 +73,7 @@ _SIGNATURES = {
                                     C.POINTER(C.c_double)]),
     "skimi_gemm": (C.c_int, [C.POINTER(GemmDesc), _vp]),
     "skimi_gemm_last_path": (C.c_int32, []),
+    "skimi_dpt_fold_pack": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "skimi_quant_mx": (C.c_int, [_vp, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, _vp]),
     "skimi_layernorm_mx": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, C.c_float, _vp, _vp, _vp]),
     "skimi_gemm_fp8": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, _vp, C.c_int64,

@@ -7,6 +7,7 @@
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "kernels.h"
+#include "vggt_kernels.h"
 
 namespace skimi {
 
@@ -159,6 +160,20 @@ int skimi_split_planes(const float* x, int64_t ld, int64_t rows, int32_t C, void
 int skimi_split_records(const float* x, int64_t ld, int64_t rows, int32_t C, void* records, void* stream) {
     SKIMI_CHECK_ARG(x && records && rows > 0 && C > 0, "skimi_split_records: bad arguments");
     return split_records_launch(x, (long)ld, (long)rows, C, records, (hipStream_t)stream);
+}
+
+int skimi_dpt_fold_pack(const float* w_T, const float* b_T, const float* w_rn, int32_t C_in, int32_t C_mid, int32_t C_out,
+                        int32_t s, void* w_records, float* beta, void* stream) {
+    SKIMI_CHECK_ARG(w_T && w_rn && w_records && beta, "skimi_dpt_fold_pack: null buffer");
+    SKIMI_CHECK_ARG(s >= 2 && s <= 16 && C_in > 0 && C_in % 32 == 0 && C_mid > 0 && C_out > 0, "skimi_dpt_fold_pack: bad sizes");
+    float* tmp = nullptr;   // a pack-time call: it allocates its fp32 staging and waits for the stream
+    SKIMI_HIP(hipMalloc((void**)&tmp, (size_t)(s + 2) * (s + 2) * C_out * C_in * 4));
+    const int rc = dpt_fold_pack_launch(w_T, b_T, w_rn, C_in, C_mid, C_out, s, tmp, w_records, beta, (hipStream_t)stream);
+    const hipError_t e = hipStreamSynchronize((hipStream_t)stream);
+    (void)hipFree(tmp);
+    if (rc) return rc;
+    SKIMI_HIP(e);
+    return SKIMI_OK;
 }
 
 int skimi_quant_mx(const void* x, int32_t dtype, int64_t ldx, int64_t rows, int32_t K, void* payload, void* scales,

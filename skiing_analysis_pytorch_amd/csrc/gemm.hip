@@ -432,8 +432,19 @@ int gemm_dispatch(const skimi_gemm_desc* d, hipStream_t st, void* scratch, size_
     SKIMI_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "skimi_gemm: empty shape M=%d N=%d K=%d", d->M, d->N, d->K);
     SKIMI_CHECK_ARG(d->K % 8 == 0, "skimi_gemm: K=%d must be a multiple of 8", d->K);
     SKIMI_CHECK_ARG(d->A && d->W && (d->out || d->out_records), "skimi_gemm: null buffer");
+    const bool fold = d->a_mode == 3 || d->store_mode == 2;
+    if (fold) {
+        SKIMI_CHECK_ARG(d->a_mode == 3 && d->store_mode == 2, "skimi_gemm: a_mode 3 and store_mode 2 come together");
+        SKIMI_CHECK_ARG(d->cC > 0 && d->cC % 32 == 0 && d->K == 4 * d->cC && (long)d->cN * d->cH * d->cW == d->M &&
+                            d->ps_s >= 2 && d->N == d->ps_C && d->N % 32 == 0 && d->lda >= d->cC,
+                        "skimi_gemm: bad phase-folded geometry (K = 4 cC, M = cN cH cW, N = ps_C, ps_s >= 2)");
+        SKIMI_CHECK_ARG(gemm_x3dma_eligible(d),
+                        "skimi_gemm: the phase-folded ConvTranspose + 3x3 conv runs on the 256-column LDS-DMA bf16x3 kernel only "
+                        "(W_split, the 9-class bias table, fp32 out / records, ReLU or no activation, ps_C > 128, cW >= 2, a "
+                        "chip's worth of tiles)");
+    }
     if (d->out_records) {
-        SKIMI_CHECK_ARG(d->N % 32 == 0 && d->store_mode == 0 && d->out_rows_per_batch == 0 && d->out_row_off == 0 &&
+        SKIMI_CHECK_ARG(d->N % 32 == 0 && (d->store_mode == 0 || fold) && d->out_rows_per_batch == 0 && d->out_row_off == 0 &&
                             d->out2 == nullptr && ((uintptr_t)d->out_records & 127) == 0,
                         "skimi_gemm: out_records needs N %% 32 == 0, plain output rows, no out2, 128-byte alignment");
         SKIMI_CHECK_ARG(d->out || d->out_dtype == SKIMI_F32, "skimi_gemm: records-only output is written from fp32 results");
@@ -451,7 +462,7 @@ int gemm_dispatch(const skimi_gemm_desc* d, hipStream_t st, void* scratch, size_
         SKIMI_CHECK_ARG(d->out_dtype == SKIMI_F32 || d->out_dtype == SKIMI_BF16 || d->out_dtype == SKIMI_F16, "skimi_gemm: bad out_dtype %d", d->out_dtype);
     }
     const int BK = d->prec == SKIMI_PREC_BF16X3 ? 32 : 64;
-    if (d->a_mode != 0) {
+    if (d->a_mode != 0 && !fold) {
         SKIMI_CHECK_ARG(d->cC % BK == 0, "skimi_gemm: conv gather needs cC %% %d == 0 (cC=%d)", BK, d->cC);
         SKIMI_CHECK_ARG(d->a_mode != 2 || BK == 32, "skimi_gemm: slice-major conv weights (a_mode 2) need a K-tile of 32 (fp32-accurate mode)");
         SKIMI_CHECK_ARG(d->K == d->KH * d->KW * d->cC, "skimi_gemm: K != KH*KW*cC");

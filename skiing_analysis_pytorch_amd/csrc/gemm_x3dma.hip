@@ -164,11 +164,38 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
         id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
     }
     const int tm = id / p.ntn, tn = id - tm * p.ntn;
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int nkt = (p.K + BK - 1) / BK;
+    const int m0 = tm * BM;
+    int n0 = tn * BN;
+    // the gather window of this tile (wave-uniform): the launch's, or (FOLD) the one of the tile's output phase
+    constexpr bool FOLD = AMODE == 3;
+    int gKH = p.KH, gKW = p.KW, gpy = p.pad, gpx = p.pad, gstride = p.stride, gdil = p.dil, gOH = p.OH, gOW = p.OW;
+    int nkt = (p.K + BK - 1) / BK;
+    const char* wbase = pl.w;
+    long w_row_bytes = pl.w_row_bytes;
+    int fp = 0, fq = 0;   // FOLD: output phase (y mod s, x mod s) of this tile
+    if constexpr (FOLD) {
+        // A stride-s transposed conv followed by a 3x3 conv, as s x s small convs on the coarse map: column tile
+        // tn = (phase, 256 channels of it).  Along an axis phase 0 reads coarse pixels {-1, 0}, phase s-1 {0, +1},
+        // the others {0}; the weights are the phases' [ps_C][taps * cC] matrices (slice-major K) one after another.
+        const int s = p.ps_s, ntc = (p.ps_C + BN - 1) / BN;
+        const int f = tn / ntc;
+        n0 = (tn - f * ntc) * BN;
+        fp = f / s;
+        fq = f - fp * s;
+        gKH = (fp == 0 || fp == s - 1) ? 2 : 1;
+        gKW = (fq == 0 || fq == s - 1) ? 2 : 1;
+        gpy = fp == 0 ? 1 : 0;
+        gpx = fq == 0 ? 1 : 0;
+        gstride = 1; gdil = 1; gOH = p.cH; gOW = p.cW;
+        // taps of the phases before this one: every phase row above holds (s + 2) column taps per row tap
+        const int taps_before = (fp + (fp > 0 ? 1 : 0)) * (s + 2) + gKH * (fq + (fq > 0 ? 1 : 0));
+        wbase += (long)taps_before * p.ps_C * p.cC * 4;
+        w_row_bytes = (long)gKH * gKW * p.cC * 4;
+        nkt = gKH * gKW * (p.cC / 32);
+    }
     // records output: the 256 zero bytes behind them (the consumer's padding taps)
     if (p.out_rec != nullptr && blockIdx.x == 0 && tid < 16)
-        reinterpret_cast<uint4*>(p.out_rec + (long)p.M * p.rec_row)[tid] = uint4{0, 0, 0, 0};
+        reinterpret_cast<uint4*>(p.out_rec + (long)p.M * (FOLD ? p.ps_s * p.ps_s : 1) * p.rec_row)[tid] = uint4{0, 0, 0, 0};
 
     // ---- staging: a piece is 16 wave-instructions of 8 rows x 128 B; this wave issues 4*wave + j ----
     unsigned a_off[2][4], w_off[2][4];
@@ -184,21 +211,21 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
             if (AMODE == 0) {
                 a_off[q][j] = (unsigned)((long)m * pl.a_row_bytes + c * 16);
             } else {
-                const int ohw = p.OH * p.OW;
+                const int ohw = gOH * gOW;
                 const int img = m / ohw;
                 const int rem = m - img * ohw;
-                const int oy = rem / p.OW;
-                const int iy0 = oy * p.stride - p.pad, ix0 = (rem - oy * p.OW) * p.stride - p.pad;
+                const int oy = rem / gOW;
+                const int iy0 = oy * gstride - gpy, ix0 = (rem - oy * gOW) * gstride - gpx;
                 a_off[q][j] = (unsigned)((((long)img * p.cH + iy0) * p.cW + ix0) * pl.a_row_bytes + c * 16 + pl.a_bias);
                 unsigned ok = 0;
-                for (int ky = 0; ky < p.KH; ++ky)
-                    for (int kx = 0; kx < p.KW; ++kx) {
-                        const int iy = iy0 + ky * p.dil, ix = ix0 + kx * p.dil;
-                        if (iy >= 0 && iy < p.cH && ix >= 0 && ix < p.cW) ok |= 1u << (ky * p.KW + kx);
+                for (int ky = 0; ky < gKH; ++ky)
+                    for (int kx = 0; kx < gKW; ++kx) {
+                        const int iy = iy0 + ky * gdil, ix = ix0 + kx * gdil;
+                        if (iy >= 0 && iy < p.cH && ix >= 0 && ix < p.cW) ok |= 1u << (ky * gKW + kx);
                     }
                 a_ok[q][j] = ok;
             }
-            w_off[q][j] = (unsigned)((long)min(n0 + 128 * q + row, p.N - 1) * pl.w_row_bytes + c * 16);
+            w_off[q][j] = (unsigned)((long)min(n0 + 128 * q + row, p.N - 1) * w_row_bytes + c * 16);
         }
     // K-tiles are requested in order, so the (tap, channel slice) of the next one is kept as scalar
     // counters: no integer division in the loop
@@ -210,17 +237,17 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
         int tap;
     };
     auto a_tile = [&](int kt) {
-        const int tap = cur_tap, tap_dy = cur_ky * p.dil, tap_dx = cur_kx * p.dil;
+        const int tap = cur_tap, tap_dy = cur_ky * gdil, tap_dx = cur_kx * gdil;
         const int cs = AMODE == 0 ? kt : cur_cs;
-        if (AMODE == 2) {          // slice-major K: the taps of a 32-channel slice are consecutive K-tiles
+        if (AMODE == 2 || FOLD) {  // slice-major K: the taps of a 32-channel slice are consecutive K-tiles
             ++cur_tap;
-            if (++cur_kx == p.KW) { cur_kx = 0; ++cur_ky; }
-            if (cur_tap == p.KH * p.KW) { cur_tap = 0; cur_ky = 0; ++cur_cs; }
+            if (++cur_kx == gKW) { cur_kx = 0; ++cur_ky; }
+            if (cur_tap == gKH * gKW) { cur_tap = 0; cur_ky = 0; ++cur_cs; }
         } else if (AMODE == 1) {   // tap-major K: the channel slices of a tap are consecutive K-tiles
             if (++cur_cs == p.cC / 32) {
                 cur_cs = 0;
                 ++cur_tap;
-                if (++cur_kx == p.KW) { cur_kx = 0; ++cur_ky; }
+                if (++cur_kx == gKW) { cur_kx = 0; ++cur_ky; }
             }
         }
         const long kbytes = ((long)tap_dy * p.cW + tap_dx) * pl.a_row_bytes + (long)cs * 128 - (AMODE != 0 ? pl.a_bias : 0);
@@ -237,7 +264,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
     };
     auto dma_w = [&](int kt, int q, int j, int slot) {
         if (ABL & 1) return;
-        __builtin_amdgcn_global_load_lds((gbl_void*)(pl.w + (long)kt * 128 + (size_t)w_off[q][j]),
+        __builtin_amdgcn_global_load_lds((gbl_void*)(wbase + (long)kt * 128 + (size_t)w_off[q][j]),
                                          (lds_void*)(smem + slot * PIECE + (4 * wave + j) * 8 * RB), 16, 0, 0);
     };
     auto issue_a = [&](int kt, int slot0, int slot1) {
@@ -516,6 +543,88 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
         }
     };
     const int n = n0 + wc * 128 + 4 * (lane & 31);
+    if constexpr (FOLD) {
+        // Pixel-shuffle store of the tile's phase: coarse pixel m = (img, cy, cx) -> fine pixel (s cy + fp, s cx + fq),
+        // one whole channel row per pixel.  The bias is beta[class][n]: the transposed conv's bias seen through the 3x3
+        // taps that stay inside the fine map, class = 3 * (0 inside | 1 top row | 2 bottom row) + the same for columns.
+        // It is a per-row 16-byte load from a 9-row table (like a residual), so border tiles take the same
+        // branch-free path as interior ones.  Dispatch admits only fp32 out / records, bias, ReLU or no activation.
+        const int s = p.ps_s, cW = p.cW, cH = p.cH;
+        const float lo1 = p.act == SKIMI_ACT_RELU ? 0.f : -__builtin_inff();
+        float* out = reinterpret_cast<float*>(p.out);
+        const long fine_w = (long)cW * s;
+        auto fine_row = [&](int r, int cx) { return ((long)r * s + fp) * fine_w + (long)cx * s + fq; };   // r = img * cH + cy
+        auto beta_off = [&](int cy, int cx) {
+            const int yc = (fp == 0 && cy == 0) ? 1 : (fp == s - 1 && cy == cH - 1) ? 2 : 0;
+            const int xc = (fq == 0 && cx == 0) ? 1 : (fq == s - 1 && cx == cW - 1) ? 2 : 0;
+            return (yc * 3 + xc) * p.ps_C;
+        };
+        if (m0 + BM <= p.M && n0 + BN <= p.N) {   // block-uniform
+            // this lane's rows are lh + 2 k of the wave's 128, in order: (r, cy, cx) advance by two pixels per row
+            // (cW >= 2, checked at dispatch), so no row pays an integer division
+            const int mb = m0 + wr * 128 + lh;
+            int r = mb / cW, cx = mb - r * cW, cy = r % cH;
+#define SKIMI_X3_FOLD_PASS(HAS_OUT, HAS_REC)                                                                       \
+    _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                \
+        to_slab(i);                                                                                                \
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                     \
+        __builtin_amdgcn_s_waitcnt(0xC07F);                                                                        \
+        _Pragma("unroll") for (int half = 0; half < 2; ++half) {                                                   \
+            float4 v[8], bs[8];                                                                                    \
+            long orow[8];                                                                                          \
+            _Pragma("unroll") for (int it = 0; it < 8; ++it)                                                       \
+                v[it] = *reinterpret_cast<const float4*>(&stg[(half * 16 + it * 2 + lh) * SP + 4 * (lane & 31)]);  \
+            _Pragma("unroll") for (int it = 0; it < 8; ++it) {                                                     \
+                orow[it] = fine_row(r, cx);                                                                        \
+                bs[it] = *reinterpret_cast<const float4*>(p.bias + beta_off(cy, cx) + n);                          \
+                cx += 2;                                                                                           \
+                const bool wrap = cx >= cW;                                                                        \
+                cx -= wrap ? cW : 0;                                                                               \
+                r += wrap ? 1 : 0;                                                                                 \
+                cy += wrap ? 1 : 0;                                                                                \
+                cy = cy == cH ? 0 : cy;                                                                            \
+            }                                                                                                      \
+            _Pragma("unroll") for (int it = 0; it < 8; ++it) {                                                     \
+                const float4 y = make_float4(fmaxf(v[it].x + bs[it].x, lo1), fmaxf(v[it].y + bs[it].y, lo1),       \
+                                             fmaxf(v[it].z + bs[it].z, lo1), fmaxf(v[it].w + bs[it].w, lo1));      \
+                if (HAS_OUT) *reinterpret_cast<float4*>(out + orow[it] * p.ldo + n) = y;                           \
+                if (HAS_REC) store_rec4(p, orow[it], n, y.x, y.y, y.z, y.w);                                       \
+            }                                                                                                      \
+        }                                                                                                          \
+        __builtin_amdgcn_s_waitcnt(0xC07F);                                                                        \
+    }
+            // compile-time variants, as below: a uniform branch inside the unrolled passes costs a vmcnt(0) per store
+            switch ((out ? 2 : 0) | (p.out_rec ? 1 : 0)) {
+                case 3: SKIMI_X3_FOLD_PASS(true, true) break;
+                case 2: SKIMI_X3_FOLD_PASS(true, false) break;
+                case 1: SKIMI_X3_FOLD_PASS(false, true) break;
+                default: break;
+            }
+#undef SKIMI_X3_FOLD_PASS
+            return;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            to_slab(i);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_s_waitcnt(0xC07F);
+#pragma unroll 1
+            for (int it = 0; it < 16; ++it) {
+                const int row_l = it * 2 + lh;
+                const int m = m0 + wr * 128 + i * 32 + row_l;
+                if (m >= p.M || n >= p.N) continue;
+                const float4 v = *reinterpret_cast<const float4*>(&stg[row_l * SP + 4 * (lane & 31)]);
+                const int r = m / cW, cx = m - r * cW, cy = r % cH;
+                const float4 b = *reinterpret_cast<const float4*>(p.bias + beta_off(cy, cx) + n);
+                const float4 y = make_float4(fmaxf(v.x + b.x, lo1), fmaxf(v.y + b.y, lo1), fmaxf(v.z + b.z, lo1), fmaxf(v.w + b.w, lo1));
+                const long orow = fine_row(r, cx);
+                if (out) *reinterpret_cast<float4*>(out + orow * p.ldo + n) = y;
+                if (p.out_rec) store_rec4(p, orow, n, y.x, y.y, y.z, y.w);
+            }
+            __builtin_amdgcn_s_waitcnt(0xC07F);
+        }
+        return;
+    }
     // Interior tiles of the common case (fp32 rows, bias, ReLU before / after one fp32 residual): a
     // straight-line path, 8 rows of loads and stores in flight per lane (the checked loop below
     // pays a vmcnt(0) per row: stores share the counter with loads and hipcc cannot count across
@@ -1032,6 +1141,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
 
 static long x3_rows_in(const skimi_gemm_desc* d) { return d->a_mode == 0 ? (long)d->M : (long)d->cN * d->cH * d->cW; }
 static long x3_cp(const skimi_gemm_desc* d) { return ((d->a_mode == 0 ? (long)d->K : (long)d->cC) + 31) / 32 * 32; }
+static int x3_pad(const skimi_gemm_desc* d) { return d->a_mode == 3 ? 1 : d->pad; }   // a_mode 3: windows start at -1 or 0
 
 size_t gemm_x3dma_scratch_bytes(const skimi_gemm_desc* d) {
     return (size_t)x3_rows_in(d) * x3_cp(d) * 4 + 256;   // A records + 256 zero bytes
@@ -1053,13 +1163,23 @@ bool gemm_x3dma_eligible(const skimi_gemm_desc* d) {
     } else {
         return false;
     }
-    if (d->store_mode != 0 && d->store_mode != 1) return false;
+    const bool fold = d->a_mode == 3;   // phase-folded ConvTranspose + 3x3 conv: its gather and its store come together
+    if (fold != (d->store_mode == 2)) return false;
+    if (d->store_mode < 0 || d->store_mode > 2) return false;
     if (d->K % 4 != 0) return false;
     if (d->a_mode != 0 && (d->cC % 32 != 0 || d->KH * d->KW > 32)) return false;
     // 32-bit lane offsets from a scalar base
     const long kp = ((long)d->K + 31) / 32 * 32;
-    const long bias = d->a_mode == 0 ? 0 : ((long)d->pad * d->cW + d->pad) * x3_cp(d) * 4;
+    const long bias = d->a_mode == 0 ? 0 : ((long)x3_pad(d) * d->cW + x3_pad(d)) * x3_cp(d) * 4;
     if ((long)gemm_x3dma_scratch_bytes(d) + bias >= (1ll << 32) || (long)d->N * kp * 4 >= (1ll << 32)) return false;
+    if (fold) {
+        // the 256-column loop only (a tile is one phase's channels), its epilogue's forms only
+        if (d->ps_s < 2 || d->ps_C <= 128 || d->ps_C % 32 != 0 || d->N != d->ps_C || d->cW < 2 || d->bias == nullptr ||
+            d->out_dtype != SKIMI_F32 || (d->act != SKIMI_ACT_NONE && d->act != SKIMI_ACT_RELU) || d->post_act != SKIMI_ACT_NONE ||
+            d->gamma != nullptr || d->resid != nullptr || d->resid2 != nullptr || d->out2 != nullptr || d->ldo % 4 != 0 ||
+            ((uintptr_t)d->out & 15) != 0 || ((uintptr_t)d->bias & 15) != 0)
+            return false;
+    }
     // enough 256-row tiles for most of the chip (one workgroup per CU).  Measured in the bench: the level
     // with 172 tiles (M = 43808) is already faster here than on the generic 128x128 kernel (17.38 vs
     // 17.18 frames/s at a threshold of 160 vs 200); below that the generic kernel's smaller tiles win.
@@ -1067,16 +1187,16 @@ bool gemm_x3dma_eligible(const skimi_gemm_desc* d) {
     static const bool dyn = getenv("SKIMI_ENV_DYNAMIC") && atoi(getenv("SKIMI_ENV_DYNAMIC"));
     static long min_tiles = -1;
     if (min_tiles < 0 || dyn) min_tiles = getenv("SKIMI_X3_MIN_TILES") ? atol(getenv("SKIMI_X3_MIN_TILES")) : 160;
-    const long tiles = cdiv(d->M, 256) * (d->N > 128 ? cdiv(d->N, 256) : 1);
+    const long tiles = cdiv(d->M, 256) * (d->N > 128 ? cdiv(d->N, 256) : 1) * (fold ? d->ps_s * d->ps_s : 1);
     return d->M >= (min_tiles <= 1 ? 256 : 4096) && d->N >= 96 && tiles >= min_tiles;
 }
 
 template <int AMODE, int ABL = 0, bool M16 = false>
-static int launch_x3w4_(GemmArgs& a, const X3Rec& pl, hipStream_t st) {
+static int launch_x3w4_(GemmArgs& a, const X3Rec& pl, hipStream_t st, int phases) {
     constexpr size_t lds = 10ull * 128 * 128;
     SKIMI_LDS_OPT_IN((gemm_x3w4_kernel<AMODE, ABL, M16>), lds, "gemm_x3w4");
     a.ntm = (int)cdiv(a.M, 256);
-    a.ntn = (int)cdiv(a.N, 256);
+    a.ntn = (int)cdiv(a.N, 256) * phases;   // a_mode 3: every output phase has its own column tiles
     a.splitk = 1;
     hipLaunchKernelGGL((gemm_x3w4_kernel<AMODE, ABL, M16>), dim3(a.ntm * a.ntn), dim3(256), lds, st, a, pl);
     SKIMI_LAUNCH_CHECK();
@@ -1105,8 +1225,8 @@ static bool x3_m16() {
 }
 
 template <int AMODE, int ABL = 0>
-static int launch_x3w4(GemmArgs& a, const X3Rec& pl, hipStream_t st) {
-    return x3_m16() ? launch_x3w4_<AMODE, ABL, true>(a, pl, st) : launch_x3w4_<AMODE, ABL, false>(a, pl, st);
+static int launch_x3w4(GemmArgs& a, const X3Rec& pl, hipStream_t st, int phases = 1) {
+    return x3_m16() ? launch_x3w4_<AMODE, ABL, true>(a, pl, st, phases) : launch_x3w4_<AMODE, ABL, false>(a, pl, st, phases);
 }
 
 template <int AMODE>
@@ -1133,9 +1253,10 @@ int gemm_x3dma_launch(GemmArgs& a, const skimi_gemm_desc* d, hipStream_t st) {
     pl.zero = zpage;
     pl.a_row_bytes = cp * 4;
     pl.w_row_bytes = ((long)d->K + 31) / 32 * 32 * 4;
-    pl.a_bias = d->a_mode == 0 ? 0 : ((long)d->pad * d->cW + d->pad) * pl.a_row_bytes;
+    pl.a_bias = d->a_mode == 0 ? 0 : ((long)x3_pad(d) * d->cW + x3_pad(d)) * pl.a_row_bytes;
     a.dbg = 0;
     set_gemm_path(d->N <= 128 ? SKIMI_GEMM_PATH_X3DMA_NARROW : SKIMI_GEMM_PATH_X3DMA_WIDE, 0, x3_m16() ? 1 : 2, 0, 1);
+    if (a.a_mode == 3) return launch_x3w4<3>(a, pl, st, d->ps_s * d->ps_s);
     if (d->N <= 128) {
         if (a.a_mode == 0) return launch_x3w4n<0>(a, pl, st);
         if (a.a_mode == 1) return launch_x3w4n<1>(a, pl, st);

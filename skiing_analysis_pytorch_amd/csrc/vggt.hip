@@ -58,6 +58,8 @@ struct DptW {
     LNw norm;
     Lin proj[4];
     Lin rs0, rs1;       // ConvTranspose k=s=4 / 2 as pixel-shuffle GEMMs (bias tiled s*s times)
+    Lin fold[2];        // rs0 . rn[0] and rs1 . rn[1] folded per output phase (dpt_fold_pack_launch): w_split = the phase
+                        // matrices' records, b = beta [9][features]; w_split NULL = not folded (SKIMI_DPT_FOLD=0, 16-bit heads)
     ConvW rs3;
     ConvW rn[4];
     FusionW ref[4];     // ref[0] = refinenet1 ... ref[3] = refinenet4
@@ -126,6 +128,7 @@ struct skimi_vggt {
     std::map<std::string, std::pair<float*, int64_t>> raw;   // staged fp32 weights (device)
     std::vector<void*> owned;                                // packed device buffers
     bool finalized = false;
+    bool dpt_fold = true;   // SKIMI_DPT_FOLD (read at create): fold the bf16x3 heads' ConvTranspose resizes into layer1_rn / layer2_rn
     // packed model
     Lin patch_proj;                 // [C, Kp] patchify GEMM (K = 3*p*p padded to 8)
     int patch_kp = 0;
@@ -278,6 +281,27 @@ struct Packer {
         if (L.b) rc = rc ? rc : tile_vec_launch(bsrc, L.b, C, s * s, st);
         return L;
     }
+    // resize_layers[i] (ConvTranspose2d(C, C, k = s, stride = s)) folded into layer{i+1}_rn (3x3, C -> Co, no bias): the
+    // per-phase matrices as weight records + the 9 border classes of the folded bias, from the staged fp32 weights
+    // (float64 sums, one rounding).  K = 4 C is the longest phase; the kernel derives each phase's own from its taps.
+    Lin conv_fold(const std::string& pT, const std::string& pRn, int C, int Co, int s) {
+        Lin L;
+        L.N = Co; L.K = 4 * C; L.prec = SKIMI_PREC_BF16X3; L.wdt = SKIMI_F32;
+        float* wT = raw(pT + ".weight", (int64_t)C * C * s * s);
+        float* bT = raw(pT + ".bias", C);
+        float* wrn = raw(pRn + ".weight", (int64_t)Co * C * 9);
+        if (rc) return L;
+        const size_t n = (size_t)(s + 2) * (s + 2) * Co * C;
+        float* tmp = nullptr;
+        if (hipMalloc((void**)&tmp, n * 4) != hipSuccess) { rc = SKIMI_ERR_HIP; return L; }
+        L.w_split = dmalloc(n * 4);
+        L.b = (float*)dmalloc((size_t)9 * Co * 4);
+        L.w = L.w_split;   // the descriptor's W: this form has no plain fp32 matrix
+        if (!rc) rc = dpt_fold_pack_launch(wT, bT, wrn, C, C, Co, s, tmp, L.w_split, L.b, st);
+        (void)hipStreamSynchronize(st);
+        (void)hipFree(tmp);
+        return L;
+    }
     // MXFP8 copy of a packed Linear (from the staged fp32 weights: one rounding)
     void add_fp8(Lin& L, const std::string& p, int N, int K) {
         if (rc) return;
@@ -337,6 +361,12 @@ struct Packer {
         d.rs3 = conv(p + ".resize_layers.3", oc[3], oc[3], 3, 2, 1, prec, true);
         for (int i = 0; i < 4; ++i)
             d.rn[i] = conv(p + ".scratch.layer" + std::to_string(i + 1) + "_rn", features, oc[i], 3, 1, 1, prec, false);
+        // the unfolded rs0 / rs1 / rn[0..1] stay packed: launches too small for the 256-row kernel take them
+        if (h->dpt_fold && prec == SKIMI_PREC_BF16X3 && features % 32 == 0 && features > 128)
+            for (int i = 0; i < 2; ++i)
+                if (oc[i] % 32 == 0)
+                    d.fold[i] = conv_fold(p + ".resize_layers." + std::to_string(i), p + ".scratch.layer" + std::to_string(i + 1) + "_rn",
+                                          oc[i], features, i == 0 ? 4 : 2);
         for (int r = 0; r < 4; ++r) {
             const std::string rp = p + ".scratch.refinenet" + std::to_string(r + 1);
             FusionW& f = d.ref[r];
@@ -626,6 +656,34 @@ void* run_dpt(Ctx& c, const DptW& w, float* const* sf, float* const* sg, int F, 
                 }
                 c.ln(sf[i], sg[i], C, (long)F * np, D, w.norm, 1e-5f, rec_in ? lnb_rec : lnb, rec_in ? SKIMI_BF16X3_REC : adt, np, P, nsp);
                 c.gemm(d);
+            }
+            // Levels 0 / 1: resize_layers[i] (ConvTranspose, k = stride = s) and layer{i+1}_rn (3x3) are adjacent linear
+            // maps; where the folded weights exist and the launch fills the 256-row kernel they run as ONE launch of
+            // s x s phase convs on the coarse map (gemm_x3w4_kernel<3>): the s^2 x larger intermediate is never written.
+            // Its A operand is t0 + UV embedding as records, written by the embedding pass instead of back to t0.
+            if (i < 2 && adt == SKIMI_F32 && w.fold[i].w_split != nullptr) {
+                const size_t t0_bytes = (size_t)F * np * w.oc[i] * 4;
+                char* fake = (char*)(uintptr_t)0x10000000;   // eligibility looks at alignment and distances only
+                auto d = c.desc(w.fold[i], fake, SKIMI_BF16X3_REC, w.oc[i], F * np, fake, adt, feat);
+                d.a_mode = 3; d.store_mode = 2; d.ps_s = i == 0 ? 4 : 2; d.ps_C = feat;
+                d.cN = F; d.cH = ph; d.cW = pw; d.cC = w.oc[i];
+                d.x3_scratch = fake + t0_bytes; d.x3_scratch_bytes = 256;
+                d.act = SKIMI_ACT_RELU;
+                if (gemm_x3dma_eligible(&d)) {
+                    char* t0_rec = (char*)c.ar.alloc(t0_bytes + 256);
+                    const UvTab* t = w.pos_embed ? find_uv(c.tabs, pw, ph, w.oc[i]) : nullptr;
+                    if (w.pos_embed && !t && !c.rc && !c.dry()) { set_error("uv table missing"); c.rc = SKIMI_ERR_STATE; }
+                    if (!c.rc && !c.dry())
+                        c.rc = add_uv_pos_records_launch((const float*)t0, t ? t->tx : nullptr, t ? t->ty : nullptr, F, ph, pw, w.oc[i],
+                                                         t0_rec, c.st);
+                    d.A = t0_rec;
+                    d.x3_scratch = t0_rec + t0_bytes;
+                    d.out = rn[i];
+                    d.out_records = rn_rec[i];
+                    c.gemm(d);
+                    c.ar.release(mk3);
+                    continue;
+                }
             }
             if (w.pos_embed && !c.rc && !c.dry()) {
                 const UvTab* t = find_uv(c.tabs, pw, ph, w.oc[i]);
@@ -1117,6 +1175,8 @@ skimi_vggt* skimi_vggt_create(const skimi_vggt_config* cfg) {
     }
     skimi_vggt* h = new skimi_vggt();
     h->cfg = *cfg;
+    // SKIMI_DPT_FOLD=0: the heads' levels 0 / 1 as ConvTranspose GEMM + 3x3 conv (interleaved A/B timing, equivalence tests)
+    h->dpt_fold = !(getenv("SKIMI_DPT_FOLD") && atoi(getenv("SKIMI_DPT_FOLD")) == 0);
     return h;
 }
 

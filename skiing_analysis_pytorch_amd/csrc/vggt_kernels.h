@@ -15,6 +15,13 @@ int bilinear_ac_launch(const void* in, void* out, int dtype, int N, int h, int w
                        const float* ln_g = nullptr, const float* ln_b = nullptr, float ln_eps = 0.f);   // C == 128, fp32 out: LayerNorm of every resized pixel in the same pass
 int add_uv_pos_launch(void* x, int dtype, const float* tabx, const float* taby, int N, int H, int W, int C,
                       hipStream_t st);
+// x + UV embedding (tabx NULL: x alone) -> bf16x3 records [pixel][C/32][hi 32 | lo 32] + 256 zero bytes; x is left as it is
+int add_uv_pos_records_launch(const float* x, const float* tabx, const float* taby, int N, int H, int W, int C, void* rec,
+                              hipStream_t st);
+// ConvTranspose2d(Ci, Cm, k = s, stride = s) + 3x3 conv Cm -> Co folded per output phase (vggt_kernels.hip): weight
+// records of the (s + 2)^2 phase taps ((s + 2)^2 * Co * Ci * 4 bytes, as many floats of scratch in tmp) and beta [9][Co]
+int dpt_fold_pack_launch(const float* wT, const float* bT, const float* wrn, int Ci, int Cm, int Co, int s, float* tmp, void* rec,
+                         float* beta, hipStream_t st);
 int adaln_launch(const float* xn, const float* x, const float* mod, float* out, long rows, int D, hipStream_t st);
 int pose_update_launch(const float* delta, float* pred_pad, float* act_out, long rows, int first, hipStream_t st);
 int dpt_out_launch(const void* in, int dtype, const float* W, const float* b, int n_out, float* pts, float* conf,

@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "gemm_epilogue.h"
 #include "vggt_kernels.h"
 
 namespace skimi {
@@ -509,6 +510,121 @@ __global__ void permute_convT_kernel(const float* __restrict__ in, float* __rest
 }
 int permute_convT_launch(const float* in, float* out, int Ci, int Co, int s, hipStream_t st) {
     hipLaunchKernelGGL(permute_convT_kernel, dim3(grid_for((long)Ci * Co * s * s)), dim3(256), 0, st, in, out, Ci, Co, s);
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// ConvTranspose2d(Ci, Cm, k = s, stride = s) followed by a bias-free 3x3 / pad 1 conv Cm -> Co, with nothing
+// non-linear between them (dpt_head.py:218-221, 273-274: resize_layers[i] then layer{i+1}_rn), folded into s x s
+// small convs on the COARSE map, one per output phase (p, q) = (y mod s, x mod s).  An upsampled pixel comes from
+// exactly one coarse pixel, so along an axis the 3x3 window of phase p reaches coarse offsets
+//     T(0) = {-1, 0},  T(s - 1) = {0, +1},  T(p) = {0} otherwise,
+// and   Wc[p, q, di, dj] = sum over 3x3 taps (a, b) with floor((p + a - 1) / s) = di, floor((q + b - 1) / s) = dj
+//                          of  W_rn[:, :, a, b] . W_T[:, :, (p + a - 1) mod s, (q + b - 1) mod s]^T     [Co, Ci].
+// Layout: the phases row-major, each a matrix [Co][taps * Ci] with slice-major K (k = ((ci / 32) * taps + ky * KW +
+// kx) * 32 + ci % 32, ky / kx counting T(p) / T(q) upwards): what gemm_x3w4_kernel<3> walks.  The transposed conv's
+// bias becomes beta[class][co] = sum over the 3x3 taps that stay inside the fine map of W_rn[co, :, a, b] . b_T,
+// class = 3 * yc + xc, yc / xc = 0 inside, 1 first row / column, 2 last.  Sums in float64, rounded once to fp32.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void dpt_fold_phase_kernel(const float* __restrict__ wT, const float* __restrict__ wrn, int Ci,
+                                                             int Cm, int Co, int s, int p, int q, float* __restrict__ out) {
+    const int KH = (p == 0 || p == s - 1) ? 2 : 1, KW = (q == 0 || q == s - 1) ? 2 : 1;
+    const int oy = p == 0 ? -1 : 0, ox = q == 0 ? -1 : 0;
+    const long K = (long)KH * KW * Ci, total = (long)Co * K;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int co = (int)(i / K);
+        const int k = (int)(i - co * K);
+        const int u = k >> 5, tap = u % (KH * KW);
+        const int ci = (u / (KH * KW)) * 32 + (k & 31);
+        const int ky = tap / KW, kx = tap - ky * KW;
+        double acc = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            const int ty = p + a - 1, fy = ty < 0 ? -1 : ty >= s ? 1 : 0;
+            if (fy != oy + ky) continue;
+            for (int b = 0; b < 3; ++b) {
+                const int tx = q + b - 1, fx = tx < 0 ? -1 : tx >= s ? 1 : 0;
+                if (fx != ox + kx) continue;
+                const float* r = wrn + (long)co * Cm * 9 + a * 3 + b;
+                const float* t = wT + (long)ci * Cm * s * s + (ty - fy * s) * s + (tx - fx * s);
+                for (int cm = 0; cm < Cm; ++cm) acc += (double)r[(long)cm * 9] * (double)t[(long)cm * s * s];
+            }
+        }
+        out[i] = (float)acc;
+    }
+}
+__global__ __launch_bounds__(256) void dpt_fold_bias_kernel(const float* __restrict__ bT, const float* __restrict__ wrn, int Cm, int Co,
+                                                            float* __restrict__ beta) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= 9 * Co) return;
+    const int cls = i / Co, co = i - cls * Co, yc = cls / 3, xc = cls - yc * 3;
+    double acc = 0.0;
+    if (bT != nullptr)
+        for (int a = 0; a < 3; ++a) {
+            if ((yc == 1 && a == 0) || (yc == 2 && a == 2)) continue;
+            for (int b = 0; b < 3; ++b) {
+                if ((xc == 1 && b == 0) || (xc == 2 && b == 2)) continue;
+                for (int cm = 0; cm < Cm; ++cm) acc += (double)wrn[((long)co * Cm + cm) * 9 + a * 3 + b] * (double)bT[cm];
+            }
+        }
+    beta[i] = (float)acc;
+}
+// tmp: (s + 2)^2 * Co * Ci floats of scratch; rec: as many 4-byte record elements; beta: [9][Co]
+int dpt_fold_pack_launch(const float* wT, const float* bT, const float* wrn, int Ci, int Cm, int Co, int s, float* tmp, void* rec,
+                         float* beta, hipStream_t st) {
+    SKIMI_CHECK_ARG(s >= 2 && Ci % 32 == 0 && Ci > 0 && Cm > 0 && Co > 0, "dpt_fold_pack: needs s >= 2 and Ci %% 32 == 0");
+    long off = 0;
+    for (int p = 0; p < s; ++p)
+        for (int q = 0; q < s; ++q) {
+            const int taps = ((p == 0 || p == s - 1) ? 2 : 1) * ((q == 0 || q == s - 1) ? 2 : 1);
+            const long n = (long)Co * taps * Ci;
+            hipLaunchKernelGGL(dpt_fold_phase_kernel, dim3(grid_for(n)), dim3(256), 0, st, wT, wrn, Ci, Cm, Co, s, p, q, tmp + off);
+            SKIMI_LAUNCH_CHECK();
+            const int rc = split_records_launch(tmp + off, (long)taps * Ci, Co, taps * Ci, (char*)rec + off * 4, st);
+            if (rc) return rc;
+            off += n;
+        }
+    hipLaunchKernelGGL(dpt_fold_bias_kernel, dim3((unsigned)cdiv(9L * Co, 256)), dim3(256), 0, st, bT, wrn, Cm, Co, beta);
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
+// the UV positional embedding added to x [N, H, W, C] fp32 (add_uv_pos_kernel's add) with the sum written as bf16x3
+// operand records [pixel][C / 32][hi 32 | lo 32] instead of back to x, and the zero page behind them cleared
+__global__ __launch_bounds__(256) void add_uv_pos_records_kernel(const float* __restrict__ x, const float* __restrict__ tabx,
+                                                                 const float* __restrict__ taby, int N, int H, int W, int C,
+                                                                 unsigned short* __restrict__ rec) {
+    const int C4 = C / 4, half = C / 2;
+    const long total = (long)N * H * W * C4;
+    if (blockIdx.x == 0 && threadIdx.x < 16) reinterpret_cast<uint4*>(rec + total * 8)[threadIdx.x] = uint4{0, 0, 0, 0};
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+        const int c = (int)(i % C4) * 4;
+        float4 v = *reinterpret_cast<const float4*>(x + i * 4);
+        if (tabx != nullptr) {
+            const int X = (int)((i / C4) % W);
+            const int Y = (int)((i / ((long)C4 * W)) % H);
+            const float4 e = *reinterpret_cast<const float4*>(c < half ? tabx + (long)X * half + c : taby + (long)Y * half + (c - half));
+            v.x += e.x; v.y += e.y; v.z += e.z; v.w += e.w;
+        }
+        const float f[4] = {v.x, v.y, v.z, v.w};
+        bf16x4 h, l;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned short hb = f2bf(f[k]);
+            h[k] = (short)hb;
+            l[k] = (short)f2bf(f[k] - bf2f(hb));
+        }
+        unsigned short* o = rec + (i / C4) * (2L * C) + (c >> 5) * 64 + (c & 31);
+        *reinterpret_cast<bf16x4*>(o) = h;
+        *reinterpret_cast<bf16x4*>(o + 32) = l;
+    }
+}
+int add_uv_pos_records_launch(const float* x, const float* tabx, const float* taby, int N, int H, int W, int C, void* rec,
+                              hipStream_t st) {
+    SKIMI_CHECK_ARG(C % 32 == 0, "uv pos embed to records needs C %% 32 == 0");
+    const long total = (long)N * H * W * (C / 4);
+    hipLaunchKernelGGL(add_uv_pos_records_kernel, dim3(grid_for(total, 256, 65536)), dim3(256), 0, st, x, tabx, taby, N, H, W, C,
+                       (unsigned short*)rec);
     SKIMI_LAUNCH_CHECK();
     return SKIMI_OK;
 }

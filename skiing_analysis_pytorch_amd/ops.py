@@ -281,6 +281,58 @@ def x3_scratch_numel(rows, Cc):
     return rows * ((Cc + 31) // 32 * 32) + 64
 
 
+def dpt_fold_pack(w_T, b_T, w_rn):
+    """ConvTranspose2d(kernel = stride = s) weight [Ci, Cm, s, s] (+ bias [Cm] or None) and the following bias-free 3x3
+    conv's weight [Co, Cm, 3, 3] -> (weight records of the (s + 2)^2 phase taps, beta [9, Co]): the operands of
+    `convT_conv3x3_folded` (skimi_dpt_fold_pack in include/skimi.h)."""
+    _require_cuda(w_T, b_T, w_rn)
+    Ci, Cm, s, s2 = w_T.shape
+    Co = w_rn.shape[0]
+    assert s == s2 and w_rn.shape == (Co, Cm, 3, 3)
+    rec = torch.empty((s + 2) * (s + 2) * Co * Ci * 2, dtype=torch.bfloat16, device=w_T.device)
+    beta = torch.empty((9, Co), dtype=torch.float32, device=w_T.device)
+    check(lib().skimi_dpt_fold_pack(ptr(w_T.contiguous()), ptr(b_T.contiguous()) if b_T is not None else None, ptr(w_rn.contiguous()),
+                                    Ci, Cm, Co, s, ptr(rec), ptr(beta), _lib.current_stream()), "skimi_dpt_fold_pack")
+    return rec, beta
+
+
+def convT_conv3x3_folded(x, w_records, beta, s, Co, *, act=ACT_NONE, out=None, out_records=None, records_only=False,
+                         a_records=None):
+    """conv2d(conv_transpose2d(x, w_T, b_T, stride = s), w_rn, padding = 1) of a channels-last fp32 x [F, h, w, Ci] in one
+    launch of s x s phase convs on x (skimi_gemm_desc.a_mode 3; operands from `dpt_fold_pack`) -> fp32 [F, s h, s w, Co];
+    out_records = a `records_buffer(F * s h * s w, Co)`: the result also (records_only: only) as bf16x3 records.
+    a_records: x already as a `records_buffer(F * h * w, Ci)` (then x is its shape (F, h, w, Ci))."""
+    _require_cuda(w_records, beta, out, out_records, a_records)
+    F_, h, w_, Ci = x if a_records is not None else x.shape
+    nrec = F_ * h * w_ * Ci * 2
+    ar = a_records
+    if ar is None:
+        _require_cuda(x)
+        ar = records_buffer(F_ * h * w_, Ci, device=x.device)
+        ar[:nrec] = split_records(x.reshape(-1, Ci).contiguous()).reshape(-1)
+        ar[nrec:] = 0
+    d = GemmDesc()
+    d.M, d.N, d.K = F_ * h * w_, Co, 4 * Ci
+    d.A, d.a_dtype, d.lda = ptr(ar), _lib.BF16X3_REC, Ci
+    d.W, d.w_dtype, d.ldw = ptr(w_records), _lib.F32, 4 * Ci
+    d.W_split = ptr(w_records)
+    d.x3_scratch, d.x3_scratch_bytes = ptr(ar) + nrec * 2, 256
+    d.prec = PREC_BF16X3
+    d.a_mode, d.store_mode, d.ps_s, d.ps_C = 3, 2, s, Co
+    d.cN, d.cH, d.cW, d.cC = F_, h, w_, Ci
+    d.bias, d.act = ptr(beta), act
+    d.out_dtype = _lib.F32
+    if not records_only:
+        if out is None:
+            out = torch.empty((F_, h * s, w_ * s, Co), dtype=torch.float32, device=w_records.device)
+        d.out = ptr(out)
+    d.ldo = Co
+    if out_records is not None:
+        d.out_records = ptr(out_records)
+    check(lib().skimi_gemm(C.byref(d), _lib.current_stream()), "skimi_gemm")
+    return out
+
+
 def split_planes(x):
     """fp32 [rows, C] -> bf16 [2, rows, C] (hi, lo) with hi + lo ~= x to ~2^-17 relative."""
     _require_cuda(x)
