@@ -460,6 +460,43 @@ int skimi_unproject_depth(const float* depth, const float* extrinsic, const floa
 int skimi_triangulate_dlt(const float* K, const float* R, const float* t, const float* keypoints,
                           float* joints3d, int64_t steps, int32_t views, int32_t joints, void* stream);
 
+/* Triangulation with a verdict: skimi_triangulate_dlt's solve (same inputs, same float32 joints3d), then per (step, joint)
+ * the stored joint through every view's OWN camera in float64: xh = K_v (R_v X + t_v), depth [steps, views, joints] = its
+ * third component, err [steps, views, joints] = ||xh / depth - keypoint|| in pixels (plain division: a non-finite result
+ * stays non-finite).  em = mean over the views of err; keep [steps, joints] (u8) = every depth > 0 and em finite and
+ * <= err_thresh_px and, when conf [steps, views, joints] (dev f32, NULL allowed) is given, every score >= conf_thr;
+ * joints3d_clean = joints3d where kept, NaN elsewhere.  view_stats [steps, views, 4] = rmse, mean, median, max of err over
+ * the joints; report [steps, 5] = rmse_px, median_err_px (of em), pos_depth_ratio, kept_ratio, kept_count; NaN entries are
+ * ignored as by nanmean / nanmedian / nanmax.  2 <= views <= 8, 1 <= joints <= 32.  One launch, no synchronisation.
+ * Replaces reproject_and_visualize's error dict (vggt/reproject.py:108-144, :334-341) and post_triage_single
+ * (triangulation/postprocess.py:70-121); rules and the one deliberate difference: DESIGN §2 "Triage". */
+int skimi_triangulate_triage(const float* K, const float* R, const float* t, const float* keypoints, const float* conf,
+                             double conf_thr, double err_thresh_px, int64_t steps, int32_t views, int32_t joints,
+                             float* joints3d, float* joints3d_clean, double* err, double* depth, uint8_t* keep,
+                             double* view_stats, double* report, void* stream);
+
+/* Person origin of dense point maps (extract_person_points and the mean its caller takes,
+ * vggt/multi_view_process.py:356-395, :195-199, which run in NumPy on the host).  points: dev f32 [maps, H, W, 3];
+ * boxes: dev f32 [maps, 4] = x1, y1, x2, y2 in the pixels of a src_h x src_w image.  Per map: crop as the reference
+ * (scale factors and products in float64, truncation toward zero, x1 in [0, W-1], x2 in [0, W], likewise y; a box with
+ * a non-finite corner is empty), valid = all three coordinates finite, median = the exact middle order statistic of the
+ * valid z (even count: the float64 mean of the two middle ones), std = population standard deviation in float64 (two
+ * passes), kept = |z - median| < 3 std (strict, float64), origin = float64 mean of the kept points.
+ * stats: dev f64 [maps, 8] = n_box, n_valid, n_kept, median, std, origin x, y, z (NaN where undefined: median and std
+ * without a valid point, the origin without a kept one).  One workgroup per map, one launch, no synchronisation; sums
+ * have a fixed order, so results are bitwise reproducible.  workspace: skimi_person_workspace_bytes(maps, H, W) bytes,
+ * which is 0 for this kernel shape (NULL allowed).  Rules: DESIGN §2 "Person origin". */
+size_t skimi_person_workspace_bytes(int64_t maps, int32_t H, int32_t W);
+int skimi_person_origin(const float* points, const float* boxes, int64_t maps, int32_t H, int32_t W, int32_t src_h,
+                        int32_t src_w, void* workspace, double* stats, void* stream);
+/* The camera update that follows (:201-217), one thread per step: stats [steps, views, 8] from skimi_person_origin,
+ * extrinsic dev f32 [steps, views, 3, 4] -> origin_out dev f64 [steps, 3] = the float64 mean of the views' origins in
+ * view order (0 if any view kept no point), t_out [steps, views, 3] = t_c + R_c origin (float64, stored as f32),
+ * R_out [steps, views, 3, 3] = R_c, except at views == 2 where view 1 is turned: R_1 <- diag(-1, 1, -1) R_1 and t_1 is
+ * left as it is (the reference turns it and then mirrors x and z back). */
+int skimi_recenter_cameras(const double* stats, const float* extrinsic, int64_t steps, int32_t views, double* origin_out,
+                           float* R_out, float* t_out, void* stream);
+
 /* Point-to-plane ICP of two dense point maps (replaces ICP_with_bbox, vggt/multi_view_process.py:427-520, which
  * calls Open3D's estimate_normals and registration_icp on the host).  Clouds are raw dev f32 [n, 3]; the validity
  * filter runs inside: a point is kept iff its coordinates are finite and x^2 + y^2 + z^2 > 1e-12 (the reference keeps

@@ -109,6 +109,11 @@ _SIGNATURES = {
     "skimi_pose_to_cameras": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "skimi_unproject_depth": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "skimi_triangulate_dlt": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp]),
+    "skimi_triangulate_triage": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "skimi_person_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
+    "skimi_person_origin": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "skimi_recenter_cameras": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp]),
     "skimi_icp_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "skimi_estimate_normals": (C.c_int, [_vp, C.c_int64, C.c_double, _vp, _vp, _vp, C.c_size_t, _vp]),
     "skimi_icp_correspondences": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, C.POINTER(C.c_double), C.c_double, _vp, _vp,

@@ -54,16 +54,13 @@ __global__ __launch_bounds__(256) void unproject_kernel(const float* __restrict_
     }
 }
 
-// One thread per (time step, joint): A = rows {u P[2] - P[0], v P[1]...} over V views, the
+// One (time step, joint): A = rows {u P[2] - P[0], v P[1]...} over V views, the
 // solution is the right-singular vector of A for the smallest singular value = eigenvector of
 // A^T A (4x4, symmetric) for the smallest eigenvalue; cyclic Jacobi in double precision.
-__global__ void triangulate_dlt_kernel(const float* __restrict__ Kc, const float* __restrict__ Rc,
-                                       const float* __restrict__ tc, const float* __restrict__ kp, float* __restrict__ X,
-                                       long T, int V, int J) {
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= T * J) return;
-    const long t = idx / J;
-    const int j = (int)(idx - t * J);
+// dlt_point is that solve for joint j of step t, shared by the plain and the triage kernel -> X rounded to float32.
+__device__ __forceinline__ void dlt_point(const float* __restrict__ Kc, const float* __restrict__ Rc,
+                                          const float* __restrict__ tc, const float* __restrict__ kp, long t, int j, int V,
+                                          int J, float* __restrict__ o) {
     double M[4][4] = {{0}};
     for (int v = 0; v < V; ++v) {
         const float* K = Kc + (t * V + v) * 9;
@@ -120,10 +117,121 @@ __global__ void triangulate_dlt_kernel(const float* __restrict__ Kc, const float
     for (int a = 1; a < 4; ++a)
         if (M[a][a] < M[best][best]) best = a;
     const double wv = Q[3][best];
-    float* o = X + idx * 3;
     o[0] = (float)(Q[0][best] / wv);   // (X / X[3])[:3]  (triangulate.py:33-34)
     o[1] = (float)(Q[1][best] / wv);
     o[2] = (float)(Q[2][best] / wv);
+}
+
+__global__ void triangulate_dlt_kernel(const float* __restrict__ Kc, const float* __restrict__ Rc,
+                                       const float* __restrict__ tc, const float* __restrict__ kp, float* __restrict__ X,
+                                       long T, int V, int J) {
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= T * J) return;
+    const long t = idx / J;
+    const int j = (int)(idx - t * J);
+    dlt_point(Kc, Rc, tc, kp, t, j, V, J, X + idx * 3);
+}
+
+// Triangulation with a verdict (reproject_and_visualize, vggt/reproject.py:108-144, :334-341; post_triage_single,
+// triangulation/postprocess.py:38-43, :102-121, from two views to V; rules: DESIGN §2 "Triage").  One workgroup per time
+// step, thread j < J owns joint j: the DLT above, then the stored float32 X through every view's own K (R X + t) in
+// float64.  After a barrier thread v < V reduces view v's errors over the joints and thread V the step's report, NaN-aware
+// as nanmean / nanmedian / nanmax, every sum in joint order.
+constexpr int kTriageMaxJ = 32, kTriageMaxV = 8;
+
+// NaN-aware statistics of n <= 32 values: rmse, mean, median, max of the non-NaN ones (all NaN when there is none)
+__device__ inline void nan_stats(const double* x, int n, double* rmse, double* mean, double* median, double* mx) {
+    double s[kTriageMaxJ];
+    int m = 0;
+    double sum = 0, sq = 0, big = -INFINITY;
+    for (int i = 0; i < n; ++i) {
+        const double v = x[i];
+        if (v != v) continue;
+        sum += v;
+        sq += v * v;
+        big = v > big ? v : big;
+        int k = m++;   // insertion sort: n is tiny
+        while (k > 0 && s[k - 1] > v) {
+            s[k] = s[k - 1];
+            --k;
+        }
+        s[k] = v;
+    }
+    const double nan = __longlong_as_double(0x7FF8000000000000LL);
+    if (rmse) *rmse = m ? sqrt(sq / m) : nan;
+    if (mean) *mean = m ? sum / m : nan;
+    if (median) *median = m ? ((m & 1) ? s[m / 2] : (s[m / 2 - 1] + s[m / 2]) / 2.0) : nan;
+    if (mx) *mx = m ? big : nan;
+}
+
+__global__ __launch_bounds__(64) void triangulate_triage_kernel(
+    const float* __restrict__ Kc, const float* __restrict__ Rc, const float* __restrict__ tc, const float* __restrict__ kp,
+    const float* __restrict__ conf, double conf_thr, double err_thresh, int V, int J, float* __restrict__ X,
+    float* __restrict__ X_clean, double* __restrict__ err, double* __restrict__ depth, unsigned char* __restrict__ keep,
+    double* __restrict__ view_stats, double* __restrict__ report) {
+    __shared__ double s_err[kTriageMaxV][kTriageMaxJ];
+    __shared__ double s_em[kTriageMaxJ];
+    __shared__ int s_pos[kTriageMaxJ], s_keep[kTriageMaxJ];
+    const long t = blockIdx.x;
+    const int j = threadIdx.x;
+    if (j < J) {
+        float x[3];
+        dlt_point(Kc, Rc, tc, kp, t, j, V, J, x);
+        bool pos = true, seen = true;
+        double em = 0;
+        for (int v = 0; v < V; ++v) {
+            const float* K = Kc + (t * V + v) * 9;
+            const float* R = Rc + (t * V + v) * 9;
+            const float* tt = tc + (t * V + v) * 3;
+            double c[3], p[3];
+            for (int a = 0; a < 3; ++a) {
+                double s = 0;
+                for (int b = 0; b < 3; ++b) s += (double)R[a * 3 + b] * (double)x[b];
+                c[a] = s + (double)tt[a];
+            }
+            for (int a = 0; a < 3; ++a) {
+                double s = 0;
+                for (int b = 0; b < 3; ++b) s += (double)K[a * 3 + b] * c[b];
+                p[a] = s;
+            }
+            const long o = (t * V + v) * J + j;
+            const double du = p[0] / p[2] - (double)kp[o * 2], dv = p[1] / p[2] - (double)kp[o * 2 + 1];
+            const double e = sqrt(du * du + dv * dv);
+            depth[o] = p[2];
+            err[o] = e;
+            s_err[v][j] = e;
+            em += e;
+            pos = pos && p[2] > 0;
+            if (conf) seen = seen && (double)conf[o] >= conf_thr;
+        }
+        em /= (double)V;
+        const bool k = pos && isfinite(em) && em <= err_thresh && seen;
+        const float nanf_ = __uint_as_float(0x7FC00000u);
+        for (int a = 0; a < 3; ++a) {
+            X[(t * J + j) * 3 + a] = x[a];
+            X_clean[(t * J + j) * 3 + a] = k ? x[a] : nanf_;
+        }
+        keep[t * J + j] = k ? 1 : 0;
+        s_em[j] = em;
+        s_pos[j] = pos;
+        s_keep[j] = k;
+    }
+    __syncthreads();
+    if (j < V) {
+        double* o = view_stats + (t * V + j) * 4;
+        nan_stats(s_err[j], J, o, o + 1, o + 2, o + 3);
+    } else if (j == V) {
+        double* o = report + t * 5;
+        nan_stats(s_em, J, o, nullptr, o + 1, nullptr);
+        int np = 0, nk = 0;
+        for (int i = 0; i < J; ++i) {
+            np += s_pos[i];
+            nk += s_keep[i];
+        }
+        o[2] = (double)np / J;
+        o[3] = (double)nk / J;
+        o[4] = (double)nk;
+    }
 }
 
 }  // namespace skimi
@@ -160,6 +268,21 @@ int skimi_triangulate_dlt(const float* K, const float* R, const float* t, const 
     const long n = steps * joints;
     hipLaunchKernelGGL(triangulate_dlt_kernel, dim3((unsigned)cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, K, R, t,
                        keypoints, joints3d, (long)steps, views, joints);
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
+int skimi_triangulate_triage(const float* K, const float* R, const float* t, const float* keypoints, const float* conf,
+                             double conf_thr, double err_thresh_px, int64_t steps, int32_t views, int32_t joints,
+                             float* joints3d, float* joints3d_clean, double* err, double* depth, uint8_t* keep,
+                             double* view_stats, double* report, void* stream) {
+    SKIMI_CHECK_ARG(K && R && t && keypoints && joints3d && joints3d_clean && err && depth && keep && view_stats && report &&
+                        steps > 0 && steps < ((int64_t)1 << 31) && views >= 2 && views <= kTriageMaxV && joints >= 1 &&
+                        joints <= kTriageMaxJ,
+                    "skimi_triangulate_triage: bad arguments (need 2..8 views, 1..32 joints)");
+    hipLaunchKernelGGL(triangulate_triage_kernel, dim3((unsigned)steps), dim3(64), 0, (hipStream_t)stream, K, R, t, keypoints,
+                       conf, conf_thr, err_thresh_px, views, joints, joints3d, joints3d_clean, err, depth, keep, view_stats,
+                       report);
     SKIMI_LAUNCH_CHECK();
     return SKIMI_OK;
 }

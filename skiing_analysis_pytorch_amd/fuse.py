@@ -69,6 +69,46 @@ _ALPHA_FACTOR[[1, 2, 69]] = 0.85
 _ALPHA_FACTOR[[13, 14, 41, 62]] = 1.15
 
 
+def _savgol_interp(x: np.ndarray, win: int, poly: int) -> np.ndarray:
+    """scipy.signal.savgol_filter(x, win, poly) with its defaults (deriv 0, mode="interp") on a 1-D float64 series of at
+    least `win` samples: interior samples are the centre value of the least-squares polynomial over their window (a
+    fixed FIR filter), the first and last win // 2 samples are read off the polynomial fitted to the first / last
+    window."""
+    n, half = x.shape[0], win // 2
+    if poly >= win:
+        raise ValueError("polyorder must be less than window_length.")
+    A = np.arange(-half, half + 1, dtype=np.float64)[::-1] ** np.arange(poly + 1)[:, None]
+    e0 = np.zeros(poly + 1)
+    e0[0] = 1.0
+    coeffs = np.linalg.lstsq(A, e0, rcond=None)[0]
+    y = np.empty(n, dtype=np.float64)
+    y[half:n - half] = np.convolve(x, coeffs, mode="valid")
+    grid = np.arange(win)
+    if half:
+        y[:half] = np.polyval(np.polyfit(grid, x[:win], poly), grid[:half])
+        y[n - half:] = np.polyval(np.polyfit(grid, x[n - win:], poly), grid[win - half:])
+    return y
+
+
+def smooth_skeleton(X: np.ndarray, win: int = 9, poly: int = 2) -> np.ndarray:
+    """triangulation/postprocess.py:54-67 on a [T, J, 3] array: Savitzky-Golay smoothing over time of every (joint,
+    coordinate) series, NaN-aware: only the finite samples of a series are filtered (as one contiguous series), and only
+    if there are at least `win` of them.  The window is the reference's min(odd(win), max(1 if T is odd else T - 1, 3)),
+    which is 3 for every odd T (its quirk, reproduced).  Host NumPy like temporal_smooth_ema: O(T J), sequential per
+    series."""
+    X = np.asarray(X, dtype=np.float64)
+    Xs = X.copy()
+    T, J, C = X.shape
+    win = min(win if win % 2 == 1 else win + 1, max(1 if T % 2 == 1 else T - 1, 3))
+    for j in range(J):
+        for c in range(C):
+            vec = X[:, j, c]
+            mask = np.isfinite(vec)
+            if mask.sum() >= win:
+                Xs[mask, j, c] = _savgol_interp(vec[mask], win, poly)
+    return Xs
+
+
 def temporal_smooth_ema(X: np.ndarray, target_ids: Sequence[int] = None, alpha: float = 0.7, adaptive: bool = True,
                         alpha_min: float = 0.45, alpha_max: float = 0.92, speed_gain: float = 0.25) -> np.ndarray:
     """fuse/fuse.py:329-412 on a [T, J, 3] array (NaN rows = missing joints): an exponential moving average

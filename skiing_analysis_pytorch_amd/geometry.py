@@ -1,16 +1,19 @@
 """Device-side geometry post-processing (C-ABI: skimi_pose_to_cameras, skimi_unproject_depth,
-skimi_triangulate_dlt, and the point-to-plane ICP: skimi_estimate_normals, skimi_icp_correspondences,
+skimi_triangulate_dlt, skimi_triangulate_triage, the person origin: skimi_person_origin, skimi_recenter_cameras,
+and the point-to-plane ICP: skimi_estimate_normals, skimi_icp_correspondences,
 skimi_icp_point_to_plane; the bundle adjustment: skimi_bundle_adjust) plus the small host helpers of the reference's
 VGGT wrapper.
 
 Reference: vggt/vggt/utils/pose_enc.py:62-124, rotation.py:14-44, geometry.py:15-117,
-vggt/triangulate.py:13-71, vggt/vggt/infer.py:107-155, vggt/multi_view_process.py:427-520 (ICP),
+vggt/triangulate.py:13-71, vggt/reproject.py:108-144 + triangulation/postprocess.py:70-121 (triage),
+vggt/multi_view_process.py:195-217 + :356-395 (person origin), vggt/vggt/infer.py:107-155, vggt/multi_view_process.py:427-520 (ICP),
 :523-564 + bundle_adjustment/loss.py (bundle adjustment).
 """
 from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -61,6 +64,131 @@ def triangulate_joints(K: torch.Tensor, R: torch.Tensor, t: torch.Tensor, keypoi
     check(lib().skimi_triangulate_dlt(ptr(K), ptr(R), ptr(t), ptr(kp), ptr(out), T, V, J, _lib.current_stream()),
           "skimi_triangulate_dlt")
     return out
+
+
+class TriageResult(NamedTuple):
+    """triangulate_triage's outputs (device tensors; T steps, V views, J joints)."""
+    X: torch.Tensor            # float32 [T, J, 3]: triangulate_joints' result
+    X_clean: torch.Tensor      # float32 [T, J, 3]: X where kept, NaN elsewhere
+    err: torch.Tensor          # float64 [T, V, J]: reprojection error in pixels
+    depth: torch.Tensor        # float64 [T, V, J]: depth of X in each view's camera
+    keep: torch.Tensor         # bool [T, J]
+    view_stats: torch.Tensor   # float64 [T, V, 4]: VIEW_STAT_FIELDS of err over the joints (NaN-aware)
+    report: torch.Tensor       # float64 [T, 5]: rmse_px, median_err_px, pos_depth_ratio, kept_ratio, kept_count (postprocess.py:115-121)
+
+
+VIEW_STAT_FIELDS = ("rmse", "mean_err", "median_err", "max_err")   # vggt/reproject.py:334-341
+
+
+def triage_launch(K, R, t, kp, conf, conf_thr, err_thresh_px):
+    """the launch of triangulate_triage on prepared float32 device tensors; keep stays uint8 (it travels in the packed
+    all-gather of infer.process_multi_view_clip that way)"""
+    if kp.dim() != 4 or kp.shape[-1] != 2:
+        raise ValueError(f"triangulate_triage: keypoints must be [T, V, J, 2], got {list(kp.shape)}")
+    T, V, J, _ = kp.shape
+    dev = kp.device
+    want = {"K": (T, V, 3, 3), "R": (T, V, 3, 3), "t": (T, V, 3), "keypoints": (T, V, J, 2), "conf": (T, V, J)}
+    for name, a in (("K", K), ("R", R), ("t", t), ("keypoints", kp), ("conf", conf)):
+        if a is None:
+            continue
+        if not a.is_cuda or a.device != dev:
+            raise _lib.SkimiError(f"triangulate_triage needs device tensors on one device ({name} is on {a.device})")
+        if tuple(a.shape) != want[name] or a.dtype != torch.float32 or not a.is_contiguous():
+            raise ValueError(f"triangulate_triage: {name} must be contiguous float32 {list(want[name])}, got {a.dtype} "
+                             f"{list(a.shape)}")
+    X = torch.empty((T, J, 3), dtype=torch.float32, device=dev)
+    Xc = torch.empty((T, J, 3), dtype=torch.float32, device=dev)
+    err = torch.empty((T, V, J), dtype=torch.float64, device=dev)
+    depth = torch.empty((T, V, J), dtype=torch.float64, device=dev)
+    keep = torch.empty((T, J), dtype=torch.uint8, device=dev)
+    vs = torch.empty((T, V, 4), dtype=torch.float64, device=dev)
+    rep = torch.empty((T, 5), dtype=torch.float64, device=dev)
+    check(lib().skimi_triangulate_triage(ptr(K), ptr(R), ptr(t), ptr(kp), ptr(conf), float(conf_thr), float(err_thresh_px),
+                                         T, V, J, ptr(X), ptr(Xc), ptr(err), ptr(depth), ptr(keep), ptr(vs), ptr(rep),
+                                         _lib.current_stream()), "skimi_triangulate_triage")
+    return X, Xc, err, depth, keep, vs, rep
+
+
+def triangulate_triage(K: torch.Tensor, R: torch.Tensor, t: torch.Tensor, keypoints: torch.Tensor, conf=None,
+                       conf_thr: float = 0.3, err_thresh_px: float = 2.0) -> TriageResult:
+    """triangulate_joints with a verdict, in one launch: K, R [T, V, 3, 3], t [T, V, 3], keypoints [T, V, J, 2] (pixels),
+    conf [T, V, J] detector scores or None -> TriageResult (unpacks as X, X_clean, err, depth, keep, view_stats, report).
+    Every view is projected through its own (K, R, t): err = ||K (R X + t) / depth - keypoint||, em = mean over the views;
+    a joint is kept iff every depth > 0, em is finite and <= err_thresh_px, and every score >= conf_thr
+    (post_triage_single, triangulation/postprocess.py:70-121, from two views to V).  2 <= V <= 8, 1 <= J <= 32."""
+    for a in (K, R, t, keypoints) + (() if conf is None else (conf,)):
+        if not a.is_cuda:
+            raise _lib.SkimiError("triangulate_triage needs device tensors")
+    K, R, t = (a.contiguous().to(torch.float32) for a in (K, R, t))
+    kp = keypoints.contiguous().to(torch.float32)
+    if conf is not None:
+        conf = conf.contiguous().to(torch.float32)
+    X, Xc, err, depth, keep, vs, rep = triage_launch(K, R, t, kp, conf, conf_thr, err_thresh_px)
+    return TriageResult(X, Xc, err, depth, keep.bool(), vs, rep)
+
+
+@dataclass
+class PersonOrigin:
+    """person_origin's outputs (device tensors, one entry per map; lead = the maps' leading shape)."""
+    origin: torch.Tensor    # float64 [..., 3]: mean of the kept points; NaN where nothing was kept
+    n_valid: torch.Tensor   # int64 [...]: finite points inside the box
+    n_kept: torch.Tensor    # int64 [...]: of those, within 3 sigma of the median depth
+    median: torch.Tensor    # float64 [...]
+    std: torch.Tensor       # float64 [...]
+    stats: torch.Tensor     # float64 [..., 8]: the kernel's record (n_box, n_valid, n_kept, median, std, origin)
+
+
+def person_stats(points: torch.Tensor, boxes: torch.Tensor, source_size) -> torch.Tensor:
+    """the launch of person_origin: points [M, H, W, 3], boxes [M, 4], float32, contiguous, device -> stats [M, 8]"""
+    M, H, W, _ = points.shape
+    stats = torch.empty((M, 8), dtype=torch.float64, device=points.device)
+    nws = int(lib().skimi_person_workspace_bytes(M, H, W))
+    ws = torch.empty(nws, dtype=torch.uint8, device=points.device) if nws else None
+    check(lib().skimi_person_origin(ptr(points), ptr(boxes), M, H, W, int(source_size[0]), int(source_size[1]), ptr(ws),
+                                    ptr(stats), _lib.current_stream()), "skimi_person_origin")
+    return stats
+
+
+def person_origin(point_maps: torch.Tensor, boxes: torch.Tensor, source_size) -> PersonOrigin:
+    """The person-centred origin of dense world-point maps (extract_person_points + the mean its caller takes,
+    vggt/multi_view_process.py:356-395, :195-199) without leaving the device: point_maps [..., H, W, 3], boxes [..., 4]
+    = (x1, y1, x2, y2) in the pixels of the `source_size` = (height, width) image the detector saw.  Per map: the
+    pixels inside the scaled box, finite, within 3 sigma of their median depth (exact median, float64 statistics;
+    DESIGN §2 "Person origin") -> their float64 mean."""
+    if not point_maps.is_cuda or not boxes.is_cuda:
+        raise _lib.SkimiError("person_origin needs device tensors")
+    if point_maps.dim() < 3 or point_maps.shape[-1] != 3:
+        raise _lib.SkimiError(f"person_origin: point_maps must be [..., H, W, 3], got {tuple(point_maps.shape)}")
+    lead = tuple(point_maps.shape[:-3])
+    if tuple(boxes.shape) != lead + (4,):
+        raise _lib.SkimiError(f"person_origin: boxes must be {list(lead + (4,))}, got {list(boxes.shape)}")
+    H, W = point_maps.shape[-3:-1]
+    p = point_maps.reshape(-1, H, W, 3).contiguous().to(torch.float32)
+    b = boxes.reshape(-1, 4).contiguous().to(torch.float32)
+    stats = person_stats(p, b, source_size).reshape(*lead, 8)
+    return PersonOrigin(stats[..., 5:8], stats[..., 1].to(torch.int64), stats[..., 2].to(torch.int64), stats[..., 3],
+                        stats[..., 4], stats)
+
+
+def recenter_cameras(stats: torch.Tensor, extrinsic: torch.Tensor):
+    """The camera update that follows the person origins (multi_view_process.py:201-217), one small launch: stats
+    [n, S, 8] (PersonOrigin.stats), extrinsic [n, S, 3, 4] float32 -> (origin [n, 3] float64 = mean of the S origins in
+    view order, zero if a view kept nothing; R [n, S, 3, 3], t [n, S, 3] float32 with t_c += R_c origin and, at S = 2,
+    view 1 turned by diag(-1, 1, -1) with its t left as the reference's turn-then-mirror leaves it)."""
+    if not stats.is_cuda or not extrinsic.is_cuda:
+        raise _lib.SkimiError("recenter_cameras needs device tensors")
+    n, S = extrinsic.shape[:2]
+    if tuple(stats.shape) != (n, S, 8) or tuple(extrinsic.shape[2:]) != (3, 4):
+        raise ValueError(f"recenter_cameras: need stats [n, S, 8] and extrinsic [n, S, 3, 4], got {list(stats.shape)}, "
+                         f"{list(extrinsic.shape)}")
+    stats = stats.contiguous().to(torch.float64)
+    E = extrinsic.contiguous().to(torch.float32)
+    origin = torch.empty((n, 3), dtype=torch.float64, device=E.device)
+    R = torch.empty((n, S, 3, 3), dtype=torch.float32, device=E.device)
+    t = torch.empty((n, S, 3), dtype=torch.float32, device=E.device)
+    check(lib().skimi_recenter_cameras(ptr(stats), ptr(E), n, S, ptr(origin), ptr(R), ptr(t), _lib.current_stream()),
+          "skimi_recenter_cameras")
+    return origin, R, t
 
 
 # ---- point-to-plane ICP (Open3D's estimate_normals + registration_icp, restated; DESIGN §2 "ICP") ------------

@@ -172,13 +172,16 @@ class CameraHead:
         return self.reconstruct_batch([frame_id], [imgs])[0]
 
     @torch.no_grad()
-    def reconstruct_batch(self, frame_ids: Sequence[int], steps: Sequence[List[torch.Tensor]], write: Optional[Sequence[bool]] = None):
+    def reconstruct_batch(self, frame_ids: Sequence[int], steps: Sequence[List[torch.Tensor]], write: Optional[Sequence[bool]] = None,
+                          dense_to_host: bool = True):
         """`reconstruct_from_frames` for several independent time steps in ONE model call (B = len(steps),
         every step S frames of one source size): the steps of a clip are independent
         (vggt/multi_view_process.py:133), and batching them is what fills the chip.  Returns one
         reconstruct_from_frames tuple per step; per step `<outdir>/frame_XXXX/predictions.npz` holds the
         camera arrays of the reference's predictions.npz (vggt/save.py:52-56; the dense maps are returned,
-        not written: the per-frame PNG / GLB / dense dumps are out of scope)."""
+        not written: the per-frame PNG / GLB / dense dumps are out of scope).  dense_to_host=False skips the host copy
+        of the world points (26 MB at B = 4, S = 2, 518 x 518): that tuple slot is then None, and `last_world_points`
+        still holds the device copy."""
         B, S = len(steps), len(steps[0])
         H, W = steps[0][0].shape[:2]
         flat = [im for st in steps for im in st]
@@ -194,7 +197,8 @@ class CameraHead:
         E, K = geometry.pose_encoding_to_extri_intri(preds["pose_enc"], (oh, ow))
         wp = torch.stack([geometry.unproject_depth_map_to_point_map(preds["depth"][b], E[b], K[b]) for b in range(B)])
         self.last_world_points = wp   # the device copy of the returned maps [B, S, H, W, 3] (the ICP of process_multi_view_video)
-        En, Kn, wpn, pen = E.cpu().numpy(), K.cpu().numpy(), wp.cpu().numpy(), preds["pose_enc"].cpu().numpy()
+        En, Kn, pen = E.cpu().numpy(), K.cpu().numpy(), preds["pose_enc"].cpu().numpy()
+        wpn = wp.cpu().numpy() if dense_to_host else [None] * B
         out = []
         for b in range(B):
             R, t, C = self.extrinsic_to_RT(En[b])
@@ -233,7 +237,9 @@ def _side_streams(dev, n):
 
 @torch.no_grad()
 def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.Tensor, steps_per_call: int = 4,
-                            want_dense: bool = False, streams: int = 1, smooth: bool = False) -> Dict[str, torch.Tensor]:
+                            want_dense: bool = False, streams: int = 1, smooth: bool = False, boxes: Optional[torch.Tensor] = None,
+                            scores: Optional[torch.Tensor] = None, source_size=None, triage: bool = False,
+                            conf_thr: float = 0.3, err_thresh_px: float = 2.0) -> Dict[str, torch.Tensor]:
     """The hot loop of process_multi_view_video (vggt/multi_view_process.py:133-309) for a clip
     already in memory: frames [T, S, 3, H, W] in [0,1] (device), keypoints [T, S, J, 2] in the
     pixels of the H x W frames.  Per time step: one S-view VGGT call -> cameras -> DLT
@@ -247,11 +253,39 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
     streams > 1: the calls of this rank (chunks of steps_per_call time steps, independent of each
     other) are issued from that many host threads on as many HIP streams, so the HBM-bound phases of
     one call (GEMM store bursts, LayerNorm, upsamples) overlap the MFMA-bound phases of another:
-    measured +5.5 % frames/s at 2 x 4 time steps in flight on one MI355X (tools/two_streams.py)."""
+    measured +5.5 % frames/s at 2 x 4 time steps in flight on one MI355X (tools/two_streams.py).
+
+    boxes [T, S, 4] (device; detector boxes x1, y1, x2, y2 in the pixels of a `source_size` = (height, width) image,
+    default the frames' own H x W): the joints come out in the reference's person-centred frame
+    (multi_view_process.py:176-217).  The call then also asks the model for depth, unprojects it, takes the S person
+    origins of the step (geometry.person_origin), moves the world origin onto their mean and, at S = 2, turns view 1
+    (geometry.recenter_cameras); the dict gains "origin" [T, 3] float64 and the cameras the joints were triangulated
+    with, "R" [T, S, 3, 3] and "t" [T, S, 3].  triage=True: geometry.triangulate_triage replaces the plain DLT (scores
+    [T, S, J], optional, are the detector's keypoint scores) and the dict gains "joints3d_clean", "reproj_err" [T, S, J],
+    "keep" [T, J] bool, "view_stats" [T, S, 4], "triage_report" [T, 5]; with smooth=True also
+    "joints3d_clean_smoothed" (fuse.smooth_skeleton).  All of it runs on the device between the model call and the
+    gather, without a host copy or a host wait, and travels in the same single packed all-gather.  Without these
+    arguments the function does what it did before them."""
     T, S = frames.shape[:2]
     H, W = frames.shape[-2:]
     lo, hi, T_pad = parallel.shard_range(T)
     want = {"camera", "depth", "point"} if want_dense else {"camera"}
+    if boxes is not None:
+        want = want | {"depth"}
+        if not boxes.is_cuda or tuple(boxes.shape) != (T, S, 4):
+            raise ValueError(f"process_multi_view_clip: boxes must be a device tensor {[T, S, 4]}, got {list(boxes.shape)} "
+                             f"on {boxes.device}")
+        src = (H, W) if source_size is None else (int(source_size[0]), int(source_size[1]))
+    if scores is not None and not triage:
+        raise ValueError("process_multi_view_clip: scores are only read by triage=True")
+    if boxes is not None or triage:   # these reach the kernels as raw pointers: device tensors of the clip's shape only
+        J = keypoints.shape[2] if keypoints.dim() == 4 else -1
+        if not keypoints.is_cuda or tuple(keypoints.shape) != (T, S, J, 2):
+            raise ValueError(f"process_multi_view_clip: keypoints must be a device tensor [{T}, {S}, J, 2], got "
+                             f"{list(keypoints.shape)} on {keypoints.device}")
+        if scores is not None and (not scores.is_cuda or tuple(scores.shape) != (T, S, J)):
+            raise ValueError(f"process_multi_view_clip: scores must be a device tensor {[T, S, J]}, got "
+                             f"{list(scores.shape)} on {scores.device}")
     starts = list(range(lo, hi, steps_per_call))
 
     n_par = max(1, min(int(streams), len(starts) - 1))
@@ -263,7 +297,31 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
         out = model(frames[idx], want=want)
         E, K = geometry.pose_encoding_to_extri_intri(out["pose_enc"], (H, W))
         R, t = E[..., :3, :3].contiguous(), E[..., :3, 3].contiguous()
-        return geometry.triangulate_joints(K, R, t, keypoints[idx])[:n], E[:n], K[:n]
+        if boxes is None and not triage:
+            return geometry.triangulate_joints(K, R, t, keypoints[idx])[:n], E[:n], K[:n]
+        # from here to the gather nothing crosses to the host and the host waits for nothing: the steps' slices of
+        # boxes / keypoints / scores are taken on the device (a list index would upload an index tensor)
+        # steps a .. b-1, those at or beyond T repeating step T-1 (a chunk of a padded shard may lie wholly beyond T)
+        def steps_of(x):
+            if b <= T:
+                return x[a:b]
+            return torch.cat([x[min(a, T):T], x[T - 1:T].expand(b - max(a, T), *x.shape[1:])])
+
+        extra = []
+        if boxes is not None:
+            depth = out["depth"]
+            oh, ow = depth.shape[2:4]
+            wp = geometry.unproject_depth_map_to_point_map(depth.reshape(n * S, oh, ow, -1), E.reshape(n * S, 3, 4),
+                                                           K.reshape(n * S, 3, 3))
+            stats = geometry.person_stats(wp, steps_of(boxes).reshape(n * S, 4).contiguous().to(torch.float32), src)
+            origin, R, t = geometry.recenter_cameras(stats.view(n, S, 8), E)
+            extra = [origin, R, t]
+        if not triage:
+            return (geometry.triangulate_joints(K, R, t, steps_of(keypoints)), E, K, *extra)
+        kp = steps_of(keypoints).contiguous().to(torch.float32)
+        conf = None if scores is None else steps_of(scores).contiguous().to(torch.float32)
+        X, Xc, err, _depth, keep, vs, rep = geometry.triage_launch(K.contiguous(), R, t, kp, conf, conf_thr, err_thresh_px)
+        return (X, E, K, *extra, Xc, err, keep, vs, rep)
 
     results = [None] * len(starts)
     if n_par <= 1:
@@ -300,17 +358,23 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
         for r in results:   # the side streams' results are read on the caller's stream from here on
             for x in r:
                 x.record_stream(main)
-    joints = torch.cat([r[0] for r in results])
-    Es = torch.cat([r[1] for r in results])
-    Ks = torch.cat([r[2] for r in results])
-    # the path's ONE collective: joints + cameras of this rank's steps as one packed record per step
-    joints, Es, Ks = parallel.all_gather_packed([joints, Es, Ks], T)
-    out = {"joints3d": joints, "extrinsic": Es, "intrinsic": Ks}
+    # the path's ONE collective: joints + cameras (+ origin, triage verdicts) of this rank's steps as one packed record
+    # per step
+    names = ["joints3d", "extrinsic", "intrinsic"] + (["origin", "R", "t"] if boxes is not None else []) + (
+        ["joints3d_clean", "reproj_err", "keep", "view_stats", "triage_report"] if triage else [])
+    parts = parallel.all_gather_packed([torch.cat([r[k] for r in results]) for k in range(len(names))], T)
+    out = dict(zip(names, parts))
+    joints = out["joints3d"]
+    if triage:
+        out["keep"] = out["keep"].bool()
     if smooth:
         # BASELINE config 4: after the gather, fuse/'s temporal smoothing over the whole clip (sequential in t,
         # O(T J) on the host as in the reference: fuse/fuse.py:329-412); every rank holds the same result
         from . import fuse
         out["joints3d_smoothed"] = torch.from_numpy(fuse.temporal_smooth_ema(joints.cpu().numpy().astype(np.float64)))
+        if triage:   # the reference's post_triage_sequence(smooth=True): Savitzky-Golay over the kept joints
+            out["joints3d_clean_smoothed"] = torch.from_numpy(
+                fuse.smooth_skeleton(out["joints3d_clean"].cpu().numpy().astype(np.float64)))
     return out
 
 

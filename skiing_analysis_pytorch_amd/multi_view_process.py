@@ -26,6 +26,15 @@ reference never defines; its parity is unpinned beyond bundle_adjustment/loss.py
 own `run_ba` key is not read: it ships true while the reference never runs BA.  Flag off (the default): the NPZ is
 unchanged.
 
+With `cfg.infer.device_origin` true the person origins come from the device (geometry.person_origin on the world
+points the model call left in HBM; 16 numbers per step cross to the host instead of the dense maps, which
+`reconstruct_batch(dense_to_host=False)` then never copies).  The kept point sets are the host path's; the origin is
+their float64 mean where the host path sums in float32 (DESIGN §2 "Person origin").  With `cfg.infer.triage` true
+geometry.triangulate_triage replaces the plain DLT: the NPZ gains reproj_err, x3d_clean, triage_keep, triage_report and
+reproj_view_stats, and `raw_reprojection_error.txt` holds the per-step errors in the reference's layout (:244-250; its
+`out_path` line names a panel image this build does not draw and is left out).  `cfg.triangulation.conf_thr` /
+`.err_thresh_px` override post_triage_single's defaults (0.3, 2.0).  Both flags are off by default: the NPZ is unchanged.
+
 What it leaves out (out of scope): video decode (frames come from the `.pt` files, which
 `prepare_dataset` can embed; the video paths only name the subject), PNG / GLB / matplotlib output and the
 bundle adjustment's images (:566-627).  The time steps are independent: they go through the HIP model `steps_per_call` at a
@@ -156,6 +165,18 @@ def run_local_ba(K_torch, R_init_torch, t_init_torch, X3d_init_torch, x2d_torch,
     return r.R, r.t, r.X, r.history
 
 
+def write_reprojection_errors(path: Path, view_stats: np.ndarray) -> None:
+    """`raw_reprojection_error.txt` in the reference's layout (multi_view_process.py:244-250): per step a header line and
+    the scalar entries of reproject_and_visualize's dict (vggt/reproject.py:334-341) in its order -- rmse_L, rmse_R,
+    mean_err_L, ... max_err_R.  view_stats [T, 2, 4] (geometry.triangulate_triage)."""
+    with open(path, "w") as f:
+        for i, step in enumerate(view_stats):
+            f.write(f"Frame {i:04d} Reprojection Error (in pixels):\n")
+            for k, field in enumerate(geometry.VIEW_STAT_FIELDS):
+                for v, side in enumerate("LR"):
+                    f.write(f"  {field}_{side}: {float(step[v, k])}\n")
+
+
 def _bbox_of(bboxes: np.ndarray, idx: int):
     b = bboxes[idx]
     return b if b.ndim == 1 else b[0]
@@ -197,18 +218,33 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
     source_size = tuple(lf.shape[1:3])
     icp = bool(cfg_get(cfg, "infer.icp", False))
     ba = bool(cfg_get(cfg, "infer.ba", False))
+    device_origin = bool(cfg_get(cfg, "infer.device_origin", False))
+    triage = bool(cfg_get(cfg, "infer.triage", False))
+    conf_thr = float(cfg_get(cfg, "triangulation.conf_thr", 0.3))
+    err_thresh_px = float(cfg_get(cfg, "triangulation.err_thresh_px", 2.0))
     x3d_l, K_l, R_l, t_l, C_l = [], [], [], [], []
+    triage_l = []   # per call: X_clean, err, keep (uint8), view_stats, report on the device
     for a in range(lo, hi, steps_per_call):
         idx = [min(i, T - 1) for i in range(a, min(a + steps_per_call, hi))]     # padded steps repeat the last one
         # a padded step (index >= T on the last ranks) is computed to keep the collective uniform, but does not
         # write frame_{T-1}/predictions.npz a second time
         write = [i < T for i in range(a, min(a + steps_per_call, hi))]
-        recs = head.reconstruct_batch(idx, [[lf[i], rf[i]] for i in idx], write=write)
+        if device_origin:
+            recs = head.reconstruct_batch(idx, [[lf[i], rf[i]] for i in idx], write=write, dense_to_host=False)
+            bx = np.stack([np.stack([_bbox_of(lb, i), _bbox_of(rb, i)]) for i in idx]).astype(np.float32)
+            po = geometry.person_origin(head.last_world_points[:, :2], torch.from_numpy(bx).to(head.device), source_size)
+            po_stats = po.stats.cpu().numpy()   # [n, 2, 8]: the only numbers of the dense maps that reach the host
+        else:
+            recs = head.reconstruct_batch(idx, [[lf[i], rf[i]] for i in idx], write=write)
         Ks, Rs, ts = [], [], []
         for b, (i, (_E, K_res, R, t, C, wp)) in enumerate(zip(idx, recs)):
-            pl = extract_person_points(wp[0], _bbox_of(lb, i), source_size)
-            pr = extract_person_points(wp[1], _bbox_of(rb, i), source_size)
-            origin = 0.5 * (pl.mean(axis=0) + pr.mean(axis=0)) if len(pl) and len(pr) else np.zeros(3)
+            if device_origin:
+                kept_both = po_stats[b, 0, 2] > 0 and po_stats[b, 1, 2] > 0
+                origin = 0.5 * (po_stats[b, 0, 5:8] + po_stats[b, 1, 5:8]) if kept_both else np.zeros(3)
+            else:
+                pl = extract_person_points(wp[0], _bbox_of(lb, i), source_size)
+                pr = extract_person_points(wp[1], _bbox_of(rb, i), source_size)
+                origin = 0.5 * (pl.mean(axis=0) + pr.mean(axis=0)) if len(pl) and len(pr) else np.zeros(3)
             R2, t2 = recenter_and_align(R, t, origin)
             if icp:   # :263-275: ICP of view 0's map onto view 1's (the device copy of wp), then R[1], t[1] updated
                 wpd = head.last_world_points[b]
@@ -222,7 +258,13 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
         Rd = torch.from_numpy(np.stack(Rs)).to(head.device, torch.float32)
         td = torch.from_numpy(np.stack(ts)).to(head.device, torch.float32)
         kp = torch.from_numpy(np.stack([np.stack([lk[i], rk[i]]) for i in idx])).to(head.device, torch.float32)
-        x3d_l.append(geometry.triangulate_joints(Kd, Rd, td, kp))          # [n, 17, 3] on the device
+        if triage:
+            conf = torch.from_numpy(np.stack([np.stack([ls[i], rs[i]]) for i in idx])).to(head.device, torch.float32)
+            X, Xc, err, _depth, keep, vs, rep = geometry.triage_launch(Kd, Rd, td, kp, conf, conf_thr, err_thresh_px)
+            x3d_l.append(X)
+            triage_l.append((Xc, err, keep, vs, rep))
+        else:
+            x3d_l.append(geometry.triangulate_joints(Kd, Rd, td, kp))          # [n, 17, 3] on the device
         K_l += Ks
         R_l += Rs
         t_l += ts
@@ -230,8 +272,10 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
     # (no-op on one rank)
     dev = head.device
     todev = lambda lst: torch.from_numpy(np.stack(lst)).to(dev)   # noqa: E731
-    x3d, Ka, Ra, ta, Ca = (a.cpu().numpy() for a in parallel.all_gather_packed(
-        [torch.cat(x3d_l), todev(K_l), todev(R_l), todev(t_l), todev(C_l)], T))
+    gathered = [a.cpu().numpy() for a in parallel.all_gather_packed(
+        [torch.cat(x3d_l), todev(K_l), todev(R_l), todev(t_l), todev(C_l)]
+        + ([torch.cat([r[k] for r in triage_l]) for k in range(5)] if triage else []), T)]
+    x3d, Ka, Ra, ta, Ca = gathered[:5]
     # fuse/'s temporal smoothing of the gathered joints (BASELINE config 4; fuse/fuse.py:329-412)
     x3d_smoothed = fuse.temporal_smooth_ema(x3d.astype(np.float64)) if cfg_get(cfg, "infer.smooth", True) else None
     if parallel.world()[0] == 0:
@@ -240,6 +284,11 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
         if not icp:
             logger.warning("[Run-MV] cameras / joints are written without the reference's Open3D ICP refinement (icp_refined=False)")
         extra = {"icp_refined": np.array(icp)} | ({"x3d_smoothed": x3d_smoothed} if x3d_smoothed is not None else {})
+        if triage:
+            x3d_clean, reproj_err, keep, view_stats, report = gathered[5:]
+            extra |= {"x3d_clean": x3d_clean, "reproj_err": reproj_err, "triage_keep": keep.astype(bool),
+                      "triage_report": report, "reproj_view_stats": view_stats}
+            write_reprojection_errors(out_dir / "raw_reprojection_error.txt", view_stats)
         if ba:   # the reference's commented-out stage (:321-353), every mode in one launch
             modes, num_iters, lr, weights = ba_settings(cfg)
             x2d = np.stack([np.stack([lk[i], rk[i]]) for i in range(T)]).astype(np.float64)     # (T,C,J,2)

@@ -541,6 +541,67 @@ def gen_ba():
 GENERATORS["ba"] = gen_ba
 
 
+def gen_post_triage():
+    """DESIGN §2 "Triage": the reference's OWN post_triage_sequence (triangulation/postprocess.py:125-170, with
+    post_triage_single and smooth_skeleton) on a synthetic two-view clip -- X_clean without and with smoothing and the
+    per-step reports.  The module imports cv2 and matplotlib at its top and uses neither on this path (dist = None, no
+    plots): empty stand-in modules satisfy the two imports when the real ones are not installed."""
+    import importlib.util
+    import types
+
+    for name in ("cv2", "matplotlib", "matplotlib.pyplot"):
+        try:
+            __import__(name)
+        except ImportError:
+            sys.modules[name] = types.ModuleType(name)
+    if not hasattr(sys.modules["matplotlib"], "pyplot"):
+        sys.modules["matplotlib"].pyplot = sys.modules["matplotlib.pyplot"]
+    spec = importlib.util.spec_from_file_location("ref_postprocess", os.path.join(REF, "triangulation", "postprocess.py"))
+    P = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(P)
+
+    rng = np.random.default_rng(7)
+    Tn, J = 12, 17
+    K1 = np.array([[1000.0, 0, 960], [0, 1005, 540], [0, 0, 1]])
+    K2 = np.array([[990.0, 0, 950], [0, 1000, 545], [0, 0, 1]])
+    a = -0.4
+    R = np.array([[np.cos(a), 0, np.sin(a)], [0, 1, 0], [-np.sin(a), 0, np.cos(a)]])
+    T = np.array([2.0, 0.05, 0.4])
+    X = rng.normal(size=(J, 3)) * [0.4, 0.8, 0.3] + [0, 0, 6.0] + np.cumsum(rng.normal(scale=0.02, size=(Tn, J, 3)), axis=0)
+    X[3, 5] = [0.5, 0.2, -1.0]                 # behind camera 1
+    X[4, 6] = R.T @ (np.array([0.1, 0.1, -2.0]) - T)   # 2 m behind camera 2
+
+    def proj(Kc, Rc, tc, Xf):
+        p = (Xf @ Rc.T + tc) @ Kc.T
+        return p[:, :2] / p[:, 2:3]
+
+    kL = np.stack([proj(K1, np.eye(3), np.zeros(3), X[i]) for i in range(Tn)])
+    kR = np.stack([proj(K2, R, T, X[i]) for i in range(Tn)])
+    kL += rng.normal(scale=0.6, size=kL.shape) * rng.choice([1.0, 5.0], size=(Tn, J, 1), p=[0.75, 0.25])
+    kR += rng.normal(scale=0.6, size=kR.shape)
+    kL[7, 2] = np.nan
+    cL, cR = rng.uniform(0.2, 1.0, (Tn, J)), rng.uniform(0.2, 1.0, (Tn, J))
+    out = dict(X=X, kL=kL, kR=kR, K1=K1, K2=K2, R=R, T=T, confL=cL, confR=cR, conf_thr=np.array(0.3),
+               err_thresh_px=np.array(2.0))
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        for tag, kw in (("conf", dict(confL=cL, confR=cR)), ("noconf", {})):
+            Xc, stats = P.post_triage_sequence(X, kL, kR, K1, K2, R, T, **kw)
+            out[f"{tag}_X_clean"] = Xc
+            out[f"{tag}_report"] = np.array([[s["rmse_px"], s["median_err_px"], s["pos_depth_ratio"], s["kept_ratio"],
+                                              s["kept_count"]] for s in stats])
+        out["conf_X_clean_smoothed"] = P.post_triage_sequence(X, kL, kR, K1, K2, R, T, confL=cL, confR=cR, smooth=True,
+                                                              sg_win=5)[0]
+        out["sg_win"] = np.array(5)
+    path = GOLD / "post_triage.npz"
+    np.savez_compressed(path, **out)
+    print("wrote", path.name, path.stat().st_size, "bytes")
+
+
+GENERATORS["post_triage"] = gen_post_triage
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GENERATORS)
     for w in which:
