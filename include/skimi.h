@@ -475,6 +475,45 @@ int skimi_triangulate_triage(const float* K, const float* R, const float* t, con
                              float* joints3d, float* joints3d_clean, double* err, double* depth, uint8_t* keep,
                              double* view_stats, double* report, void* stream);
 
+/* Outlier-robust triangulation over 2 <= views <= 8 views (1 <= joints <= 32): inputs as skimi_triangulate_triage.  All
+ * arithmetic float64, P_v = K_v [R_v | t_v] as skimi_triangulate_dlt forms it.  Per (step, joint), independent of every other
+ * (rules: DESIGN §2 "Robust triangulation"):
+ *  1. view v is eligible iff both keypoint coordinates are finite and (conf NULL or (double)conf >= conf_thr); fewer than
+ *     two eligible views: the joint fails.
+ *  2. hypotheses: every pair a < b of eligible views in lexicographic order (<= 28), the DLT solution of those two views
+ *     alone (skimi_triangulate_dlt's 4 x 4 Jacobi eigen-solve); one whose system or solution is non-finite is skipped.
+ *  3. scoring of a point X in every eligible view: z_v = third component of P_v (X, 1), e_v = ||(x, y) / z - keypoint||
+ *     (plain division); inlier iff z_v > 0 and e_v <= inlier_px; truncated cost = sum in view order of min(e_v, inlier_px)^2,
+ *     a view with z_v <= 0 or a non-finite e_v counting inlier_px^2.
+ *  4. selection: most inliers, then the smaller cost, then the earlier pair; fewer than two inliers: the joint fails.
+ *  5. refit, up to three rounds: X <- DLT over the inlier set (rows of view v times w_v), scored as in 3; fewer than two
+ *     inliers: the previous X and set are kept (in the first round the winning hypothesis') and the refit stops; set
+ *     unchanged: stop; otherwise the new set is taken.
+ *  6. refine_iters (0..32) Gauss-Newton steps on c(X) = sum over the set of w_v^2 ||pi_v(X) - keypoint_v||^2: 3 x 3 normal
+ *     equations from the analytic Jacobians in view order, LDL^T without pivoting; a step is taken only if it is finite
+ *     and c strictly decreases, otherwise the refinement stops.  The decrease is judged by c(X + d) - c(X) formed from the
+ *     step itself (per view dr . (2 r + dr), with dr the change of the residual), not by comparing two rounded sums, which
+ *     cannot see steps under ~1e-10 and would leave the stopping point to the last bits of the start; d is the step X can
+ *     take in float64, (X + d) - X.  The set is not re-thresholded afterwards.
+ *  7. outputs: joints3d [steps, joints, 3] f32 = X (NaN x 3 for a failed joint); err [steps, views, joints] f64 = e_v of
+ *     the final X for every view with finite keypoints, eligible or not (NaN otherwise; all NaN for a failed joint);
+ *     inlier_views [steps, joints] u8, bit v = view v is in the final set (0: failed); rms_px [steps, joints] f64 =
+ *     sqrt(mean over the set of e_v^2), unweighted; ok [steps, joints] u8 = not failed and popcount(inlier_views) >=
+ *     min_inliers (2..views) and X finite; joints3d_ok = joints3d where ok, NaN elsewhere; view_inlier_ratio [steps, views]
+ *     f64 = over the joints that did not fail, the share with view v in its set (NaN when all failed); report [steps, 4]
+ *     f64 = ok count, ok ratio, mean popcount over the ok joints, rms of rms_px over the ok joints (NaN-aware).
+ *  8. weights: weighted == 0 or conf NULL: w_v = 1; else w_v = min(max(conf, 0), 1), non-finite -> 0
+ *     (VideoPose3D/slove_rt_from_3d.py:88-95).  They act in 5 and 6 only; a set with fewer than two w_v > 0 is refitted and
+ *     refined unweighted.
+ * One launch for all steps, no synchronisation, no allocation, no atomics, every sum in a fixed order: results are bitwise
+ * reproducible and independent of `steps` and of a step's position.  Bad arguments: SKIMI_ERR_ARG before any launch.
+ * The reference has no such stage (its rigs have two cameras). */
+int skimi_triangulate_robust(const float* K, const float* R, const float* t, const float* keypoints, const float* conf,
+                             double conf_thr, double inlier_px, int32_t min_inliers, int32_t refine_iters, int32_t weighted,
+                             int64_t steps, int32_t views, int32_t joints, float* joints3d, double* err,
+                             uint8_t* inlier_views, double* rms_px, uint8_t* ok, float* joints3d_ok,
+                             double* view_inlier_ratio, double* report, void* stream);
+
 /* Person origin of dense point maps (extract_person_points and the mean its caller takes,
  * vggt/multi_view_process.py:356-395, :195-199, which run in NumPy on the host).  points: dev f32 [maps, H, W, 3];
  * boxes: dev f32 [maps, 4] = x1, y1, x2, y2 in the pixels of a src_h x src_w image.  Per map: crop as the reference

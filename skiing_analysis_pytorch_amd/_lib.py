@@ -111,6 +111,8 @@ _SIGNATURES = {
     "skimi_triangulate_dlt": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp]),
     "skimi_triangulate_triage": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int64, C.c_int32, C.c_int32,
                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "skimi_triangulate_robust": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "skimi_person_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "skimi_person_origin": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "skimi_recenter_cameras": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp]),

@@ -1,5 +1,5 @@
 """Device-side geometry post-processing (C-ABI: skimi_pose_to_cameras, skimi_unproject_depth,
-skimi_triangulate_dlt, skimi_triangulate_triage, the person origin: skimi_person_origin, skimi_recenter_cameras,
+skimi_triangulate_dlt, skimi_triangulate_triage, skimi_triangulate_robust, the person origin: skimi_person_origin, skimi_recenter_cameras,
 and the point-to-plane ICP: skimi_estimate_normals, skimi_icp_correspondences,
 skimi_icp_point_to_plane; the bundle adjustment: skimi_bundle_adjust) plus the small host helpers of the reference's
 VGGT wrapper.
@@ -125,6 +125,85 @@ def triangulate_triage(K: torch.Tensor, R: torch.Tensor, t: torch.Tensor, keypoi
         conf = conf.contiguous().to(torch.float32)
     X, Xc, err, depth, keep, vs, rep = triage_launch(K, R, t, kp, conf, conf_thr, err_thresh_px)
     return TriageResult(X, Xc, err, depth, keep.bool(), vs, rep)
+
+
+class RobustResult(NamedTuple):
+    """triangulate_robust's outputs (device tensors; T steps, V views, J joints), in the order of rule 7."""
+    joints3d: torch.Tensor           # float32 [T, J, 3]: the consensus X; NaN x 3 for a failed joint
+    err: torch.Tensor                # float64 [T, V, J]: reprojection error of X in every view with finite keypoints
+    inlier_views: torch.Tensor       # uint8 [T, J]: bit v = view v is in the final inlier set (0: failed)
+    rms_px: torch.Tensor             # float64 [T, J]: sqrt(mean over the set of err^2)
+    ok: torch.Tensor                 # bool [T, J]: not failed, popcount(inlier_views) >= min_inliers, X finite
+    joints3d_ok: torch.Tensor        # float32 [T, J, 3]: joints3d where ok, NaN elsewhere (what fuse.smooth_skeleton takes)
+    view_inlier_ratio: torch.Tensor  # float64 [T, V]: share of the joints that did not fail which hold view v
+    report: torch.Tensor             # float64 [T, 4]: ok count, ok ratio, mean popcount and rms of rms_px over the ok joints
+
+
+ROBUST_MAX_VIEWS, ROBUST_MAX_JOINTS, ROBUST_MAX_REFINE_ITERS = 8, 32, 32
+
+
+def robust_launch(K, R, t, kp, conf, conf_thr, inlier_px, min_inliers, refine_iters, weighted):
+    """the launch of triangulate_robust on prepared float32 device tensors; ok stays uint8 (it travels in the packed
+    all-gather of infer.process_multi_view_clip that way).  Everything is checked before the launch."""
+    if kp.dim() != 4 or kp.shape[-1] != 2:
+        raise ValueError(f"triangulate_robust: keypoints must be [T, V, J, 2], got {list(kp.shape)}")
+    T, V, J, _ = kp.shape
+    if T < 1 or not 2 <= V <= ROBUST_MAX_VIEWS or not 1 <= J <= ROBUST_MAX_JOINTS:
+        raise ValueError(f"triangulate_robust: need T >= 1, 2..{ROBUST_MAX_VIEWS} views and 1..{ROBUST_MAX_JOINTS} joints, "
+                         f"got keypoints {list(kp.shape)}")
+    min_inliers, refine_iters = int(min_inliers), int(refine_iters)
+    if not 2 <= min_inliers <= V:
+        raise ValueError(f"triangulate_robust: min_inliers must be in 2..{V} (the views), got {min_inliers}")
+    if not 0 <= refine_iters <= ROBUST_MAX_REFINE_ITERS:
+        raise ValueError(f"triangulate_robust: refine_iters must be in 0..{ROBUST_MAX_REFINE_ITERS}, got {refine_iters}")
+    if not float(inlier_px) >= 0:
+        raise ValueError(f"triangulate_robust: inlier_px must be >= 0, got {inlier_px}")
+    dev = kp.device
+    want = {"K": (T, V, 3, 3), "R": (T, V, 3, 3), "t": (T, V, 3), "keypoints": (T, V, J, 2), "conf": (T, V, J)}
+    for name, a in (("K", K), ("R", R), ("t", t), ("keypoints", kp), ("conf", conf)):
+        if a is None:
+            continue
+        if not a.is_cuda or a.device != dev:
+            raise _lib.SkimiError(f"triangulate_robust needs device tensors on one device ({name} is on {a.device})")
+        if tuple(a.shape) != want[name] or a.dtype != torch.float32 or not a.is_contiguous():
+            raise ValueError(f"triangulate_robust: {name} must be contiguous float32 {list(want[name])}, got {a.dtype} "
+                             f"{list(a.shape)}")
+    X = torch.empty((T, J, 3), dtype=torch.float32, device=dev)
+    err = torch.empty((T, V, J), dtype=torch.float64, device=dev)
+    inl = torch.empty((T, J), dtype=torch.uint8, device=dev)
+    rms = torch.empty((T, J), dtype=torch.float64, device=dev)
+    ok = torch.empty((T, J), dtype=torch.uint8, device=dev)
+    Xok = torch.empty((T, J, 3), dtype=torch.float32, device=dev)
+    ratio = torch.empty((T, V), dtype=torch.float64, device=dev)
+    rep = torch.empty((T, 4), dtype=torch.float64, device=dev)
+    check(lib().skimi_triangulate_robust(ptr(K), ptr(R), ptr(t), ptr(kp), ptr(conf), float(conf_thr), float(inlier_px),
+                                         min_inliers, refine_iters, 1 if weighted else 0, T, V, J, ptr(X), ptr(err), ptr(inl),
+                                         ptr(rms), ptr(ok), ptr(Xok), ptr(ratio), ptr(rep), _lib.current_stream()),
+          "skimi_triangulate_robust")
+    return X, err, inl, rms, ok, Xok, ratio, rep
+
+
+def triangulate_robust(K: torch.Tensor, R: torch.Tensor, t: torch.Tensor, keypoints: torch.Tensor, conf=None,
+                       conf_thr: float = 0.3, inlier_px: float = 2.0, min_inliers: int = 2, refine_iters: int = 5,
+                       weighted: bool = False) -> RobustResult:
+    """Outlier-robust triangulation in one launch: K, R [T, V, 3, 3], t [T, V, 3], keypoints [T, V, J, 2] (pixels), conf
+    [T, V, J] detector scores or None -> RobustResult.  Per joint: every pair of eligible views (finite keypoint, score >=
+    conf_thr) gives a two-view DLT hypothesis; the one with the most views within inlier_px (then the smaller truncated
+    cost, then the earlier pair) wins; up to three DLT refits over its inlier set, then refine_iters Gauss-Newton steps on
+    the reprojection error of that set.  weighted=True weights refit and refinement by the scores clipped to [0, 1].  A
+    joint with fewer than two agreeing views fails (NaN); `ok` also asks for min_inliers views in the final set.  With
+    every view an inlier, refine_iters=0 and no weighting the result is triangulate_joints'.  Rules: DESIGN §2 "Robust
+    triangulation".  2 <= V <= 8, 1 <= J <= 32, 2 <= min_inliers <= V, 0 <= refine_iters <= 32."""
+    for a in (K, R, t, keypoints) + (() if conf is None else (conf,)):
+        if not a.is_cuda:
+            raise _lib.SkimiError("triangulate_robust needs device tensors")
+    K, R, t = (a.contiguous().to(torch.float32) for a in (K, R, t))
+    kp = keypoints.contiguous().to(torch.float32)
+    if conf is not None:
+        conf = conf.contiguous().to(torch.float32)
+    X, err, inl, rms, ok, Xok, ratio, rep = robust_launch(K, R, t, kp, conf, conf_thr, inlier_px, min_inliers, refine_iters,
+                                                          weighted)
+    return RobustResult(X, err, inl, rms, ok.bool(), Xok, ratio, rep)
 
 
 @dataclass

@@ -239,7 +239,9 @@ def _side_streams(dev, n):
 def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.Tensor, steps_per_call: int = 4,
                             want_dense: bool = False, streams: int = 1, smooth: bool = False, boxes: Optional[torch.Tensor] = None,
                             scores: Optional[torch.Tensor] = None, source_size=None, triage: bool = False,
-                            conf_thr: float = 0.3, err_thresh_px: float = 2.0) -> Dict[str, torch.Tensor]:
+                            conf_thr: float = 0.3, err_thresh_px: float = 2.0, robust: bool = False,
+                            inlier_px: Optional[float] = None, min_inliers: int = 2, refine_iters: int = 5,
+                            weighted: bool = False) -> Dict[str, torch.Tensor]:
     """The hot loop of process_multi_view_video (vggt/multi_view_process.py:133-309) for a clip
     already in memory: frames [T, S, 3, H, W] in [0,1] (device), keypoints [T, S, J, 2] in the
     pixels of the H x W frames.  Per time step: one S-view VGGT call -> cameras -> DLT
@@ -265,7 +267,14 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
     "keep" [T, J] bool, "view_stats" [T, S, 4], "triage_report" [T, 5]; with smooth=True also
     "joints3d_clean_smoothed" (fuse.smooth_skeleton).  All of it runs on the device between the model call and the
     gather, without a host copy or a host wait, and travels in the same single packed all-gather.  Without these
-    arguments the function does what it did before them."""
+    arguments the function does what it did before them.
+
+    robust=True: geometry.triangulate_robust runs as well, on the same cameras (the recentred ones with `boxes`), keypoints
+    and scores (conf_thr as for triage; inlier_px defaults to err_thresh_px; min_inliers, refine_iters, weighted as
+    there), and the dict gains "joints3d_robust", "joints3d_robust_ok", "robust_err" [T, S, J], "inlier_views" [T, J]
+    uint8, "robust_rms_px" [T, J], "robust_ok" [T, J] bool, "view_inlier_ratio" [T, S], "robust_report" [T, 4]; with
+    smooth=True also "joints3d_robust_smoothed" = fuse.smooth_skeleton(joints3d_robust_ok).  "joints3d" and the triage
+    outputs stay what they are: robust and triage are independent and may both be on.  2 <= S <= 8, J <= 32."""
     T, S = frames.shape[:2]
     H, W = frames.shape[-2:]
     lo, hi, T_pad = parallel.shard_range(T)
@@ -276,9 +285,23 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
             raise ValueError(f"process_multi_view_clip: boxes must be a device tensor {[T, S, 4]}, got {list(boxes.shape)} "
                              f"on {boxes.device}")
         src = (H, W) if source_size is None else (int(source_size[0]), int(source_size[1]))
-    if scores is not None and not triage:
-        raise ValueError("process_multi_view_clip: scores are only read by triage=True")
-    if boxes is not None or triage:   # these reach the kernels as raw pointers: device tensors of the clip's shape only
+    if scores is not None and not (triage or robust):
+        raise ValueError("process_multi_view_clip: scores are only read by triage=True or robust=True")
+    if robust:   # what skimi_triangulate_robust would refuse, refused before the model is called
+        inlier_px = float(err_thresh_px if inlier_px is None else inlier_px)
+        min_inliers, refine_iters = int(min_inliers), int(refine_iters)
+        Jk = keypoints.shape[2] if keypoints.dim() == 4 else -1
+        if not 2 <= S <= geometry.ROBUST_MAX_VIEWS or not 1 <= Jk <= geometry.ROBUST_MAX_JOINTS:
+            raise ValueError(f"process_multi_view_clip: robust=True needs 2..8 views and 1..32 joints, got frames "
+                             f"{list(frames.shape)}, keypoints {list(keypoints.shape)}")
+        if not 2 <= min_inliers <= S:
+            raise ValueError(f"process_multi_view_clip: min_inliers must be in 2..{S} (the views), got {min_inliers}")
+        if not 0 <= refine_iters <= geometry.ROBUST_MAX_REFINE_ITERS:
+            raise ValueError(f"process_multi_view_clip: refine_iters must be in 0..{geometry.ROBUST_MAX_REFINE_ITERS}, got "
+                             f"{refine_iters}")
+        if not inlier_px >= 0:
+            raise ValueError(f"process_multi_view_clip: inlier_px must be >= 0, got {inlier_px}")
+    if boxes is not None or triage or robust:   # these reach the kernels as raw pointers: device tensors of the clip's shape only
         J = keypoints.shape[2] if keypoints.dim() == 4 else -1
         if not keypoints.is_cuda or tuple(keypoints.shape) != (T, S, J, 2):
             raise ValueError(f"process_multi_view_clip: keypoints must be a device tensor [{T}, {S}, J, 2], got "
@@ -297,7 +320,7 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
         out = model(frames[idx], want=want)
         E, K = geometry.pose_encoding_to_extri_intri(out["pose_enc"], (H, W))
         R, t = E[..., :3, :3].contiguous(), E[..., :3, 3].contiguous()
-        if boxes is None and not triage:
+        if boxes is None and not triage and not robust:
             return geometry.triangulate_joints(K, R, t, keypoints[idx])[:n], E[:n], K[:n]
         # from here to the gather nothing crosses to the host and the host waits for nothing: the steps' slices of
         # boxes / keypoints / scores are taken on the device (a list index would upload an index tensor)
@@ -316,12 +339,19 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
             stats = geometry.person_stats(wp, steps_of(boxes).reshape(n * S, 4).contiguous().to(torch.float32), src)
             origin, R, t = geometry.recenter_cameras(stats.view(n, S, 8), E)
             extra = [origin, R, t]
-        if not triage:
+        if not triage and not robust:
             return (geometry.triangulate_joints(K, R, t, steps_of(keypoints)), E, K, *extra)
         kp = steps_of(keypoints).contiguous().to(torch.float32)
         conf = None if scores is None else steps_of(scores).contiguous().to(torch.float32)
-        X, Xc, err, _depth, keep, vs, rep = geometry.triage_launch(K.contiguous(), R, t, kp, conf, conf_thr, err_thresh_px)
-        return (X, E, K, *extra, Xc, err, keep, vs, rep)
+        Kc = K.contiguous()
+        if triage:
+            X, Xc, err, _depth, keep, vs, rep = geometry.triage_launch(Kc, R, t, kp, conf, conf_thr, err_thresh_px)
+            extra += [Xc, err, keep, vs, rep]
+        else:
+            X = geometry.triangulate_joints(K, R, t, kp)
+        if robust:
+            extra += geometry.robust_launch(Kc, R, t, kp, conf, conf_thr, inlier_px, min_inliers, refine_iters, weighted)
+        return (X, E, K, *extra)
 
     results = [None] * len(starts)
     if n_par <= 1:
@@ -358,15 +388,19 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
         for r in results:   # the side streams' results are read on the caller's stream from here on
             for x in r:
                 x.record_stream(main)
-    # the path's ONE collective: joints + cameras (+ origin, triage verdicts) of this rank's steps as one packed record
+    # the path's ONE collective: joints + cameras (+ origin, triage verdicts, robust joints) of this rank's steps as one packed record
     # per step
     names = ["joints3d", "extrinsic", "intrinsic"] + (["origin", "R", "t"] if boxes is not None else []) + (
-        ["joints3d_clean", "reproj_err", "keep", "view_stats", "triage_report"] if triage else [])
+        ["joints3d_clean", "reproj_err", "keep", "view_stats", "triage_report"] if triage else []) + (
+        ["joints3d_robust", "robust_err", "inlier_views", "robust_rms_px", "robust_ok", "joints3d_robust_ok", "view_inlier_ratio",
+         "robust_report"] if robust else [])
     parts = parallel.all_gather_packed([torch.cat([r[k] for r in results]) for k in range(len(names))], T)
     out = dict(zip(names, parts))
     joints = out["joints3d"]
     if triage:
         out["keep"] = out["keep"].bool()
+    if robust:
+        out["robust_ok"] = out["robust_ok"].bool()
     if smooth:
         # BASELINE config 4: after the gather, fuse/'s temporal smoothing over the whole clip (sequential in t,
         # O(T J) on the host as in the reference: fuse/fuse.py:329-412); every rank holds the same result
@@ -375,6 +409,9 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
         if triage:   # the reference's post_triage_sequence(smooth=True): Savitzky-Golay over the kept joints
             out["joints3d_clean_smoothed"] = torch.from_numpy(
                 fuse.smooth_skeleton(out["joints3d_clean"].cpu().numpy().astype(np.float64)))
+        if robust:   # the same filter over the joints the consensus accepted
+            out["joints3d_robust_smoothed"] = torch.from_numpy(
+                fuse.smooth_skeleton(out["joints3d_robust_ok"].cpu().numpy().astype(np.float64)))
     return out
 
 

@@ -35,6 +35,12 @@ reproj_view_stats, and `raw_reprojection_error.txt` holds the per-step errors in
 `out_path` line names a panel image this build does not draw and is left out).  `cfg.triangulation.conf_thr` /
 `.err_thresh_px` override post_triage_single's defaults (0.3, 2.0).  Both flags are off by default: the NPZ is unchanged.
 
+With `cfg.infer.robust` true geometry.triangulate_robust runs as well (the consensus over the views of DESIGN §2 "Robust
+triangulation"; with the reference's two cameras it can only accept or fail a joint, with more it recovers joints that
+single views got wrong): the NPZ gains x3d_robust, x3d_robust_ok, robust_inlier_views, robust_rms_px and
+robust_view_inlier_ratio.  `cfg.triangulation.inlier_px` (default: err_thresh_px), `.min_inliers` (2), `.refine_iters` (5)
+and `.weighted` (false) are its parameters; x3d and the triage arrays are not touched.  Off by default: the NPZ is unchanged.
+
 What it leaves out (out of scope): video decode (frames come from the `.pt` files, which
 `prepare_dataset` can embed; the video paths only name the subject), PNG / GLB / matplotlib output and the
 bundle adjustment's images (:566-627).  The time steps are independent: they go through the HIP model `steps_per_call` at a
@@ -222,8 +228,14 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
     triage = bool(cfg_get(cfg, "infer.triage", False))
     conf_thr = float(cfg_get(cfg, "triangulation.conf_thr", 0.3))
     err_thresh_px = float(cfg_get(cfg, "triangulation.err_thresh_px", 2.0))
+    robust = bool(cfg_get(cfg, "infer.robust", False))
+    inlier_px = float(cfg_get(cfg, "triangulation.inlier_px", err_thresh_px))
+    min_inliers = int(cfg_get(cfg, "triangulation.min_inliers", 2))
+    refine_iters = int(cfg_get(cfg, "triangulation.refine_iters", 5))
+    weighted = bool(cfg_get(cfg, "triangulation.weighted", False))
     x3d_l, K_l, R_l, t_l, C_l = [], [], [], [], []
     triage_l = []   # per call: X_clean, err, keep (uint8), view_stats, report on the device
+    robust_l = []   # per call: geometry.robust_launch's eight outputs on the device
     for a in range(lo, hi, steps_per_call):
         idx = [min(i, T - 1) for i in range(a, min(a + steps_per_call, hi))]     # padded steps repeat the last one
         # a padded step (index >= T on the last ranks) is computed to keep the collective uniform, but does not
@@ -258,8 +270,11 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
         Rd = torch.from_numpy(np.stack(Rs)).to(head.device, torch.float32)
         td = torch.from_numpy(np.stack(ts)).to(head.device, torch.float32)
         kp = torch.from_numpy(np.stack([np.stack([lk[i], rk[i]]) for i in idx])).to(head.device, torch.float32)
-        if triage:
+        if triage or robust:
             conf = torch.from_numpy(np.stack([np.stack([ls[i], rs[i]]) for i in idx])).to(head.device, torch.float32)
+        if robust:
+            robust_l.append(geometry.robust_launch(Kd, Rd, td, kp, conf, conf_thr, inlier_px, min_inliers, refine_iters, weighted))
+        if triage:
             X, Xc, err, _depth, keep, vs, rep = geometry.triage_launch(Kd, Rd, td, kp, conf, conf_thr, err_thresh_px)
             x3d_l.append(X)
             triage_l.append((Xc, err, keep, vs, rep))
@@ -274,7 +289,8 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
     todev = lambda lst: torch.from_numpy(np.stack(lst)).to(dev)   # noqa: E731
     gathered = [a.cpu().numpy() for a in parallel.all_gather_packed(
         [torch.cat(x3d_l), todev(K_l), todev(R_l), todev(t_l), todev(C_l)]
-        + ([torch.cat([r[k] for r in triage_l]) for k in range(5)] if triage else []), T)]
+        + ([torch.cat([r[k] for r in triage_l]) for k in range(5)] if triage else [])
+        + ([torch.cat([r[k] for r in robust_l]) for k in range(8)] if robust else []), T)]
     x3d, Ka, Ra, ta, Ca = gathered[:5]
     # fuse/'s temporal smoothing of the gathered joints (BASELINE config 4; fuse/fuse.py:329-412)
     x3d_smoothed = fuse.temporal_smooth_ema(x3d.astype(np.float64)) if cfg_get(cfg, "infer.smooth", True) else None
@@ -285,10 +301,14 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
             logger.warning("[Run-MV] cameras / joints are written without the reference's Open3D ICP refinement (icp_refined=False)")
         extra = {"icp_refined": np.array(icp)} | ({"x3d_smoothed": x3d_smoothed} if x3d_smoothed is not None else {})
         if triage:
-            x3d_clean, reproj_err, keep, view_stats, report = gathered[5:]
+            x3d_clean, reproj_err, keep, view_stats, report = gathered[5:10]
             extra |= {"x3d_clean": x3d_clean, "reproj_err": reproj_err, "triage_keep": keep.astype(bool),
                       "triage_report": report, "reproj_view_stats": view_stats}
             write_reprojection_errors(out_dir / "raw_reprojection_error.txt", view_stats)
+        if robust:
+            xr, _err, inl, rms, _ok, xr_ok, ratio, _rep = gathered[-8:]
+            extra |= {"x3d_robust": xr, "x3d_robust_ok": xr_ok, "robust_inlier_views": inl, "robust_rms_px": rms,
+                      "robust_view_inlier_ratio": ratio}
         if ba:   # the reference's commented-out stage (:321-353), every mode in one launch
             modes, num_iters, lr, weights = ba_settings(cfg)
             x2d = np.stack([np.stack([lk[i], rk[i]]) for i in range(T)]).astype(np.float64)     # (T,C,J,2)
