@@ -593,6 +593,54 @@ int skimi_bundle_adjust(const double* K, const double* R0, const double* t0, con
                         double w_bone_length, double w_pose_temporal, int32_t placement, double* R_out, double* t_out,
                         double* X_out, double* history_out, void* ws, size_t ws_bytes, void* stream);
 
+/* Camera resection from 3D points and 2D keypoints (VideoPose3D/slove_rt_from_3d.py: the lifter's joints and each view's
+ * keypoints -> that camera's (R, t); the reference initialises with cv2's EPnP and refines with scipy's least_squares).
+ * Inputs (dev f64): X [n_points, 3]; x2d [views, n_points, 2] pixels; conf [views, n_points] or NULL; K [views, 3, 3] or
+ * NULL (inferred per problem); R0 [groups, views, 3, 3] and t0 [groups, views, 3], both or neither.  The points are cut
+ * into groups = n_points / group_size consecutive groups; a problem is one (group, view) pair, solved by one workgroup
+ * (one wave up to 64 points, up to 1024 threads beyond).  1 <= views <= 8, group_size <= (2^31 - 1) / 3.  All arithmetic float64.  Rules (DESIGN §2
+ * "Resection", restated in tests/resect_restated.py):
+ *  1. a point is used iff X is finite, its keypoint is finite in EVERY view and every view's weight >= min_conf; the weight
+ *     is w = conf with non-finite -> 0, clipped to [0, 1], or 1 when conf is NULL.  Fewer than 6 used points: the problem
+ *     fails (R, t, costs, statistics NaN, err NaN, n_evals 0, success 0; K_out NaN where it was to be inferred).
+ *  2. K NULL: cx, cy = means of the problem's used keypoints, f = 2 max(std_x + 1e-6, std_y + 1e-6), population std in
+ *     two passes.  Of K the entries (0,0), (0,1), (0,2), (1,1), (1,2) are read.
+ *  3. start: R0, t0 when given; else a DLT resection: rays y = K^-1 (x, y, 1), X shifted to its centroid and scaled to mean
+ *     distance sqrt(3), the 12 x 12 A^T A of the rows [Xh, 0, -u Xh], [0, Xh, -v Xh] (unweighted), the eigenvector p of its
+ *     smallest eigenvalue by cyclic Jacobi to convergence, sign such that det M > 0 (M the left 3 x 3 of p as 3 x 4),
+ *     R = U V^T of M = U S V^T, t = p4 3 / trace S, de-normalised.  A non-finite start (or start cost) fails the problem.
+ *  4. residuals r = w (pi(K, R X + t) - x), plain division by z; loss per residual COMPONENT: SKIMI_RESECT_LINEAR, cost
+ *     1/2 sum r^2; SKIMI_RESECT_SOFT_L1 with f = f_scale: z = (r / f)^2, cost 1/2 f^2 sum 2 (sqrt(1 + z) - 1), weight
+ *     rho' = 1 / sqrt(1 + z).
+ *  5. Levenberg-Marquardt on d = (omega, dt), R <- Exp(omega) R, t <- t + dt: H = sum rho' J^T J, g = sum rho' J^T r from
+ *     the analytic Jacobian (dXc / d omega = -[R X]x), (H + lam I) d = -g by LDL^T, lam0 = 1e-3 max diag H.  A trial is
+ *     accepted iff its cost c + dc is finite and <= c (1 + 1e-14), then lam <- lam / 10; else lam <- 10 lam and the trial
+ *     is repeated with the same H, g.  dc is formed from the step itself (the change of each camera point, ray and
+ *     residual: dr (2 r + dr) per component), not as the difference of two rounded sums.  Stop on an accepted step with
+ *     ||d|| <= 1e-14 (1 + ||t||), on lam >= 1e30, or after max_evals cost evaluations.  What is counted is the start and
+ *     every trial (n_evals = 1 + trials); the pass that forms H, g and c afresh at an accepted point is not, so the passes
+ *     over the points are at most about twice max_evals.
+ *  6. outputs (dev, problem-major [groups, views, ...]): R, t, K_out [.., 3, 3]; cost0, cost; n_evals, n_used (the masked
+ *     count), success (i32: not failed and stopped by a criterion other than max_evals); err [views, n_points] f64 = the
+ *     unweighted pixel error of the final pose, NaN for unused points; stats [groups, views, 3] = mean, rms, max of err
+ *     over the used points.
+ * One launch, no synchronisation, no allocation, no atomics; every sum has a fixed order that depends only on a point's
+ * index within its group: a group's results are bitwise the same alone or among others.  ws: at least
+ * skimi_resect_workspace_bytes(...) bytes, which is 0 for this kernel (NULL allowed).  Bad arguments: SKIMI_ERR_ARG before
+ * any launch. */
+#define SKIMI_RESECT_LINEAR 0
+#define SKIMI_RESECT_SOFT_L1 1
+size_t skimi_resect_workspace_bytes(int64_t n_points, int32_t views, int64_t group_size);
+int skimi_resect_cameras(const double* X, const double* x2d, const double* conf, const double* K, const double* R0,
+                         const double* t0, int64_t n_points, int32_t views, int64_t group_size, int32_t loss, double f_scale,
+                         double min_conf, int32_t max_evals, double* R, double* t, double* K_out, double* cost0, double* cost,
+                         int32_t* n_evals, int32_t* n_used, int32_t* success, double* err, double* stats, void* ws,
+                         size_t ws_bytes, void* stream);
+/* The pose of every view relative to view 0 of its group (slove_rt_from_3d.py:252-254), one thread per (group, view):
+ * R, t dev f64 [groups, views, ...] -> R_rel = R_v R_0^T, t_rel = t_v - R_rel t_0. */
+int skimi_relative_pose(const double* R, const double* t, int64_t groups, int32_t views, double* R_rel, double* t_rel,
+                        void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,11 @@ _SIGNATURES = {
     "skimi_bundle_adjust": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                       C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                       C.c_double, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "skimi_resect_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int64]),
+    "skimi_resect_cameras": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_double,
+                                       C.c_double, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
+                                       _vp]),
+    "skimi_relative_pose": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp]),
     "skimi_vggt_create": (_vp, [_vp]),
     "skimi_vggt_destroy": (None, [_vp]),
     "skimi_vggt_set_weight": (C.c_int, [_vp, C.c_char_p, _vp, C.c_int64, C.c_int32]),

@@ -1,13 +1,13 @@
 """Device-side geometry post-processing (C-ABI: skimi_pose_to_cameras, skimi_unproject_depth,
 skimi_triangulate_dlt, skimi_triangulate_triage, skimi_triangulate_robust, the person origin: skimi_person_origin, skimi_recenter_cameras,
 and the point-to-plane ICP: skimi_estimate_normals, skimi_icp_correspondences,
-skimi_icp_point_to_plane; the bundle adjustment: skimi_bundle_adjust) plus the small host helpers of the reference's
-VGGT wrapper.
+skimi_icp_point_to_plane; the bundle adjustment: skimi_bundle_adjust; the camera resection: skimi_resect_cameras,
+skimi_relative_pose) plus the small host helpers of the reference's VGGT wrapper.
 
 Reference: vggt/vggt/utils/pose_enc.py:62-124, rotation.py:14-44, geometry.py:15-117,
 vggt/triangulate.py:13-71, vggt/reproject.py:108-144 + triangulation/postprocess.py:70-121 (triage),
 vggt/multi_view_process.py:195-217 + :356-395 (person origin), vggt/vggt/infer.py:107-155, vggt/multi_view_process.py:427-520 (ICP),
-:523-564 + bundle_adjustment/loss.py (bundle adjustment).
+:523-564 + bundle_adjustment/loss.py (bundle adjustment), VideoPose3D/slove_rt_from_3d.py (resection).
 """
 from __future__ import annotations
 
@@ -423,6 +423,86 @@ def bundle_adjust(K, R, t, X, x2d, conf, modes=("pose_only",), num_iters: int = 
                                     ptr(hist) if hist.numel() else None, ptr(ws), ws.numel(), _lib.current_stream()),
           "skimi_bundle_adjust")
     return [BAResult(m, R_out[p], t_out[p], X_out[p], hist[p]) for p, m in enumerate(modes)]
+
+
+# ---- camera resection (VideoPose3D/slove_rt_from_3d.py; rules: DESIGN §2 "Resection") ------------------------------
+RESECT_LOSSES = {"linear": 0, "soft_l1": 1}
+
+
+class ResectResult(NamedTuple):
+    """resect_cameras' outputs (device tensors; G groups, V views, N points)."""
+    R: torch.Tensor          # float64 [G, V, 3, 3]; NaN for a failed problem
+    t: torch.Tensor          # float64 [G, V, 3]
+    K: torch.Tensor          # float64 [G, V, 3, 3]: the K used (given, or inferred from the problem's keypoints)
+    cost0: torch.Tensor      # float64 [G, V]: cost of the start
+    cost: torch.Tensor       # float64 [G, V]
+    n_evals: torch.Tensor    # int32 [G, V]: cost evaluations, the start's included
+    n_points: torch.Tensor   # int32 [G, V]: the masked count
+    success: torch.Tensor    # bool [G, V]: not failed and stopped by a criterion other than max_evals
+    err: torch.Tensor        # float64 [V, N]: pixel error of the final pose, NaN for unused points
+    mean_err: torch.Tensor   # float64 [G, V]
+    rms_err: torch.Tensor    # float64 [G, V]
+    max_err: torch.Tensor    # float64 [G, V]
+    R_rel: torch.Tensor      # float64 [G, V, 3, 3] = R_v R_0^T
+    t_rel: torch.Tensor      # float64 [G, V, 3] = t_v - R_rel t_0
+
+
+def relative_pose(R: torch.Tensor, t: torch.Tensor):
+    """R [G, V, 3, 3], t [G, V, 3] (float64, device) -> the pose of every view relative to view 0 of its group:
+    R_rel = R_v R_0^T, t_rel = t_v - R_rel t_0 (slove_rt_from_3d.py:252-254), one small launch."""
+    if not R.is_cuda or not t.is_cuda:
+        raise _lib.SkimiError("relative_pose needs device tensors")
+    if R.dim() != 4 or tuple(R.shape[2:]) != (3, 3) or tuple(t.shape) != tuple(R.shape[:2]) + (3,):
+        raise ValueError(f"relative_pose: need R [G, V, 3, 3] and t [G, V, 3], got {list(R.shape)}, {list(t.shape)}")
+    R, t = R.contiguous().to(torch.float64), t.contiguous().to(torch.float64)
+    R_rel, t_rel = torch.empty_like(R), torch.empty_like(t)
+    check(lib().skimi_relative_pose(ptr(R), ptr(t), R.shape[0], R.shape[1], ptr(R_rel), ptr(t_rel), _lib.current_stream()),
+          "skimi_relative_pose")
+    return R_rel, t_rel
+
+
+def resect_cameras(X: torch.Tensor, x2d: torch.Tensor, K=None, conf=None, group_size=None, R0=None, t0=None,
+                   loss: str = "linear", f_scale: float = 1.0, min_conf: float = 0.0, max_evals: int = 200) -> ResectResult:
+    """Each camera's (R, t) from 3D points and their 2D keypoints, in one launch: X [N, 3], x2d [V, N, 2] pixels, K
+    [V, 3, 3] or None (inferred from the keypoints' spread), conf [V, N] detector scores or None -> ResectResult.  The
+    points are cut into N / group_size consecutive groups (default: one group) and every (group, view) pair is solved on
+    its own: group_size = N gives one pose per clip, group_size = J one per step.  Per problem: the points finite in X and
+    in every view's keypoint whose weights (scores clipped to [0, 1]) reach min_conf; a DLT resection as the start unless
+    R0 [G, V, 3, 3], t0 [G, V, 3] are given; Levenberg-Marquardt on the weighted reprojection residuals with loss
+    "linear" or "soft_l1" (scipy's, scale f_scale) until the step vanishes or max_evals cost evaluations are spent (the
+    start and every trial count; the fresh linearisation after an accepted trial does not).
+    Fewer than 6 usable points or a non-finite start: R, t NaN and success False.  Rules: DESIGN §2 "Resection"."""
+    given = [a for a in (X, x2d, K, conf, R0, t0) if a is not None]
+    for a in given:
+        if not isinstance(a, torch.Tensor) or not a.is_cuda:
+            raise _lib.SkimiError("resect_cameras needs device tensors")
+    if loss not in RESECT_LOSSES:
+        raise ValueError(f"resect_cameras: unknown loss {loss!r}; known: {list(RESECT_LOSSES)}")
+    if X.dim() != 2 or X.shape[1] != 3 or x2d.dim() != 3 or x2d.shape[1:] != (X.shape[0], 2):
+        raise ValueError(f"resect_cameras: need X [N, 3] and x2d [V, N, 2], got {list(X.shape)}, {list(x2d.shape)}")
+    if (R0 is None) != (t0 is None):
+        raise ValueError("resect_cameras: R0 and t0 go together")
+    N, V = X.shape[0], x2d.shape[0]
+    gs = N if group_size is None else int(group_size)
+    G = N // gs if gs >= 1 and N >= 1 else 0
+    want = {"K": (V, 3, 3), "conf": (V, N), "R0": (G, V, 3, 3), "t0": (G, V, 3)}
+    for name, a in (("K", K), ("conf", conf), ("R0", R0), ("t0", t0)):
+        if a is not None and tuple(a.shape) != want[name]:
+            raise ValueError(f"resect_cameras: {name} must be {list(want[name])}, got {list(a.shape)}")
+    dev = X.device
+    X, x2d, K, conf, R0, t0 = (None if a is None else a.to(dev, torch.float64).contiguous() for a in (X, x2d, K, conf, R0, t0))
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)     # noqa: E731
+    R, t, Ko, c0, c, err, stats = f64(G, V, 3, 3), f64(G, V, 3), f64(G, V, 3, 3), f64(G, V), f64(G, V), f64(V, N), f64(G, V, 3)
+    ne, npts, ok = i32(G, V), i32(G, V), i32(G, V)
+    nws = int(lib().skimi_resect_workspace_bytes(N, V, gs))
+    ws = torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None
+    check(lib().skimi_resect_cameras(ptr(X), ptr(x2d), ptr(conf), ptr(K), ptr(R0), ptr(t0), N, V, gs, RESECT_LOSSES[loss],
+                                     float(f_scale), float(min_conf), int(max_evals), ptr(R), ptr(t), ptr(Ko), ptr(c0), ptr(c),
+                                     ptr(ne), ptr(npts), ptr(ok), ptr(err), ptr(stats), ptr(ws), nws, _lib.current_stream()),
+          "skimi_resect_cameras")
+    R_rel, t_rel = relative_pose(R, t)
+    return ResectResult(R, t, Ko, c0, c, ne, npts, ok.bool(), err, stats[..., 0], stats[..., 1], stats[..., 2], R_rel, t_rel)
 
 
 # ---- host helpers of the wrapper (small arrays, NumPy as in the reference) -----------------

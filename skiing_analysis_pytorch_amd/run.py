@@ -9,6 +9,9 @@ flip TTA (:1070-1081, common/generators.py:216-239), `evaluate(return_prediction
 `<out_dir>/<video_name>.npy` with the camera-space joints (:1086-1092), and the returned joints turned by
 the dummy H36M camera and rebased in height (:1094-1108).  Left out: training, the
 evaluation protocols, the rendered GIF.  The model call is the HIP `TemporalModel` (vp3d.py).
+
+`solve_rt_from_3d` is the counterpart of VideoPose3D/slove_rt_from_3d.py: the lifter's 3D joints and both views' 2D
+keypoints -> each camera's (R, t) and the pair's relative pose, on the device (geometry.resect_cameras).
 """
 from __future__ import annotations
 
@@ -17,7 +20,7 @@ from pathlib import Path
 import numpy as np
 import torch
 
-from . import formats
+from . import formats, geometry
 from .infer import cfg_get
 from .vp3d import (JOINTS_LEFT, JOINTS_RIGHT, KPS_LEFT, KPS_RIGHT, TemporalModel, merge_augmented,
                    normalize_screen_coordinates, pad_and_augment)
@@ -83,3 +86,60 @@ def run_video_pose_3d(config, pt_path: Path, out_dir: Path, args, model_pos: Tem
     if isinstance(depth, torch.Tensor):
         depth = depth.squeeze()
     return prediction, depth
+
+
+RT_KEYS = ("RL", "tL", "RR", "tR", "R_rel", "t_rel", "K_L", "K_R", "mean_err_L", "median_err_L", "mean_err_R", "median_err_R",
+           "success", "n_points")      # slove_rt_from_3d.py:263-271
+
+
+def solve_rt_from_3d(X3d, x2d_left, x2d_right, conf_left=None, conf_right=None, K_left=None, K_right=None, refine="camera",
+                     huber=0.0, min_conf=0.0, out=None, init="pnp"):
+    """VideoPose3D/slove_rt_from_3d.py's main with its command-line arguments as keywords: X3d (N,3) | (T,J,3), x2d_*
+    (N,2) | (T,J,2), conf_* (N,) | (T,J), K_* (3,3), host arrays or tensors -> dict with the reference's npz keys (host
+    values), written to `out` when given.  One pose per view over the whole clip; loss soft_l1 with f_scale = max(huber, 1)
+    when huber > 0 (:237, :244); an absent K is inferred from that view's masked keypoints (:65-73).  The start is this
+    build's DLT resection where the reference calls cv2's EPnP, and refine="none" returns it.  init="essential" and
+    refine="camera_points" are out of scope (DESIGN §2 "Resection")."""
+    if init == "essential":
+        raise NotImplementedError('init="essential" (cv2 findEssentialMat / recoverPose) is out of scope: DESIGN §2 "Resection"')
+    if refine == "camera_points":
+        raise NotImplementedError('refine="camera_points" (the views no longer decouple) is out of scope: DESIGN §2 "Resection"')
+    if init != "pnp" or refine not in ("none", "camera"):
+        raise ValueError(f"solve_rt_from_3d: init {init!r} / refine {refine!r}; known: pnp; none, camera")
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def up(a, last):       # to_Nx (:47-63) + upload
+        a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
+        if a.dim() not in (2, 3) if last else a.dim() not in (1, 2):
+            raise ValueError(f"Bad shape {tuple(a.shape)}")
+        return (a.reshape(-1, last) if last else a.reshape(-1)).to(dev, torch.float64)
+
+    X = up(X3d, 3)
+    x2d = torch.stack([up(x2d_left, 2), up(x2d_right, 2)])
+    conf = None
+    if conf_left is not None or conf_right is not None:
+        conf = torch.stack([torch.ones_like(X[:, 0]) if c is None else up(c, 0) for c in (conf_left, conf_right)])
+    kw = dict(conf=conf, loss="soft_l1" if huber > 0 else "linear", f_scale=max(float(huber), 1.0), min_conf=float(min_conf))
+    Ks = [None if k is None else up(k, 3).reshape(3, 3) for k in (K_left, K_right)]
+    if Ks[0] is None and Ks[1] is None:
+        K = None
+    elif Ks[0] is None or Ks[1] is None:
+        # one K given: the other is the one a call without K infers for that view from the points rule 1 keeps.  That is a
+        # second launch (mask, K, start and one linearisation of both views: one pass set over the clip) spent so that the
+        # mask and the two-pass std stay the kernel's own and are not restated here
+        K_inf = geometry.resect_cameras(X, x2d, max_evals=1, **kw).K[0]
+        K = torch.stack([K_inf[v] if k is None else k for v, k in enumerate(Ks)])
+    else:
+        K = torch.stack(Ks)
+    r = geometry.resect_cameras(X, x2d, K=K, max_evals=1 if refine == "none" else 200, **kw)
+    R, t, err = r.R[0].cpu().numpy(), r.t[0].cpu().numpy(), r.err.cpu().numpy()
+    used = ~np.isnan(err)
+    med = [float(np.median(err[v][used[v]])) if used[v].any() else float("nan") for v in range(2)]
+    ok = bool(r.success[0].all()) if refine != "none" else bool(np.isfinite(R).all() and np.isfinite(t).all())
+    res = dict(RL=R[0], tL=t[0], RR=R[1], tR=t[1], R_rel=r.R_rel[0, 1].cpu().numpy(), t_rel=r.t_rel[0, 1].cpu().numpy(),
+               K_L=r.K[0, 0].cpu().numpy(), K_R=r.K[0, 1].cpu().numpy(), mean_err_L=float(r.mean_err[0, 0]), median_err_L=med[0],
+               mean_err_R=float(r.mean_err[0, 1]), median_err_R=med[1], success=int(ok), n_points=int(r.n_points[0, 0]))
+    if out is not None:
+        Path(out).parent.mkdir(parents=True, exist_ok=True)
+        np.savez(out, **res)
+    return res
