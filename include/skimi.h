@@ -641,6 +641,38 @@ int skimi_resect_cameras(const double* X, const double* x2d, const double* conf,
 int skimi_relative_pose(const double* R, const double* t, int64_t groups, int32_t views, double* R_rel, double* t_rel,
                         void* stream);
 
+/* The filtered, coloured point cloud of a time step (predictions_to_glb, vggt/visual_util.py:39-236, which runs in NumPy
+ * on the host).  A scene is one step: n = S H W pixels in view-major, row-major order; all B scenes go through every launch.
+ * Inputs (dev f32): points [B, S, H, W, 3]; conf [B, S, H, W]; images [B, S, 3, H, W] (images_nchw != 0) or
+ * [B, S, H, W, 3]; extrinsic [B, S, 3, 4].  Rules (DESIGN §2 "Scene cloud", restated in tests/scene_restated.py):
+ *  1. colour = (uint8)(float32(v) * 255.0f), truncated toward zero; NaN -> 0, below 0 -> 0, >= 256 -> 255.
+ *  2. thr: conf_thres == 0 -> 0; else the conf_thres-th percentile of the scene's conf by NumPy's `linear` method in float64
+ *     on the exact order statistics: v = q / 100 (n - 1), i = floor(v), g = v - i, lo = s[i], hi = s[min(i + 1, n - 1)],
+ *     d = hi - lo, thr = lo + d g if g < 0.5 else hi - d (1 - g).  The order is that of the order-preserving 32-bit key
+ *     (-0.0 just below +0.0, +-inf ordered).  Any NaN conf: thr = lo = hi = NaN and nothing is kept (thr stays 0 at
+ *     conf_thres == 0, where a NaN conf is merely not kept).
+ *  3. kept: (double)conf >= thr and conf > float32(1e-5); mask_black_bg: R + G + B >= 16; mask_white_bg: not (R, G, B all
+ *     > 240).  Non-finite points are not filtered; their number among the kept is reported.
+ *  4. the kept pixels go to xyz [B, cap, 3] f32 and rgb [B, cap, 3] u8 in pixel order; count [B] i64 is the full number
+ *     kept; beyond row min(count, cap) - 1 nothing is written.
+ *  5. per axis the 5th and 95th percentile (rule 2's lerp) of ALL kept raw vertices -> lower, upper; scale = ||upper -
+ *     lower|| in float64.  A kept NaN in an axis: that axis's percentiles and the scale are NaN.  count == 0: lower = upper =
+ *     NaN, scale = 1.
+ *  6. transform [B, 4, 4] f64 = E0^-1 diag(-1, -1, 1, 1), E0 the 4 x 4 of view 0, its 3 x 3 inverted by the adjugate in
+ *     float64 (a general inverse).  align != 0: the written xyz is float32(A (x, y, z, 1)) formed in float64; else raw.
+ *  7. stats [B, 16] f64 = thr, lo, hi, NaN confs, non-finite kept vertices, lower[3], upper[3], scale, count, 0, 0, 0.
+ * 1 <= n <= (2^31 - 1) / 3, 1 <= B <= 65535, 0 <= conf_thres <= 100, cap >= 1.  workspace: skimi_scene_workspace_bytes(B, n)
+ * bytes (0 for sizes out of range).  skimi_scene_tile(n): the consecutive pixels one workgroup handles per pass;
+ * ceil(n / tile) workgroups per scene.  Ten launches whatever the data, no synchronisation, no allocation, no
+ * floating-point atomics (integer histograms and counters only): results are bitwise reproducible, and a scene's results
+ * are bitwise the same alone or inside a batch.  Bad arguments: SKIMI_ERR_ARG before any launch. */
+int64_t skimi_scene_tile(int64_t n);
+size_t skimi_scene_workspace_bytes(int64_t B, int64_t n);
+int skimi_scene_cloud(const float* points, const float* conf, const float* images, const float* extrinsic, int64_t B, int32_t S,
+                      int32_t H, int32_t W, int32_t images_nchw, double conf_thres, int32_t mask_black_bg, int32_t mask_white_bg,
+                      int32_t align, int64_t cap, void* workspace, float* xyz, uint8_t* rgb, int64_t* count, double* stats,
+                      double* transform, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

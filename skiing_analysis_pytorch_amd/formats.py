@@ -8,8 +8,9 @@ read as the reference's loaders do (vggt/load.py:268-370 `load_info`,
 VideoPose3D/common/custom_dataset.py:106-164), minus the video decode: torchvision / PyAV are
 not part of this build, so frames come from the `.pt` itself when present or from the caller.
 
-Output: `.npy [T,17,3]` of the lifter (VideoPose3D/run.py:1089-1092) and the camera NPZ of the
-VGGT stage (vggt/save.py:84-110, `infer.save_camera_info`).
+Output: `.npy [T,17,3]` of the lifter (VideoPose3D/run.py:1089-1092), the camera NPZ of the
+VGGT stage (vggt/save.py:84-110, `infer.save_camera_info`) and the per-step scene GLB as a point cloud
+(vggt/save.py:58-73; `write_glb_points` / `read_glb_points`, a minimal glTF-2.0 binary of this package's own).
 """
 from __future__ import annotations
 
@@ -163,3 +164,108 @@ def save_predictions_npz(outdir, preds: dict) -> Path:
         arrays[k] = np.asarray(v)
     np.savez(out / "predictions.npz", **arrays)
     return out / "predictions.npz"
+
+
+# ---- GLB point clouds (glTF 2.0 binary; the scene file of vggt/save.py:58-73, points only) ----
+_GLB_MAGIC, _GLB_JSON, _GLB_BIN = 0x46546C67, 0x4E4F534A, 0x004E4942
+
+
+def write_glb_points(path, xyz, rgb) -> Path:
+    """A coloured point cloud as a minimal glTF-2.0 binary: one mesh, one primitive of mode 0 (POINTS); POSITION float32
+    VEC3 with the `min` / `max` the specification requires (taken over the finite coordinates: JSON cannot hold NaN or
+    inf), COLOR_0 normalised unsigned-byte VEC4 with alpha 255.  The JSON chunk is padded with spaces and the BIN chunk
+    with zeros to 4 bytes.  xyz [N, 3], rgb [N, 3] uint8; an empty cloud is written as the reference's single white point
+    (1, 0, 0) (vggt/visual_util.py:194-196).  The bytes are this writer's own, not trimesh's."""
+    import json
+    import struct
+
+    xyz = np.ascontiguousarray(np.asarray(xyz, dtype=np.float32).reshape(-1, 3))
+    rgb = np.asarray(rgb, dtype=np.uint8).reshape(-1, 3)
+    if len(xyz) != len(rgb):
+        raise ValueError(f"write_glb_points: {len(xyz)} vertices but {len(rgb)} colours")
+    if len(xyz) == 0:
+        xyz = np.array([[1.0, 0.0, 0.0]], np.float32)
+        rgb = np.array([[255, 255, 255]], np.uint8)
+    n = len(xyz)
+    rgba = np.full((n, 4), 255, np.uint8)
+    rgba[:, :3] = rgb
+    lo, hi = [], []
+    for a in range(3):
+        col = xyz[:, a][np.isfinite(xyz[:, a])]
+        lo.append(float(col.min()) if col.size else 0.0)
+        hi.append(float(col.max()) if col.size else 0.0)
+    gltf = {
+        "asset": {"version": "2.0", "generator": "skiing_analysis_pytorch_amd"},
+        "scene": 0,
+        "scenes": [{"nodes": [0]}],
+        "nodes": [{"mesh": 0}],
+        "meshes": [{"primitives": [{"attributes": {"POSITION": 0, "COLOR_0": 1}, "mode": 0}]}],
+        "accessors": [
+            {"bufferView": 0, "componentType": 5126, "count": n, "type": "VEC3", "min": lo, "max": hi},
+            {"bufferView": 1, "componentType": 5121, "normalized": True, "count": n, "type": "VEC4"},
+        ],
+        "bufferViews": [
+            {"buffer": 0, "byteOffset": 0, "byteLength": 12 * n, "target": 34962},
+            {"buffer": 0, "byteOffset": 12 * n, "byteLength": 4 * n, "target": 34962},
+        ],
+        "buffers": [{"byteLength": 16 * n}],
+    }
+    js = json.dumps(gltf, separators=(",", ":")).encode("utf-8")
+    js += b" " * (-len(js) % 4)
+    blob = xyz.astype("<f4").tobytes() + rgba.tobytes()
+    blob += b"\0" * (-len(blob) % 4)
+    total = 12 + 8 + len(js) + 8 + len(blob)
+    p = Path(path)
+    with open(p, "wb") as f:
+        f.write(struct.pack("<III", _GLB_MAGIC, 2, total))
+        f.write(struct.pack("<II", len(js), _GLB_JSON))
+        f.write(js)
+        f.write(struct.pack("<II", len(blob), _GLB_BIN))
+        f.write(blob)
+    return p
+
+
+def read_glb_points(path) -> Tuple[np.ndarray, np.ndarray]:
+    """Reader of the point clouds `write_glb_points` writes -> (xyz float32 [N, 3], rgb uint8 [N, 3]).  It follows the
+    accessors of the first primitive (float32 VEC3 POSITION, unsigned-byte VEC3 / VEC4 COLOR_0, tightly packed or strided
+    views of the one embedded buffer); anything else is a ValueError."""
+    import json
+    import struct
+
+    data = Path(path).read_bytes()
+    if len(data) < 20 or struct.unpack_from("<I", data, 0)[0] != _GLB_MAGIC:
+        raise ValueError(f"{path}: not a GLB file")
+    version, total = struct.unpack_from("<II", data, 4)
+    if version != 2 or total != len(data):
+        raise ValueError(f"{path}: GLB version {version}, length {total} in a file of {len(data)} bytes")
+    chunks, off = {}, 12
+    while off + 8 <= total:
+        size, kind = struct.unpack_from("<II", data, off)
+        chunks.setdefault(kind, data[off + 8:off + 8 + size])
+        off += 8 + size
+    if _GLB_JSON not in chunks or _GLB_BIN not in chunks:
+        raise ValueError(f"{path}: needs a JSON and a BIN chunk")
+    gltf, blob = json.loads(chunks[_GLB_JSON].decode("utf-8")), chunks[_GLB_BIN]
+    prim = gltf["meshes"][0]["primitives"][0]
+    if prim.get("mode", 4) != 0:
+        raise ValueError(f"{path}: the first primitive is not a point list")
+
+    def view(index, dtype, width_ok):
+        acc = gltf["accessors"][index]
+        bv = gltf["bufferViews"][acc["bufferView"]]
+        width = {"VEC3": 3, "VEC4": 4}.get(acc["type"])
+        if acc["componentType"] != {"<f4": 5126, "u1": 5121}[dtype] or width not in width_ok:
+            raise ValueError(f"{path}: accessor {index} is {acc['componentType']} {acc['type']}")
+        item = np.dtype(dtype).itemsize * width
+        stride = bv.get("byteStride", item)
+        start = bv.get("byteOffset", 0) + acc.get("byteOffset", 0)
+        count = acc["count"]
+        if count and start + (count - 1) * stride + item > len(blob):
+            raise ValueError(f"{path}: accessor {index} runs past the buffer")
+        rows = np.frombuffer(blob, np.uint8, offset=start, count=(count - 1) * stride + item if count else 0)
+        rows = np.lib.stride_tricks.as_strided(rows, (count, item), (stride, 1)) if count else rows.reshape(0, item)
+        return np.ascontiguousarray(rows).view(dtype).reshape(count, width)
+
+    xyz = view(prim["attributes"]["POSITION"], "<f4", (3,)).astype(np.float32)
+    rgb = view(prim["attributes"]["COLOR_0"], "u1", (3, 4))[:, :3].copy()
+    return xyz, rgb

@@ -1,8 +1,10 @@
 """Counterparts of the reference's VGGT entry points, with the same signatures and return values
-but none of the per-frame PNG / GLB / matplotlib I/O (out of scope: SURVEY §8):
+but none of the per-frame PNG / matplotlib I/O (out of scope: SURVEY §8; the per-step GLB point cloud is
+opt-in: `predictions_to_glb_points`, `CameraHead.reconstruct_batch(scene=True)`):
 
     load_and_preprocess_images        vggt/load.py:38-183
     CameraHead                        vggt/vggt/infer.py:46-215   (run_vggt, reconstruct_from_frames, ...)
+    predictions_to_glb_points         vggt/visual_util.py:39-236  (the point cloud of predictions_to_glb)
     process_multi_view_clip           the hot loop of vggt/multi_view_process.py:133-309
     process_single_view_clip          vggt/single_view_process.py:130-170
 
@@ -108,6 +110,48 @@ def cfg_get(cfg, dotted: str, default=None):
     return cur
 
 
+def predictions_to_glb_points(preds: dict, conf_thres=50.0, prediction_mode: str = "Predicted Pointmap", filter_by_frames="all",
+                              mask_black_bg: bool = False, mask_white_bg: bool = False, mask_sky: bool = False):
+    """The point cloud of the reference's predictions_to_glb (vggt/visual_util.py:39-236) from a prediction dict of DEVICE
+    tensors, [S, ...] as the reference's or [B, S, ...] for B time steps at once -> geometry.SceneCloud (device).  The
+    branch is the reference's (:89-101): "Pointmap" in prediction_mode takes world_points / world_points_conf, or without
+    world_points falls back to world_points_from_depth / depth_conf; any other mode string ("All" included) takes the
+    depth branch.  A missing confidence map is all ones.  conf_thres=None becomes 10 (:77-78).  filter_by_frames="k:..."
+    keeps view k only (:82-87, :158-162), anything unparsable keeps all.  mask_sky needs a downloaded ONNX model and is not
+    part of this build.  The camera cones of show_cam are not built: `scale` and `transform` are returned for a caller who
+    adds them."""
+    if not isinstance(preds, dict):
+        raise ValueError("predictions must be a dictionary")
+    if mask_sky:
+        raise NotImplementedError("mask_sky needs the reference's downloaded sky-segmentation model (skyseg.onnx)")
+    if conf_thres is None:
+        conf_thres = 10.0
+    selected = None
+    if filter_by_frames != "all" and filter_by_frames != "All":
+        try:
+            selected = int(str(filter_by_frames).split(":")[0])
+        except (ValueError, IndexError):
+            pass
+    if "Pointmap" in prediction_mode and "world_points" in preds:
+        points, conf = preds["world_points"], preds.get("world_points_conf")
+    else:
+        points, conf = preds["world_points_from_depth"], preds.get("depth_conf")
+    images, extrinsic = preds["images"], preds["extrinsic"]
+    if points.dim() == 4:   # one time step, the reference's layout
+        points, images, extrinsic = points[None], images[None], extrinsic[None]
+        conf = None if conf is None else conf[None]
+    if conf is None:
+        conf = torch.ones_like(points[..., 0])
+    if selected is not None:
+        S = points.shape[1]
+        if not -S <= selected < S:
+            raise IndexError(f"filter_by_frames: view {selected} of {S}")
+        k = selected % S
+        points, conf, images, extrinsic = (x[:, k:k + 1] for x in (points, conf, images, extrinsic))
+    return geometry.scene_point_cloud(points, conf, images, extrinsic, conf_thres=float(conf_thres), mask_black_bg=mask_black_bg,
+                                      mask_white_bg=mask_white_bg)
+
+
 class CameraHead:
     """Drop-in for vggt.vggt.infer.CameraHead (the reference-side VGGT wrapper)."""
 
@@ -173,15 +217,19 @@ class CameraHead:
 
     @torch.no_grad()
     def reconstruct_batch(self, frame_ids: Sequence[int], steps: Sequence[List[torch.Tensor]], write: Optional[Sequence[bool]] = None,
-                          dense_to_host: bool = True):
+                          dense_to_host: bool = True, scene: bool = False):
         """`reconstruct_from_frames` for several independent time steps in ONE model call (B = len(steps),
         every step S frames of one source size): the steps of a clip are independent
         (vggt/multi_view_process.py:133), and batching them is what fills the chip.  Returns one
         reconstruct_from_frames tuple per step; per step `<outdir>/frame_XXXX/predictions.npz` holds the
         camera arrays of the reference's predictions.npz (vggt/save.py:52-56; the dense maps are returned,
-        not written: the per-frame PNG / GLB / dense dumps are out of scope).  dense_to_host=False skips the host copy
+        not written: the per-frame PNG / dense dumps are out of scope).  dense_to_host=False skips the host copy
         of the world points (26 MB at B = 4, S = 2, 518 x 518): that tuple slot is then None, and `last_world_points`
-        still holds the device copy."""
+        still holds the device copy.  scene=True: one geometry.scene_point_cloud call builds the reference's filtered,
+        coloured cloud of all B steps on the device (`predictions_to_glb_points` with this head's conf_thres and
+        prediction_mode; the point head runs only when the mode asks for it), `last_scene` keeps the device result, and
+        every written step also gets the reference's `scene_conf{conf_thres}_mode{mode}.glb` (vggt/save.py:59-61): only
+        the kept rows cross to the host.  Everything else is what scene=False gives, bitwise."""
         B, S = len(steps), len(steps[0])
         H, W = steps[0][0].shape[:2]
         flat = [im for st in steps for im in st]
@@ -193,10 +241,18 @@ class CameraHead:
         on_dev = all(_rgb8(im) for im in flat)
         imgs = load_and_preprocess_images(flat, device=self.device if on_dev else None).to(self.device)
         oh, ow = imgs.shape[-2:]
-        preds = self.vggt(imgs.view(B, S, 3, oh, ow), want={"camera", "depth"})
+        want = {"camera", "depth"}
+        if scene and "Pointmap" in self.prediction_mode:
+            want = want | {"point"}
+        preds = self.vggt(imgs.view(B, S, 3, oh, ow), want=want)
         E, K = geometry.pose_encoding_to_extri_intri(preds["pose_enc"], (oh, ow))
         wp = torch.stack([geometry.unproject_depth_map_to_point_map(preds["depth"][b], E[b], K[b]) for b in range(B)])
         self.last_world_points = wp   # the device copy of the returned maps [B, S, H, W, 3] (the ICP of process_multi_view_video)
+        if scene:
+            cloud = predictions_to_glb_points(dict(preds, world_points_from_depth=wp, images=imgs.view(B, S, 3, oh, ow), extrinsic=E),
+                                              self.conf_thres, self.prediction_mode)
+            self.last_scene = cloud
+            kept = torch.clamp(cloud.count, max=cloud.xyz.shape[1]).cpu().tolist()
         En, Kn, pen = E.cpu().numpy(), K.cpu().numpy(), preds["pose_enc"].cpu().numpy()
         wpn = wp.cpu().numpy() if dense_to_host else [None] * B
         out = []
@@ -207,6 +263,10 @@ class CameraHead:
                 d = self.outdir / f"frame_{int(frame_ids[b]):04d}"
                 d.mkdir(parents=True, exist_ok=True)
                 np.savez(d / "predictions.npz", extrinsic=En[b], intrinsic=Kn[b], pose_enc=pen[b])
+                if scene:
+                    from . import formats
+                    name = f"scene_conf{self.conf_thres}_mode{self.prediction_mode.replace(' ', '_')}.glb"
+                    formats.write_glb_points(d / name, cloud.xyz[b, :kept[b]].cpu().numpy(), cloud.rgb[b, :kept[b]].cpu().numpy())
             out.append((En[b], K_resized, R, t, C, wpn[b]))
         return out
 

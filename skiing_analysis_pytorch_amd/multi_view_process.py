@@ -42,8 +42,9 @@ robust_view_inlier_ratio.  `cfg.triangulation.inlier_px` (default: err_thresh_px
 and `.weighted` (false) are its parameters; x3d and the triage arrays are not touched.  Off by default: the NPZ is unchanged.
 
 What it leaves out (out of scope): video decode (frames come from the `.pt` files, which
-`prepare_dataset` can embed; the video paths only name the subject), PNG / GLB / matplotlib output and the
-bundle adjustment's images (:566-627).  The time steps are independent: they go through the HIP model `steps_per_call` at a
+`prepare_dataset` can embed; the video paths only name the subject), PNG / matplotlib output, the camera cones and
+sky mask of the scene GLB (its point cloud is written per step with `cfg.infer.scene_glb` true, default false:
+`CameraHead.reconstruct_batch(scene=True)`) and the bundle adjustment's images (:566-627).  The time steps are independent: they go through the HIP model `steps_per_call` at a
 time, sharded over ranks under torch.distributed, and the per-step joints are re-assembled with one
 all-gather (parallel.py).
 """
@@ -229,6 +230,7 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
     conf_thr = float(cfg_get(cfg, "triangulation.conf_thr", 0.3))
     err_thresh_px = float(cfg_get(cfg, "triangulation.err_thresh_px", 2.0))
     robust = bool(cfg_get(cfg, "infer.robust", False))
+    scene_glb = bool(cfg_get(cfg, "infer.scene_glb", False))   # opt-in: the reference's per-step scene GLB (vggt/save.py:58-73)
     inlier_px = float(cfg_get(cfg, "triangulation.inlier_px", err_thresh_px))
     min_inliers = int(cfg_get(cfg, "triangulation.min_inliers", 2))
     refine_iters = int(cfg_get(cfg, "triangulation.refine_iters", 5))
@@ -242,12 +244,12 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
         # write frame_{T-1}/predictions.npz a second time
         write = [i < T for i in range(a, min(a + steps_per_call, hi))]
         if device_origin:
-            recs = head.reconstruct_batch(idx, [[lf[i], rf[i]] for i in idx], write=write, dense_to_host=False)
+            recs = head.reconstruct_batch(idx, [[lf[i], rf[i]] for i in idx], write=write, dense_to_host=False, scene=scene_glb)
             bx = np.stack([np.stack([_bbox_of(lb, i), _bbox_of(rb, i)]) for i in idx]).astype(np.float32)
             po = geometry.person_origin(head.last_world_points[:, :2], torch.from_numpy(bx).to(head.device), source_size)
             po_stats = po.stats.cpu().numpy()   # [n, 2, 8]: the only numbers of the dense maps that reach the host
         else:
-            recs = head.reconstruct_batch(idx, [[lf[i], rf[i]] for i in idx], write=write)
+            recs = head.reconstruct_batch(idx, [[lf[i], rf[i]] for i in idx], write=write, scene=scene_glb)
         Ks, Rs, ts = [], [], []
         for b, (i, (_E, K_res, R, t, C, wp)) in enumerate(zip(idx, recs)):
             if device_origin:

@@ -6,7 +6,8 @@
 Every 30th frame of ONE camera forms a single S = ceil(T / 30) view stack (single_view_process.py:130),
 which goes through `CameraHead.reconstruct_from_frames` once (:152-163); the cameras of those frames are
 written with `save_camera_info` (:171-178, vggt/save.py:84-110).  Left out: the video decode
-(frames come from the `.pt` file when embedded), the per-frame skeleton PNGs, GLB export.
+(frames come from the `.pt` file when embedded), the per-frame skeleton PNGs.  The scene GLB (vggt/save.py:58-73; point
+cloud only) is written with `cfg.infer.scene_glb` true (default false).
 """
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ from pathlib import Path
 from typing import Optional
 
 from . import formats
-from .infer import CameraHead, save_camera_info
+from .infer import CameraHead, cfg_get, save_camera_info
 
 logger = logging.getLogger(__name__)
 
@@ -39,7 +40,8 @@ def process_single_view_video(video_path: Path, pt_path: Path, out_root: Path, i
     if head.outdir is None:
         head.outdir = out_dir / "vggt_infer"
     inference_imgs = [frames[idx] for idx in range(0, len(frames), FRAME_STRIDE)]
-    _E, K_resized, R, t, C, _wp = head.reconstruct_from_frames(imgs=inference_imgs, frame_id=0)
+    scene_glb = bool(cfg_get(cfg, "infer.scene_glb", False))
+    _E, K_resized, R, t, C, _wp = head.reconstruct_batch([0], [inference_imgs], scene=scene_glb)[0]
     # the reference keeps the "multi_view" file name here too (single_view_process.py:172)
     save_camera_info(out_pt_path=inference_output_path / f"{subject}_multi_view_3d_info.npz",
                      all_frame_camera_intrinsics=[K_resized], all_frame_R=[R], all_frame_t=[t], all_frame_C=[C])

@@ -602,6 +602,102 @@ def gen_post_triage():
 GENERATORS["post_triage"] = gen_post_triage
 
 
+def gen_scene():
+    """DESIGN §2 "Scene cloud": the reference's OWN predictions_to_glb (vggt/visual_util.py:39-236) on a synthetic
+    two-view step.  The module imports trimesh, gradio, cv2 and requests at its top; stand-in modules satisfy the
+    imports, and the trimesh stand-in records what the function hands it: the vertices and colours of the PointCloud,
+    the matrix of Scene.apply_transform, and the radius and height of every creation.cone (scene_scale * 0.05 and
+    * 0.1), for which it returns a tiny dummy mesh."""
+    import importlib.util
+    import json
+    import types
+
+    rec = {}
+
+    class Scene:
+        def __init__(self):
+            self.geometry = []
+
+        def add_geometry(self, g):
+            self.geometry.append(g)
+
+        def apply_transform(self, M):
+            rec["transform"] = np.array(M, dtype=np.float64)
+            return self
+
+    class PointCloud:
+        def __init__(self, vertices=None, colors=None):
+            rec["vertices"], rec["colors"] = np.array(vertices), np.array(colors)
+
+    class Trimesh:
+        def __init__(self, vertices=None, faces=None):
+            self.vertices, self.faces = np.asarray(vertices), np.asarray(faces)
+            self.visual = types.SimpleNamespace(face_colors=np.zeros((len(self.faces), 4), np.uint8))
+
+    def cone(radius, height, sections=None):
+        rec.setdefault("cones", []).append((float(radius), float(height)))
+        return Trimesh(np.zeros((3, 3)), np.array([[0, 1, 2]]))
+
+    tm = types.ModuleType("trimesh")
+    tm.Scene, tm.PointCloud, tm.Trimesh = Scene, PointCloud, Trimesh
+    tm.creation = types.ModuleType("trimesh.creation")
+    tm.creation.cone = cone
+    saved = {name: sys.modules.get(name) for name in ("trimesh", "trimesh.creation", "gradio", "cv2", "requests")}
+    sys.modules["trimesh"], sys.modules["trimesh.creation"] = tm, tm.creation
+    for name in ("gradio", "cv2", "requests"):
+        sys.modules[name] = types.ModuleType(name)
+    try:
+        spec = importlib.util.spec_from_file_location("ref_visual_util", os.path.join(REF, "vggt", "visual_util.py"))
+        V = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(V)
+    finally:
+        for name, mod in saved.items():
+            if mod is None:
+                sys.modules.pop(name, None)
+            else:
+                sys.modules[name] = mod
+
+    rng = np.random.default_rng(11)
+    S, H, Wd = 2, 12, 16
+    images = rng.random((S, 3, H, Wd)).astype(np.float32)
+    dark, bright = rng.random((S, H, Wd)) < 0.15, rng.random((S, H, Wd)) < 0.15
+    for c in range(3):
+        images[:, c][dark] = (rng.integers(0, 8, int(dark.sum())) / 255.0 + 0.001).astype(np.float32)    # sums around 16
+        images[:, c][bright] = (rng.integers(239, 244, int(bright.sum())) / 255.0 + 0.001).astype(np.float32)   # around 240
+    extrinsic = np.zeros((S, 3, 4), np.float32)
+    for i in range(S):
+        q, _ = np.linalg.qr(rng.normal(size=(3, 3)))
+        extrinsic[i, :, :3] = q + rng.normal(0, 0.01, (3, 3))
+        extrinsic[i, :, 3] = rng.normal(0, 1.5, 3)
+    preds = dict(world_points=rng.normal(0, 2, (S, H, Wd, 3)).astype(np.float32),
+                 world_points_conf=(1 + np.exp(rng.normal(size=(S, H, Wd)))).astype(np.float32),
+                 world_points_from_depth=rng.normal(0, 3, (S, H, Wd, 3)).astype(np.float32),
+                 depth_conf=(1 + np.exp(rng.normal(size=(S, H, Wd)))).astype(np.float32), images=images, extrinsic=extrinsic)
+    pm = "Predicted Pointmap"
+    sets = [dict(conf_thres=50.0, prediction_mode=pm), dict(conf_thres=0.0, prediction_mode=pm),
+            dict(conf_thres=10.0, prediction_mode=pm), dict(conf_thres=99.9, prediction_mode=pm),
+            dict(conf_thres=50.0, prediction_mode=pm, mask_black_bg=True), dict(conf_thres=50.0, prediction_mode=pm, mask_white_bg=True),
+            dict(conf_thres=50.0, prediction_mode="All"), dict(conf_thres=50.0, prediction_mode=pm, filter_by_frames="1:")]
+    out = dict(preds, sets_json=np.array(json.dumps(sets)))
+    import contextlib
+    import io
+    for i, kw in enumerate(sets):
+        rec.clear()
+        with contextlib.redirect_stdout(io.StringIO()):
+            V.predictions_to_glb(dict(preds), show_cam=True, **kw)
+        cones = np.array(rec["cones"])
+        assert (cones == cones[0]).all() and len(cones) == (1 if "filter_by_frames" in kw else S)
+        out[f"s{i}_vertices"], out[f"s{i}_colors"] = rec["vertices"], rec["colors"].astype(np.uint8)
+        out[f"s{i}_transform"], out[f"s{i}_cone"] = rec["transform"], cones[0]
+        assert rec["vertices"].dtype == np.float32 and len(rec["vertices"]) > 0
+    path = GOLD / "scene_cloud.npz"
+    np.savez_compressed(path, **out)
+    print("wrote", path.name, path.stat().st_size, "bytes")
+
+
+GENERATORS["scene"] = gen_scene
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GENERATORS)
     for w in which:
