@@ -641,6 +641,50 @@ int skimi_resect_cameras(const double* X, const double* x2d, const double* conf,
 int skimi_relative_pose(const double* R, const double* t, int64_t groups, int32_t views, double* R_rel, double* t_rel,
                         void* stream);
 
+/* Camera-and-points refinement (VideoPose3D/slove_rt_from_3d.py --refine camera_points: the lifter's joints are refined
+ * together with the cameras, under an optional prior lambda_x that ties them to their start; the reference calls scipy's
+ * least_squares on x0 = pack(init, X), :236, :244).  Inputs (dev f64): X [n_points, 3]; x2d [views, n_points, 2] pixels; conf
+ * [views, n_points] or NULL; K [views, 3, 3] or NULL (inferred per group and view); R0 [groups, views, 3, 3] and t0 [groups,
+ * views, 3], both required.  The points are cut into groups = n_points / group_size consecutive groups; a problem is one
+ * group, all its views and its used points together, solved by one workgroup (one wave up to 64 points, up to 512 threads
+ * beyond).  1 <= views <= 4, group_size <= (2^31 - 1) / 3.  All arithmetic float64.  Rules (DESIGN §2 "Camera + points
+ * refinement", restated in tests/refine_restated.py):
+ *  1. mask and weights: rule 1 of skimi_resect_cameras.  Fewer than 6 used points: the group fails (R, t, costs, statistics,
+ *     moved NaN, err NaN, n_evals 0, success 0; K_out NaN where it was to be inferred; X_opt = X bit for bit).
+ *  2. K NULL: rule 2 of skimi_resect_cameras, per group and view.
+ *  3. start: R0, t0 and X itself.  A non-finite start (or start cost) fails the group.
+ *  4. residuals: per view and used point r = w (pi(K_v, R_v X_i + t_v) - x_vi) as in skimi_resect_cameras; when lambda_x > 0
+ *     three more per used point, sqrt(lambda_x) (X_i - X0_i), X0 the caller's X.  Loss per residual COMPONENT, the prior's
+ *     included: SKIMI_RESECT_LINEAR or SKIMI_RESECT_SOFT_L1 with f_scale (cost, rho' as there).
+ *  5. parameters: per view d_v = (omega, dt), R <- Exp(omega) R, t <- t + dt; per used point dX_i.
+ *  6. step: (H + lam I) d = -g over all 6 views + 3 n parameters, H = sum rho' J^T J, g = sum rho' J^T r from the analytic
+ *     Jacobian (dXc / d omega = -[R X]x, dXc / dX = R), solved exactly through the Schur complement on the points:
+ *     V*_i = V_i + lam I (3 x 3 LDL^T), S = U + lam I - sum_i W_i V*_i^-1 W_i^T (6 views x 6 views), rhs = -g_c + sum_i W_i
+ *     V*_i^-1 g_i, d_c = S^-1 rhs by LDL^T without pivoting, dX_i = -V*_i^-1 (g_i + W_i^T d_c).  lam0 = 1e-3 max diag H.
+ *  7. a trial is accepted iff its cost c + dc is finite and <= c (1 + 1e-14), then lam <- lam / 10, floored by rule 9; else
+ *     lam <- 10 lam and the trial is repeated from the stored blocks.  dc is formed from the step itself: dXc = A (omega x
+ *     R X) + B omega x (omega x R X) + Exp(omega) R dX + dt with dX = (X + dX) - X, then the ray, the residual and
+ *     dr (2 r + dr) as in skimi_resect_cameras; the prior's dr = sqrt(lambda_x) dX.
+ *  8. stop on an accepted step with ||d|| <= 3e-8 (1 + ||(t, X)||) over all cameras and used points, on lam >= 1e30, or
+ *     after max_evals cost evaluations (the start and every trial count).
+ *  9. gauge: with lambda_x = 0 H is singular along the seven directions of a similarity, so lam never falls below
+ *     1e-9 max diag H of the current linearisation; only costs, err and stats are determined then.
+ * 10. outputs (dev): R, t, K_out [groups, views, ..]; X_opt [n_points, 3] (an unused point and a failed group keep X bit for
+ *     bit; X_opt must not be X); cost0, cost, moved [groups] (moved = rms ||X_opt - X|| over the used points); n_evals,
+ *     n_used, success [groups] i32; err [views, n_points] = the unweighted pixel error of the final cameras at X_opt, NaN
+ *     for unused points; stats [groups, views, 3] = mean, rms, max of err.
+ * One launch, no synchronisation, no allocation, no atomics; every sum has a fixed order that depends only on a point's
+ * index within its group: a group's results are bitwise the same alone or among others.  ws: at least
+ * skimi_refine_workspace_bytes(...) bytes = (12 + 18 views) n_points doubles: per point V_i (6), g_i (3), the trial point (3)
+ * and W_iv (18 per view); 0 where n_points, views or group_size is one that skimi_refine_cameras_points refuses.  Bad arguments: SKIMI_ERR_ARG before any launch. */
+size_t skimi_refine_workspace_bytes(int64_t n_points, int32_t views, int64_t group_size);
+int skimi_refine_cameras_points(const double* X, const double* x2d, const double* conf, const double* K, const double* R0,
+                                const double* t0, int64_t n_points, int32_t views, int64_t group_size, double lambda_x,
+                                int32_t loss, double f_scale, double min_conf, int32_t max_evals, double* R, double* t,
+                                double* K_out, double* X_opt, double* cost0, double* cost, int32_t* n_evals, int32_t* n_used,
+                                int32_t* success, double* err, double* stats, double* moved, void* ws, size_t ws_bytes,
+                                void* stream);
+
 /* The filtered, coloured point cloud of a time step (predictions_to_glb, vggt/visual_util.py:39-236, which runs in NumPy
  * on the host).  A scene is one step: n = S H W pixels in view-major, row-major order; all B scenes go through every launch.
  * Inputs (dev f32): points [B, S, H, W, 3]; conf [B, S, H, W]; images [B, S, 3, H, W] (images_nchw != 0) or

@@ -1,7 +1,7 @@
 """Device-side geometry post-processing (C-ABI: skimi_pose_to_cameras, skimi_unproject_depth,
 skimi_triangulate_dlt, skimi_triangulate_triage, skimi_triangulate_robust, the person origin: skimi_person_origin, skimi_recenter_cameras,
 and the point-to-plane ICP: skimi_estimate_normals, skimi_icp_correspondences,
-skimi_icp_point_to_plane; the bundle adjustment: skimi_bundle_adjust; the camera resection: skimi_resect_cameras,
+skimi_icp_point_to_plane; the bundle adjustment: skimi_bundle_adjust; the camera resection: skimi_resect_cameras, the camera-and-points refinement: skimi_refine_cameras_points,
 skimi_relative_pose) plus the small host helpers of the reference's VGGT wrapper.
 
 Reference: vggt/vggt/utils/pose_enc.py:62-124, rotation.py:14-44, geometry.py:15-117,
@@ -591,6 +591,77 @@ def resect_cameras(X: torch.Tensor, x2d: torch.Tensor, K=None, conf=None, group_
           "skimi_resect_cameras")
     R_rel, t_rel = relative_pose(R, t)
     return ResectResult(R, t, Ko, c0, c, ne, npts, ok.bool(), err, stats[..., 0], stats[..., 1], stats[..., 2], R_rel, t_rel)
+
+
+# ---- camera-and-points refinement (slove_rt_from_3d.py --refine camera_points; DESIGN §2 "Camera + points refinement") ----
+class RefineResult(NamedTuple):
+    """refine_cameras_points' outputs (device tensors; G groups, V views, N points)."""
+    R: torch.Tensor          # float64 [G, V, 3, 3]; NaN for a failed group
+    t: torch.Tensor          # float64 [G, V, 3]
+    K: torch.Tensor          # float64 [G, V, 3, 3]: the K used (given, or inferred from the group's keypoints)
+    X_opt: torch.Tensor      # float64 [N, 3]: the refined points; unused points and failed groups keep X bit for bit
+    cost0: torch.Tensor      # float64 [G]: cost of the start
+    cost: torch.Tensor       # float64 [G]
+    n_evals: torch.Tensor    # int32 [G]: cost evaluations, the start's included
+    n_points: torch.Tensor   # int32 [G]: the masked count
+    success: torch.Tensor    # bool [G]: not failed and stopped by a criterion other than max_evals
+    err: torch.Tensor        # float64 [V, N]: pixel error of the final cameras at X_opt, NaN for unused points
+    mean_err: torch.Tensor   # float64 [G, V]
+    rms_err: torch.Tensor    # float64 [G, V]
+    max_err: torch.Tensor    # float64 [G, V]
+    moved: torch.Tensor      # float64 [G]: rms ||X_opt - X|| over the used points
+    R_rel: torch.Tensor      # float64 [G, V, 3, 3] = R_v R_0^T
+    t_rel: torch.Tensor      # float64 [G, V, 3] = t_v - R_rel t_0
+
+
+def refine_cameras_points(X: torch.Tensor, x2d: torch.Tensor, K=None, R0=None, t0=None, conf=None, group_size=None,
+                          lambda_x: float = 0.0, loss: str = "linear", f_scale: float = 1.0, min_conf: float = 0.0,
+                          max_evals: int = 200) -> RefineResult:
+    """The cameras of a group and its 3D points refined together, in one launch: X [N, 3], x2d [V, N, 2] pixels (V <= 4), K
+    [V, 3, 3] or None (inferred per group), R0 [G, V, 3, 3] and t0 [G, V, 3] or None (then the DLT start of
+    resect_cameras(..., max_evals=1)), conf [V, N] or None -> RefineResult.  The points are cut into N / group_size
+    consecutive groups (default: one); per group a Levenberg-Marquardt over all its cameras and used points on the weighted
+    reprojection residuals plus, when lambda_x > 0, the prior sqrt(lambda_x) (X - X0), with loss "linear" or "soft_l1"
+    (scipy's, per component, scale f_scale); the step is solved exactly through the Schur complement on the points.  With
+    lambda_x = 0 the solution is determined up to a similarity only: costs, err and the statistics are then what is
+    promised, not R, t, X_opt themselves.  Fewer than 6 usable points or a non-finite start: R, t NaN, success False, the
+    group's X_opt = X.  Rules: DESIGN §2 "Camera + points refinement"."""
+    given = [a for a in (X, x2d, K, conf, R0, t0) if a is not None]
+    for a in given:
+        if not isinstance(a, torch.Tensor) or not a.is_cuda:
+            raise _lib.SkimiError("refine_cameras_points needs device tensors")
+    if loss not in RESECT_LOSSES:
+        raise ValueError(f"refine_cameras_points: unknown loss {loss!r}; known: {list(RESECT_LOSSES)}")
+    if X.dim() != 2 or X.shape[1] != 3 or x2d.dim() != 3 or x2d.shape[1:] != (X.shape[0], 2):
+        raise ValueError(f"refine_cameras_points: need X [N, 3] and x2d [V, N, 2], got {list(X.shape)}, {list(x2d.shape)}")
+    if (R0 is None) != (t0 is None):
+        raise ValueError("refine_cameras_points: R0 and t0 go together")
+    N, V = X.shape[0], x2d.shape[0]
+    gs = N if group_size is None else int(group_size)
+    G = N // gs if gs >= 1 and N >= 1 else 0
+    want = {"K": (V, 3, 3), "conf": (V, N), "R0": (G, V, 3, 3), "t0": (G, V, 3)}
+    for name, a in (("K", K), ("conf", conf), ("R0", R0), ("t0", t0)):
+        if a is not None and tuple(a.shape) != want[name]:
+            raise ValueError(f"refine_cameras_points: {name} must be {list(want[name])}, got {list(a.shape)}")
+    dev = X.device
+    X, x2d, K, conf, R0, t0 = (None if a is None else a.to(dev, torch.float64).contiguous() for a in (X, x2d, K, conf, R0, t0))
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)     # noqa: E731
+    if R0 is None and G >= 1 and 1 <= V <= 4:
+        r0 = resect_cameras(X, x2d, K=K, conf=conf, group_size=gs, loss=loss, f_scale=f_scale, min_conf=min_conf, max_evals=1)
+        R0, t0 = r0.R, r0.t            # NaN where the resection failed: the group then fails here too
+    R, t, Ko, Xo, err, stats = f64(G, V, 3, 3), f64(G, V, 3), f64(G, V, 3, 3), f64(N, 3), f64(V, N), f64(G, V, 3)
+    c0, c, moved, ne, npts, ok = f64(G), f64(G), f64(G), i32(G), i32(G), i32(G)
+    nws = int(lib().skimi_refine_workspace_bytes(N, V, gs))
+    ws = torch.empty(max(nws, 8), dtype=torch.uint8, device=dev)
+    check(lib().skimi_refine_cameras_points(ptr(X), ptr(x2d), ptr(conf), ptr(K), ptr(R0), ptr(t0), N, V, gs, float(lambda_x),
+                                            RESECT_LOSSES[loss], float(f_scale), float(min_conf), int(max_evals), ptr(R), ptr(t),
+                                            ptr(Ko), ptr(Xo), ptr(c0), ptr(c), ptr(ne), ptr(npts), ptr(ok), ptr(err), ptr(stats),
+                                            ptr(moved), ptr(ws), nws, _lib.current_stream()),
+          "skimi_refine_cameras_points")
+    R_rel, t_rel = relative_pose(R, t)
+    return RefineResult(R, t, Ko, Xo, c0, c, ne, npts, ok.bool(), err, stats[..., 0], stats[..., 1], stats[..., 2], moved,
+                        R_rel, t_rel)
 
 
 # ---- host helpers of the wrapper (small arrays, NumPy as in the reference) -----------------

@@ -12,6 +12,8 @@ evaluation protocols, the rendered GIF.  The model call is the HIP `TemporalMode
 
 `solve_rt_from_3d` is the counterpart of VideoPose3D/slove_rt_from_3d.py: the lifter's 3D joints and both views' 2D
 keypoints -> each camera's (R, t) and the pair's relative pose, on the device (geometry.resect_cameras).
+`solve_rt_and_points` is that script's `--refine camera_points` mode: the joints are refined together with the cameras
+(geometry.refine_cameras_points).
 """
 from __future__ import annotations
 
@@ -88,24 +90,8 @@ def run_video_pose_3d(config, pt_path: Path, out_dir: Path, args, model_pos: Tem
     return prediction, depth
 
 
-RT_KEYS = ("RL", "tL", "RR", "tR", "R_rel", "t_rel", "K_L", "K_R", "mean_err_L", "median_err_L", "mean_err_R", "median_err_R",
-           "success", "n_points")      # slove_rt_from_3d.py:263-271
-
-
-def solve_rt_from_3d(X3d, x2d_left, x2d_right, conf_left=None, conf_right=None, K_left=None, K_right=None, refine="camera",
-                     huber=0.0, min_conf=0.0, out=None, init="pnp"):
-    """VideoPose3D/slove_rt_from_3d.py's main with its command-line arguments as keywords: X3d (N,3) | (T,J,3), x2d_*
-    (N,2) | (T,J,2), conf_* (N,) | (T,J), K_* (3,3), host arrays or tensors -> dict with the reference's npz keys (host
-    values), written to `out` when given.  One pose per view over the whole clip; loss soft_l1 with f_scale = max(huber, 1)
-    when huber > 0 (:237, :244); an absent K is inferred from that view's masked keypoints (:65-73).  The start is this
-    build's DLT resection where the reference calls cv2's EPnP, and refine="none" returns it.  init="essential" and
-    refine="camera_points" are out of scope (DESIGN §2 "Resection")."""
-    if init == "essential":
-        raise NotImplementedError('init="essential" (cv2 findEssentialMat / recoverPose) is out of scope: DESIGN §2 "Resection"')
-    if refine == "camera_points":
-        raise NotImplementedError('refine="camera_points" (the views no longer decouple) is out of scope: DESIGN §2 "Resection"')
-    if init != "pnp" or refine not in ("none", "camera"):
-        raise ValueError(f"solve_rt_from_3d: init {init!r} / refine {refine!r}; known: pnp; none, camera")
+def _rt_inputs(X3d, x2d_left, x2d_right, conf_left, conf_right, K_left, K_right, huber, min_conf):
+    """the script's inputs on the device -> X [N,3], x2d [2,N,2], K [2,3,3] | None, keywords (conf, loss, f_scale, min_conf)"""
     dev = torch.device("cuda", torch.cuda.current_device())
 
     def up(a, last):       # to_Nx (:47-63) + upload
@@ -131,6 +117,29 @@ def solve_rt_from_3d(X3d, x2d_left, x2d_right, conf_left=None, conf_right=None, 
         K = torch.stack([K_inf[v] if k is None else k for v, k in enumerate(Ks)])
     else:
         K = torch.stack(Ks)
+    return X, x2d, K, kw
+
+
+RT_KEYS = ("RL", "tL", "RR", "tR", "R_rel", "t_rel", "K_L", "K_R", "mean_err_L", "median_err_L", "mean_err_R", "median_err_R",
+           "success", "n_points")      # slove_rt_from_3d.py:263-271
+
+
+def solve_rt_from_3d(X3d, x2d_left, x2d_right, conf_left=None, conf_right=None, K_left=None, K_right=None, refine="camera",
+                     huber=0.0, min_conf=0.0, out=None, init="pnp"):
+    """VideoPose3D/slove_rt_from_3d.py's main with its command-line arguments as keywords: X3d (N,3) | (T,J,3), x2d_*
+    (N,2) | (T,J,2), conf_* (N,) | (T,J), K_* (3,3), host arrays or tensors -> dict with the reference's npz keys (host
+    values), written to `out` when given.  One pose per view over the whole clip; loss soft_l1 with f_scale = max(huber, 1)
+    when huber > 0 (:237, :244); an absent K is inferred from that view's masked keypoints (:65-73).  The start is this
+    build's DLT resection where the reference calls cv2's EPnP, and refine="none" returns it.  init="essential" is out
+    of scope (DESIGN §2 "Resection"); refine="camera_points" is solve_rt_and_points, an entry point of its own."""
+    if init == "essential":
+        raise NotImplementedError('init="essential" (cv2 findEssentialMat / recoverPose) is out of scope: DESIGN §2 "Resection"')
+    if refine == "camera_points":
+        raise NotImplementedError('refine="camera_points" (the views no longer decouple) is not a mode of solve_rt_from_3d, DESIGN §2 '
+                                  '"Resection": call solve_rt_and_points')
+    if init != "pnp" or refine not in ("none", "camera"):
+        raise ValueError(f"solve_rt_from_3d: init {init!r} / refine {refine!r}; known: pnp; none, camera")
+    X, x2d, K, kw = _rt_inputs(X3d, x2d_left, x2d_right, conf_left, conf_right, K_left, K_right, huber, min_conf)
     r = geometry.resect_cameras(X, x2d, K=K, max_evals=1 if refine == "none" else 200, **kw)
     R, t, err = r.R[0].cpu().numpy(), r.t[0].cpu().numpy(), r.err.cpu().numpy()
     used = ~np.isnan(err)
@@ -139,6 +148,35 @@ def solve_rt_from_3d(X3d, x2d_left, x2d_right, conf_left=None, conf_right=None, 
     res = dict(RL=R[0], tL=t[0], RR=R[1], tR=t[1], R_rel=r.R_rel[0, 1].cpu().numpy(), t_rel=r.t_rel[0, 1].cpu().numpy(),
                K_L=r.K[0, 0].cpu().numpy(), K_R=r.K[0, 1].cpu().numpy(), mean_err_L=float(r.mean_err[0, 0]), median_err_L=med[0],
                mean_err_R=float(r.mean_err[0, 1]), median_err_R=med[1], success=int(ok), n_points=int(r.n_points[0, 0]))
+    if out is not None:
+        Path(out).parent.mkdir(parents=True, exist_ok=True)
+        np.savez(out, **res)
+    return res
+
+
+def solve_rt_and_points(X3d, x2d_left, x2d_right, conf_left=None, conf_right=None, K_left=None, K_right=None, lambda_x=0.0,
+                        huber=0.0, min_conf=0.0, out=None):
+    """VideoPose3D/slove_rt_from_3d.py --init pnp --refine camera_points with its arguments as keywords: inputs as
+    solve_rt_from_3d takes them -> dict with RT_KEYS plus `X_opt` (N,3) float64, the refined joints (a point the mask drops
+    keeps its input value), and `mask` (N,) bool, the points rule 1 keeps (from the inputs alone: it is what it is
+    when the solve fails, and sums to n_points); written to `out` when given.  Both cameras and the
+    masked joints are refined together from the DLT start and X3d itself (:236), under the prior lambda_x ||X - X3d||^2
+    (:159-161); with lambda_x = 0, the reference's default, the result is determined up to a similarity only.  The
+    reference computes X_opt (:247) and takes its errors there (:257-260) but forgets to save it (:263-271); this build
+    returns and writes it.  The errors are those of the final cameras at X_opt."""
+    X, x2d, K, kw = _rt_inputs(X3d, x2d_left, x2d_right, conf_left, conf_right, K_left, K_right, huber, min_conf)
+    r = geometry.refine_cameras_points(X, x2d, K=K, lambda_x=float(lambda_x), max_evals=200, **kw)
+    R, t, err = r.R[0].cpu().numpy(), r.t[0].cpu().numpy(), r.err.cpu().numpy()
+    used = ~np.isnan(err)
+    med = [float(np.median(err[v][used[v]])) if used[v].any() else float("nan") for v in range(2)]
+    mask = torch.isfinite(X).all(dim=1) & torch.isfinite(x2d).all(dim=2).all(dim=0)           # DESIGN rule 1
+    if kw["conf"] is not None:
+        w = torch.where(torch.isfinite(kw["conf"]), kw["conf"].clamp(0.0, 1.0), torch.zeros_like(kw["conf"]))
+        mask = mask & (w >= kw["min_conf"]).all(dim=0)
+    res = dict(RL=R[0], tL=t[0], RR=R[1], tR=t[1], R_rel=r.R_rel[0, 1].cpu().numpy(), t_rel=r.t_rel[0, 1].cpu().numpy(),
+               K_L=r.K[0, 0].cpu().numpy(), K_R=r.K[0, 1].cpu().numpy(), mean_err_L=float(r.mean_err[0, 0]), median_err_L=med[0],
+               mean_err_R=float(r.mean_err[0, 1]), median_err_R=med[1], success=int(bool(r.success[0])),
+               n_points=int(r.n_points[0]), X_opt=r.X_opt.cpu().numpy(), mask=mask.cpu().numpy())
     if out is not None:
         Path(out).parent.mkdir(parents=True, exist_ok=True)
         np.savez(out, **res)
