@@ -685,6 +685,66 @@ int skimi_refine_cameras_points(const double* X, const double* x2d, const double
                                 int32_t* success, double* err, double* stats, double* moved, void* ws, size_t ws_bytes,
                                 void* stream);
 
+/* Essential matrix between two calibrated views by RANSAC over five-point hypotheses, and the pose recovered from it
+ * (cv2.findEssentialMat(RANSAC, prob 0.999, threshold 1) + cv2.recoverPose as VideoPose3D/slove_rt_from_3d.py --init
+ * essential and triangulation/camera_position/camera_position.py call them).  Inputs (dev f64): x2d [2, n_points, 2]
+ * pixels; conf [2, n_points] or NULL; K [2, 3, 3].  The points are cut into groups = n_points / group_size consecutive
+ * groups, each a problem of its own.  Four launches over all groups (mask + normalise, hypotheses, scoring, finish), no
+ * host synchronisation between them, no allocation, no floating-point atomics, every floating-point sum in a fixed order.
+ * All arithmetic float64.  Rules (DESIGN §2 "Essential matrix", restated in tests/essential_restated.py):
+ *  1. a point is used iff both keypoints are finite and (conf NULL or both weights >= min_conf); weights as rule 1 of
+ *     skimi_resect_cameras.  Normalised coordinates a = K0^-1 (x, y, 1), b = K1^-1 (x, y, 1) from K's entries (0,0),
+ *     (0,1), (0,2), (1,1), (1,2): v = (y - cy) / fy, u = (x - cx - s v) / fx.  m = the used count; the used points are
+ *     ranked 0 .. m - 1 in index order.  m < 5: the group fails (E, R, t, cost, confidence NaN, counts and masks 0
+ *     except n_used = m, winner -1, -1, success 0).
+ *  2. tau = threshold / ((fx0 + fy0 + fx1 + fy1) / 4).
+ *  3. sampling: splitmix64 (s += 0x9E3779B97F4A7C15; z = s; z = (z ^ z >> 30) 0xBF58476D1CE4E5B9; z = (z ^ z >> 27)
+ *     0x94D049BB133111EB; z ^= z >> 31), s0 = seed ^ ((g + group_offset) 2^32 + h) for hypothesis h of group g; the first
+ *     output is discarded; each draw is the next output mod m, drawn again while that rank is in the sample already; after 64
+ *     outputs (the discarded one not counted) the sample is completed with the smallest ranks not yet drawn.  No early
+ *     termination: all `hypotheses` samples are solved and scored.
+ *  4. five-point solver (Stewenius): rows kron(b_i, a_i) (row . vec(E) = b^T E a, E row-major), the 9 x 9 A^T A (sums in
+ *     point order), cyclic Jacobi to convergence (the stopping rule of the resection's), N0..N3 = the eigenvectors of the
+ *     four smallest eigenvalues in ascending order (ties: lower index), E(x, y, z) = x N0 + y N1 + z N2 + N3.  The ten
+ *     cubic constraints det E = 0 and 2 E E^T E - tr(E E^T) E = 0 (row-major) over the monomials x^3, x^2 y, x y^2, y^3,
+ *     x^2 z, x y z, y^2 z, x z^2, y z^2, z^3 | x^2, x y, y^2, x z, y z, z^2, x, y, z, 1 give the 10 x 20 M; B = M[:, :10]^-1
+ *     M[:, 10:] by Gauss-Jordan with partial pivoting (a pivot below 1e-14 times the largest entry of its column, or a
+ *     non-finite one, skips the sample); action matrix of x on the second ten monomials: rows 0..5 = -B rows 0, 1, 2, 4, 5,
+ *     7; (6,0) = (7,1) = (8,3) = (9,6) = 1.  Every real eigenpair (lambda, v), v9 != 0 gives (x, y, z) = v6..8 / v9; here:
+ *     Hessenberg reduction and Francis QR for the eigenvalues, the null vector of A - lambda I by elimination with full
+ *     pivoting.  Each candidate is polished by a fixed number of Gauss-Newton steps on the ten constraints (10 x 3 Jacobian,
+ *     3 x 3 normal equations) and kept iff max |M mon| / (1 + x^2 + y^2 + z^2)^(3/2) is finite and under a bound (steps
+ *     and bound: DESIGN).  E is scaled to ||E||_F = sqrt 2; a sample's solutions are ordered by x ascending.
+ *  5. Sampson e^2 = (b^T E a)^2 / ((E a)_1^2 + (E a)_2^2 + (E^T b)_1^2 + (E^T b)_2^2); inlier iff e^2 is finite and <=
+ *     tau^2; cost = sum min(e^2, tau^2) in rank order, a non-finite e^2 counting tau^2.
+ *  6. winner: most inliers, then the smaller cost, then the smaller hypothesis, then the smaller solution index (costs that
+ *     compare neither way, NaN under a non-finite tau, count as equal).  None: the group fails.  No refit.
+ *  7. E = U diag(1, 1, 0) V^T from the Jacobi eigenvectors Q of E^T E: v3 = the column k of the smallest eigenvalue, v1, v2
+ *     = the columns (k + 1) % 3, (k + 2) % 3, u_i = E v_i / ||E v_i||, u3 = u1 x u2; W = [[0, -1, 0], [1, 0, 0], [0, 0, 1]];
+ *     candidates (U W V^T, +u3), (U W V^T, -u3), (U W^T V^T, +u3), (U W^T V^T, -u3).
+ *  8. cheirality per candidate and INLIER of the winner: the depths (z0, z1) are the least-squares solution of z0 (R a) -
+ *     z1 b = -t (2 x 2 normal equations); a point passes iff both are finite, > 0 and < distance_thresh; the candidate with
+ *     the most passes wins, the earlier one on a tie.
+ *  9. outputs (dev): R [G, 3, 3]; t [G, 3] = baseline t^; E [G, 3, 3] = [t^]x R; inliers, pose_mask [n_points] u8 (0 for
+ *     unused points); n_used, n_inliers, n_pose [G] i32; cheirality [G, 4] i32; cost [G]; winner [G, 2] i32 (hypothesis,
+ *     solution); n_solutions [G] i32 (all kept candidates); confidence [G] = 1 - (1 - w^5)^H, w = n_inliers / m; success
+ *     [G] i32 = a winner exists, n_inliers >= 5 and n_pose > 0.  Convention: X1 = R X0 + t, b^T E a = 0.
+ * 10. 1 <= hypotheses <= 65536, 1 <= group_size <= n_points, n_points % group_size == 0, threshold > 0 and finite; and the
+ *     sizes the 32-bit indices of the kernels allow: group_size <= (2^31 - 1) / 4, n_points <= 2^40, groups * hypotheses <=
+ *     2^25, 0 <= group_offset <= 2^31; min_conf, baseline, distance_thresh not NaN: else SKIMI_ERR_ARG before any launch.  Results are bitwise reproducible, and a group is bitwise what it is alone with the
+ *     matching group_offset.
+ * ws: at least skimi_essential_workspace_bytes(...) bytes (0 for sizes that skimi_essential_ransac refuses). */
+size_t skimi_essential_workspace_bytes(int64_t n_points, int64_t group_size, int32_t hypotheses);
+int skimi_essential_ransac(const double* x2d, const double* conf, const double* K, int64_t n_points, int64_t group_size,
+                           double min_conf, double threshold, int32_t hypotheses, uint64_t seed, int64_t group_offset,
+                           double baseline, double distance_thresh, double* R, double* t, double* E, uint8_t* inliers,
+                           uint8_t* pose_mask, int32_t* n_used, int32_t* n_inliers, int32_t* n_pose, int32_t* cheirality,
+                           double* cost, int32_t* winner, int32_t* n_solutions, double* confidence, int32_t* success,
+                           void* ws, size_t ws_bytes, void* stream);
+/* Rule 4 alone, one thread per sample: a, b dev f64 [samples, 5, 2] normalised coordinates -> E [samples, 10, 3, 3] (the
+ * first counts[s] are solutions, the rest NaN), counts [samples] i32. */
+int skimi_five_point(const double* a, const double* b, int64_t samples, double* E, int32_t* counts, void* stream);
+
 /* The filtered, coloured point cloud of a time step (predictions_to_glb, vggt/visual_util.py:39-236, which runs in NumPy
  * on the host).  A scene is one step: n = S H W pixels in view-major, row-major order; all B scenes go through every launch.
  * Inputs (dev f32): points [B, S, H, W, 3]; conf [B, S, H, W]; images [B, S, 3, H, W] (images_nchw != 0) or

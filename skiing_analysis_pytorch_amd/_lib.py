@@ -136,6 +136,11 @@ _SIGNATURES = {
     "skimi_refine_cameras_points": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int64, C.c_double, C.c_int32,
                                               C.c_double, C.c_double, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                               _vp, _vp, _vp, C.c_size_t, _vp]),
+    "skimi_essential_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "skimi_essential_ransac": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_double, C.c_double, C.c_int32, C.c_uint64,
+                                         C.c_int64, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "skimi_five_point": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, _vp]),
     "skimi_scene_tile": (C.c_int64, [C.c_int64]),
     "skimi_scene_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "skimi_scene_cloud": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,

@@ -13,7 +13,8 @@ evaluation protocols, the rendered GIF.  The model call is the HIP `TemporalMode
 `solve_rt_from_3d` is the counterpart of VideoPose3D/slove_rt_from_3d.py: the lifter's 3D joints and both views' 2D
 keypoints -> each camera's (R, t) and the pair's relative pose, on the device (geometry.resect_cameras).
 `solve_rt_and_points` is that script's `--refine camera_points` mode: the joints are refined together with the cameras
-(geometry.refine_cameras_points).
+(geometry.refine_cameras_points).  `solve_rt_from_essential` is its `--init essential` path: the right camera's pose relative to
+the left one from the essential matrix of the 2D keypoints alone (geometry.essential_ransac), then the same refinement.
 """
 from __future__ import annotations
 
@@ -130,10 +131,11 @@ def solve_rt_from_3d(X3d, x2d_left, x2d_right, conf_left=None, conf_right=None, 
     (N,2) | (T,J,2), conf_* (N,) | (T,J), K_* (3,3), host arrays or tensors -> dict with the reference's npz keys (host
     values), written to `out` when given.  One pose per view over the whole clip; loss soft_l1 with f_scale = max(huber, 1)
     when huber > 0 (:237, :244); an absent K is inferred from that view's masked keypoints (:65-73).  The start is this
-    build's DLT resection where the reference calls cv2's EPnP, and refine="none" returns it.  init="essential" is out
-    of scope (DESIGN §2 "Resection"); refine="camera_points" is solve_rt_and_points, an entry point of its own."""
+    build's DLT resection where the reference calls cv2's EPnP, and refine="none" returns it.  init="essential" is
+    solve_rt_from_essential and refine="camera_points" is solve_rt_and_points, entry points of their own."""
     if init == "essential":
-        raise NotImplementedError('init="essential" (cv2 findEssentialMat / recoverPose) is out of scope: DESIGN §2 "Resection"')
+        raise NotImplementedError('init="essential" (the start comes from the 2D keypoints alone and K is required) is not a mode of '
+                                  'solve_rt_from_3d, DESIGN §2 "Essential matrix": call solve_rt_from_essential')
     if refine == "camera_points":
         raise NotImplementedError('refine="camera_points" (the views no longer decouple) is not a mode of solve_rt_from_3d, DESIGN §2 '
                                   '"Resection": call solve_rt_and_points')
@@ -177,6 +179,46 @@ def solve_rt_and_points(X3d, x2d_left, x2d_right, conf_left=None, conf_right=Non
                K_L=r.K[0, 0].cpu().numpy(), K_R=r.K[0, 1].cpu().numpy(), mean_err_L=float(r.mean_err[0, 0]), median_err_L=med[0],
                mean_err_R=float(r.mean_err[0, 1]), median_err_R=med[1], success=int(bool(r.success[0])),
                n_points=int(r.n_points[0]), X_opt=r.X_opt.cpu().numpy(), mask=mask.cpu().numpy())
+    if out is not None:
+        Path(out).parent.mkdir(parents=True, exist_ok=True)
+        np.savez(out, **res)
+    return res
+
+
+def solve_rt_from_essential(X3d, x2d_left, x2d_right, conf_left=None, conf_right=None, K_left=None, K_right=None, refine="camera",
+                            huber=0.0, min_conf=0.0, out=None, hypotheses=1024, seed=0, threshold=1.0):
+    """VideoPose3D/slove_rt_from_3d.py --init essential with its arguments as keywords: inputs as solve_rt_from_3d takes
+    them, K_left and K_right required (the script's usage says so; each view is normalised through its own K where the
+    script passes K_L for both) -> dict with RT_KEYS plus `inliers` (N,) bool, the keypoint pairs the winning essential
+    matrix keeps; written to `out` when given.  The left camera starts at the identity and the right one at (R, t^) of
+    geometry.essential_ransac over the points rule 1 of the resection keeps (:227-232; ||t^|| = 1: the scale is unknown,
+    and the refinement against X3d supplies it); refine="none" returns that start with its errors, refine="camera" hands it
+    to geometry.resect_cameras(R0=, t0=).  No essential matrix (fewer than 5 usable pairs): RuntimeError, as the script."""
+    if refine == "camera_points":
+        raise NotImplementedError('refine="camera_points" is not a mode of solve_rt_from_essential, DESIGN §2 "Essential matrix": '
+                                  'call solve_rt_and_points')
+    if refine not in ("none", "camera"):
+        raise ValueError(f"solve_rt_from_essential: refine {refine!r}; known: none, camera")
+    if K_left is None or K_right is None:
+        raise ValueError("solve_rt_from_essential: K_left and K_right are required (slove_rt_from_3d.py: --init essential needs K)")
+    X, x2d, K, kw = _rt_inputs(X3d, x2d_left, x2d_right, conf_left, conf_right, K_left, K_right, huber, min_conf)
+    # the script masks first (:97-101) and estimates E on what is left: a point without a finite X3d takes no part
+    nan = torch.full_like(x2d, float("nan"))
+    e = geometry.essential_ransac(torch.where(torch.isfinite(X).all(dim=1)[None, :, None], x2d, nan), K, conf=kw["conf"],
+                                  min_conf=kw["min_conf"], threshold=threshold, hypotheses=hypotheses, seed=seed)
+    if not bool(e.success[0]):
+        raise RuntimeError("findEssentialMat failed")
+    R0 = torch.stack([torch.eye(3, dtype=torch.float64, device=X.device), e.R[0]])[None]
+    t0 = torch.stack([torch.zeros(3, dtype=torch.float64, device=X.device), e.t[0]])[None]
+    r = geometry.resect_cameras(X, x2d, K=K, R0=R0, t0=t0, max_evals=1 if refine == "none" else 200, **kw)
+    R, t, err = r.R[0].cpu().numpy(), r.t[0].cpu().numpy(), r.err.cpu().numpy()
+    used = ~np.isnan(err)
+    med = [float(np.median(err[v][used[v]])) if used[v].any() else float("nan") for v in range(2)]
+    ok = bool(r.success[0].all()) if refine != "none" else bool(np.isfinite(R).all() and np.isfinite(t).all())
+    res = dict(RL=R[0], tL=t[0], RR=R[1], tR=t[1], R_rel=r.R_rel[0, 1].cpu().numpy(), t_rel=r.t_rel[0, 1].cpu().numpy(),
+               K_L=r.K[0, 0].cpu().numpy(), K_R=r.K[0, 1].cpu().numpy(), mean_err_L=float(r.mean_err[0, 0]), median_err_L=med[0],
+               mean_err_R=float(r.mean_err[0, 1]), median_err_R=med[1], success=int(ok), n_points=int(r.n_points[0, 0]),
+               inliers=e.inliers.bool().cpu().numpy())
     if out is not None:
         Path(out).parent.mkdir(parents=True, exist_ok=True)
         np.savez(out, **res)
