@@ -777,6 +777,78 @@ int skimi_scene_cloud(const float* points, const float* conf, const float* image
                       int32_t align, int64_t cap, void* workspace, float* xyz, uint8_t* rgb, int64_t* count, double* stats,
                       double* transform, void* stream);
 
+/* Fusion and temporal smoothing of a clip's joints on the device (the host functions of fuse.py are the restatement:
+ * VideoPose3D/fuse/fuse.py + fuse_check.py, fuse/main_raw.py:194-250, fuse/fuse.py:289-412, fuse/confidence.py,
+ * triangulation/postprocess.py:54-67).  All arithmetic float64, compiled without FMA contraction; inputs and outputs are dev
+ * f64 except status / fit_ok (dev i32).  One launch per call, no synchronisation, no allocation, no atomics; every sum is a
+ * lane's own sum over its joints followed by a fixed butterfly over the wave, so results are bitwise reproducible, a frame's
+ * results do not depend on `frames` or on the frame's position, and a joint's smoothed series does not depend on the other
+ * joints.  frames == 0 is valid and launches nothing.  Bad arguments: SKIMI_ERR_ARG before any launch, outputs untouched.
+ * Rules (DESIGN §2 "Fusion + smoothing on the device"):
+ *
+ * skimi_fuse_h36m = fuse_pose_no_extrinsics_h36m per frame.  left, right [frames, 17, 3]; tau_j [17] or NULL (then the
+ * scalar tau); wL, wR NULL (all ones) or [17] (stride 0) or [frames, 17] (stride 17).
+ *  1. mirror_right_x: the right view's x and z negated.  center_scale_h36m of both views: pelvis (joint 0) to the origin,
+ *     divided by the pelvis-neck (joint 9) distance d unless d > 1e-8 is false (then by 1).
+ *  2. estimate_rigid_umeyama on the torso joints 0, 9, 4, 1, 11, 14 finite on both sides (n of them; n < 3: rule 6): Sigma =
+ *     Yc^T Xc / n (X left, Y right, centred) = U S V^T; R = U V^T (the reference's quirk: the transpose of the least-squares
+ *     rotation), with the last column of U flipped when det R < 0; s = sum S / (||Yc||^2 / n + 1e-12) if allow_scale else 1;
+ *     t = mean X - s R mean Y.  The SVD is a one-sided Jacobi to convergence; R is formed from the two largest singular
+ *     triplets and their cross products, which equals the rule for every sign choice of an SVD (rank(Sigma) < 2 is open).
+ *  3. fuse_two of the left pose and s R right + t per joint: the only finite side; both finite: ||L - R|| > tau_j picks the
+ *     side of the larger weight (left on a tie), else (wL L + wR R) / (wL + wR + 1e-9); neither: NaN.
+ *  4. center_scale_h36m of the result -> fused [frames, 17, 3].
+ *  5. diag [frames, 4] = LR_before, Fused_vs_L, Fused_vs_R, gain: the plain means over the 17 joints of ||Ln - Rn||, ||fused -
+ *     Ln||, ||fused - Rn|| (NaN-propagating) and LR_before - (Fused_vs_L + Fused_vs_R) / 2.  R [frames, 3, 3], t [frames, 3],
+ *     s [frames], status [frames] = 1.
+ *  6. n < 3, where the host raises ValueError: the frame's fused, R, t, s and diag are NaN and status = 0. */
+int skimi_fuse_h36m(const double* left, const double* right, int64_t frames, double tau, const double* tau_j, const double* wL,
+                    int64_t wL_stride, const double* wR, int64_t wR_stride, int32_t allow_scale, int32_t mirror_right_x,
+                    double* fused, double* R, double* t, double* s, double* diag, int32_t* status, void* stream);
+
+/* skimi_fuse_views = the per-frame body of fuse/main_raw.py:194-240.  X_l, X_r [frames, joints, 3]; U_l, U_r [frames, joints,
+ * 2] pixels; 1 <= joints <= 128; the five key joints in 0 .. joints - 1; sigma_px, sigma_3d finite; min_points >= 1.
+ *  1. align_right_to_left: on the joints finite in both views (fewer than 3: aligned = X_r), Kabsch R = V U^T of (X_r -
+ *     mean)^T (X_l - mean) = U S V^T with the last column of V flipped when det R < 0 (SVD as in skimi_fuse_h36m), t = mean_l
+ *     - R mean_r; aligned = R X_r + t on those joints, X_r elsewhere.
+ *  2. weakpersp_reproj_confidence of each view on its RAW 3D: on the rows finite in X and U, M = P[:, :2] Q^T of Xc^T Uc = P S
+ *     Q^T, s = sum S / sum Xc^2, t = mean U - s mean X M; err = ||s X M + t - U|| where both are finite, else NaN; conf =
+ *     exp(-err^2 / (2 max(sigma_px, 1e-12)^2)), 0 where err is NaN.  Fewer than min_points rows, or sum Xc^2 < 1e-12, where
+ *     the host raises: that view's conf is 0 and its err NaN for every joint of the frame, and its fit_ok = 0.
+ *  3. crossview_consistency_confidence of the raw pair: canonicalize_pose_3d of each view (origin at the root, x = left hip ->
+ *     right hip, y = hip centre -> shoulder centre made orthogonal to x, z = x cross y, unit vectors with eps 1e-9; divided
+ *     by the hip width, SKIMI_FUSE_SCALE_HIP, or the hip-shoulder distance, SKIMI_FUSE_SCALE_TORSO; a non-finite key joint
+ *     or a scale < 1e-9: all NaN); dist = the distance of the two canonical poses per joint, NaN where either is; conf_x =
+ *     exp(-dist^2 / (2 max(sigma_3d, 1e-12)^2)), 0 where dist is NaN.
+ *  4. q = sqrt(conf conf_x) per view; fuse_frame_3d(X_l, aligned, q_l, q_r): softmax2 weights w = exp(q - max) / (sum + 1e-8);
+ *     a joint present on one side takes that side, on both (wl X_l + wr aligned) / (wl + wr + 1e-8), on neither NaN.
+ * Outputs: fused, aligned [frames, joints, 3]; q_l, q_r, conf_l, conf_r, conf_x, err_l, err_r, dist [frames, joints]; fit_ok
+ * [frames, 2] i32 (left, right). */
+#define SKIMI_FUSE_SCALE_HIP 0
+#define SKIMI_FUSE_SCALE_TORSO 1
+int skimi_fuse_views(const double* X_l, const double* X_r, const double* U_l, const double* U_r, int64_t frames, int32_t joints,
+                     int32_t root_idx, int32_t left_hip_idx, int32_t right_hip_idx, int32_t left_shoulder_idx,
+                     int32_t right_shoulder_idx, double sigma_px, double sigma_3d, int32_t scale_mode, int32_t min_points,
+                     double* fused, double* aligned, double* q_l, double* q_r, double* conf_l, double* conf_r, double* conf_x,
+                     double* err_l, double* err_r, double* dist, int32_t* fit_ok, void* stream);
+
+/* skimi_smooth_ema = temporal_smooth_ema.  X, Y [frames, joints, 3] (Y must not be X); base [joints]: the per-joint base
+ * factor clip(alpha factor, alpha_min, alpha_max) when adaptive, alpha itself otherwise.  One thread per joint, sequential
+ * in t.  Y[0] = X[0] bit for bit; then per step a joint is (three finite coordinates now) + 2 (the previous OUTPUT row is
+ * finite): 0 -> NaN, 1 -> the observation, 2 -> the previous output, 3 -> a x + (1 - a) y with a = min(max(base + speed_gain
+ * ||x - y||, alpha_min), alpha_max) (adaptive) or base; two products and a sum, no fused multiply-add. */
+int skimi_smooth_ema(const double* X, int64_t frames, int64_t joints, const double* base, int32_t adaptive, double alpha_min,
+                     double alpha_max, double speed_gain, double* Y, void* stream);
+
+/* skimi_smooth_savgol = smooth_skeleton with the window already chosen.  X, Y [frames, joints, 3] (Y must not be X); win odd
+ * in 1..33, 0 <= poly < win (poly is only checked); fir [win]; first, last [win / 2, win] (fuse.savgol_operators).  One thread
+ * per (joint, coordinate) series: its finite samples in time order form the sequence x_0 .. x_{n-1}; with n >= win, y_k =
+ * sum_m fir[m] x_{k - win/2 + m} for win/2 <= k < n - win/2, y_e = sum_m first[e][m] x_m and y_{n - win/2 + e} = sum_m
+ * last[e][m] x_{n - win + m} for e < win/2 (sums in ascending m), written back to the samples' own time steps.  Non-finite
+ * samples, and series with n < win, pass through bit for bit. */
+int skimi_smooth_savgol(const double* X, int64_t frames, int64_t joints, int32_t win, int32_t poly, const double* fir,
+                        const double* first, const double* last, double* Y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,13 @@ _SIGNATURES = {
     "skimi_scene_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "skimi_scene_cloud": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double,
                                     C.c_int32, C.c_int32, C.c_int32, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "skimi_fuse_h36m": (C.c_int, [_vp, _vp, C.c_int64, C.c_double, _vp, _vp, C.c_int64, _vp, C.c_int64, C.c_int32, C.c_int32,
+                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "skimi_fuse_views": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_double, C.c_double, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _vp]),
+    "skimi_smooth_ema": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, C.c_int32, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    "skimi_smooth_savgol": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "skimi_vggt_create": (_vp, [_vp]),
     "skimi_vggt_destroy": (None, [_vp]),
     "skimi_vggt_set_weight": (C.c_int, [_vp, C.c_char_p, _vp, C.c_int64, C.c_int32]),

@@ -1,0 +1,629 @@
+// The consumers of the gathered [T, J, 3] joints on the device: the VideoPose3D left/right fusion without extrinsics
+// (fuse.fuse_pose_no_extrinsics_h36m), the two-view fusion with its confidences (the per-frame body of fuse/main_raw.py:
+// align_right_to_left, weakpersp_reproj_confidence, crossview_consistency_confidence, fuse_frame_3d), the adaptive EMA
+// (fuse.temporal_smooth_ema) and the NaN-aware Savitzky-Golay filter (fuse.smooth_skeleton).  The host functions of fuse.py
+// are the restatement; rules: DESIGN §2 "Fusion + smoothing on the device".
+//
+// Fusion: one wave per frame (four frames per workgroup, no LDS, no barrier), lanes over joints (two joints per lane above
+// 64).  Every sum is a per-lane sum over the lane's joints followed by a fixed xor-butterfly over the 64 lanes, so it
+// depends on nothing but the frame's own data and every lane ends with the same bits: the 3 x 3 decomposition then runs
+// uniformly across the wave (one lane's time, no broadcast).  The polar factors come from a one-sided (Hestenes) Jacobi
+// SVD: the columns are rotated until they are orthogonal, which keeps the small singular value to relative accuracy where
+// the eigen-decomposition of M^T M would square the condition number.
+// Smoothing: one thread per joint (EMA) or per (joint, coordinate) series (Savitzky-Golay), sequential in t, the loads of
+// eight steps issued together; neighbouring threads read neighbouring addresses.  All arithmetic is float64 and the file
+// is compiled without FMA contraction, so a x + (1 - a) y is two products and a sum wherever it appears.
+#include <math.h>
+
+#include "common.h"
+
+namespace skimi {
+namespace {
+
+constexpr int kH36mJoints = 17;
+constexpr int kMaxJoints = 128;              // two joints per lane
+constexpr int kMaxWin = 33;                  // Savitzky-Golay window: the ring of a series lives in LDS
+constexpr int kSweeps = 40;
+constexpr int kBatch = 8;                    // time steps loaded together by the smoothers
+constexpr unsigned kTorsoMask = (1u << 0) | (1u << 9) | (1u << 4) | (1u << 1) | (1u << 11) | (1u << 14);
+
+__device__ inline bool is_fin(double x) { return fabs(x) <= 1.79769313486231570815e308; }
+__device__ inline bool fin3(const double* x) { return is_fin(x[0]) && is_fin(x[1]) && is_fin(x[2]); }
+__device__ inline double norm3(double a, double b, double c) { return sqrt(a * a + b * b + c * c); }
+
+// the sum over the wave in a fixed order; every lane gets the same bits (a + b == b + a)
+__device__ inline double wsum(double x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+    return x;
+}
+
+// A (row-major 3 x 3) = U S V^T by one-sided Jacobi on the columns -> Q = u1 v1^T + u2 v2^T + (u1 x u2)(v1 x v2)^T over the
+// two largest singular values, and ssum = the sum of the three.  Q is the polar factor U V^T with the singular vector of
+// the smallest singular value flipped when det(U V^T) < 0: what the reference's "flip the last column" produces, whatever
+// signs its SVD chose.  A zero third column (a 3 x 2 problem) is never rotated and comes out as the smallest.
+__device__ inline void polar3(const double* A, double* Q, double& ssum) {
+    double a[3][3], v[3][3];                   // [column][row]
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            a[c][r] = A[3 * r + c];
+            v[c][r] = r == c ? 1.0 : 0.0;
+        }
+    for (int sweep = 0; sweep < kSweeps; ++sweep) {
+        bool rotated = false;
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int q = p + 1; q < 3; ++q) {
+                const double al = a[p][0] * a[p][0] + a[p][1] * a[p][1] + a[p][2] * a[p][2];
+                const double be = a[q][0] * a[q][0] + a[q][1] * a[q][1] + a[q][2] * a[q][2];
+                const double ga = a[p][0] * a[q][0] + a[p][1] * a[q][1] + a[p][2] * a[q][2];
+                if (fabs(ga) > 1e-15 * sqrt(al * be)) {
+                    rotated = true;
+                    const double zeta = (be - al) / (2.0 * ga);
+                    const double tn = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(zeta * zeta + 1.0));
+                    const double cs = 1.0 / sqrt(tn * tn + 1.0), sn = tn * cs;
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) {
+                        const double ap = a[p][r], aq = a[q][r], vp = v[p][r], vq = v[q][r];
+                        a[p][r] = cs * ap - sn * aq;
+                        a[q][r] = sn * ap + cs * aq;
+                        v[p][r] = cs * vp - sn * vq;
+                        v[q][r] = sn * vp + cs * vq;
+                    }
+                }
+            }
+        if (!rotated) break;
+    }
+    double sg[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) sg[c] = norm3(a[c][0], a[c][1], a[c][2]);
+    ssum = sg[0] + sg[1] + sg[2];
+    const int k = (sg[0] <= sg[1] && sg[0] <= sg[2]) ? 0 : (sg[1] <= sg[2] ? 1 : 2);      // the smallest
+    double u1[3], u2[3], v1[3], v2[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double s1 = k == 0 ? sg[1] : k == 1 ? sg[2] : sg[0], s2 = k == 0 ? sg[2] : k == 1 ? sg[0] : sg[1];
+        u1[r] = (k == 0 ? a[1][r] : k == 1 ? a[2][r] : a[0][r]) / s1;
+        u2[r] = (k == 0 ? a[2][r] : k == 1 ? a[0][r] : a[1][r]) / s2;
+        v1[r] = k == 0 ? v[1][r] : k == 1 ? v[2][r] : v[0][r];
+        v2[r] = k == 0 ? v[2][r] : k == 1 ? v[0][r] : v[1][r];
+    }
+    const double u3[3] = {u1[1] * u2[2] - u1[2] * u2[1], u1[2] * u2[0] - u1[0] * u2[2], u1[0] * u2[1] - u1[1] * u2[0]};
+    const double v3[3] = {v1[1] * v2[2] - v1[2] * v2[1], v1[2] * v2[0] - v1[0] * v2[2], v1[0] * v2[1] - v1[1] * v2[0]};
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Q[3 * r + c] = u1[r] * v1[c] + u2[r] * v2[c] + u3[r] * v3[c];
+}
+
+// ---- VideoPose3D left/right fusion ---------------------------------------------------------------------------------
+struct H36mArgs {
+    const double *left, *right, *tau_j, *wL, *wR;
+    double *fused, *R, *t, *s, *diag;
+    int32_t* status;
+    long T, wL_stride, wR_stride;
+    double tau;
+    int allow_scale, mirror;
+};
+
+// center_scale_h36m over the wave: pelvis (lane 0) to the origin, pelvis-neck (lane 9) distance 1 unless it is not > 1e-8
+__device__ inline void center_scale(double* X) {
+    double p[3], d[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        p[c] = __shfl(X[c], 0, 64);
+        d[c] = __shfl(X[c], 9, 64) - p[c];
+    }
+    double s = norm3(d[0], d[1], d[2]);
+    s = s > 1e-8 ? s : 1.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) X[c] = (X[c] - p[c]) / s;
+}
+
+__global__ __launch_bounds__(256) void fuse_h36m_kernel(H36mArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= a.T) return;                      // the whole wave leaves: no barrier in this kernel
+    const bool act = lane < kH36mJoints;
+    const int j = act ? lane : 0;
+    const double nan = __builtin_nan("");
+    double L[3], Rn[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        L[c] = a.left[(t * kH36mJoints + j) * 3 + c];
+        Rn[c] = a.right[(t * kH36mJoints + j) * 3 + c];
+    }
+    if (a.mirror) {
+        Rn[0] = -Rn[0];
+        Rn[2] = -Rn[2];
+    }
+    center_scale(L);
+    center_scale(Rn);
+    // estimate_rigid_umeyama(X = left torso, Y = right torso) on the rows finite on both sides
+    const bool tor = act && ((kTorsoMask >> lane) & 1u) && fin3(L) && fin3(Rn);
+    const double n = wsum(tor ? 1.0 : 0.0);
+    double* Ro = a.R + 9 * t;
+    double* to = a.t + 3 * t;
+    double* dg = a.diag + 4 * t;
+    if (n < 3.0) {
+        if (act)
+            for (int c = 0; c < 3; ++c) a.fused[(t * kH36mJoints + j) * 3 + c] = nan;
+        if (lane == 0) {
+            for (int k = 0; k < 9; ++k) Ro[k] = nan;
+            for (int k = 0; k < 3; ++k) to[k] = nan;
+            for (int k = 0; k < 4; ++k) dg[k] = nan;
+            a.s[t] = nan;
+            a.status[t] = 0;
+        }
+        return;
+    }
+    double mx[3], my[3], Xc[3], Yc[3], Sg[9];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        mx[c] = wsum(tor ? L[c] : 0.0) / n;
+        my[c] = wsum(tor ? Rn[c] : 0.0) / n;
+        Xc[c] = L[c] - mx[c];
+        Yc[c] = Rn[c] - my[c];
+    }
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Sg[3 * r + c] = wsum(tor ? Yc[r] * Xc[c] : 0.0) / n;
+    const double vy = wsum(tor ? Yc[0] * Yc[0] + Yc[1] * Yc[1] + Yc[2] * Yc[2] : 0.0);
+    double Rm[9], ssum;
+    polar3(Sg, Rm, ssum);
+    const double s = a.allow_scale ? ssum / (vy / n + 1e-12) : 1.0;
+    double tv[3], Al[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        tv[r] = mx[r] - s * (Rm[3 * r] * my[0] + Rm[3 * r + 1] * my[1] + Rm[3 * r + 2] * my[2]);
+        Al[r] = s * (Rm[3 * r] * Rn[0] + Rm[3 * r + 1] * Rn[1] + Rm[3 * r + 2] * Rn[2]) + tv[r];
+    }
+    // fuse_two
+    const double tau = a.tau_j ? a.tau_j[j] : a.tau;
+    const double wl = a.wL ? a.wL[t * a.wL_stride + j] : 1.0, wr = a.wR ? a.wR[t * a.wR_stride + j] : 1.0;
+    const bool lok = fin3(L), rok = fin3(Al);
+    double F[3];
+    const bool far = norm3(L[0] - Al[0], L[1] - Al[1], L[2] - Al[2]) > tau;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double blend = (wl * L[c] + wr * Al[c]) / (wl + wr + 1e-9);
+        const double pick = far ? (wl >= wr ? L[c] : Al[c]) : blend;
+        F[c] = lok ? (rok ? pick : L[c]) : (rok ? Al[c] : nan);
+    }
+    center_scale(F);
+    const double before = wsum(act ? norm3(L[0] - Rn[0], L[1] - Rn[1], L[2] - Rn[2]) : 0.0) / kH36mJoints;
+    const double to_l = wsum(act ? norm3(F[0] - L[0], F[1] - L[1], F[2] - L[2]) : 0.0) / kH36mJoints;
+    const double to_r = wsum(act ? norm3(F[0] - Rn[0], F[1] - Rn[1], F[2] - Rn[2]) : 0.0) / kH36mJoints;
+    if (act)
+        for (int c = 0; c < 3; ++c) a.fused[(t * kH36mJoints + j) * 3 + c] = F[c];
+    if (lane == 0) {
+        for (int k = 0; k < 9; ++k) Ro[k] = Rm[k];
+        for (int k = 0; k < 3; ++k) to[k] = tv[k];
+        dg[0] = before, dg[1] = to_l, dg[2] = to_r, dg[3] = before - 0.5 * (to_l + to_r);
+        a.s[t] = s;
+        a.status[t] = 1;
+    }
+}
+
+// ---- two-view fusion with confidences ------------------------------------------------------------------------------
+struct ViewsArgs {
+    const double *Xl, *Xr, *Ul, *Ur;
+    double *fused, *aligned, *q_l, *q_r, *conf_l, *conf_r, *conf_x, *err_l, *err_r, *dist;
+    int32_t* fit_ok;
+    long T;
+    int J, key[5], torso, min_points;
+    double sigma_px, sigma_3d;
+};
+
+// weakpersp_reproj_confidence of one view: u ~ s (X M) + t fitted on the rows finite in X and U -> conf, err per joint;
+// false (conf 0, err NaN) for fewer than min_points rows or an energy under 1e-12, where the host raises
+__device__ inline bool weakpersp(const double (*X)[3], const double (*U)[2], const bool* act, int min_points, double sigma,
+                                 double* conf, double* err) {
+    const double nan = __builtin_nan("");
+    bool used[2];
+    double cnt = 0.0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        used[k] = act[k] && fin3(X[k]) && is_fin(U[k][0]) && is_fin(U[k][1]);
+        cnt += used[k] ? 1.0 : 0.0;
+    }
+    const double n = wsum(cnt);
+    double mx[3], mu[2], A[9], energy = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) mx[c] = wsum((used[0] ? X[0][c] : 0.0) + (used[1] ? X[1][c] : 0.0)) / n;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) mu[c] = wsum((used[0] ? U[0][c] : 0.0) + (used[1] ? U[1][c] : 0.0)) / n;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            A[3 * r + c] = wsum((used[0] ? (X[0][r] - mx[r]) * (U[0][c] - mu[c]) : 0.0) +
+                                (used[1] ? (X[1][r] - mx[r]) * (U[1][c] - mu[c]) : 0.0));
+        A[3 * r + 2] = 0.0;
+        energy += wsum((used[0] ? (X[0][r] - mx[r]) * (X[0][r] - mx[r]) : 0.0) + (used[1] ? (X[1][r] - mx[r]) * (X[1][r] - mx[r]) : 0.0));
+    }
+    const bool ok = n >= (double)min_points && !(energy < 1e-12) && n > 0.0;
+    double M[9], ssum;
+    polar3(A, M, ssum);                        // M[:, :2] = P[:, :2] Q^T
+    const double s = ssum / energy;
+    double tt[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) tt[c] = mu[c] - s * (mx[0] * M[c] + mx[1] * M[3 + c] + mx[2] * M[6 + c]);
+    const double sg = fmax(sigma, 1e-12), var = sg * sg;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double h0 = s * (X[k][0] * M[0] + X[k][1] * M[3] + X[k][2] * M[6]) + tt[0];
+        const double h1 = s * (X[k][0] * M[1] + X[k][1] * M[4] + X[k][2] * M[7]) + tt[1];
+        const bool fin = ok && act[k] && is_fin(U[k][0]) && is_fin(U[k][1]) && is_fin(h0) && is_fin(h1);
+        const double d0 = h0 - U[k][0], d1 = h1 - U[k][1];
+        const double e = fin ? sqrt(d0 * d0 + d1 * d1) : nan;
+        err[k] = e;
+        conf[k] = is_fin(e) ? exp(-(e * e) / (2.0 * var)) : 0.0;
+    }
+    return ok;
+}
+
+__device__ inline void unit3(double* v, double eps) {
+    const double n = norm3(v[0], v[1], v[2]);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = n < eps ? v[c] * 0.0 : v[c] / n;
+}
+
+// canonicalize_pose_3d: the frame's pose `F` ([J, 3] in memory, for the key joints) applied to the lane's rows X -> C;
+// a missing key joint or a degenerate scale gives NaN rows
+__device__ inline void canonicalize(const double* F, const int* key, int torso, const double (*X)[3], double (*C)[3]) {
+    const double nan = __builtin_nan("");
+    double K[5][3];
+    bool ok = true;
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            K[i][c] = F[3 * key[i] + c];
+            ok = ok && is_fin(K[i][c]);
+        }
+    double lh[3], rh[3], hips[3], sh[3], ex[3], ey[3], ez[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        lh[c] = K[1][c] - K[0][c];
+        rh[c] = K[2][c] - K[0][c];
+        hips[c] = 0.5 * (lh[c] + rh[c]);
+        sh[c] = 0.5 * ((K[3][c] - K[0][c]) + (K[4][c] - K[0][c]));
+        ex[c] = rh[c] - lh[c];
+        ey[c] = sh[c] - hips[c];
+    }
+    const double s = torso ? norm3(ey[0], ey[1], ey[2]) : norm3(ex[0], ex[1], ex[2]);
+    unit3(ex, 1e-9);
+    unit3(ey, 1e-9);
+    ez[0] = ex[1] * ey[2] - ex[2] * ey[1], ez[1] = ex[2] * ey[0] - ex[0] * ey[2], ez[2] = ex[0] * ey[1] - ex[1] * ey[0];
+    unit3(ez, 1e-9);
+    ey[0] = ez[1] * ex[2] - ez[2] * ex[1], ey[1] = ez[2] * ex[0] - ez[0] * ex[2], ey[2] = ez[0] * ex[1] - ez[1] * ex[0];
+    unit3(ey, 1e-9);
+    ok = ok && is_fin(s) && !(s < 1e-9);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double x0 = X[k][0] - K[0][0], x1 = X[k][1] - K[0][1], x2 = X[k][2] - K[0][2];
+        C[k][0] = ok ? (ex[0] * x0 + ex[1] * x1 + ex[2] * x2) / s : nan;
+        C[k][1] = ok ? (ey[0] * x0 + ey[1] * x1 + ey[2] * x2) / s : nan;
+        C[k][2] = ok ? (ez[0] * x0 + ez[1] * x1 + ez[2] * x2) / s : nan;
+    }
+}
+
+__global__ __launch_bounds__(256) void fuse_views_kernel(ViewsArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= a.T) return;                      // the whole wave leaves: no barrier in this kernel
+    const double nan = __builtin_nan("");
+    const int J = a.J;
+    bool act[2];
+    double Xl[2][3], Xr[2][3], Ul[2][2], Ur[2][2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int j = lane + 64 * k;
+        act[k] = j < J;
+        const long row = t * J + (act[k] ? j : 0);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            Xl[k][c] = act[k] ? a.Xl[row * 3 + c] : nan;
+            Xr[k][c] = act[k] ? a.Xr[row * 3 + c] : nan;
+        }
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            Ul[k][c] = act[k] ? a.Ul[row * 2 + c] : nan;
+            Ur[k][c] = act[k] ? a.Ur[row * 2 + c] : nan;
+        }
+    }
+    // align_right_to_left: Kabsch right -> left on the joints finite in both; fewer than 3: the right view unchanged
+    bool both[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) both[k] = act[k] && fin3(Xl[k]) && fin3(Xr[k]);
+    const double nb = wsum((both[0] ? 1.0 : 0.0) + (both[1] ? 1.0 : 0.0));
+    double Al[2][3];
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Al[k][c] = Xr[k][c];
+    if (nb >= 3.0) {
+        double cs[3], cd[3], H[9], P[9], ssum, tv[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            cs[c] = wsum((both[0] ? Xr[0][c] : 0.0) + (both[1] ? Xr[1][c] : 0.0)) / nb;
+            cd[c] = wsum((both[0] ? Xl[0][c] : 0.0) + (both[1] ? Xl[1][c] : 0.0)) / nb;
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                H[3 * r + c] = wsum((both[0] ? (Xr[0][r] - cs[r]) * (Xl[0][c] - cd[c]) : 0.0) +
+                                    (both[1] ? (Xr[1][r] - cs[r]) * (Xl[1][c] - cd[c]) : 0.0));
+        polar3(H, P, ssum);                    // R = V U^T = P^T
+#pragma unroll
+        for (int r = 0; r < 3; ++r) tv[r] = cd[r] - (P[r] * cs[0] + P[3 + r] * cs[1] + P[6 + r] * cs[2]);
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+                if (both[k]) Al[k][r] = (Xr[k][0] * P[r] + Xr[k][1] * P[3 + r] + Xr[k][2] * P[6 + r]) + tv[r];
+    }
+    // the confidences, each view on its raw 3D
+    double cl[2], cr[2], el[2], er[2], Ca[2][3], Cb[2][3];
+    const bool okl = weakpersp(Xl, Ul, act, a.min_points, a.sigma_px, cl, el);
+    const bool okr = weakpersp(Xr, Ur, act, a.min_points, a.sigma_px, cr, er);
+    canonicalize(a.Xl + t * J * 3, a.key, a.torso, Xl, Ca);
+    canonicalize(a.Xr + t * J * 3, a.key, a.torso, Xr, Cb);
+    const double s3 = fmax(a.sigma_3d, 1e-12), var3 = s3 * s3;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (!act[k]) continue;
+        const bool ok = fin3(Ca[k]) && fin3(Cb[k]);
+        const double d0 = Ca[k][0] - Cb[k][0], d1 = Ca[k][1] - Cb[k][1], d2 = Ca[k][2] - Cb[k][2];
+        const double d = ok ? sqrt(d0 * d0 + d1 * d1 + d2 * d2) : nan;
+        const double cx = is_fin(d) ? exp(-(d * d) / (2.0 * var3)) : 0.0;
+        const double ql = sqrt(cl[k] * cx), qr = sqrt(cr[k] * cx);
+        // fuse_frame_3d: softmax2 of the qualities, then (left present) + 2 (right present)
+        const double m = (ql != ql || qr != qr) ? nan : fmax(ql, qr);
+        const double ea = exp(ql - m), eb = exp(qr - m), se = ea + eb + 1e-8;
+        const double wl = ea / se, wr = eb / se;
+        const bool lok = fin3(Xl[k]), rok = fin3(Al[k]);
+        const long row = t * J + lane + 64 * k;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double blend = (wl * Xl[k][c] + wr * Al[k][c]) / (wl + wr + 1e-8);
+            a.fused[row * 3 + c] = lok ? (rok ? blend : Xl[k][c]) : (rok ? Al[k][c] : nan);
+            a.aligned[row * 3 + c] = Al[k][c];
+        }
+        a.q_l[row] = ql, a.q_r[row] = qr;
+        a.conf_l[row] = cl[k], a.conf_r[row] = cr[k], a.conf_x[row] = cx;
+        a.err_l[row] = el[k], a.err_r[row] = er[k], a.dist[row] = d;
+    }
+    if (lane == 0) {
+        a.fit_ok[2 * t] = okl ? 1 : 0;
+        a.fit_ok[2 * t + 1] = okr ? 1 : 0;
+    }
+}
+
+// ---- temporal_smooth_ema: one thread per joint ----------------------------------------------------------------------
+__global__ __launch_bounds__(64) void smooth_ema_kernel(const double* __restrict__ X, long T, long J, const double* __restrict__ base,
+                                                        int adaptive, double amin, double amax, double gain, double* __restrict__ Y) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= J) return;
+    const double nan = __builtin_nan("");
+    const double b = base[j];
+    double st[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) Y[j * 3 + c] = st[c] = X[j * 3 + c];
+    bool has = fin3(st);
+    for (long t0 = 1; t0 < T; t0 += kBatch) {
+        double xb[kBatch][3];
+#pragma unroll
+        for (int i = 0; i < kBatch; ++i)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) xb[i][c] = t0 + i < T ? X[((t0 + i) * J + j) * 3 + c] : nan;
+#pragma unroll
+        for (int i = 0; i < kBatch; ++i) {
+            if (t0 + i >= T) break;
+            const double* x = xb[i];
+            const bool obs = fin3(x);
+            double y[3];
+            if (obs && has) {
+                const double d0 = x[0] - st[0], d1 = x[1] - st[1], d2 = x[2] - st[2];
+                const double al = adaptive ? fmin(fmax(b + gain * sqrt(d0 * d0 + d1 * d1 + d2 * d2), amin), amax) : b;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) y[c] = al * x[c] + (1.0 - al) * st[c];
+            } else {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) y[c] = obs ? x[c] : (has ? st[c] : nan);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Y[((t0 + i) * J + j) * 3 + c] = st[c] = y[c];
+            has = fin3(st);
+        }
+    }
+}
+
+// ---- smooth_skeleton: one thread per (joint, coordinate) series -----------------------------------------------------
+// The finite samples of a series form one contiguous sequence x_0 .. x_{n-1}.  Sample k goes to slot k % win of the
+// thread's ring (values and time indices, LDS, [slot][thread]); once `win` samples are in, every new sample completes the
+// window of the sample win / 2 behind it.  The first and the last window also give the win / 2 edge samples.
+// WIN: the window as a compile-time constant (the loops over it unroll and the FIR row stays in registers), or 0 for any
+// window up to kMaxWin; the arithmetic and its order are the same.
+template <int WIN>
+__global__ __launch_bounds__(64) void smooth_savgol_kernel(const double* __restrict__ X, long T, long S, int win_arg, const double* __restrict__ fir,
+                                                           const double* __restrict__ first, const double* __restrict__ last,
+                                                           double* __restrict__ Y) {
+    const int win = WIN ? WIN : win_arg;
+    __shared__ double ring[WIN ? WIN : kMaxWin][64];
+    __shared__ int ring_t[WIN ? WIN : kMaxWin][64];
+    const int tid = threadIdx.x;
+    const long s = (long)blockIdx.x * 64 + tid;
+    if (s >= S) return;                        // no barrier in this kernel: a thread owns its ring columns
+    const int half = win / 2;
+    long n = 0;
+    for (long t0 = 0; t0 < T; t0 += kBatch) {
+        double xb[kBatch];
+#pragma unroll
+        for (int i = 0; i < kBatch; ++i) xb[i] = t0 + i < T ? X[(t0 + i) * S + s] : __builtin_nan("");
+#pragma unroll
+        for (int i = 0; i < kBatch; ++i) n += is_fin(xb[i]) ? 1 : 0;
+    }
+    const bool filter = n >= win;
+    long k = 0;
+    int head = 0;                              // k % win: the slot of the next sample = of the window's oldest
+    for (long t0 = 0; t0 < T; t0 += kBatch) {
+        double xb[kBatch];
+#pragma unroll
+        for (int i = 0; i < kBatch; ++i) xb[i] = t0 + i < T ? X[(t0 + i) * S + s] : 0.0;
+#pragma unroll
+        for (int i = 0; i < kBatch; ++i) {
+            const long t = t0 + i;
+            if (t >= T) break;
+            const double x = xb[i];
+            if (!filter || !is_fin(x)) {
+                Y[t * S + s] = x;
+                continue;
+            }
+            ring[head][tid] = x;
+            ring_t[head][tid] = (int)t;
+            head = head + 1 == win ? 0 : head + 1;
+            ++k;
+            if (k < win) continue;
+            // the window: element m at slot (head + m) % win
+            if (k == win)
+                for (int e = 0; e < half; ++e) {
+                    double acc = 0.0;
+                    int p = head;
+                    for (int m = 0; m < win; ++m) {
+                        acc += first[e * win + m] * ring[p][tid];
+                        p = p + 1 == win ? 0 : p + 1;
+                    }
+                    const int pe = head + e >= win ? head + e - win : head + e;
+                    Y[(long)ring_t[pe][tid] * S + s] = acc;
+                }
+            {
+                double acc = 0.0;
+                int p = head;
+                for (int m = 0; m < win; ++m) {
+                    acc += fir[m] * ring[p][tid];
+                    p = p + 1 == win ? 0 : p + 1;
+                }
+                const int pc = head + half >= win ? head + half - win : head + half;
+                Y[(long)ring_t[pc][tid] * S + s] = acc;
+            }
+            if (k == n)
+                for (int e = 0; e < half; ++e) {
+                    double acc = 0.0;
+                    int p = head;
+                    for (int m = 0; m < win; ++m) {
+                        acc += last[e * win + m] * ring[p][tid];
+                        p = p + 1 == win ? 0 : p + 1;
+                    }
+                    const int o = head + half + 1 + e;
+                    const int pe = o >= win ? o - win : o;
+                    Y[(long)ring_t[pe][tid] * S + s] = acc;
+                }
+        }
+    }
+}
+
+constexpr long kMaxElems = 1L << 40;          // T * J: every offset 3 (T J) + 2 stays far inside 63 bits
+
+}  // namespace
+}  // namespace skimi
+
+using namespace skimi;
+
+extern "C" {
+
+int skimi_fuse_h36m(const double* left, const double* right, int64_t frames, double tau, const double* tau_j, const double* wL,
+                    int64_t wL_stride, const double* wR, int64_t wR_stride, int32_t allow_scale, int32_t mirror_right_x,
+                    double* fused, double* R, double* t, double* s, double* diag, int32_t* status, void* stream) {
+    SKIMI_CHECK_ARG(frames >= 0 && frames <= kMaxElems / kH36mJoints, "skimi_fuse_h36m: frames = %lld outside 0..2^40 / 17", (long long)frames);
+    SKIMI_CHECK_ARG((wL_stride == 0 || wL_stride == kH36mJoints) && (wR_stride == 0 || wR_stride == kH36mJoints),
+                    "skimi_fuse_h36m: weight strides %lld, %lld are neither 0 ([17]) nor 17 ([frames, 17])", (long long)wL_stride,
+                    (long long)wR_stride);
+    if (frames == 0) return SKIMI_OK;
+    SKIMI_CHECK_ARG(left && right, "skimi_fuse_h36m: NULL input");
+    SKIMI_CHECK_ARG(fused && R && t && s && diag && status, "skimi_fuse_h36m: NULL output");
+    H36mArgs a{};
+    a.left = left, a.right = right, a.tau_j = tau_j, a.wL = wL, a.wR = wR;
+    a.fused = fused, a.R = R, a.t = t, a.s = s, a.diag = diag, a.status = status;
+    a.T = frames, a.wL_stride = wL_stride, a.wR_stride = wR_stride, a.tau = tau;
+    a.allow_scale = allow_scale != 0, a.mirror = mirror_right_x != 0;
+    hipLaunchKernelGGL(fuse_h36m_kernel, dim3((unsigned)cdiv(frames, 4)), dim3(256), 0, (hipStream_t)stream, a);
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
+int skimi_fuse_views(const double* X_l, const double* X_r, const double* U_l, const double* U_r, int64_t frames, int32_t joints,
+                     int32_t root_idx, int32_t left_hip_idx, int32_t right_hip_idx, int32_t left_shoulder_idx,
+                     int32_t right_shoulder_idx, double sigma_px, double sigma_3d, int32_t scale_mode, int32_t min_points,
+                     double* fused, double* aligned, double* q_l, double* q_r, double* conf_l, double* conf_r, double* conf_x,
+                     double* err_l, double* err_r, double* dist, int32_t* fit_ok, void* stream) {
+    SKIMI_CHECK_ARG(joints >= 1 && joints <= kMaxJoints, "skimi_fuse_views: joints = %d outside 1..%d", joints, kMaxJoints);
+    SKIMI_CHECK_ARG(frames >= 0 && frames <= kMaxElems / kMaxJoints, "skimi_fuse_views: frames = %lld outside 0..2^33", (long long)frames);
+    const int32_t key[5] = {root_idx, left_hip_idx, right_hip_idx, left_shoulder_idx, right_shoulder_idx};
+    for (int i = 0; i < 5; ++i)
+        SKIMI_CHECK_ARG(key[i] >= 0 && key[i] < joints, "skimi_fuse_views: key joint %d = %d outside 0..%d", i, key[i], joints - 1);
+    SKIMI_CHECK_ARG(fabs(sigma_px) <= 1.79769313486231570815e308 && fabs(sigma_3d) <= 1.79769313486231570815e308,
+                    "skimi_fuse_views: sigma_px = %g, sigma_3d = %g must be finite", sigma_px, sigma_3d);
+    SKIMI_CHECK_ARG(scale_mode == SKIMI_FUSE_SCALE_HIP || scale_mode == SKIMI_FUSE_SCALE_TORSO, "skimi_fuse_views: unknown scale_mode %d",
+                    scale_mode);
+    SKIMI_CHECK_ARG(min_points >= 1, "skimi_fuse_views: min_points = %d < 1", min_points);
+    if (frames == 0) return SKIMI_OK;
+    SKIMI_CHECK_ARG(X_l && X_r && U_l && U_r, "skimi_fuse_views: NULL input");
+    SKIMI_CHECK_ARG(fused && aligned && q_l && q_r && conf_l && conf_r && conf_x && err_l && err_r && dist && fit_ok,
+                    "skimi_fuse_views: NULL output");
+    ViewsArgs a{};
+    a.Xl = X_l, a.Xr = X_r, a.Ul = U_l, a.Ur = U_r;
+    a.fused = fused, a.aligned = aligned, a.q_l = q_l, a.q_r = q_r, a.conf_l = conf_l, a.conf_r = conf_r, a.conf_x = conf_x;
+    a.err_l = err_l, a.err_r = err_r, a.dist = dist, a.fit_ok = fit_ok;
+    a.T = frames, a.J = joints, a.torso = scale_mode == SKIMI_FUSE_SCALE_TORSO, a.min_points = min_points;
+    for (int i = 0; i < 5; ++i) a.key[i] = key[i];
+    a.sigma_px = sigma_px, a.sigma_3d = sigma_3d;
+    hipLaunchKernelGGL(fuse_views_kernel, dim3((unsigned)cdiv(frames, 4)), dim3(256), 0, (hipStream_t)stream, a);
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
+int skimi_smooth_ema(const double* X, int64_t frames, int64_t joints, const double* base, int32_t adaptive, double alpha_min,
+                     double alpha_max, double speed_gain, double* Y, void* stream) {
+    SKIMI_CHECK_ARG(frames >= 0 && joints >= 0 && joints <= 0x7fffffffLL && (joints == 0 || frames <= kMaxElems / joints),
+                    "skimi_smooth_ema: frames = %lld, joints = %lld outside frames, joints >= 0, frames * joints <= 2^40",
+                    (long long)frames, (long long)joints);
+    if (frames == 0 || joints == 0) return SKIMI_OK;
+    SKIMI_CHECK_ARG(X && base && Y && X != Y, "skimi_smooth_ema: NULL input or output, or Y is X");
+    hipLaunchKernelGGL(smooth_ema_kernel, dim3((unsigned)cdiv(joints, 64)), dim3(64), 0, (hipStream_t)stream, X, (long)frames,
+                       (long)joints, base, adaptive != 0, alpha_min, alpha_max, speed_gain, Y);
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
+int skimi_smooth_savgol(const double* X, int64_t frames, int64_t joints, int32_t win, int32_t poly, const double* fir,
+                        const double* first, const double* last, double* Y, void* stream) {
+    SKIMI_CHECK_ARG(frames >= 0 && frames <= 0x7fffffffLL && joints >= 0 && joints <= 0x7fffffffLL / 3 &&
+                        (joints == 0 || frames <= kMaxElems / joints),
+                    "skimi_smooth_savgol: frames = %lld, joints = %lld outside 0 <= frames < 2^31, joints >= 0, frames * joints <= 2^40",
+                    (long long)frames, (long long)joints);
+    SKIMI_CHECK_ARG(win >= 1 && win <= kMaxWin && win % 2 == 1, "skimi_smooth_savgol: win = %d is not an odd number in 1..%d", win, kMaxWin);
+    SKIMI_CHECK_ARG(poly >= 0 && poly < win, "skimi_smooth_savgol: poly = %d outside 0..win - 1 = %d", poly, win - 1);
+    if (frames == 0 || joints == 0) return SKIMI_OK;
+    SKIMI_CHECK_ARG(X && Y && X != Y && fir && (win == 1 || (first && last)), "skimi_smooth_savgol: NULL input, operator or output, or Y is X");
+    const long S = 3 * joints;
+    const dim3 grid((unsigned)cdiv(S, 64)), block(64);
+    hipStream_t st = (hipStream_t)stream;
+    switch (win) {      // the windows smooth_skeleton's default reaches get a kernel of their own
+        case 3: hipLaunchKernelGGL(smooth_savgol_kernel<3>, grid, block, 0, st, X, (long)frames, S, win, fir, first, last, Y); break;
+        case 5: hipLaunchKernelGGL(smooth_savgol_kernel<5>, grid, block, 0, st, X, (long)frames, S, win, fir, first, last, Y); break;
+        case 7: hipLaunchKernelGGL(smooth_savgol_kernel<7>, grid, block, 0, st, X, (long)frames, S, win, fir, first, last, Y); break;
+        case 9: hipLaunchKernelGGL(smooth_savgol_kernel<9>, grid, block, 0, st, X, (long)frames, S, win, fir, first, last, Y); break;
+        default: hipLaunchKernelGGL(smooth_savgol_kernel<0>, grid, block, 0, st, X, (long)frames, S, win, fir, first, last, Y);
+    }
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
+}  // extern "C"

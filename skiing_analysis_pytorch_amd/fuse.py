@@ -6,7 +6,10 @@ the VideoPose3D left/right fusion without extrinsics (VideoPose3D/fuse/fuse.py, 
 O(T*J) host NumPy in the reference and here — the EMA is sequential in t, the data are a few KB,
 and the NaN-aware masks (missing joints) must be preserved bit-for-bit, so these run on the
 gathered tensor on every rank rather than as GPU kernels.  Array form ([J,3] / [T,J,3] with NaN
-for missing joints) of the reference's dict form; `to_dicts` / `from_dicts` convert."""
+for missing joints) of the reference's dict form; `to_dicts` / `from_dicts` convert.
+
+Opt-in device counterparts (csrc/fuse.hip): geometry.fuse_h36m, fuse_views, smooth_ema, smooth_savgol.  The functions here
+stay as they are: pinned to the reference by tests/golden/fuse_*.npz, they are what the kernels are tested against."""
 from __future__ import annotations
 
 from typing import Dict, Iterable, List, Sequence
@@ -88,6 +91,30 @@ def _savgol_interp(x: np.ndarray, win: int, poly: int) -> np.ndarray:
         y[:half] = np.polyval(np.polyfit(grid, x[:win], poly), grid[:half])
         y[n - half:] = np.polyval(np.polyfit(grid, x[n - win:], poly), grid[win - half:])
     return y
+
+
+def savgol_window(T: int, win: int = 9) -> int:
+    """the window smooth_skeleton uses on a clip of T steps: the reference's min(odd(win), max(1 if T is odd else T - 1, 3))"""
+    return min(win if win % 2 == 1 else win + 1, max(1 if T % 2 == 1 else T - 1, 3))
+
+
+def savgol_operators(win: int, poly: int):
+    """_savgol_interp as three linear operators in float64, for geometry.smooth_savgol: (fir [win], first [win // 2, win],
+    last [win // 2, win]).  On a series x of n >= win samples y[k] = fir @ x[k - win // 2 : k + win // 2 + 1] in the
+    interior, y[:win // 2] = first @ x[:win] and y[n - win // 2:] = last @ x[n - win:].  All three are rows of the hat matrix
+    Q Q^T of the degree-`poly` least-squares fit on `win` equally spaced samples (Q: the orthonormal basis of the
+    polynomials on the centred, scaled grid, which keeps the rows to rounding where the raw Vandermonde matrix would not):
+    the fitted polynomial read off at the window's centre, at its first and at its last win // 2 samples."""
+    win, poly = int(win), int(poly)
+    if win < 1 or win % 2 == 0:
+        raise ValueError("window_length must be a positive odd integer.")
+    if poly < 0 or poly >= win:
+        raise ValueError("polyorder must be less than window_length.")
+    half = win // 2
+    grid = np.arange(-half, half + 1, dtype=np.float64) / max(half, 1)
+    Q, _ = np.linalg.qr(grid[:, None] ** np.arange(poly + 1)[None, :])
+    H = Q @ Q.T
+    return H[half].copy(), H[:half].copy(), H[win - half:].copy()
 
 
 def smooth_skeleton(X: np.ndarray, win: int = 9, poly: int = 2) -> np.ndarray:

@@ -301,7 +301,7 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
                             scores: Optional[torch.Tensor] = None, source_size=None, triage: bool = False,
                             conf_thr: float = 0.3, err_thresh_px: float = 2.0, robust: bool = False,
                             inlier_px: Optional[float] = None, min_inliers: int = 2, refine_iters: int = 5,
-                            weighted: bool = False) -> Dict[str, torch.Tensor]:
+                            weighted: bool = False, device_smooth: bool = False) -> Dict[str, torch.Tensor]:
     """The hot loop of process_multi_view_video (vggt/multi_view_process.py:133-309) for a clip
     already in memory: frames [T, S, 3, H, W] in [0,1] (device), keypoints [T, S, J, 2] in the
     pixels of the H x W frames.  Per time step: one S-view VGGT call -> cameras -> DLT
@@ -311,6 +311,9 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
     [T, J, 3] joints (+ cameras) are re-assembled on every rank with ONE all-gather of packed per-step
     records (parallel.all_gather_packed).  smooth=True chains BASELINE config 4's last stage on the gathered
     joints: `fuse.temporal_smooth_ema` (fuse/fuse.py:329-412) -> "joints3d_smoothed" [T, J, 3] float64 (host).
+    device_smooth=True (with smooth=True) computes the smoothed keys with geometry.smooth_ema / geometry.smooth_savgol
+    instead and returns them as device float64 tensors: the joints are not read back.  Off (the default), the function
+    is what it was.
 
     streams > 1: the calls of this rank (chunks of steps_per_call time steps, independent of each
     other) are issued from that many host threads on as many HIP streams, so the HBM-bound phases of
@@ -465,6 +468,13 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
         # BASELINE config 4: after the gather, fuse/'s temporal smoothing over the whole clip (sequential in t,
         # O(T J) on the host as in the reference: fuse/fuse.py:329-412); every rank holds the same result
         from . import fuse
+        if device_smooth:   # the same three keys as device float64 tensors: the joints never leave the device
+            out["joints3d_smoothed"] = geometry.smooth_ema(joints).X
+            if triage:
+                out["joints3d_clean_smoothed"] = geometry.smooth_savgol(out["joints3d_clean"]).X
+            if robust:
+                out["joints3d_robust_smoothed"] = geometry.smooth_savgol(out["joints3d_robust_ok"]).X
+            return out
         out["joints3d_smoothed"] = torch.from_numpy(fuse.temporal_smooth_ema(joints.cpu().numpy().astype(np.float64)))
         if triage:   # the reference's post_triage_sequence(smooth=True): Savitzky-Golay over the kept joints
             out["joints3d_clean_smoothed"] = torch.from_numpy(

@@ -289,13 +289,21 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
     # (no-op on one rank)
     dev = head.device
     todev = lambda lst: torch.from_numpy(np.stack(lst)).to(dev)   # noqa: E731
-    gathered = [a.cpu().numpy() for a in parallel.all_gather_packed(
+    parts = parallel.all_gather_packed(
         [torch.cat(x3d_l), todev(K_l), todev(R_l), todev(t_l), todev(C_l)]
         + ([torch.cat([r[k] for r in triage_l]) for k in range(5)] if triage else [])
-        + ([torch.cat([r[k] for r in robust_l]) for k in range(8)] if robust else []), T)]
+        + ([torch.cat([r[k] for r in robust_l]) for k in range(8)] if robust else []), T)
+    gathered = [a.cpu().numpy() for a in parts]
     x3d, Ka, Ra, ta, Ca = gathered[:5]
-    # fuse/'s temporal smoothing of the gathered joints (BASELINE config 4; fuse/fuse.py:329-412)
-    x3d_smoothed = fuse.temporal_smooth_ema(x3d.astype(np.float64)) if cfg_get(cfg, "infer.smooth", True) else None
+    # fuse/'s temporal smoothing of the gathered joints (BASELINE config 4; fuse/fuse.py:329-412); opt-in
+    # infer.device_smooth: the same filter as one launch on the gathered device tensor (geometry.smooth_ema)
+    if not cfg_get(cfg, "infer.smooth", True):
+        x3d_smoothed = None
+    elif cfg_get(cfg, "infer.device_smooth", False):
+        with torch.cuda.device(dev):
+            x3d_smoothed = geometry.smooth_ema(parts[0]).X.cpu().numpy()
+    else:
+        x3d_smoothed = fuse.temporal_smooth_ema(x3d.astype(np.float64))
     if parallel.world()[0] == 0:
         # the reference stores R, t and the joints AFTER its ICP update (multi_view_process.py:285-319); with
         # infer.icp off (the default) the arrays are the pre-ICP quantities under the same keys, icp_refined = False

@@ -15,6 +15,9 @@ keypoints -> each camera's (R, t) and the pair's relative pose, on the device (g
 `solve_rt_and_points` is that script's `--refine camera_points` mode: the joints are refined together with the cameras
 (geometry.refine_cameras_points).  `solve_rt_from_essential` is its `--init essential` path: the right camera's pose relative to
 the left one from the essential matrix of the 2D keypoints alone (geometry.essential_ransac), then the same refinement.
+
+`process_video_3d` is the counterpart of VideoPose3D/main.py's process_video_3d: both views lifted, then fused per frame
+without extrinsics on the device (geometry.fuse_h36m), and the fused joints written as the reference writes them.
 """
 from __future__ import annotations
 
@@ -89,6 +92,28 @@ def run_video_pose_3d(config, pt_path: Path, out_dir: Path, args, model_pos: Tem
     if isinstance(depth, torch.Tensor):
         depth = depth.squeeze()
     return prediction, depth
+
+
+def process_video_3d(config, left_path: Path, right_path: Path, out_dir: Path, npy_dir: Path, args, model_pos: TemporalModel = None):
+    """VideoPose3D/main.py:33-103 process_video_3d without its GIF and without eval_fused_pose: both views' clips are lifted
+    (run_video_pose_3d into <out_dir>/videopose3d/left and /right) and fused frame by frame with the reference's settings
+    (tau = 0.06, allow_scale = False, mirror_right_x = False) -- here as ONE geometry.fuse_h36m launch over the clip, in
+    float64, where the reference loops over the frames on the host.  The fused, left and right joints are written with
+    formats.save_3d_joints to "<npy_dir>_fused_keypoints.npy" (:85-90).  The clips are cut to the shorter one (the reference
+    indexes the right clip by the left one's length and would raise).  `args` is passed in where the reference parses the
+    command line (:41).  -> (fused [T, 17, 3] float64 on the device, geometry.FuseH36MResult with the per-frame R, t, s,
+    diagnostics, status, mean_gain and bad_frames on the device)."""
+    out_dir = Path(out_dir)
+    left, _ = run_video_pose_3d(config, left_path, out_dir / "videopose3d" / "left", args, model_pos=model_pos)
+    right, _ = run_video_pose_3d(config, right_path, out_dir / "videopose3d" / "right", args, model_pos=model_pos)
+    T = min(left.shape[0], right.shape[0])
+    left, right = left[:T], right[:T]
+    dev = torch.device("cuda", torch.cuda.current_device())
+    res = geometry.fuse_h36m(torch.from_numpy(np.ascontiguousarray(left)).to(dev, torch.float64),
+                             torch.from_numpy(np.ascontiguousarray(right)).to(dev, torch.float64), tau=0.06, allow_scale=False,
+                             mirror_right_x=False)
+    formats.save_3d_joints(res.fused.cpu().numpy(), left, right, Path(str(npy_dir) + "_fused_keypoints.npy"))
+    return res.fused, res
 
 
 def _rt_inputs(X3d, x2d_left, x2d_right, conf_left, conf_right, K_left, K_right, huber, min_conf):
