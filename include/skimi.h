@@ -849,6 +849,86 @@ int skimi_smooth_ema(const double* X, int64_t frames, int64_t joints, const doub
 int skimi_smooth_savgol(const double* X, int64_t frames, int64_t joints, int32_t win, int32_t poly, const double* fir,
                         const double* first, const double* last, double* Y, void* stream);
 
+/* ---- VGGT head and track-head helper kernels, one launch each ----
+ * The kernels skimi_vggt_forward runs between its GEMMs, exposed singly so that each can be tested against a float64
+ * restatement.  All maps are channels-last and dense; dtype / out_dtype are SKIMI_F32, SKIMI_BF16 or SKIMI_F16.  Every
+ * call rejects null buffers, non-positive sizes and the shapes named below with SKIMI_ERR_ARG. */
+
+/* F.interpolate(mode="bilinear", align_corners=True) of in [N, h, w, C] to out [N, H, W, C]; C % 4 == 0, N * H < 65536,
+ * buffers 16-byte aligned.  Index arithmetic in float32 as ATen: scale = (in - 1) / (out - 1) (0 when out == 1), src =
+ * scale * dst, i0 = min((int)src, in - 1), i1 = min(i0 + 1, in - 1), l1 = clamp(src - i0, 0, 1), l0 = 1 - l1;
+ * v = l0y (l0x p00 + l1x p01) + l1y (l0x p10 + l1x p11) in fp32.  out_dtype < 0: the input's; else the input's, or
+ * SKIMI_F32 from a 16-bit map.  tabx [W, C/2], taby [H, C/2] fp32 (both or neither, C % 8 == 0): v += c < C/2 ?
+ * tabx[X][c] : taby[Y][c - C/2].  ln_g, ln_b [128] (both or neither; C == 128, fp32 out): every output pixel is then
+ * LayerNorm'ed over its channels (two-pass variance, eps ln_eps) before it is stored. */
+int skimi_resize_bilinear(const void* in, void* out, int32_t dtype, int32_t out_dtype, int32_t N, int32_t h, int32_t w,
+                          int32_t H, int32_t W, int32_t C, const float* tabx, const float* taby, const float* ln_g,
+                          const float* ln_b, float ln_eps, void* stream);
+/* The same resize (+ tables) of an fp32 map written as bf16 halves hi = bf16(v), lo = bf16(v - hi) (round to nearest
+ * even).  slice_records == 0: out [N, H, W, hi C | lo C], C % 16 == 0.  slice_records != 0: out [N, H, W, C/32,
+ * hi 32 | lo 32], C % 32 == 0.  zpage (or NULL): 256 bytes that are cleared. */
+int skimi_resize_bilinear_planes(const float* in, void* out, int32_t N, int32_t h, int32_t w, int32_t H, int32_t W,
+                                 int32_t C, const float* tabx, const float* taby, int32_t slice_records, void* zpage,
+                                 void* stream);
+/* x [N, H, W, C] += c < C/2 ? tabx[X][c] : taby[Y][c - C/2] in place (sum in fp32, one rounding to x's type);
+ * tabx [W, C/2], taby [H, C/2] fp32; C % 8 == 0. */
+int skimi_add_uv_pos(void* x, int32_t dtype, const float* tabx, const float* taby, int32_t N, int32_t H, int32_t W,
+                     int32_t C, void* stream);
+/* The same sum of an fp32 x (tabx NULL: x alone), x left as it is, written as records rec [N * H * W, C/32, hi 32 |
+ * lo 32] bf16 followed by 256 zero bytes (rec holds N * H * W * 2 C * 2 + 256 bytes); C % 32 == 0. */
+int skimi_add_uv_pos_records(const float* x, const float* tabx, const float* taby, int32_t N, int32_t H, int32_t W,
+                             int32_t C, void* rec, void* stream);
+/* y[px][n] = sum_k in[px][k] W[n][k] + b[n], in [npix, 32], W [n_out, 32], n_out 2 or 4, fp32 accumulate in ascending k.
+ * pts [npix, n_out - 1]: mode 0 exp(y), mode 1 sign(y) expm1(|y|); conf [npix] = 1 + exp(y[n_out - 1]). */
+int skimi_dpt_out(const void* in, int32_t dtype, const float* W, const float* b, int32_t n_out, float* pts, float* conf,
+                  int64_t npix, int32_t mode, void* stream);
+/* img [F, 3, H, W] fp32 -> out [F * (H/p) * (W/p), Kp]: out[(f, py, px)][c p^2 + dy p + dx] = (img[f, c, py p + dy,
+ * px p + dx] - mean[c]) / std[c] (ImageNet statistics), columns 3 p^2 .. Kp - 1 zero; Kp >= 3 p^2. */
+int skimi_patch_gather(const float* img, void* out, int32_t out_dtype, int32_t F, int32_t H, int32_t W, int32_t p,
+                       int32_t Kp, void* stream);
+/* out = gate * (xn * (1 + scale) + shift) + x; xn, x, out [rows, D], mod [rows, shift D | scale D | gate D]. */
+int skimi_adaln(const float* xn, const float* x, const float* mod, float* out, int64_t rows, int32_t D, void* stream);
+/* pred = first ? delta : pred + delta on columns 0..8 of pred_pad [rows, 16] (columns 9..15 are left alone);
+ * act_out [rows, 9] = pred with relu on columns 7 and 8; delta [rows, 9]. */
+int skimi_pose_update(const float* delta, float* pred_pad, float* act_out, int64_t rows, int32_t first, void* stream);
+/* x [F, P, C]: x[f, 0:n, :] = table[f % S == 0 ? 0 : 1][0:n, :], table [2, n, C]; rows n..P-1 are left alone. */
+int skimi_special_tokens(float* x, const float* table, int32_t F, int32_t S, int32_t P, int32_t n, int32_t C, void* stream);
+
+/* F.avg_pool2d(2, 2) of in [N, H, W, C] to out [N, H/2, W/2, C] (an odd last row / column is dropped). */
+int skimi_track_avgpool2(const float* in, float* out, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
+/* Bilinear sample (align_corners, border padding) of image b of fmap (images [H, W, C], img_stride floats apart,
+ * img_stride >= H W C) at (x, y) = coords[(b N + n) coord_stride + 0 / 1] (coord_stride >= 2) -> out [B, N, C]. */
+int skimi_track_sample_border(const float* fmap, int64_t img_stride, const float* coords, int64_t coord_stride, float* out,
+                              int32_t B, int32_t N, int32_t H, int32_t W, int32_t C, void* stream);
+/* One pyramid level of CorrBlock.corr_sample without the correlation volume: for row = (b, n, s) of rows = B N S,
+ * out[row ldo + out_off + i (2r+1) + j] = <tgt[row], sample(fmap[b S + s])> / sqrt(C), sampled bilinearly (align_corners,
+ * zeros padding) at (coords[row][0] / 2^level + i - r, coords[row][1] / 2^level + j - r): grid row i offsets x, column j
+ * offsets y.  tgt [rows, C], fmap [B S, H, W, C], coords [rows, 2]; ldo >= out_off + (2r+1)^2. */
+int skimi_track_corr_sample(const float* tgt, const float* fmap, const float* coords, float* out, int64_t rows, int32_t N,
+                            int32_t S, int32_t H, int32_t W, int32_t C, int32_t r, int32_t level, int64_t ldo,
+                            int32_t out_off, void* stream);
+/* The 2D sin/cos position embedding of an H x W grid (get_2d_sincos_pos_embed, table values rounded to fp32) sampled
+ * as skimi_track_sample_border does at coords[bn coord_stride + 0 / 1] -> out [BN, D]; D % 4 == 0: [sin x | cos x |
+ * sin y | cos y], D/4 frequencies 1 / 10000^(k / (D/4)) each. */
+int skimi_track_pos_embed_sample(const float* coords, int64_t coord_stride, float* out, int32_t BN, int32_t H, int32_t W,
+                                 int32_t D, void* stream);
+/* x[row] = [emb(flow) L | flow / max_scale, twice | fcorr[row] L | tfeat[row] L] + pos[bn] + qrt[s == 0 ? 0 : 1] for
+ * row = (bn, s) of coords [rows, 2]; flow = coords[row] - coords[(bn, 0)]; emb = [x part L/2 | y part L/2], element
+ * 2k sin(flow 2k (1000 / (L/2))), element 2k + 1 its cos.  pos [rows / S, 3L + 4], qrt [2, 3L + 4]; x has row stride
+ * ldx >= 3L + 4 and its columns 3L + 4 .. ldx - 1 are written 0; L % 4 == 0. */
+int skimi_track_input(const float* coords, const float* fcorr, const float* tfeat, const float* pos, const float* qrt,
+                      float* x, int64_t rows, int32_t S, int32_t L, int64_t ldx, float max_scale, void* stream);
+/* coords [rows, 2] += delta[row ldd + 0 / 1] (ldd >= 2), rows (b, n, s); rows with s == 0 are set to query[b, n]
+ * instead.  pred (or NULL) [B, S, N, 2] = the new coords * stride. */
+int skimi_track_coord_update(float* coords, const float* delta, int64_t ldd, const float* query, float* pred, int64_t rows,
+                             int32_t N, int32_t S, float stride, void* stream);
+/* coords [BN, S, 2] = q [BN, 2] * (1 / stride) for every s; qs [BN, 2] the same. */
+int skimi_track_init(const float* q, float* coords, float* qs, int64_t BN, int32_t S, float stride, void* stream);
+/* dst [BN, S, C] = src [BN, C] repeated over S. */
+int skimi_track_repeat_rows(const float* src, float* dst, int64_t BN, int32_t S, int32_t C, void* stream);
+/* out [B, S, N] = in [B, N, S]. */
+int skimi_track_bns_to_bsn(const float* in, float* out, int32_t B, int32_t N, int32_t S, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,24 @@ _SIGNATURES = {
                                    _vp, _vp]),
     "skimi_smooth_ema": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, C.c_int32, C.c_double, C.c_double, C.c_double, _vp, _vp]),
     "skimi_smooth_savgol": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
+    "skimi_resize_bilinear": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_float, _vp]),
+    "skimi_resize_bilinear_planes": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
+    "skimi_add_uv_pos": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "skimi_add_uv_pos_records": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "skimi_dpt_out": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp, C.c_int64, C.c_int32, _vp]),
+    "skimi_patch_gather": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "skimi_adaln": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, _vp]),
+    "skimi_pose_update": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int32, _vp]),
+    "skimi_special_tokens": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "skimi_track_avgpool2": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "skimi_track_sample_border": (C.c_int, [_vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "skimi_track_corr_sample": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, _vp]),
+    "skimi_track_pos_embed_sample": (C.c_int, [_vp, C.c_int64, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "skimi_track_input": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_float, _vp]),
+    "skimi_track_coord_update": (C.c_int, [_vp, _vp, C.c_int64, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, C.c_float, _vp]),
+    "skimi_track_init": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int32, C.c_float, _vp]),
+    "skimi_track_repeat_rows": (C.c_int, [_vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp]),
+    "skimi_track_bns_to_bsn": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "skimi_vggt_create": (_vp, [_vp]),
     "skimi_vggt_destroy": (None, [_vp]),
     "skimi_vggt_set_weight": (C.c_int, [_vp, C.c_char_p, _vp, C.c_int64, C.c_int32]),

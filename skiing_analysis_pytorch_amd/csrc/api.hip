@@ -7,6 +7,7 @@
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "kernels.h"
+#include "track_kernels.h"
 #include "vggt_kernels.h"
 
 namespace skimi {
@@ -256,6 +257,161 @@ int skimi_attention_ex(const void* qkv, void* out, int32_t dtype, int32_t out_dt
 
 uint64_t skimi_attention_x3_scratch_bytes(int64_t tokens, int64_t row_elems) {
     return (uint64_t)attention_x3_scratch_bytes((long)tokens, (long)row_elems);
+}
+
+// ---- VGGT head / track-head helper kernels, one launch each (vggt_kernels.hip, track_kernels.hip): the forward
+// calls the launches directly with sizes it derived itself; here every scalar a caller supplies is checked first ----
+static inline bool is_elem_dtype(int32_t d) { return d == SKIMI_F32 || d == SKIMI_BF16 || d == SKIMI_F16; }
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+int skimi_resize_bilinear(const void* in, void* out, int32_t dtype, int32_t out_dtype, int32_t N, int32_t h, int32_t w,
+                          int32_t H, int32_t W, int32_t C, const float* tabx, const float* taby, const float* ln_g,
+                          const float* ln_b, float ln_eps, void* stream) {
+    SKIMI_CHECK_ARG(in && out, "skimi_resize_bilinear: null map");
+    SKIMI_CHECK_ARG(N > 0 && h > 0 && w > 0 && H > 0 && W > 0 && C > 0, "skimi_resize_bilinear: sizes must be positive");
+    SKIMI_CHECK_ARG(is_elem_dtype(dtype) && (out_dtype < 0 || is_elem_dtype(out_dtype)), "skimi_resize_bilinear: bad dtype");
+    SKIMI_CHECK_ARG(al16(in) && al16(out) && al16(tabx) && al16(taby), "skimi_resize_bilinear: 16-byte aligned buffers");
+    return bilinear_ac_launch(in, out, dtype, N, h, w, H, W, C, (hipStream_t)stream, tabx, taby, out_dtype, ln_g, ln_b, ln_eps);
+}
+
+int skimi_resize_bilinear_planes(const float* in, void* out, int32_t N, int32_t h, int32_t w, int32_t H, int32_t W,
+                                 int32_t C, const float* tabx, const float* taby, int32_t slice_records, void* zpage,
+                                 void* stream) {
+    SKIMI_CHECK_ARG(in && out, "skimi_resize_bilinear_planes: null map");
+    SKIMI_CHECK_ARG(N > 0 && h > 0 && w > 0 && H > 0 && W > 0 && C > 0, "skimi_resize_bilinear_planes: sizes must be positive");
+    SKIMI_CHECK_ARG(al16(in) && al16(out) && al16(tabx) && al16(taby) && al16(zpage),
+                    "skimi_resize_bilinear_planes: 16-byte aligned buffers");
+    return bilinear_ac_planes_launch(in, (unsigned short*)out, N, h, w, H, W, C, (hipStream_t)stream, tabx, taby, slice_records,
+                                     zpage);
+}
+
+int skimi_add_uv_pos(void* x, int32_t dtype, const float* tabx, const float* taby, int32_t N, int32_t H, int32_t W,
+                     int32_t C, void* stream) {
+    SKIMI_CHECK_ARG(x && tabx && taby, "skimi_add_uv_pos: null map or table");
+    SKIMI_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0, "skimi_add_uv_pos: sizes must be positive");
+    SKIMI_CHECK_ARG(is_elem_dtype(dtype), "skimi_add_uv_pos: bad dtype %d", dtype);
+    SKIMI_CHECK_ARG(al16(x) && al16(tabx) && al16(taby), "skimi_add_uv_pos: 16-byte aligned buffers");
+    return add_uv_pos_launch(x, dtype, tabx, taby, N, H, W, C, (hipStream_t)stream);
+}
+
+int skimi_add_uv_pos_records(const float* x, const float* tabx, const float* taby, int32_t N, int32_t H, int32_t W,
+                             int32_t C, void* rec, void* stream) {
+    SKIMI_CHECK_ARG(x && rec, "skimi_add_uv_pos_records: null map or records");
+    SKIMI_CHECK_ARG(tabx == nullptr || taby != nullptr, "skimi_add_uv_pos_records: needs both tables or none");
+    SKIMI_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0, "skimi_add_uv_pos_records: sizes must be positive");
+    SKIMI_CHECK_ARG(al16(x) && al16(tabx) && al16(taby) && al16(rec), "skimi_add_uv_pos_records: 16-byte aligned buffers");
+    return add_uv_pos_records_launch(x, tabx, taby, N, H, W, C, rec, (hipStream_t)stream);
+}
+
+int skimi_dpt_out(const void* in, int32_t dtype, const float* W, const float* b, int32_t n_out, float* pts, float* conf,
+                  int64_t npix, int32_t mode, void* stream) {
+    SKIMI_CHECK_ARG(in && W && b && pts && conf, "skimi_dpt_out: null buffer");
+    SKIMI_CHECK_ARG(npix > 0, "skimi_dpt_out: npix must be positive");
+    SKIMI_CHECK_ARG(is_elem_dtype(dtype) && (mode == 0 || mode == 1), "skimi_dpt_out: bad dtype or mode");
+    SKIMI_CHECK_ARG(al16(in), "skimi_dpt_out: 16-byte aligned input");
+    return dpt_out_launch(in, dtype, W, b, n_out, pts, conf, (long)npix, mode, (hipStream_t)stream);
+}
+
+int skimi_patch_gather(const float* img, void* out, int32_t out_dtype, int32_t F, int32_t H, int32_t W, int32_t p,
+                       int32_t Kp, void* stream) {
+    SKIMI_CHECK_ARG(img && out, "skimi_patch_gather: null buffer");
+    SKIMI_CHECK_ARG(F > 0 && p > 0 && H >= p && W >= p, "skimi_patch_gather: needs F > 0 and 0 < p <= H, W");
+    SKIMI_CHECK_ARG(is_elem_dtype(out_dtype), "skimi_patch_gather: bad out_dtype %d", out_dtype);
+    SKIMI_CHECK_ARG((long)Kp >= 3L * p * p, "skimi_patch_gather: Kp = %d is less than 3 p^2", Kp);
+    return patch_gather_launch(img, out, out_dtype, F, H, W, p, Kp, (hipStream_t)stream);
+}
+
+int skimi_adaln(const float* xn, const float* x, const float* mod, float* out, int64_t rows, int32_t D, void* stream) {
+    SKIMI_CHECK_ARG(xn && x && mod && out, "skimi_adaln: null buffer");
+    SKIMI_CHECK_ARG(rows > 0 && D > 0, "skimi_adaln: sizes must be positive");
+    return adaln_launch(xn, x, mod, out, (long)rows, D, (hipStream_t)stream);
+}
+
+int skimi_pose_update(const float* delta, float* pred_pad, float* act_out, int64_t rows, int32_t first, void* stream) {
+    SKIMI_CHECK_ARG(delta && pred_pad && act_out, "skimi_pose_update: null buffer");
+    SKIMI_CHECK_ARG(rows > 0, "skimi_pose_update: rows must be positive");
+    return pose_update_launch(delta, pred_pad, act_out, (long)rows, first, (hipStream_t)stream);
+}
+
+int skimi_special_tokens(float* x, const float* table, int32_t F, int32_t S, int32_t P, int32_t n, int32_t C, void* stream) {
+    SKIMI_CHECK_ARG(x && table, "skimi_special_tokens: null buffer");
+    SKIMI_CHECK_ARG(F > 0 && S > 0 && n > 0 && C > 0, "skimi_special_tokens: sizes must be positive");
+    SKIMI_CHECK_ARG(n <= P, "skimi_special_tokens: n = %d special tokens exceed the %d tokens of a frame", n, P);
+    return special_tokens_launch(x, table, F, S, P, n, C, (hipStream_t)stream);
+}
+
+int skimi_track_avgpool2(const float* in, float* out, int32_t N, int32_t H, int32_t W, int32_t C, void* stream) {
+    SKIMI_CHECK_ARG(in && out, "skimi_track_avgpool2: null buffer");
+    SKIMI_CHECK_ARG(N > 0 && H >= 2 && W >= 2 && C > 0, "skimi_track_avgpool2: needs N, C > 0 and H, W >= 2");
+    return avgpool2_launch(in, out, N, H, W, C, (hipStream_t)stream);
+}
+
+int skimi_track_sample_border(const float* fmap, int64_t img_stride, const float* coords, int64_t coord_stride, float* out,
+                              int32_t B, int32_t N, int32_t H, int32_t W, int32_t C, void* stream) {
+    SKIMI_CHECK_ARG(fmap && coords && out, "skimi_track_sample_border: null buffer");
+    SKIMI_CHECK_ARG(B > 0 && N > 0 && H > 0 && W > 0 && C > 0, "skimi_track_sample_border: sizes must be positive");
+    SKIMI_CHECK_ARG(img_stride >= (int64_t)H * W * C, "skimi_track_sample_border: img_stride is less than H * W * C");
+    SKIMI_CHECK_ARG(coord_stride >= 2, "skimi_track_sample_border: coord_stride must be >= 2");
+    return sample_border_launch(fmap, (long)img_stride, coords, (long)coord_stride, out, B, N, H, W, C, (hipStream_t)stream);
+}
+
+int skimi_track_corr_sample(const float* tgt, const float* fmap, const float* coords, float* out, int64_t rows, int32_t N,
+                            int32_t S, int32_t H, int32_t W, int32_t C, int32_t r, int32_t level, int64_t ldo,
+                            int32_t out_off, void* stream) {
+    SKIMI_CHECK_ARG(tgt && fmap && coords && out, "skimi_track_corr_sample: null buffer");
+    SKIMI_CHECK_ARG(rows > 0 && N > 0 && S > 0 && H > 0 && W > 0 && C > 0, "skimi_track_corr_sample: sizes must be positive");
+    SKIMI_CHECK_ARG(rows % ((int64_t)N * S) == 0, "skimi_track_corr_sample: rows must be a multiple of N * S");
+    SKIMI_CHECK_ARG(r >= 0 && r <= 64 && level >= 0 && level < 16, "skimi_track_corr_sample: needs 0 <= r <= 64, 0 <= level < 16");
+    SKIMI_CHECK_ARG(out_off >= 0 && ldo >= (int64_t)out_off + (2 * r + 1) * (2 * r + 1),
+                    "skimi_track_corr_sample: ldo is less than out_off + (2r+1)^2");
+    return corr_sample_launch(tgt, fmap, coords, out, (long)rows, N, S, H, W, C, r, level, (long)ldo, out_off, (hipStream_t)stream);
+}
+
+int skimi_track_pos_embed_sample(const float* coords, int64_t coord_stride, float* out, int32_t BN, int32_t H, int32_t W,
+                                 int32_t D, void* stream) {
+    SKIMI_CHECK_ARG(coords && out, "skimi_track_pos_embed_sample: null buffer");
+    SKIMI_CHECK_ARG(BN > 0 && H > 0 && W > 0 && D > 0, "skimi_track_pos_embed_sample: sizes must be positive");
+    SKIMI_CHECK_ARG(D % 4 == 0, "skimi_track_pos_embed_sample: needs D %% 4 == 0 (got %d)", D);
+    SKIMI_CHECK_ARG(coord_stride >= 2, "skimi_track_pos_embed_sample: coord_stride must be >= 2");
+    return pos_embed_sample_launch(coords, (long)coord_stride, out, BN, H, W, D, (hipStream_t)stream);
+}
+
+int skimi_track_input(const float* coords, const float* fcorr, const float* tfeat, const float* pos, const float* qrt,
+                      float* x, int64_t rows, int32_t S, int32_t L, int64_t ldx, float max_scale, void* stream) {
+    SKIMI_CHECK_ARG(coords && fcorr && tfeat && pos && qrt && x, "skimi_track_input: null buffer");
+    SKIMI_CHECK_ARG(rows > 0 && S > 0 && L > 0 && rows % S == 0, "skimi_track_input: needs rows, S, L > 0 and rows %% S == 0");
+    SKIMI_CHECK_ARG(L % 4 == 0, "skimi_track_input: needs L %% 4 == 0 (got %d)", L);
+    SKIMI_CHECK_ARG(ldx >= 3L * L + 4, "skimi_track_input: ldx is less than 3 L + 4");
+    SKIMI_CHECK_ARG(max_scale > 0.f, "skimi_track_input: max_scale must be positive");
+    return track_input_launch(coords, fcorr, tfeat, pos, qrt, x, (long)rows, S, L, (long)ldx, max_scale, (hipStream_t)stream);
+}
+
+int skimi_track_coord_update(float* coords, const float* delta, int64_t ldd, const float* query, float* pred, int64_t rows,
+                             int32_t N, int32_t S, float stride, void* stream) {
+    SKIMI_CHECK_ARG(coords && delta && query, "skimi_track_coord_update: null buffer");
+    SKIMI_CHECK_ARG(rows > 0 && N > 0 && S > 0 && rows % ((int64_t)N * S) == 0,
+                    "skimi_track_coord_update: needs rows, N, S > 0 and rows a multiple of N * S");
+    SKIMI_CHECK_ARG(ldd >= 2, "skimi_track_coord_update: ldd must be >= 2");
+    return track_coord_update_launch(coords, delta, (long)ldd, query, pred, (long)rows, N, S, stride, (hipStream_t)stream);
+}
+
+int skimi_track_init(const float* q, float* coords, float* qs, int64_t BN, int32_t S, float stride, void* stream) {
+    SKIMI_CHECK_ARG(q && coords && qs, "skimi_track_init: null buffer");
+    SKIMI_CHECK_ARG(BN > 0 && S > 0, "skimi_track_init: sizes must be positive");
+    SKIMI_CHECK_ARG(stride > 0.f, "skimi_track_init: stride must be positive");
+    return track_init_launch(q, coords, qs, (long)BN, S, stride, (hipStream_t)stream);
+}
+
+int skimi_track_repeat_rows(const float* src, float* dst, int64_t BN, int32_t S, int32_t C, void* stream) {
+    SKIMI_CHECK_ARG(src && dst, "skimi_track_repeat_rows: null buffer");
+    SKIMI_CHECK_ARG(BN > 0 && S > 0 && C > 0, "skimi_track_repeat_rows: sizes must be positive");
+    return repeat_rows_launch(src, dst, (long)BN, S, C, (hipStream_t)stream);
+}
+
+int skimi_track_bns_to_bsn(const float* in, float* out, int32_t B, int32_t N, int32_t S, void* stream) {
+    SKIMI_CHECK_ARG(in && out, "skimi_track_bns_to_bsn: null buffer");
+    SKIMI_CHECK_ARG(B > 0 && N > 0 && S > 0, "skimi_track_bns_to_bsn: sizes must be positive");
+    return bns_to_bsn_launch(in, out, B, N, S, (hipStream_t)stream);
 }
 
 }  // extern "C"

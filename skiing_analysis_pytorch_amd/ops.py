@@ -393,3 +393,173 @@ def gemm_fp8(a_q, a_s, w_q, w_s, K, *, bias=None, act=ACT_NONE, gamma=None, resi
                                resid.stride(0) if resid is not None else 0, ptr(out), _dt(out), out.stride(0), None,
                                _lib.current_stream()), "skimi_gemm_fp8")
     return out
+
+
+# ---- VGGT head / track-head helper kernels (include/skimi.h: one launch each).  Shapes come from the tensors; `out`
+# arguments may be views into larger buffers (offsets, leading dimensions); nothing is computed here. ----
+def _stream():
+    return _lib.current_stream()
+
+
+def resize_bilinear(x, H, W, *, out=None, out_dtype=None, tabx=None, taby=None, ln_g=None, ln_b=None, ln_eps=0.0):
+    """x [N, h, w, C] -> [N, H, W, C], align_corners=True (+ UV tables, + LayerNorm over C == 128)"""
+    _require_cuda(x, out, tabx, taby, ln_g, ln_b)
+    N, h, w, Cc = x.shape
+    if out is None:
+        out = torch.empty((N, H, W, Cc), dtype=out_dtype or x.dtype, device=x.device)
+    check(lib().skimi_resize_bilinear(ptr(x), ptr(out), _dt(x), _dt(out), N, h, w, H, W, Cc, ptr(tabx), ptr(taby), ptr(ln_g),
+                                      ptr(ln_b), ln_eps, _stream()), "skimi_resize_bilinear")
+    return out
+
+
+def resize_bilinear_planes(x, H, W, out, *, tabx=None, taby=None, records=False, zpage=None):
+    """x [N, h, w, C] fp32 -> out (16-bit elements, N * H * W * 2C of them) as bf16 hi / lo planes or records"""
+    _require_cuda(x, out, tabx, taby, zpage)
+    N, h, w, Cc = x.shape
+    check(lib().skimi_resize_bilinear_planes(ptr(x), ptr(out), N, h, w, H, W, Cc, ptr(tabx), ptr(taby), int(records),
+                                             ptr(zpage), _stream()), "skimi_resize_bilinear_planes")
+    return out
+
+
+def add_uv_pos_(x, tabx, taby):
+    """x [N, H, W, C] += UV embedding, in place"""
+    _require_cuda(x, tabx, taby)
+    N, H, W, Cc = x.shape
+    check(lib().skimi_add_uv_pos(ptr(x), _dt(x), ptr(tabx), ptr(taby), N, H, W, Cc, _stream()), "skimi_add_uv_pos")
+    return x
+
+
+def add_uv_pos_records(x, rec, tabx=None, taby=None):
+    """x [N, H, W, C] fp32 (+ UV embedding) -> rec: bf16x3 records followed by the 256-byte zero page"""
+    _require_cuda(x, rec, tabx, taby)
+    N, H, W, Cc = x.shape
+    check(lib().skimi_add_uv_pos_records(ptr(x), ptr(tabx), ptr(taby), N, H, W, Cc, ptr(rec), _stream()),
+          "skimi_add_uv_pos_records")
+    return rec
+
+
+def dpt_out(x, weight, bias, mode, *, pts=None, conf=None):
+    """x [npix, 32], weight [n_out, 32] -> (pts [npix, n_out - 1], conf [npix]); mode 0 exp, 1 inv_log"""
+    _require_cuda(x, weight, bias, pts, conf)
+    npix, n_out = x.shape[0], weight.shape[0]
+    if pts is None:
+        pts = torch.empty((npix, n_out - 1), dtype=torch.float32, device=x.device)
+    if conf is None:
+        conf = torch.empty((npix,), dtype=torch.float32, device=x.device)
+    check(lib().skimi_dpt_out(ptr(x), _dt(x), ptr(weight), ptr(bias), n_out, ptr(pts), ptr(conf), npix, mode, _stream()),
+          "skimi_dpt_out")
+    return pts, conf
+
+
+def patch_gather(img, p, Kp, *, out=None, out_dtype=torch.float32):
+    """img [F, 3, H, W] fp32 -> [F * (H/p) * (W/p), Kp] normalised patches"""
+    _require_cuda(img, out)
+    F, _, H, W = img.shape
+    if out is None:
+        out = torch.empty((F * (H // p) * (W // p), Kp), dtype=out_dtype, device=img.device)
+    check(lib().skimi_patch_gather(ptr(img), ptr(out), _dt(out), F, H, W, p, Kp, _stream()), "skimi_patch_gather")
+    return out
+
+
+def adaln(xn, x, mod, *, out=None):
+    _require_cuda(xn, x, mod, out)
+    rows, D = x.shape
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib().skimi_adaln(ptr(xn), ptr(x), ptr(mod), ptr(out), rows, D, _stream()), "skimi_adaln")
+    return out
+
+
+def pose_update_(delta, pred_pad, act_out, first):
+    """pred_pad [rows, 16] updated in place from delta [rows, 9]; act_out [rows, 9]"""
+    _require_cuda(delta, pred_pad, act_out)
+    check(lib().skimi_pose_update(ptr(delta), ptr(pred_pad), ptr(act_out), delta.shape[0], int(first), _stream()),
+          "skimi_pose_update")
+    return act_out
+
+
+def special_tokens_(x, table, S):
+    """x [F, P, C]: rows 0..n-1 of every frame from table [2, n, C]"""
+    _require_cuda(x, table)
+    F, P, Cc = x.shape
+    check(lib().skimi_special_tokens(ptr(x), ptr(table), F, S, P, table.shape[1], Cc, _stream()), "skimi_special_tokens")
+    return x
+
+
+def track_avgpool2(x, *, out=None):
+    _require_cuda(x, out)
+    N, H, W, Cc = x.shape
+    if out is None:
+        out = torch.empty((N, H // 2, W // 2, Cc), dtype=torch.float32, device=x.device)
+    check(lib().skimi_track_avgpool2(ptr(x), ptr(out), N, H, W, Cc, _stream()), "skimi_track_avgpool2")
+    return out
+
+
+def track_sample_border(fmap, img_stride, coords, coord_stride, B, N, H, W, Cc, *, out=None):
+    """fmap: B images [H, W, C] `img_stride` floats apart; coords: (x, y) every `coord_stride` floats -> [B, N, C]"""
+    _require_cuda(fmap, coords, out)
+    if out is None:
+        out = torch.empty((B, N, Cc), dtype=torch.float32, device=fmap.device)
+    check(lib().skimi_track_sample_border(ptr(fmap), img_stride, ptr(coords), coord_stride, ptr(out), B, N, H, W, Cc,
+                                          _stream()), "skimi_track_sample_border")
+    return out
+
+
+def track_corr_sample(tgt, fmap, coords, out, N, S, r, level, ldo, out_off):
+    """tgt [rows, C], fmap [B * S, H, W, C], coords [rows, 2] -> out[row * ldo + out_off + 0 .. (2r+1)^2 - 1]"""
+    _require_cuda(tgt, fmap, coords, out)
+    rows, Cc = tgt.shape
+    _, H, W, _ = fmap.shape
+    check(lib().skimi_track_corr_sample(ptr(tgt), ptr(fmap), ptr(coords), ptr(out), rows, N, S, H, W, Cc, r, level, ldo,
+                                        out_off, _stream()), "skimi_track_corr_sample")
+    return out
+
+
+def track_pos_embed_sample(coords, coord_stride, BN, H, W, D, *, out=None):
+    _require_cuda(coords, out)
+    if out is None:
+        out = torch.empty((BN, D), dtype=torch.float32, device=coords.device)
+    check(lib().skimi_track_pos_embed_sample(ptr(coords), coord_stride, ptr(out), BN, H, W, D, _stream()),
+          "skimi_track_pos_embed_sample")
+    return out
+
+
+def track_input(coords, fcorr, tfeat, pos, qrt, x, S, L, ldx, max_scale):
+    """coords [rows, 2], fcorr / tfeat [rows, L], pos [rows / S, 3L + 4], qrt [2, 3L + 4] -> x, row stride ldx"""
+    _require_cuda(coords, fcorr, tfeat, pos, qrt, x)
+    check(lib().skimi_track_input(ptr(coords), ptr(fcorr), ptr(tfeat), ptr(pos), ptr(qrt), ptr(x), coords.shape[0], S, L, ldx,
+                                  max_scale, _stream()), "skimi_track_input")
+    return x
+
+
+def track_coord_update_(coords, delta, ldd, query, N, S, stride, *, pred=None):
+    """coords [rows, 2] += delta[:, :2] in place, rows s == 0 reset to query [rows / S, 2]; pred [B, S, N, 2] or None"""
+    _require_cuda(coords, delta, query, pred)
+    check(lib().skimi_track_coord_update(ptr(coords), ptr(delta), ldd, ptr(query), ptr(pred), coords.shape[0], N, S, stride,
+                                         _stream()), "skimi_track_coord_update")
+    return coords
+
+
+def track_init(q, coords, qs, S, stride):
+    """q [BN, 2] -> coords [BN, S, 2], qs [BN, 2], both q / stride"""
+    _require_cuda(q, coords, qs)
+    check(lib().skimi_track_init(ptr(q), ptr(coords), ptr(qs), q.shape[0], S, stride, _stream()), "skimi_track_init")
+    return coords, qs
+
+
+def track_repeat_rows(src, S, *, out=None):
+    _require_cuda(src, out)
+    BN, Cc = src.shape
+    if out is None:
+        out = torch.empty((BN, S, Cc), dtype=torch.float32, device=src.device)
+    check(lib().skimi_track_repeat_rows(ptr(src), ptr(out), BN, S, Cc, _stream()), "skimi_track_repeat_rows")
+    return out
+
+
+def track_bns_to_bsn(x, *, out=None):
+    _require_cuda(x, out)
+    B, N, S = x.shape
+    if out is None:
+        out = torch.empty((B, S, N), dtype=torch.float32, device=x.device)
+    check(lib().skimi_track_bns_to_bsn(ptr(x), ptr(out), B, N, S, _stream()), "skimi_track_bns_to_bsn")
+    return out
