@@ -849,6 +849,85 @@ int skimi_smooth_ema(const double* X, int64_t frames, int64_t joints, const doub
 int skimi_smooth_savgol(const double* X, int64_t frames, int64_t joints, int32_t win, int32_t poly, const double* fir,
                         const double* first, const double* last, double* Y, void* stream);
 
+/* Kinematic analysis of clips of 3D joints on the device: the 14 per-frame series of angle/main.py, their 28 change series,
+ * the skier's facing heading, the split of each clip into turns and the per-turn statistics of all 42 series
+ * (angle/main.py: compute_angles, compute_tilt_angles, compute_torso_knee_angle, compute_knee_difference,
+ * compute_elbow_distance_from_midline, compute_facing_heading, compute_series_changes, detect_turn_segments and the
+ * statistics of save_turn_reports; tests/kinematics_restated.py is the restatement).  All arithmetic float64, compiled
+ * without FMA contraction.  Three launches for all clips (two when frames == 0, none when clips == 0), no synchronisation,
+ * no allocation, no floating-point atomics; the turn count stays on the device.  Every sum runs in an order that depends
+ * only on positions inside the clip (or inside the turn), so results are bitwise reproducible and a clip's results are the
+ * same bits alone or in a batch, at any place in it, in either placement (below), whatever lies beyond its length.
+ * Bad arguments: SKIMI_ERR_ARG before any launch, outputs untouched.  Rules (DESIGN §2 "Kinematics"):
+ *
+ * Input.  X [clips, frames, joints, 3] dev f64; lengths [clips] dev i32 or NULL (every clip has `frames` frames).  A length
+ * is clamped to 0 .. frames on the device.  Frames at or beyond a clip's length are never read: there the series, heading,
+ * heading_smooth and velocity_smooth are NaN and boundary is 0, and everything below speaks of the clip's first `length`
+ * frames, T of them.  layout [13] (host): the joint index of each role, SKIMI_KIN_SHOULDER_L .. SKIMI_KIN_NECK, in 0 ..
+ * joints - 1, or -1 for absent; an absent role behaves as a non-finite joint.  up [3] (host), finite and not zero.
+ *
+ * The 14 base series, series[:, 0..13, :] of series [clips, 42, frames]:
+ *  0-7  knee_l, knee_r, elbow_l, elbow_r, shoulder_l, shoulder_r, hip_l, hip_r: the angle ABC in degrees of (hip, knee,
+ *       foot), (shoulder, elbow, hand), (neck, shoulder, elbow), (neck, hip, knee): NaN unless the three joints are finite
+ *       and |BA| and |BC| are non-zero; acos of BA.BC / (|BA| |BC|) clipped to [-1, 1], times 180 / pi.
+ *  8    torso_knee_angle: the angle (shoulder centre, pelvis centre, knee centre).  A centre is the mean of the finite ones
+ *       of its two joints (hips, shoulders, knees): (a + b) / 2, the one finite joint, or NaN.
+ *  9    knee_diff_lr = knee_l - knee_r where both are finite.
+ *  10-11 elbow_distance_l, _r = sqrt(dx^2 + dz^2) of the elbow from the pelvis centre, both finite.
+ *  12-13 tilt_upper, tilt_lower of v = shoulder centre - pelvis centre and knee centre - pelvis centre: lr = hip_r - hip_l when
+ *       both hips are finite, else shoulder_r - shoulder_l when both are, else the frame has no tilt and no heading; l =
+ *       lr / |lr|, u = up / |up|, forward f = unit(u x l) when up[1] < 0, else unit(l x u) (a zero or non-finite norm
+ *       anywhere: no tilt, no heading).  p = unit(v - (v.l) l); tilt = acos(clip(p.u)) 180 / pi, negated where p.f >= 0 is
+ *       false.  heading [clips, frames] = atan2(f.x, f.z) 180 / pi.
+ * The 28 change series, series[:, 14 + 2k] = name_d and series[:, 15 + 2k] = name_abs_d of base series k: d[i] = s[i] - s[i-1]
+ * where both are finite, else NaN, NaN at i = 0; abs_d = |d|.
+ *
+ * Turns of a clip (detect_turn_segments):
+ *  1. Fewer than 5 finite headings: no turns, heading_smooth and velocity_smooth NaN.
+ *  2. Fill: a non-finite heading at i between the nearest finite ones at l < i < r is (h[r] - h[l]) / (r - l) * (i - l) + h[l];
+ *     before the first / after the last finite one it is that one's value (np.interp).
+ *  3. Unwrap (np.unwrap, period 2 pi) of p = h pi / 180: dd = p[i] - p[i-1]; m = mod(dd + pi, 2 pi) - pi with the sign of the
+ *     divisor, m = pi where m == -pi and dd > 0; correction c = m - dd, 0 where |dd| < pi; p[i] += c[1] + .. + c[i]; back to
+ *     degrees with 180 / pi.  The running sum is a fixed blocked prefix sum: chunks of ceil(T / 256) samples in time order,
+ *     then the chunk totals in order.
+ *  4. heading_smooth [clips, frames] = box mean of window heading_window: the sum over the samples of i - w/2 .. i + w/2 that
+ *     lie inside the clip, in ascending order, divided by their number.  This is also the rule for T < window, where the
+ *     reference raises IndexError (np.convolve(mode="same") then returns the window's length); for T >= window the two agree.
+ *  5. velocity = np.gradient: (s[i+1] - s[i-1]) / 2 inside, s[1] - s[0] and s[T-1] - s[T-2] at the ends;
+ *     velocity_smooth [clips, frames] = its box mean of window velocity_window.
+ *  6. Extrema: the i >= 1 with v[i-1] v[i] < 0.  Boundaries: 0; then, greedily, the first extremum >= min_turn_frames after
+ *     the last boundary; then T - 1 (unless it already is the last boundary).
+ *  7. A segment (s, e) of consecutive boundaries is a turn unless e - s + 1 < min_turn_frames or |hs[e] - hs[s]| <
+ *     min_heading_change_deg.  Kept turns are numbered from 0 in time order: turn_frames [clips, max_turns, 2] i32 = (s, e),
+ *     turn_heading_change [clips, max_turns] = hs[e] - hs[s], turn_direction [clips, max_turns] i32 = +1 where that is > 0,
+ *     else -1; n_turns [clips] i32; boundary [clips, frames] u8 = 1 at the s and e of kept turns.  max_turns must be
+ *     (frames - 1) / min_turn_frames + 1 (0 for frames == 0): boundaries after 0 are >= min_turn_frames apart, so at most
+ *     (T - 1) / min_turn_frames extrema are taken and T - 1 adds at most one segment.
+ *  8. turn_stats [clips, max_turns, 42, 4] = mean, population std, min, max of each series over the finite samples of [s, e],
+ *     turn_counts [clips, max_turns, 42] i32 their number; no finite sample: four NaN.  One wave per (clip, turn, series): each
+ *     lane sums samples s + lane, s + lane + 64, .. in time order, then a fixed xor butterfly; the std is a second pass over
+ *     the deviations from that mean.
+ *  9. Rows at and beyond n_turns: turn_frames, turn_direction and turn_counts 0; turn_heading_change and turn_stats NaN.
+ *
+ * Placement.  The per-clip arrays of rules 2-6 (three of `frames` doubles) live in LDS when workspace is NULL, which needs
+ * frames <= SKIMI_KIN_LDS_FRAMES, and otherwise in workspace (dev), at least skimi_kin_workspace_bytes(clips, frames) bytes
+ * (0 for negative sizes).  Both placements run the same code on the same values. */
+#define SKIMI_KIN_SERIES 42
+#define SKIMI_KIN_BASE_SERIES 14
+#define SKIMI_KIN_ROLES 13
+#define SKIMI_KIN_LDS_FRAMES 2048
+enum {
+    SKIMI_KIN_SHOULDER_L = 0, SKIMI_KIN_SHOULDER_R, SKIMI_KIN_ELBOW_L, SKIMI_KIN_ELBOW_R, SKIMI_KIN_HIP_L, SKIMI_KIN_HIP_R,
+    SKIMI_KIN_KNEE_L, SKIMI_KIN_KNEE_R, SKIMI_KIN_FOOT_L, SKIMI_KIN_FOOT_R, SKIMI_KIN_HAND_L, SKIMI_KIN_HAND_R, SKIMI_KIN_NECK
+};
+size_t skimi_kin_workspace_bytes(int64_t clips, int64_t frames);
+int skimi_kinematics(const double* X, const int32_t* lengths, int64_t clips, int64_t frames, int32_t joints,
+                     const int32_t* layout, const double* up, int32_t min_turn_frames, double min_heading_change_deg,
+                     int32_t heading_window, int32_t velocity_window, int32_t max_turns, void* workspace,
+                     size_t workspace_bytes, double* series, double* heading, double* heading_smooth, double* velocity_smooth,
+                     uint8_t* boundary, int32_t* n_turns, int32_t* turn_frames, double* turn_heading_change,
+                     int32_t* turn_direction, double* turn_stats, int32_t* turn_counts, void* stream);
+
 /* ---- VGGT head and track-head helper kernels, one launch each ----
  * The kernels skimi_vggt_forward runs between its GEMMs, exposed singly so that each can be tested against a float64
  * restatement.  All maps are channels-last and dense; dtype / out_dtype are SKIMI_F32, SKIMI_BF16 or SKIMI_F16.  Every

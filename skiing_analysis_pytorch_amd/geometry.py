@@ -3,13 +3,15 @@ skimi_triangulate_dlt, skimi_triangulate_triage, skimi_triangulate_robust, the p
 and the point-to-plane ICP: skimi_estimate_normals, skimi_icp_correspondences,
 skimi_icp_point_to_plane; the bundle adjustment: skimi_bundle_adjust; the camera resection: skimi_resect_cameras, the camera-and-points refinement: skimi_refine_cameras_points,
 skimi_relative_pose; the essential matrix: skimi_essential_ransac, skimi_five_point; the fusion and smoothing of a clip:
-skimi_fuse_h36m, skimi_fuse_views, skimi_smooth_ema, skimi_smooth_savgol) plus the small host helpers of the reference's VGGT wrapper.
+skimi_fuse_h36m, skimi_fuse_views, skimi_smooth_ema, skimi_smooth_savgol; the kinematic analysis of clips: skimi_kinematics)
+plus the small host helpers of the reference's VGGT wrapper.
 
 Reference: vggt/vggt/utils/pose_enc.py:62-124, rotation.py:14-44, geometry.py:15-117,
 vggt/triangulate.py:13-71, vggt/reproject.py:108-144 + triangulation/postprocess.py:70-121 (triage),
 vggt/multi_view_process.py:195-217 + :356-395 (person origin), vggt/vggt/infer.py:107-155, vggt/multi_view_process.py:427-520 (ICP),
 :523-564 + bundle_adjustment/loss.py (bundle adjustment), VideoPose3D/slove_rt_from_3d.py (resection),
-VideoPose3D/fuse/fuse.py, fuse/main_raw.py:194-250, fuse/fuse.py:289-412 (fusion and smoothing; host form: fuse.py).
+VideoPose3D/fuse/fuse.py, fuse/main_raw.py:194-250, fuse/fuse.py:289-412 (fusion and smoothing; host form: fuse.py),
+angle/main.py (kinematics; entry points: angle.py).
 """
 from __future__ import annotations
 
@@ -913,6 +915,96 @@ def smooth_savgol(X: torch.Tensor, win: int = 9, poly: int = 2) -> SavgolResult:
     check(lib().skimi_smooth_savgol(ptr(X), T, J, w, int(poly), ptr(fir), ptr(first), ptr(last), ptr(Y), _lib.current_stream()),
           "skimi_smooth_savgol")
     return SavgolResult(Y, w)
+
+
+# ---- kinematic analysis of clips: angle/main.py (csrc/kinematics.hip; rules: include/skimi.h, DESIGN §2 "Kinematics") ------
+KIN_ROLES = ("shoulder_l", "shoulder_r", "elbow_l", "elbow_r", "hip_l", "hip_r", "knee_l", "knee_r", "foot_l", "foot_r",
+             "hand_l", "hand_r", "neck")
+KIN_BASE_SERIES = ("knee_l", "knee_r", "elbow_l", "elbow_r", "shoulder_l", "shoulder_r", "hip_l", "hip_r", "torso_knee_angle",
+                   "knee_diff_lr", "elbow_distance_l", "elbow_distance_r", "tilt_upper", "tilt_lower")
+KIN_SERIES = KIN_BASE_SERIES + tuple(n + s for n in KIN_BASE_SERIES for s in ("_d", "_abs_d"))      # the 42, in order
+KIN_STAT_FIELDS = ("mean", "std", "min", "max")
+# the joint of each role (KIN_ROLES order) among the reference's 15 joints: MHR-70 ids 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 62,
+# 41, 69 as positions in its TARGET_IDS order (1, 2, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 41, 62, 69)
+KIN_LAYOUT_MHR70_15 = (2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 12, 14)
+KIN_LDS_FRAMES = 2048       # SKIMI_KIN_LDS_FRAMES: longer clips keep their arrays in a workspace
+
+
+class KinematicsResult(NamedTuple):
+    """kinematics' outputs (device tensors; B clips, T frames, M = kin_max_turns(T, min_turn_frames) turn slots).  Frames at
+    and beyond a clip's length: NaN series, changes, heading, heading_smooth and velocity_smooth, boundary False.  Turn slots
+    at and beyond n_turns: turn_frames, turn_direction and turn_counts 0; turn_heading_change and turn_stats NaN."""
+    series: torch.Tensor                # float64 [B, 14, T]: KIN_BASE_SERIES
+    changes: torch.Tensor               # float64 [B, 28, T]: name_d, name_abs_d of each base series (KIN_SERIES[14:])
+    heading: torch.Tensor               # float64 [B, T] degrees
+    heading_smooth: torch.Tensor        # float64 [B, T]: filled, unwrapped, box mean; NaN with fewer than 5 finite headings
+    velocity_smooth: torch.Tensor       # float64 [B, T]
+    boundary: torch.Tensor              # bool [B, T]: first and last frame of every kept turn
+    n_turns: torch.Tensor               # int32 [B]
+    turn_frames: torch.Tensor           # int32 [B, M, 2]: (start, end), inclusive
+    turn_heading_change: torch.Tensor   # float64 [B, M]
+    turn_direction: torch.Tensor        # int32 [B, M]: +1 (heading change > 0) or -1
+    turn_stats: torch.Tensor            # float64 [B, M, 42, 4]: KIN_STAT_FIELDS of KIN_SERIES over the turn's finite samples
+    turn_counts: torch.Tensor           # int32 [B, M, 42]: the number of those samples
+    all_series: torch.Tensor            # float64 [B, 42, T]: the storage `series` and `changes` are views of
+
+
+def kin_max_turns(frames: int, min_turn_frames: int = 12) -> int:
+    """The most turns a clip of `frames` frames can hold: boundaries after frame 0 are at least min_turn_frames apart, so at
+    most (frames - 1) // min_turn_frames extrema are taken, and the last frame closes at most one more segment."""
+    return (int(frames) - 1) // int(min_turn_frames) + 1 if frames > 0 and min_turn_frames >= 1 else 0
+
+
+def kinematics(X: torch.Tensor, lengths=None, layout=KIN_LAYOUT_MHR70_15, up_axis=(0.0, -1.0, 0.0), min_turn_frames: int = 12,
+               min_heading_change_deg: float = 8.0, heading_window: int = 11, velocity_window: int = 9, *,
+               placement: str = "auto") -> KinematicsResult:
+    """angle/main.py's _compute_all_series, compute_series_changes, detect_turn_segments and the statistics of
+    save_turn_reports for a batch of clips in three launches: X [B, T, J, 3] (a [T, J, 3] input is one clip) device tensor;
+    lengths None or [B] integers, 0 <= length <= T (the frames beyond a clip's length are never read); layout the joint index
+    of each role in KIN_ROLES order, -1 for absent -> KinematicsResult.  Nothing is read back: the turn count stays on the
+    device.  placement "auto" keeps a clip's arrays in LDS up to KIN_LDS_FRAMES frames and in a workspace beyond; "workspace"
+    forces the workspace (same bits)."""
+    X = _f64_dev("kinematics", X)
+    if X.dim() == 3:
+        X = X[None]
+    if X.dim() != 4 or X.shape[3] != 3:
+        raise ValueError(f"kinematics: need X [B, T, J, 3] or [T, J, 3], got {list(X.shape)}")
+    if placement not in ("auto", "workspace"):
+        raise ValueError("placement must be 'auto' or 'workspace'")
+    B, T, J = (int(s) for s in X.shape[:3])
+    dev = X.device
+    lay = np.asarray(list(layout), dtype=np.int64)
+    if lay.shape != (len(KIN_ROLES),):
+        raise ValueError(f"kinematics: layout needs {len(KIN_ROLES)} joint indices ({', '.join(KIN_ROLES)}), got {lay.size}")
+    lay_c = (C.c_int32 * len(KIN_ROLES))(*[int(np.clip(v, -2 ** 31, 2 ** 31 - 1)) for v in lay])
+    up = np.asarray(up_axis, dtype=np.float64)
+    if up.shape != (3,):
+        raise ValueError(f"kinematics: up_axis must be [3], got {list(up.shape)}")
+    up_c = (C.c_double * 3)(*up.tolist())
+    len_t = None
+    if lengths is not None:
+        len_t = (lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(np.asarray(lengths, dtype=np.int64)))
+        if tuple(len_t.shape) != (B,):
+            raise ValueError(f"kinematics: lengths must be [{B}], got {list(len_t.shape)}")
+        len_t = len_t.to(dev, torch.int32).contiguous()
+    M = kin_max_turns(T, min_turn_frames)
+    f64 = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)   # noqa: E731
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)     # noqa: E731
+    alls, heading, hs, vs = f64(B, len(KIN_SERIES), T), f64(B, T), f64(B, T), f64(B, T)
+    boundary = torch.empty((B, T), dtype=torch.uint8, device=dev)
+    n_turns, frames, dh, direction = i32(B), i32(B, M, 2), f64(B, M), i32(B, M)
+    stats, counts = f64(B, M, len(KIN_SERIES), 4), i32(B, M, len(KIN_SERIES))
+    ws, ws_bytes = None, 0
+    if placement == "workspace" or T > KIN_LDS_FRAMES:
+        ws_bytes = int(lib().skimi_kin_workspace_bytes(B, T))
+        ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.float64, device=dev) if B and T else None
+    check(lib().skimi_kinematics(ptr(X), ptr(len_t), B, T, J, lay_c, up_c, int(min_turn_frames), float(min_heading_change_deg),
+                                 int(heading_window), int(velocity_window), M, ptr(ws), ws_bytes, ptr(alls), ptr(heading), ptr(hs),
+                                 ptr(vs), ptr(boundary), ptr(n_turns), ptr(frames), ptr(dh), ptr(direction), ptr(stats),
+                                 ptr(counts), _lib.current_stream()), "skimi_kinematics")
+    nb = len(KIN_BASE_SERIES)
+    return KinematicsResult(alls[:, :nb], alls[:, nb:], heading, hs, vs, boundary.bool(), n_turns, frames, dh, direction, stats,
+                            counts, alls)
 
 
 # ---- host helpers of the wrapper (small arrays, NumPy as in the reference) -----------------

@@ -94,7 +94,8 @@ def run_video_pose_3d(config, pt_path: Path, out_dir: Path, args, model_pos: Tem
     return prediction, depth
 
 
-def process_video_3d(config, left_path: Path, right_path: Path, out_dir: Path, npy_dir: Path, args, model_pos: TemporalModel = None):
+def process_video_3d(config, left_path: Path, right_path: Path, out_dir: Path, npy_dir: Path, args, model_pos: TemporalModel = None,
+                     analyze: bool = False):
     """VideoPose3D/main.py:33-103 process_video_3d without its GIF and without eval_fused_pose: both views' clips are lifted
     (run_video_pose_3d into <out_dir>/videopose3d/left and /right) and fused frame by frame with the reference's settings
     (tau = 0.06, allow_scale = False, mirror_right_x = False) -- here as ONE geometry.fuse_h36m launch over the clip, in
@@ -102,7 +103,10 @@ def process_video_3d(config, left_path: Path, right_path: Path, out_dir: Path, n
     formats.save_3d_joints to "<npy_dir>_fused_keypoints.npy" (:85-90).  The clips are cut to the shorter one (the reference
     indexes the right clip by the left one's length and would raise).  `args` is passed in where the reference parses the
     command line (:41).  -> (fused [T, 17, 3] float64 on the device, geometry.FuseH36MResult with the per-frame R, t, s,
-    diagnostics, status, mean_gain and bad_frames on the device)."""
+    diagnostics, status, mean_gain and bad_frames on the device).  analyze=True adds the skiing analysis of the fused clip
+    (angle/main.py's process_person without its pictures): the clip stays on the device, goes through geometry.kinematics
+    with the Human3.6M layout (angle.H36M_17, y pointing down as the lifter's camera frame has it) and the reference's CSV
+    files land in <out_dir>/angle.  With analyze off nothing else changes: every file is bitwise what it was."""
     out_dir = Path(out_dir)
     left, _ = run_video_pose_3d(config, left_path, out_dir / "videopose3d" / "left", args, model_pos=model_pos)
     right, _ = run_video_pose_3d(config, right_path, out_dir / "videopose3d" / "right", args, model_pos=model_pos)
@@ -113,6 +117,10 @@ def process_video_3d(config, left_path: Path, right_path: Path, out_dir: Path, n
                              torch.from_numpy(np.ascontiguousarray(right)).to(dev, torch.float64), tau=0.06, allow_scale=False,
                              mirror_right_x=False)
     formats.save_3d_joints(res.fused.cpu().numpy(), left, right, Path(str(npy_dir) + "_fused_keypoints.npy"))
+    if analyze:
+        from . import angle
+
+        angle.write_person(angle.analysis_from(geometry.kinematics(res.fused, layout=angle.H36M_17)), out_dir / "angle")
     return res.fused, res
 
 

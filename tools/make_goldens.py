@@ -698,6 +698,60 @@ def gen_scene():
 GENERATORS["scene"] = gen_scene
 
 
+def gen_kinematics():
+    """DESIGN §2 "Kinematics": the reference's OWN angle/main.py (imported by file spec with MPLBACKEND=Agg; its plot_angles is
+    switched off while it runs, the numbers do not pass through it) on the seeded synthetic skiers of tests/kinematics_cases.py:
+    _compute_all_series, compute_series_changes and save_turn_reports, whose turn_metrics.csv and turn_heading.csv are parsed
+    back (the csv module writes repr(float): the values round-trip exactly).  Only inputs and results are stored."""
+    import csv
+    import importlib.util
+    import tempfile
+
+    os.environ.setdefault("MPLBACKEND", "Agg")
+    sys.path.insert(0, str(ROOT / "tests"))
+    import kinematics_cases as kc
+
+    spec = importlib.util.spec_from_file_location("ref_angle_main", os.path.join(REF, "angle", "main.py"))
+    A = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(A)
+    A.plot_angles = lambda *a, **k: None
+    out = {"clips": np.array(list(kc.GOLDEN))}
+    for name, case in kc.GOLDEN.items():
+        X = case["X"]
+        up = np.asarray(case.get("up_axis", (0.0, -1.0, 0.0)), dtype=np.float64)
+        joint, body, torso, kdiff, elbow, heading, turns = A._compute_all_series(X, up)
+        base = {**joint, **torso, **kdiff, **elbow, **body}
+        change = A.compute_series_changes(base)
+        report = {**base, **change}
+        names = list(report)
+        with tempfile.TemporaryDirectory() as tmp:
+            import contextlib
+            import io
+            with contextlib.redirect_stdout(io.StringIO()):
+                A.save_turn_reports(Path(tmp), turns, heading, report)
+            with open(Path(tmp) / "turn_metrics.csv", newline="") as f:
+                rows = list(csv.reader(f))[1:]
+            with open(Path(tmp) / "turn_heading.csv", newline="") as f:
+                hrows = list(csv.reader(f))[1:]
+        stats = np.array([[float(v) for v in r[2:]] for r in rows], dtype=np.float64).reshape(len(turns), len(names), 4)
+        assert [r[1] for r in rows[:len(names)]] == names or not turns
+        out[f"{name}_X"], out[f"{name}_up"] = X, up
+        out[f"{name}_series"] = np.stack([report[n] for n in names])
+        out[f"{name}_heading"] = heading
+        out[f"{name}_turns"] = np.array([[t[k] for k in ("turn_id", "start_frame", "end_frame", "num_frames", "heading_change_deg",
+                                                         "direction")] for t in turns], dtype=np.float64).reshape(len(turns), 6)
+        out[f"{name}_stats"] = stats
+        out[f"{name}_boundary"] = np.array([int(r[2]) for r in hrows], dtype=np.uint8)
+        out["names"] = np.array(names)
+        print(f"  {name}: T = {X.shape[0]}, {len(turns)} turns, {int(np.isfinite(heading).sum())} finite headings")
+    path = GOLD / "kinematics.npz"
+    np.savez_compressed(path, **out)
+    print("wrote", path.name, path.stat().st_size, "bytes")
+
+
+GENERATORS["kinematics"] = gen_kinematics
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GENERATORS)
     for w in which:
