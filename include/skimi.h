@@ -928,6 +928,83 @@ int skimi_kinematics(const double* X, const int32_t* lengths, int64_t clips, int
                      uint8_t* boundary, int32_t* n_turns, int32_t* turn_frames, double* turn_heading_change,
                      int32_t* turn_direction, double* turn_stats, int32_t* turn_counts, void* stream);
 
+/* ---- pose evaluation: the MPJPE protocols and the ground-truth-free quality of clips (csrc/evaluate.hip) ----
+ * Everything is float64 on the device, nothing is read back, no floating-point atomics: results are bitwise reproducible,
+ * and a clip's results are the same bits alone or anywhere in a ragged batch.  lengths: NULL or [clips] i32 (dev), clamped
+ * to 0 .. frames; the frames at and beyond a clip's length are never read.  Sizes: 0 <= clips < 2^31, 0 <= frames < 2^31 -
+ * 64, 1 <= joints <= SKIMI_EVAL_MAX_JOINTS, clips * frames < 2^31, clips * joints < 2^31, clips * frames * joints * 3 <=
+ * 2^40; clips == 0 launches nothing.  Bad arguments: SKIMI_ERR_ARG before any launch, outputs untouched.
+ * Rules (DESIGN §2 "Evaluation"; T = frames, J = joints, n = the clip's length):
+ *
+ * skimi_pose_errors = VideoPose3D/common/loss.py (mpjpe, p_mpjpe, n_mpjpe, mean_velocity_error) with the per-joint tables of
+ * metrics/unity_data_compare.py (calculate_per_joint_errors, summarize_joint_errors) and the mask of fuse_eval.
+ * mean_pairwise_distance, for a batch of (pred, target) clips [clips, T, J, 3] in three launches (two when frames == 0).
+ *  1. zero_root: a joint index or -1.  With zero_root >= 0 that joint of the target counts as (0, 0, 0) (VideoPose3D/run.py:994)
+ *     and the stored values are not read.  A joint is valid in a frame when its six coordinates are finite; a frame is complete
+ *     when all J joints are valid.  n_valid_f [clips, T] i32 = the frame's number of valid joints.
+ *  2. err [clips, T, J] = ||p - g|| on valid joints, NaN elsewhere.  mpjpe_f [clips, T] = the mean of the frame's finite err,
+ *     NaN without one.
+ *  3. n_mpjpe_f [clips, T], complete frames only: scale = mean_j(g . p) / mean_j(p . p), the mean of ||scale p - g||; an
+ *     incomplete frame or a non-finite result is NaN.
+ *  4. Procrustes (loss.py:27-66), complete frames only: X0 = g - mean(g), Y0 = p - mean(p), each divided by its Frobenius norm,
+ *     H = X0^T Y0 = U S V^T, R = V U^T with the last column of V and the last singular value negated when det R < 0 (here:
+ *     the polar factor of svd3.h, which is that whatever signs an SVD chose), a = sum(S) ||X0|| / ||Y0||, t = mean(g) - a
+ *     mean(p) R, aligned = a p R + t.  p_err [clips, T, J] = ||aligned - g||, p_mpjpe_f [clips, T] its mean; aligned
+ *     [clips, T, J, 3], p_R [clips, T, 3, 3], p_scale [clips, T], p_t [clips, T, 3] are optional (NULL: not written).
+ *     p_status [clips, T] i32 = 1 where the frame is complete, both poses have extent (norms > 0) and every result is
+ *     finite; else 0 and all Procrustes outputs of the frame are NaN (the reference raises or returns NaN there).
+ *  5. vel_err [clips, T, J], t >= 1: ||(p_t - p_{t-1}) - (g_t - g_{t-1})|| where the joint is valid in both frames, else NaN;
+ *     row 0 is NaN.
+ *  6. Rows at and beyond n: every per-frame float NaN, n_valid_f and p_status 0.
+ *  7. metrics [clips, 4] (SKIMI_PE_*): MPJPE = the mean of the clip's finite err; P_MPJPE, N_MPJPE = the mean of the per-frame
+ *     value over the frames that have a finite one; MPJVE = the mean of the finite vel_err.  An empty mean is NaN.  counts
+ *     [clips, 3] i32 = n_err, n_complete, n_vel.  One workgroup per clip: thread i sums the samples i, i + 256, .. of the
+ *     clip's n J (or n) samples, then a fixed xor butterfly per wave, then the four wave totals in order.
+ *  8. joint_stats [clips, 2, J, 3] = mean, population std (two passes: the mean, then the deviations), median of a joint's
+ *     finite err (table 0) and p_err (table 1) over the clip; joint_n [clips, 2, J] i32 their number, 0: three NaN.  The
+ *     median is the mean of the two middle order statistics (one for an odd count), selected exactly.
+ *
+ * skimi_clip_quality = the figures of VideoPose3D/fuse/fuse_eval.py (bone_lengths, eval_fused_pose's CV and symmetry,
+ * temporal_stats, symmetry_score_mirror) and metrics/true_data_compare.py (compute_temporal_metrics, compute_bone_length_cv)
+ * for a batch of clips X [clips, T, J, 3] in one launch.  edges [n_edges, 2], left_edges, right_edges, lr_pairs [n_pairs, 2]
+ * as (left, right): i32 joint indices on the HOST, at most SKIMI_EVAL_MAX_EDGES edges per list and SKIMI_EVAL_MAX_PAIRS pairs.
+ *  1. L[t, e] = the distance of the edge's joints, NaN unless both are finite.  bone_len [clips, T, n_edges] (optional): L,
+ *     NaN at and beyond n.
+ *  2. scalars [clips, SKIMI_CQ_SCALARS]:
+ *     BONE_CV_POOLED = nanstd(L) / (nanmean(L) + 1e-9) over all (t, e); no length: NaN.
+ *     BONE_CV_MEAN = the mean of bone_cv_edge over the edges that have a value, in edge order; none: NaN.  bone_cv_edge
+ *       [clips, n_edges] = std / mean of the edge's lengths where it has one and the mean exceeds 1e-9, else NaN.
+ *     LR_LENGTH_SYMMETRY = |Lm - Rm| / (0.5 (Lm + Rm) + 1e-9), Lm, Rm the nanmeans over left_edges and right_edges.
+ *     SPEED_MEAN, JERK_MEAN = the mean norm of the first / second differences, over the (frame, joint) where all three
+ *       coordinates of the difference are finite; n < 3 or no such sample: NaN.
+ *     SPEED_P95, ACCEL_P95: every (joint, coordinate) series with at least 2 finite samples is filled as np.interp over the
+ *       frame index does (linear inside, the end values held outside), the others stay as they are; then NumPy's `linear`
+ *       95th percentile of the (n - 1) J norms of the first and of the (n - 2) J norms of the second differences, by exact
+ *       selection.  A NaN among the values: NaN.  n < 3: NaN.
+ *     MIRROR_SYMMETRY = over the pairs finite on both sides in frame n - 1, in pair order, the mean of ||X[l] - (-x, y, z)
+ *       of X[r]||; n == 0 or no pair: NaN.
+ *  3. Placement.  The filled clip and the two series of norms (five of frames * joints doubles) live in LDS when workspace is
+ *     NULL, which needs frames * joints <= SKIMI_EVAL_LDS_ELEMS, and otherwise in workspace (dev), at least
+ *     skimi_eval_workspace_bytes bytes (0 for sizes the call refuses).  Both placements run the same code on the same values. */
+#define SKIMI_EVAL_MAX_JOINTS 128
+#define SKIMI_EVAL_MAX_EDGES 128
+#define SKIMI_EVAL_MAX_PAIRS 64
+#define SKIMI_EVAL_LDS_ELEMS 1440
+enum { SKIMI_PE_MPJPE = 0, SKIMI_PE_P_MPJPE, SKIMI_PE_N_MPJPE, SKIMI_PE_MPJVE };
+enum {
+    SKIMI_CQ_BONE_CV_POOLED = 0, SKIMI_CQ_BONE_CV_MEAN, SKIMI_CQ_LR_LENGTH_SYMMETRY, SKIMI_CQ_SPEED_MEAN, SKIMI_CQ_JERK_MEAN,
+    SKIMI_CQ_SPEED_P95, SKIMI_CQ_ACCEL_P95, SKIMI_CQ_MIRROR_SYMMETRY, SKIMI_CQ_SCALARS
+};
+size_t skimi_eval_workspace_bytes(int64_t clips, int64_t frames, int32_t joints);
+int skimi_pose_errors(const double* pred, const double* target, const int32_t* lengths, int64_t clips, int64_t frames, int32_t joints,
+                      int32_t zero_root, double* err, double* p_err, double* vel_err, double* mpjpe_f, double* n_mpjpe_f,
+                      double* p_mpjpe_f, int32_t* n_valid_f, int32_t* p_status, double* aligned, double* p_R, double* p_scale,
+                      double* p_t, double* metrics, int32_t* counts, double* joint_stats, int32_t* joint_n, void* stream);
+int skimi_clip_quality(const double* X, const int32_t* lengths, int64_t clips, int64_t frames, int32_t joints, const int32_t* edges,
+                       int32_t n_edges, const int32_t* left_edges, int32_t n_left, const int32_t* right_edges, int32_t n_right,
+                       const int32_t* lr_pairs, int32_t n_pairs, void* workspace, size_t workspace_bytes, double* scalars,
+                       double* bone_cv_edge, double* bone_len, void* stream);
+
 /* ---- VGGT head and track-head helper kernels, one launch each ----
  * The kernels skimi_vggt_forward runs between its GEMMs, exposed singly so that each can be tested against a float64
  * restatement.  All maps are channels-last and dense; dtype / out_dtype are SKIMI_F32, SKIMI_BF16 or SKIMI_F16.  Every

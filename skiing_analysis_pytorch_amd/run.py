@@ -17,7 +17,8 @@ keypoints -> each camera's (R, t) and the pair's relative pose, on the device (g
 the left one from the essential matrix of the 2D keypoints alone (geometry.essential_ransac), then the same refinement.
 
 `process_video_3d` is the counterpart of VideoPose3D/main.py's process_video_3d: both views lifted, then fused per frame
-without extrinsics on the device (geometry.fuse_h36m), and the fused joints written as the reference writes them.
+without extrinsics on the device (geometry.fuse_h36m), and the fused joints written as the reference writes them;
+`evaluate=True` adds its fused_metrics.txt (evaluate.eval_fused_pose on the device).
 """
 from __future__ import annotations
 
@@ -95,8 +96,8 @@ def run_video_pose_3d(config, pt_path: Path, out_dir: Path, args, model_pos: Tem
 
 
 def process_video_3d(config, left_path: Path, right_path: Path, out_dir: Path, npy_dir: Path, args, model_pos: TemporalModel = None,
-                     analyze: bool = False):
-    """VideoPose3D/main.py:33-103 process_video_3d without its GIF and without eval_fused_pose: both views' clips are lifted
+                     analyze: bool = False, evaluate: bool = False):
+    """VideoPose3D/main.py:33-103 process_video_3d without its GIF (eval_fused_pose: evaluate=True): both views' clips are lifted
     (run_video_pose_3d into <out_dir>/videopose3d/left and /right) and fused frame by frame with the reference's settings
     (tau = 0.06, allow_scale = False, mirror_right_x = False) -- here as ONE geometry.fuse_h36m launch over the clip, in
     float64, where the reference loops over the frames on the host.  The fused, left and right joints are written with
@@ -106,7 +107,10 @@ def process_video_3d(config, left_path: Path, right_path: Path, out_dir: Path, n
     diagnostics, status, mean_gain and bad_frames on the device).  analyze=True adds the skiing analysis of the fused clip
     (angle/main.py's process_person without its pictures): the clip stays on the device, goes through geometry.kinematics
     with the Human3.6M layout (angle.H36M_17, y pointing down as the lifter's camera frame has it) and the reference's CSV
-    files land in <out_dir>/angle.  With analyze off nothing else changes: every file is bitwise what it was."""
+    files land in <out_dir>/angle.  evaluate=True adds the reference's last step (:92-102): evaluate.eval_fused_pose of the
+    left, right and fused clips on the device (geometry.pose_errors + geometry.clip_quality, one read-back) written to
+    <out_dir>/fused_metrics.txt in the reference's format.  With analyze and evaluate off nothing else changes: every file is
+    bitwise what it was."""
     out_dir = Path(out_dir)
     left, _ = run_video_pose_3d(config, left_path, out_dir / "videopose3d" / "left", args, model_pos=model_pos)
     right, _ = run_video_pose_3d(config, right_path, out_dir / "videopose3d" / "right", args, model_pos=model_pos)
@@ -121,6 +125,10 @@ def process_video_3d(config, left_path: Path, right_path: Path, out_dir: Path, n
         from . import angle
 
         angle.write_person(angle.analysis_from(geometry.kinematics(res.fused, layout=angle.H36M_17)), out_dir / "angle")
+    if evaluate:
+        from . import evaluate as ev
+
+        ev.write_fused_metrics(out_dir / "fused_metrics.txt", ev.eval_fused_pose(left, right, res.fused))
     return res.fused, res
 
 

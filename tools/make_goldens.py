@@ -752,6 +752,107 @@ def gen_kinematics():
 GENERATORS["kinematics"] = gen_kinematics
 
 
+def gen_evaluate():
+    """DESIGN §2 "Evaluation": the reference's OWN VideoPose3D/common/loss.py, VideoPose3D/fuse/fuse_eval.py, metrics/
+    unity_data_compare.py (calculate_per_joint_errors, summarize_joint_errors) and metrics/true_data_compare.py
+    (compute_temporal_metrics, compute_bone_length_cv), imported by file spec, on the clips of tests/evaluate_cases.py cut to
+    their lengths; loss.py in float64, p_mpjpe / n_mpjpe / mpjpe / mean_velocity_error on NaN-free clips only (they return NaN
+    or raise otherwise).  `loop_*` is the loop of VideoPose3D/run.py:998-1041 rerun in float64 on lists of clips.  Only
+    inputs and results are stored."""
+    import hashlib
+    import importlib.util
+    import warnings
+
+    sys.path.insert(0, str(ROOT / "tests"))
+    import evaluate_cases as ec
+
+    def load(name, *parts):
+        spec = importlib.util.spec_from_file_location(name, os.path.join(REF, *parts))
+        m = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(m)
+        return m
+
+    loss = load("ref_loss", "VideoPose3D", "common", "loss.py")
+    fe = load("ref_fuse_eval", "VideoPose3D", "fuse", "fuse_eval.py")
+    udc = load("ref_unity_data_compare", "metrics", "unity_data_compare.py")
+    tdc = load("ref_true_data_compare", "metrics", "true_data_compare.py")
+    warnings.simplefilter("ignore")
+    tt = lambda a: torch.from_numpy(np.ascontiguousarray(a))      # noqa: E731
+
+    def zeroed(g, zr):
+        g = g.copy()
+        if zr is not None:
+            g[:, zr] = 0          # run.py:994
+        return g
+
+    def loss_numbers(p, g):
+        """mpjpe, p_mpjpe, n_mpjpe, mpjve of a NaN-free clip with extent in every frame"""
+        e1 = float(loss.mpjpe(tt(p), tt(g)))
+        e3 = float(loss.n_mpjpe(tt(p)[None], tt(g)[None]))
+        e2 = float(loss.p_mpjpe(p.copy(), g.copy()))
+        ev = float(loss.mean_velocity_error(p, g)) if p.shape[0] >= 2 else float("nan")
+        return e1, e2, e3, ev
+
+    out = {"cases": np.array(list(ec.CASES))}
+    for name, case in ec.CASES.items():
+        for k in ("pred", "target"):      # the inputs are seeded: the large ones are stored as their digest
+            a = np.ascontiguousarray(case[k])
+            out[f"{name}_{k}"] = a if a.nbytes <= 16384 else np.array(hashlib.sha256(a.tobytes()).hexdigest())
+        J = case["pred"].shape[-2]
+        lay = ec.layout(J)
+        for b, (p, g0) in enumerate(ec.clips_of(case)):
+            g = zeroed(g0, case.get("zero_root"))
+            n = p.shape[0]
+            key = f"{name}_{b}"
+            if n >= 1:
+                out[f"{key}_mpd"] = np.float64(fe.mean_pairwise_distance(p, g))
+                box = udc.init_joint_stat_container(range(J))
+                per = np.empty((n, J))
+                for t in range(n):
+                    e = udc.calculate_per_joint_errors({j: p[t, j] for j in range(J)}, {j: g[t, j] for j in range(J)})
+                    udc.accumulate_joint_errors(box, e)
+                    per[t] = [e[j] for j in range(J)]
+                summ = udc.summarize_joint_errors(box)
+                if n <= 41:
+                    out[f"{key}_per_joint_err"] = per
+                out[f"{key}_joint_summary"] = np.array([[summ[j][k] for k in ("mean", "std", "median", "n")] for j in range(J)], dtype=np.float64)
+            clean = bool(n >= 1 and J > 1 and np.isfinite(p).all() and np.isfinite(g).all() and not name.startswith("flat"))
+            if clean:
+                out[f"{key}_loss"] = np.array(loss_numbers(p, g))
+            # the ground-truth-free figures of the prediction
+            if len(lay["edges"]):
+                out[f"{key}_bone_len"] = fe.bone_lengths(p, np.asarray(lay["edges"], dtype=int)).reshape(n, len(lay["edges"]))
+            ts = fe.temporal_stats(p)
+            out[f"{key}_p95"] = np.array([ts.get("Speed P95", np.nan), ts.get("Accel P95", np.nan)])
+            if J == 17 and n >= 1:
+                out[f"{key}_mirror"] = np.float64(fe.symmetry_score_mirror(p[-1]))
+            if J == 15:
+                seq = [{jid: p[t, i] for i, jid in enumerate(tdc.TARGET_IDS)} for t in range(n)]
+                tm = tdc.compute_temporal_metrics(seq)
+                out[f"{key}_temporal"] = np.array([tm["speed_mean"], tm["jerk_mean"]], dtype=np.float64)
+                out[f"{key}_bone_cv"] = np.float64(tdc.compute_bone_length_cv(seq)) if n else np.float64("nan")
+        print(f"  {name}: {list(case['pred'].shape)}")
+    for name in ec.FUSED:
+        left, right, fused = ec.fused_inputs(name)
+        m = fe.eval_fused_pose(left, right, fused)
+        out[f"fused_{name}_keys"] = np.array(list(m))
+        out[f"fused_{name}_values"] = np.array([m[k] for k in m], dtype=np.float64)
+        out[f"fused_{name}_text"] = np.array("Fused Pose Evaluation Metrics:\n" + "".join(f"{k:25s}: {v:.4f}\n" for k, v in m.items()))
+    for group, names in ec.EVAL_CLIPS.items():
+        tot, N = np.zeros(4), 0
+        for nm in names:
+            p, g = ec.CASES[nm]["pred"], zeroed(ec.CASES[nm]["target"], 0)
+            tot += p.shape[0] * np.array(loss_numbers(p, g))
+            N += p.shape[0]
+        out[f"loop_{group}"] = tot / N * 1000
+    path = GOLD / "evaluate.npz"
+    np.savez_compressed(path, **out)
+    print("wrote", path.name, path.stat().st_size, "bytes")
+
+
+GENERATORS["evaluate"] = gen_evaluate
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GENERATORS)
     for w in which:
