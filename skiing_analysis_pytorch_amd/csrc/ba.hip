@@ -10,12 +10,13 @@
 //   P3  per (t,c): dt = sum_j g - R dCc, dR = sum_j g X^T - t dCc^T -> dw; Adam on t and w in place
 //       per (t,j): dX = sum_c R^T g + temporal + bone terms; Adam on X into the other X buffer
 //       one tree reduction of the bone and baseline loss values -> history row
-// Every sum runs in a fixed order (per thread in item order, then a fixed shuffle/wave tree): results are bitwise
+// Every sum runs in a fixed order (per thread in item order, then reduce.h's fixed shuffle/wave tree): results are bitwise
 // reproducible, and do not depend on where the state lives.  The state (parameters, Adam moments) and the per-iteration
 // scratch live in LDS when they fit, else in the caller's workspace.  Rules: DESIGN §2 "BA".
 #include <math.h>
 
 #include "common.h"
+#include "reduce.h"
 #include "rodrigues.h"
 
 namespace skimi {
@@ -66,28 +67,6 @@ __device__ inline void adam(double& p, double& m, double& v, double g, double st
     p = p - step_size * (m / (sqrt(v) / bc2_sqrt + kEps));
 }
 
-// fixed-order workgroup sums of N values per thread: a shuffle tree inside each wave, then `total` adds the waves in
-// order, so every thread that reads total k gets the same bits.  `red` alternates between two buffers: one barrier
-// per reduction suffices, and a total stays readable until the next-but-one reduction.
-template <int N>
-__device__ inline void block_sum(const double (&v)[N], double (*red)[kRed]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        double x = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-        if (lane == 0) red[wave][k] = x;
-    }
-    __syncthreads();
-}
-__device__ inline double total(const double (*red)[kRed], int k) {
-    double s = red[0][k];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) s += red[w][k];
-    return s;
-}
-
 template <bool kLds>
 __global__ __launch_bounds__(kThreads) void ba_kernel(BaArgs a) {
     extern __shared__ double dyn[];
@@ -125,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void ba_kernel(BaArgs a) {
     double cs[1] = {0.0};
     for (int i = tid; i < TCJ; i += kThreads) cs[0] += a.conf[i];
     block_sum<1>(cs, red[1]);          // its barrier also publishes the initial state
-    const double S = total(red[1], 0) + 1e-6;     // loss.py:94
+    const double S = total<kWaves>(red[1], 0) + 1e-6;     // loss.py:94
 
     int nb = 0;                        // bones with both indices < J (loss.py:137-139)
     for (int b = 0; b < kBones; ++b) nb += (kBone[b][0] < J && kBone[b][1] < J) ? 1 : 0;
@@ -211,7 +190,7 @@ __global__ __launch_bounds__(kThreads) void ba_kernel(BaArgs a) {
             }
         }
         block_sum<kRed>(acc, red[0]);
-        const double bm = total(red[0], 3) / T;        // baseline mean, held constant (detach)
+        const double bm = total<kWaves>(red[0], 3) / T;        // baseline mean, held constant (detach)
         // ---- P3: gradients and Adam ----
         const double bc1 = 1.0 - pow(kB1, (double)(it + 1)), bc2_sqrt = sqrt(1.0 - pow(kB2, (double)(it + 1)));
         const double step = a.lr / bc1;
@@ -322,7 +301,7 @@ __global__ __launch_bounds__(kThreads) void ba_kernel(BaArgs a) {
                 if (i0 >= J || i1 >= J || (j != i0 && j != i1)) continue;
                 const double s[3] = {Xt[3 * i0] - Xt[3 * i1], Xt[3 * i0 + 1] - Xt[3 * i1 + 1], Xt[3 * i0 + 2] - Xt[3 * i1 + 2]};
                 const double L = sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
-                const double dL = L - total(red[0], 4 + b) / T;    // reference length: mean over T, held constant (detach)
+                const double dL = L - total<kWaves>(red[0], 4 + b) / T;    // reference length: mean over T, held constant (detach)
                 if (j == i0) acc2[0] += dL * dL;
                 if (L > 0.0) {               // torch.norm backward: 0 at a zero-length bone
                     const double sc = (c_bone * dL) / L;
@@ -340,11 +319,11 @@ __global__ __launch_bounds__(kThreads) void ba_kernel(BaArgs a) {
         }
         block_sum<2>(acc2, red[1]);
         if (tid == 0 && hist) {
-            const double l_rep = w_rep * total(red[0], 0) / S;
-            const double l_smooth = T > 1 ? w_smooth * (total(red[0], 1) / Ns) : 0.0;
-            const double l_base = C >= 2 ? w_base * (total(red[1], 1) / T) : 0.0;
-            const double l_bone = nb > 0 ? w_bone * (total(red[1], 0) / Nb) : 0.0;
-            const double l_temp = T > 1 ? w_temp * (total(red[0], 2) / Np) : 0.0;
+            const double l_rep = w_rep * total<kWaves>(red[0], 0) / S;
+            const double l_smooth = T > 1 ? w_smooth * (total<kWaves>(red[0], 1) / Ns) : 0.0;
+            const double l_base = C >= 2 ? w_base * (total<kWaves>(red[1], 1) / T) : 0.0;
+            const double l_bone = nb > 0 ? w_bone * (total<kWaves>(red[1], 0) / Nb) : 0.0;
+            const double l_temp = T > 1 ? w_temp * (total<kWaves>(red[0], 2) / Np) : 0.0;
             double* h = hist + 6L * it;
             h[0] = l_rep + l_smooth + l_base + l_bone + l_temp;
             h[1] = l_rep;

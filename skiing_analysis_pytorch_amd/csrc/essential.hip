@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "fp64_util.h"
 
 namespace skimi {
 namespace {
@@ -36,9 +37,6 @@ constexpr int kMaxHyp = 65536;
 constexpr int kTile = 256;                   // points per LDS tile of the scoring loop
 constexpr int kScoreThreads = 64;
 constexpr int kFinishThreads = 256;
-
-HD bool is_fin(double x) { return fabs(x) <= 1.79769313486231570815e308; }
-HD double nan_d() { return __builtin_nan(""); }
 
 // ---- rule 3: the sampling stream ----------------------------------------------------------------------------------------
 HD uint64_t splitmix64(uint64_t& s) {
@@ -401,7 +399,7 @@ HD bool null_vector(const double (*A)[10], double lam, double* xyz) {
 // ---- rule 4: a, b = the five correspondences' normalised coordinates -> up to ten E (row-major, ||E||_F = sqrt 2, by x
 // ascending), the rest NaN; returns the count ------------------------------------------------------------------------------
 HD int five_point_solve(const double (*a)[2], const double (*b)[2], double* E) {
-    for (int k = 0; k < kSol * 9; ++k) E[k] = nan_d();
+    for (int k = 0; k < kSol * 9; ++k) E[k] = qnan();
     // nullspace basis
     double AtA[81], Q[81], N[4][9];
     {
@@ -660,9 +658,7 @@ __global__ __launch_bounds__(256) void prep_kernel(EssentialArgs a) {
             x1 = a.x2d[2 * (a.N + p)], y1 = a.x2d[2 * (a.N + p) + 1];
             used = is_fin(x0) && is_fin(y0) && is_fin(x1) && is_fin(y1);
             if (a.conf) {
-                double w0 = a.conf[p], w1 = a.conf[a.N + p];
-                w0 = is_fin(w0) ? fmin(fmax(w0, 0.0), 1.0) : 0.0;
-                w1 = is_fin(w1) ? fmin(fmax(w1, 0.0), 1.0) : 0.0;
+                const double w0 = clamp_conf(a.conf[p]), w1 = clamp_conf(a.conf[a.N + p]);
                 used = used && w0 >= a.min_conf && w1 >= a.min_conf;
             }
             a.inliers[p] = 0;
@@ -738,7 +734,7 @@ __global__ __launch_bounds__(kScoreThreads) void score_kernel(EssentialArgs a) {
     if (__ballot(valid) == 0) {                // the whole wave, which is the whole workgroup
         if (in_range) {
             a.w.inl[o] = -1;
-            a.w.cost[o] = nan_d();
+            a.w.cost[o] = qnan();
         }
         return;
     }
@@ -763,7 +759,7 @@ __global__ __launch_bounds__(kScoreThreads) void score_kernel(EssentialArgs a) {
     }
     if (in_range) {
         a.w.inl[o] = valid ? inl : -1;
-        a.w.cost[o] = valid ? cost : nan_d();
+        a.w.cost[o] = valid ? cost : qnan();
     }
 }
 
@@ -787,7 +783,7 @@ __global__ __launch_bounds__(kFinishThreads) void finish_kernel(EssentialArgs a)
     const int tid = threadIdx.x;
     const long g = blockIdx.x, base = g * a.gs;
     const int m = a.w.m[g];
-    const double nan = nan_d();
+    const double nan = qnan();
     // the winner and the number of solutions
     Best mine{-1, 0x7fffffff, 0.0};
     int nsol = 0;

@@ -20,6 +20,8 @@
 #include <math.h>
 
 #include "common.h"
+#include "fp64_util.h"
+#include "reduce.h"
 #include "svd3.h"
 
 namespace skimi {
@@ -32,62 +34,24 @@ constexpr int kMaxEdges = SKIMI_EVAL_MAX_EDGES;
 constexpr int kMaxPairs = SKIMI_EVAL_MAX_PAIRS;
 constexpr long kMaxElems = 1L << 40;
 
-__device__ inline bool is_fin(double x) { return fabs(x) <= 1.79769313486231570815e308; }
-__device__ inline bool fin3(const double* x) { return is_fin(x[0]) && is_fin(x[1]) && is_fin(x[2]); }
-__device__ inline double qnan() { return __longlong_as_double(0x7ff8000000000000LL); }
-__device__ inline double norm3(double a, double b, double c) { return sqrt(a * a + b * b + c * c); }
 __device__ inline int clip_len(const int32_t* lengths, long b, long T) {
     return lengths ? (int)min(max((long)lengths[b], 0L), T) : (int)T;
 }
 
-// the sum over the wave in a fixed order; every lane gets the same bits (a + b == b + a)
-__device__ inline double wsum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ inline int wisum(int x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 // the sum over the workgroup: the waves' butterflies, then the four wave totals in order.  sh: kWaves values in LDS.
 __device__ inline double block_sum(double x, double* sh) {
-    x = wsum(x);
+    x = wave_sum(x);
     __syncthreads();                                   // the previous call's readers are done
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
     __syncthreads();
     return (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 __device__ inline int block_isum(int x, int* sh) {
-    x = wisum(x);
+    x = wave_sum(x);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = x;
     __syncthreads();
     return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-// monotone map double -> uint64 (-0.0 just below +0.0, +-inf ordered)
-__device__ inline unsigned long long dkey(double x) {
-    const unsigned long long u = (unsigned long long)__double_as_longlong(x);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ULL);
-}
-__device__ inline double dunkey(unsigned long long k) {
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffULL) : ~k));
-}
-
-// NumPy's `linear` percentile position on m >= 1 sorted values: v = q / 100 (m - 1), i = floor(v), gamma = v - i
-__device__ inline void pct_pos(double q, unsigned m, unsigned& i0, unsigned& i1, double& gamma) {
-    const double v = q / 100.0 * (double)(m - 1);
-    const double fl = floor(v);
-    i0 = (unsigned)fl;
-    i1 = min(i0 + 1u, m - 1u);
-    gamma = v - fl;
-}
-__device__ inline double pct_lerp(double lo, double hi, double g) {
-    const double d = hi - lo;
-    return g < 0.5 ? lo + d * g : hi - d * (1.0 - g);
 }
 
 // ---- skimi_pose_errors -------------------------------------------------------------------------------------------
@@ -161,9 +125,9 @@ __global__ __launch_bounds__(kThreads) void pe_frame_kernel(PeArgs a) {
                 }
             }
         }
-        se = wsum(se);
-        ce = wisum(ce);
-        nvalid = wisum(cv);
+        se = wave_sum(se);
+        ce = wave_sum(ce);
+        nvalid = wave_sum(cv);
         if (ce > 0) mf = se / (double)ce;
         if (nvalid == J) {                             // a complete frame (uniform)
             const double dJ = (double)J;
@@ -175,19 +139,19 @@ __global__ __launch_bounds__(kThreads) void pe_frame_kernel(PeArgs a) {
                     sgp += g[s][0] * p[s][0] + g[s][1] * p[s][1] + g[s][2] * p[s][2];
                     spp += p[s][0] * p[s][0] + p[s][1] * p[s][1] + p[s][2] * p[s][2];
                 }
-            const double scale = (wsum(sgp) / dJ) / (wsum(spp) / dJ);
+            const double scale = (wave_sum(sgp) / dJ) / (wave_sum(spp) / dJ);
             double sn = 0.0;
 #pragma unroll
             for (int s = 0; s < 2; ++s)
                 if (in[s]) sn += norm3(scale * p[s][0] - g[s][0], scale * p[s][1] - g[s][1], scale * p[s][2] - g[s][2]);
-            sn = wsum(sn) / dJ;
+            sn = wave_sum(sn) / dJ;
             if (is_fin(sn)) nf = sn;
             // Procrustes: centre, normalise, H = X0^T Y0, R = V U^T without reflection
             double muX[3], muY[3], x0[2][3], y0[2][3];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                muX[c] = wsum(g[0][c] + g[1][c]) / dJ;      // joints outside the frame hold 0
-                muY[c] = wsum(p[0][c] + p[1][c]) / dJ;
+                muX[c] = wave_sum(g[0][c] + g[1][c]) / dJ;      // joints outside the frame hold 0
+                muY[c] = wave_sum(p[0][c] + p[1][c]) / dJ;
             }
             double sx = 0.0, sy = 0.0;
 #pragma unroll
@@ -199,7 +163,7 @@ __global__ __launch_bounds__(kThreads) void pe_frame_kernel(PeArgs a) {
                     sx += x0[s][c] * x0[s][c];
                     sy += y0[s][c] * y0[s][c];
                 }
-            const double nX = sqrt(wsum(sx)), nY = sqrt(wsum(sy));
+            const double nX = sqrt(wave_sum(sx)), nY = sqrt(wave_sum(sy));
             double H[9];
             bool fin = nX > 0.0 && nY > 0.0;              // a pose without extent has no alignment
 #pragma unroll
@@ -214,7 +178,7 @@ __global__ __launch_bounds__(kThreads) void pe_frame_kernel(PeArgs a) {
 #pragma unroll
                     for (int s = 0; s < 2; ++s)
                         if (in[s]) h += x0[s][r] * y0[s][c];
-                    H[3 * r + c] = wsum(h);
+                    H[3 * r + c] = wave_sum(h);
                     fin = fin && is_fin(H[3 * r + c]);
                 }
             if (fin) {
@@ -237,7 +201,7 @@ __global__ __launch_bounds__(kThreads) void pe_frame_kernel(PeArgs a) {
                     d[s] = norm3(q[s][0] - g[s][0], q[s][1] - g[s][1], q[s][2] - g[s][2]);
                     if (in[s]) sp += d[s];
                 }
-                sp = wsum(sp) / dJ;
+                sp = wave_sum(sp) / dJ;
                 bool good = is_fin(sp) && is_fin(as) && fin3(tt);
 #pragma unroll
                 for (int k = 0; k < 9; ++k) good = good && is_fin(Rm[k]);
@@ -345,8 +309,8 @@ __global__ __launch_bounds__(kThreads) void pe_joint_kernel(PeArgs a) {
             ++cnt;
         }
     }
-    s = wsum(s);
-    cnt = wisum(cnt);
+    s = wave_sum(s);
+    cnt = wave_sum(cnt);
     if (cnt > 0) {
         mean = s / (double)cnt;
         double ss = 0.0;
@@ -354,7 +318,7 @@ __global__ __launch_bounds__(kThreads) void pe_joint_kernel(PeArgs a) {
             const double v = x[(long)i * J];
             if (is_fin(v)) ss += (v - mean) * (v - mean);
         }
-        sd = sqrt(wsum(ss) / (double)cnt);
+        sd = sqrt(wave_sum(ss) / (double)cnt);
         // the two middle order statistics (the same one for an odd count)
         unsigned k0 = (unsigned)(cnt - 1) / 2, k1 = (unsigned)cnt / 2;
         unsigned long long p0 = 0, p1 = 0;
@@ -363,16 +327,16 @@ __global__ __launch_bounds__(kThreads) void pe_joint_kernel(PeArgs a) {
             for (int i = lane; i < n; i += 64) {
                 const double v = x[(long)i * J];
                 if (is_fin(v)) {
-                    const unsigned long long key = dkey(v);
+                    const unsigned long long key = key64(v);
                     c0 += ((key ^ p0) >> bit) == 0;    // the bits above agree with the prefix and this one is 0
                     c1 += ((key ^ p1) >> bit) == 0;
                 }
             }
-            c0 = wisum(c0), c1 = wisum(c1);
+            c0 = wave_sum(c0), c1 = wave_sum(c1);
             if (k0 >= (unsigned)c0) k0 -= (unsigned)c0, p0 |= 1ULL << bit;
             if (k1 >= (unsigned)c1) k1 -= (unsigned)c1, p1 |= 1ULL << bit;
         }
-        med = (dunkey(p0) + dunkey(p1)) / 2.0;
+        med = (unkey64(p0) + unkey64(p1)) / 2.0;
     }
     if (lane == 0) {
         double* o = a.joint_stats + w * 3;
@@ -458,8 +422,8 @@ __global__ __launch_bounds__(kThreads) void clip_quality_kernel(CqArgs a) {
                 ++c;
             }
         }
-        s = wsum(s);
-        c = wisum(c);
+        s = wave_sum(s);
+        c = wave_sum(c);
         double cv = nan;
         int has = 0;
         if (c > 0) {
@@ -469,7 +433,7 @@ __global__ __launch_bounds__(kThreads) void clip_quality_kernel(CqArgs a) {
                 const double L = bone(Xc + (long)t * J * 3, ia, ib);
                 if (L == L) ss += (L - m) * (L - m);
             }
-            ss = wsum(ss);
+            ss = wave_sum(ss);
             if (m > 1e-9) {
                 cv = sqrt(ss / (double)c) / m;
                 has = 1;
@@ -562,25 +526,24 @@ __global__ __launch_bounds__(kThreads) void clip_quality_kernel(CqArgs a) {
         nv = block_isum(nv, shi);                       // its barriers also publish V and A
         na = block_isum(na, shi);
         // four selections in the same 64 passes: ranks i0, i1 of V and of A
-        unsigned kk[4];
-        double gv, ga;
-        pct_pos(95.0, mv, kk[0], kk[1], gv);
-        pct_pos(95.0, ma, kk[2], kk[3], ga);
+        const PctPos pv = pct_pos(95.0, mv), pa = pct_pos(95.0, ma);
+        unsigned kk[4] = {pv.i0, pv.i1, pa.i0, pa.i1};
+        const double gv = pv.gamma, ga = pa.gamma;
         unsigned long long pre[4] = {0, 0, 0, 0};
         for (int bit = 63; bit >= 0; --bit) {
             unsigned c4[4] = {0, 0, 0, 0};
             for (unsigned i = tid; i < mv; i += kThreads) {
-                const unsigned long long key = dkey(V[i]);
+                const unsigned long long key = key64(V[i]);
                 c4[0] += ((key ^ pre[0]) >> bit) == 0;
                 c4[1] += ((key ^ pre[1]) >> bit) == 0;
                 if (i < ma) {
-                    const unsigned long long ka = dkey(A[i]);
+                    const unsigned long long ka = key64(A[i]);
                     c4[2] += ((ka ^ pre[2]) >> bit) == 0;
                     c4[3] += ((ka ^ pre[3]) >> bit) == 0;
                 }
             }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) c4[k] = (unsigned)wisum((int)c4[k]);
+            for (int k = 0; k < 4; ++k) c4[k] = wave_sum(c4[k]);
             __syncthreads();
             if (lane == 0) {
 #pragma unroll
@@ -594,8 +557,8 @@ __global__ __launch_bounds__(kThreads) void clip_quality_kernel(CqArgs a) {
             }
         }
         // a NaN among the values makes the percentile NaN, whatever the passes selected
-        speed_p95 = nv ? nan : pct_lerp(dunkey(pre[0]), dunkey(pre[1]), gv);
-        accel_p95 = na ? nan : pct_lerp(dunkey(pre[2]), dunkey(pre[3]), ga);
+        speed_p95 = nv ? nan : pct_lerp(unkey64(pre[0]), unkey64(pre[1]), gv);
+        accel_p95 = na ? nan : pct_lerp(unkey64(pre[2]), unkey64(pre[3]), ga);
     }
     if (tid == 0) {
         double s = 0.0;

@@ -16,6 +16,8 @@
 #include <math.h>
 
 #include "common.h"
+#include "fp64_util.h"
+#include "reduce.h"
 #include "svd3.h"
 
 namespace skimi {
@@ -26,17 +28,6 @@ constexpr int kMaxJoints = 128;              // two joints per lane
 constexpr int kMaxWin = 33;                  // Savitzky-Golay window: the ring of a series lives in LDS
 constexpr int kBatch = 8;                    // time steps loaded together by the smoothers
 constexpr unsigned kTorsoMask = (1u << 0) | (1u << 9) | (1u << 4) | (1u << 1) | (1u << 11) | (1u << 14);
-
-__device__ inline bool is_fin(double x) { return fabs(x) <= 1.79769313486231570815e308; }
-__device__ inline bool fin3(const double* x) { return is_fin(x[0]) && is_fin(x[1]) && is_fin(x[2]); }
-__device__ inline double norm3(double a, double b, double c) { return sqrt(a * a + b * b + c * c); }
-
-// the sum over the wave in a fixed order; every lane gets the same bits (a + b == b + a)
-__device__ inline double wsum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
 
 // ---- VideoPose3D left/right fusion ---------------------------------------------------------------------------------
 struct H36mArgs {
@@ -68,7 +59,7 @@ __global__ __launch_bounds__(256) void fuse_h36m_kernel(H36mArgs a) {
     if (t >= a.T) return;                      // the whole wave leaves: no barrier in this kernel
     const bool act = lane < kH36mJoints;
     const int j = act ? lane : 0;
-    const double nan = __builtin_nan("");
+    const double nan = qnan();
     double L[3], Rn[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
@@ -83,7 +74,7 @@ __global__ __launch_bounds__(256) void fuse_h36m_kernel(H36mArgs a) {
     center_scale(Rn);
     // estimate_rigid_umeyama(X = left torso, Y = right torso) on the rows finite on both sides
     const bool tor = act && ((kTorsoMask >> lane) & 1u) && fin3(L) && fin3(Rn);
-    const double n = wsum(tor ? 1.0 : 0.0);
+    const double n = wave_sum(tor ? 1.0 : 0.0);
     double* Ro = a.R + 9 * t;
     double* to = a.t + 3 * t;
     double* dg = a.diag + 4 * t;
@@ -102,16 +93,16 @@ __global__ __launch_bounds__(256) void fuse_h36m_kernel(H36mArgs a) {
     double mx[3], my[3], Xc[3], Yc[3], Sg[9];
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-        mx[c] = wsum(tor ? L[c] : 0.0) / n;
-        my[c] = wsum(tor ? Rn[c] : 0.0) / n;
+        mx[c] = wave_sum(tor ? L[c] : 0.0) / n;
+        my[c] = wave_sum(tor ? Rn[c] : 0.0) / n;
         Xc[c] = L[c] - mx[c];
         Yc[c] = Rn[c] - my[c];
     }
 #pragma unroll
     for (int r = 0; r < 3; ++r)
 #pragma unroll
-        for (int c = 0; c < 3; ++c) Sg[3 * r + c] = wsum(tor ? Yc[r] * Xc[c] : 0.0) / n;
-    const double vy = wsum(tor ? Yc[0] * Yc[0] + Yc[1] * Yc[1] + Yc[2] * Yc[2] : 0.0);
+        for (int c = 0; c < 3; ++c) Sg[3 * r + c] = wave_sum(tor ? Yc[r] * Xc[c] : 0.0) / n;
+    const double vy = wave_sum(tor ? Yc[0] * Yc[0] + Yc[1] * Yc[1] + Yc[2] * Yc[2] : 0.0);
     double Rm[9], ssum;
     polar3(Sg, Rm, ssum);
     const double s = a.allow_scale ? ssum / (vy / n + 1e-12) : 1.0;
@@ -134,9 +125,9 @@ __global__ __launch_bounds__(256) void fuse_h36m_kernel(H36mArgs a) {
         F[c] = lok ? (rok ? pick : L[c]) : (rok ? Al[c] : nan);
     }
     center_scale(F);
-    const double before = wsum(act ? norm3(L[0] - Rn[0], L[1] - Rn[1], L[2] - Rn[2]) : 0.0) / kH36mJoints;
-    const double to_l = wsum(act ? norm3(F[0] - L[0], F[1] - L[1], F[2] - L[2]) : 0.0) / kH36mJoints;
-    const double to_r = wsum(act ? norm3(F[0] - Rn[0], F[1] - Rn[1], F[2] - Rn[2]) : 0.0) / kH36mJoints;
+    const double before = wave_sum(act ? norm3(L[0] - Rn[0], L[1] - Rn[1], L[2] - Rn[2]) : 0.0) / kH36mJoints;
+    const double to_l = wave_sum(act ? norm3(F[0] - L[0], F[1] - L[1], F[2] - L[2]) : 0.0) / kH36mJoints;
+    const double to_r = wave_sum(act ? norm3(F[0] - Rn[0], F[1] - Rn[1], F[2] - Rn[2]) : 0.0) / kH36mJoints;
     if (act)
         for (int c = 0; c < 3; ++c) a.fused[(t * kH36mJoints + j) * 3 + c] = F[c];
     if (lane == 0) {
@@ -162,7 +153,7 @@ struct ViewsArgs {
 // false (conf 0, err NaN) for fewer than min_points rows or an energy under 1e-12, where the host raises
 __device__ inline bool weakpersp(const double (*X)[3], const double (*U)[2], const bool* act, int min_points, double sigma,
                                  double* conf, double* err) {
-    const double nan = __builtin_nan("");
+    const double nan = qnan();
     bool used[2];
     double cnt = 0.0;
 #pragma unroll
@@ -170,20 +161,20 @@ __device__ inline bool weakpersp(const double (*X)[3], const double (*U)[2], con
         used[k] = act[k] && fin3(X[k]) && is_fin(U[k][0]) && is_fin(U[k][1]);
         cnt += used[k] ? 1.0 : 0.0;
     }
-    const double n = wsum(cnt);
+    const double n = wave_sum(cnt);
     double mx[3], mu[2], A[9], energy = 0.0;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) mx[c] = wsum((used[0] ? X[0][c] : 0.0) + (used[1] ? X[1][c] : 0.0)) / n;
+    for (int c = 0; c < 3; ++c) mx[c] = wave_sum((used[0] ? X[0][c] : 0.0) + (used[1] ? X[1][c] : 0.0)) / n;
 #pragma unroll
-    for (int c = 0; c < 2; ++c) mu[c] = wsum((used[0] ? U[0][c] : 0.0) + (used[1] ? U[1][c] : 0.0)) / n;
+    for (int c = 0; c < 2; ++c) mu[c] = wave_sum((used[0] ? U[0][c] : 0.0) + (used[1] ? U[1][c] : 0.0)) / n;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
 #pragma unroll
         for (int c = 0; c < 2; ++c)
-            A[3 * r + c] = wsum((used[0] ? (X[0][r] - mx[r]) * (U[0][c] - mu[c]) : 0.0) +
+            A[3 * r + c] = wave_sum((used[0] ? (X[0][r] - mx[r]) * (U[0][c] - mu[c]) : 0.0) +
                                 (used[1] ? (X[1][r] - mx[r]) * (U[1][c] - mu[c]) : 0.0));
         A[3 * r + 2] = 0.0;
-        energy += wsum((used[0] ? (X[0][r] - mx[r]) * (X[0][r] - mx[r]) : 0.0) + (used[1] ? (X[1][r] - mx[r]) * (X[1][r] - mx[r]) : 0.0));
+        energy += wave_sum((used[0] ? (X[0][r] - mx[r]) * (X[0][r] - mx[r]) : 0.0) + (used[1] ? (X[1][r] - mx[r]) * (X[1][r] - mx[r]) : 0.0));
     }
     const bool ok = n >= (double)min_points && !(energy < 1e-12) && n > 0.0;
     double M[9], ssum;
@@ -215,7 +206,7 @@ __device__ inline void unit3(double* v, double eps) {
 // canonicalize_pose_3d: the frame's pose `F` ([J, 3] in memory, for the key joints) applied to the lane's rows X -> C;
 // a missing key joint or a degenerate scale gives NaN rows
 __device__ inline void canonicalize(const double* F, const int* key, int torso, const double (*X)[3], double (*C)[3]) {
-    const double nan = __builtin_nan("");
+    const double nan = qnan();
     double K[5][3];
     bool ok = true;
 #pragma unroll
@@ -256,7 +247,7 @@ __global__ __launch_bounds__(256) void fuse_views_kernel(ViewsArgs a) {
     const int lane = threadIdx.x & 63;
     const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= a.T) return;                      // the whole wave leaves: no barrier in this kernel
-    const double nan = __builtin_nan("");
+    const double nan = qnan();
     const int J = a.J;
     bool act[2];
     double Xl[2][3], Xr[2][3], Ul[2][2], Ur[2][2];
@@ -280,7 +271,7 @@ __global__ __launch_bounds__(256) void fuse_views_kernel(ViewsArgs a) {
     bool both[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) both[k] = act[k] && fin3(Xl[k]) && fin3(Xr[k]);
-    const double nb = wsum((both[0] ? 1.0 : 0.0) + (both[1] ? 1.0 : 0.0));
+    const double nb = wave_sum((both[0] ? 1.0 : 0.0) + (both[1] ? 1.0 : 0.0));
     double Al[2][3];
 #pragma unroll
     for (int k = 0; k < 2; ++k)
@@ -290,14 +281,14 @@ __global__ __launch_bounds__(256) void fuse_views_kernel(ViewsArgs a) {
         double cs[3], cd[3], H[9], P[9], ssum, tv[3];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            cs[c] = wsum((both[0] ? Xr[0][c] : 0.0) + (both[1] ? Xr[1][c] : 0.0)) / nb;
-            cd[c] = wsum((both[0] ? Xl[0][c] : 0.0) + (both[1] ? Xl[1][c] : 0.0)) / nb;
+            cs[c] = wave_sum((both[0] ? Xr[0][c] : 0.0) + (both[1] ? Xr[1][c] : 0.0)) / nb;
+            cd[c] = wave_sum((both[0] ? Xl[0][c] : 0.0) + (both[1] ? Xl[1][c] : 0.0)) / nb;
         }
 #pragma unroll
         for (int r = 0; r < 3; ++r)
 #pragma unroll
             for (int c = 0; c < 3; ++c)
-                H[3 * r + c] = wsum((both[0] ? (Xr[0][r] - cs[r]) * (Xl[0][c] - cd[c]) : 0.0) +
+                H[3 * r + c] = wave_sum((both[0] ? (Xr[0][r] - cs[r]) * (Xl[0][c] - cd[c]) : 0.0) +
                                     (both[1] ? (Xr[1][r] - cs[r]) * (Xl[1][c] - cd[c]) : 0.0));
         polar3(H, P, ssum);                    // R = V U^T = P^T
 #pragma unroll
@@ -350,7 +341,7 @@ __global__ __launch_bounds__(64) void smooth_ema_kernel(const double* __restrict
                                                         int adaptive, double amin, double amax, double gain, double* __restrict__ Y) {
     const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= J) return;
-    const double nan = __builtin_nan("");
+    const double nan = qnan();
     const double b = base[j];
     double st[3];
 #pragma unroll
@@ -405,7 +396,7 @@ __global__ __launch_bounds__(64) void smooth_savgol_kernel(const double* __restr
     for (long t0 = 0; t0 < T; t0 += kBatch) {
         double xb[kBatch];
 #pragma unroll
-        for (int i = 0; i < kBatch; ++i) xb[i] = t0 + i < T ? X[(t0 + i) * S + s] : __builtin_nan("");
+        for (int i = 0; i < kBatch; ++i) xb[i] = t0 + i < T ? X[(t0 + i) * S + s] : qnan();
 #pragma unroll
         for (int i = 0; i < kBatch; ++i) n += is_fin(xb[i]) ? 1 : 0;
     }

@@ -20,6 +20,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "reduce.h"
 
 namespace skimi {
 namespace {
@@ -295,12 +296,6 @@ __global__ __launch_bounds__(kThreads) void normals_kernel(const float4* __restr
 }
 
 // ---- one ICP iteration -----------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // One thread per valid source point: y = T s (float64, from the original float32 s), nearest target point at
 // d^2 < r2 (ties -> smaller index), then r = (y - t).n, J = [y x n ; n] -> 21 JtJ + 6 Jtr + d^2 + 1, reduced in a
 // fixed order to one partial per workgroup (partial[blockIdx.x * kSlab + k]).  corr (optional): the correspondence's
@@ -369,7 +364,7 @@ __global__ __launch_bounds__(kThreads) void icp_iter_kernel(const float* __restr
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < kSums; ++k) {
-        const double v = wave_sum_d(acc[k]);
+        const double v = wave_sum(acc[k]);
         if (lane == 0) wpart[wave][k] = v;
     }
     __syncthreads();

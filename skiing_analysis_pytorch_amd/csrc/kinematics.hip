@@ -18,6 +18,8 @@
 #include <math.h>
 
 #include "common.h"
+#include "fp64_util.h"
+#include "reduce.h"
 
 namespace skimi {
 namespace {
@@ -42,9 +44,6 @@ struct KinArgs {
     double upu[3], thr;
 };
 
-__device__ inline bool is_fin(double x) { return fabs(x) <= 1.79769313486231570815e308; }
-__device__ inline double qnan() { return __longlong_as_double(0x7ff8000000000000LL); }
-__device__ inline double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
 __device__ inline int clip_len(const KinArgs& a, long b) {
     return a.lengths ? (int)min(max((long)a.lengths[b], 0L), a.T) : (int)a.T;
 }
@@ -72,12 +71,6 @@ __device__ inline bool unit3(const double* v, double* u) {
     if (n == 0.0 || !is_fin(n)) return false;
     u[0] = v[0] / n, u[1] = v[1] / n, u[2] = v[2] / n;
     return true;
-}
-
-__device__ inline void cross3(const double* a, const double* b, double* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
 __device__ inline double angle_abc(const Pt& a, const Pt& b, const Pt& c) {
@@ -382,12 +375,6 @@ __global__ __launch_bounds__(kThreads) void kin_turns_kernel(KinArgs a) {
 }
 
 // ---- (c) per-turn statistics: one wave per (clip, turn slot, series) --------------------------------------------------
-__device__ inline double wsum(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 __global__ __launch_bounds__(kThreads) void kin_stats_kernel(KinArgs a) {
     const long w = (long)blockIdx.x * (kThreads / 64) + threadIdx.x / 64;
     const int lane = threadIdx.x & 63;
@@ -411,7 +398,7 @@ __global__ __launch_bounds__(kThreads) void kin_stats_kernel(KinArgs a) {
                 ++cnt;
             }
         }
-        sum = wsum(sum);
+        sum = wave_sum(sum);
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             cnt += __shfl_xor(cnt, o, 64);
@@ -425,7 +412,7 @@ __global__ __launch_bounds__(kThreads) void kin_stats_kernel(KinArgs a) {
                 const double v = x[i];
                 if (is_fin(v)) ss += (v - mean) * (v - mean);
             }
-            sd = sqrt(wsum(ss) / (double)cnt);
+            sd = sqrt(wave_sum(ss) / (double)cnt);
             lo = mn, hi = mx;
         }
     }

@@ -12,6 +12,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "fp64_util.h"
 
 namespace skimi {
 
@@ -44,13 +45,6 @@ __device__ inline Crop crop_of(const float* box, int H, int W, double src_h, dou
     c.h = finite ? y2 - y1 : 0;
     return c;
 }
-
-// monotone map float -> uint32 (a < b as floats  <=>  key(a) < key(b) as unsigned; -0.0 sorts just below +0.0)
-__device__ inline unsigned key_of(float z) {
-    const unsigned u = __float_as_uint(z);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float float_of(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 // one histogram increment per lane; a wave whose active lanes all hit one bin (the usual case of the first passes: the
 // depths of a person share their exponent) adds its lane count once instead of serialising 64 atomics on one address
@@ -101,7 +95,7 @@ __global__ __launch_bounds__(kPersonThreads) void person_origin_kernel(const flo
     double* out = stats + (long)m * 8;
     const long n_box = (c.w > 0 && c.h > 0) ? (long)c.w * c.h : 0;
     const float* base = points + (long)m * H * W * 3;
-    const double nan = __longlong_as_double(0x7FF8000000000000LL);
+    const double nan = qnan();
     if (n_box == 0) {
         if (tid == 0) {
             out[0] = 0; out[1] = 0; out[2] = 0; out[3] = nan; out[4] = nan; out[5] = nan; out[6] = nan; out[7] = nan;
@@ -129,7 +123,7 @@ __global__ __launch_bounds__(kPersonThreads) void person_origin_kernel(const flo
             if (ok) {
                 acc[0] += 1.0;
                 acc[1] += (double)p[2];
-                bin = key_of(p[2]) >> 24;
+                bin = key32(p[2]) >> 24;
             }
         }
         hist_add(hist, bin, ok);
@@ -164,7 +158,7 @@ __global__ __launch_bounds__(kPersonThreads) void person_origin_kernel(const flo
                 if (i < n_box) {
                     const float* p = at(i);
                     if (valid(p)) {
-                        const unsigned k = key_of(p[2]);
+                        const unsigned k = key32(p[2]);
                         hit = (k & hi_mask) == prefix;
                         bin = (k >> shift) & 255u;
                         if (pass == 1) {
@@ -192,7 +186,7 @@ __global__ __launch_bounds__(kPersonThreads) void person_origin_kernel(const flo
     block_sum(dev, red);
     const double sd = sqrt(dev[0] / (double)n);
     const unsigned lower = s_prefix;
-    double median = (double)float_of(lower);
+    double median = (double)unkey32(lower);
     if ((n & 1) == 0) {
         // upper middle (rank n / 2): the lower one again if count(key <= lower) > n / 2, else the smallest key above it
         unsigned upper = lower;
@@ -203,7 +197,7 @@ __global__ __launch_bounds__(kPersonThreads) void person_origin_kernel(const flo
             for (long i = tid; i < n_box; i += kPersonThreads) {
                 const float* p = at(i);
                 if (valid(p)) {
-                    const unsigned k = key_of(p[2]);
+                    const unsigned k = key32(p[2]);
                     if (k > lower && k < best) best = k;
                 }
             }
@@ -212,7 +206,7 @@ __global__ __launch_bounds__(kPersonThreads) void person_origin_kernel(const flo
             __syncthreads();
             upper = s_above;
         }
-        median = ((double)float_of(lower) + (double)float_of(upper)) / 2.0;   // exact: both are float32
+        median = ((double)unkey32(lower) + (double)unkey32(upper)) / 2.0;   // exact: both are float32
     }
     // last pass: the points with |z - median| < 3 std (strict, float64) and their sum
     const double lim = 3.0 * sd;

@@ -1,0 +1,66 @@
+// Fixed-order reductions of the float64 solver kernels.  Two schemes, which give different bits and are not to be mixed:
+//  - wave_sum: a xor butterfly over the 64 lanes; every lane gets the same bits (a + b == b + a).  Overloads beside
+//    common.h's float one.
+//  - block_sum / total / block_max: a shuffle-down tree per wave into `red`, then the waves in order.
+#pragma once
+#include "common.h"
+#include "fp64_util.h"
+
+namespace skimi {
+
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ unsigned wave_sum(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
+    return v;
+}
+
+// fixed-order workgroup sums of N values per thread: a shuffle tree inside each wave, then `total` adds the waves in
+// order, so every thread that reads total k gets the same bits.  The caller alternates `red` between two buffers: one
+// barrier per reduction suffices, and a total stays readable until the next-but-one reduction.
+template <int N, int kRed>
+__device__ inline void block_sum(const double (&v)[N], double (*red)[kRed]) {
+    static_assert(N <= kRed, "red holds kRed sums per wave");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        double x = v[k];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+        if (lane == 0) red[wave][k] = x;
+    }
+    __syncthreads();
+}
+// kWaves: the workgroup's wave count where it is a constant (the compiler unrolls the sum), 0 to read it from the launch
+template <int kWaves = 0, int kRed>
+__device__ inline double total(const double (*red)[kRed], int k) {
+    const int waves = kWaves > 0 ? kWaves : (int)(blockDim.x >> 6);
+    double s = red[0][k];
+    for (int w = 1; w < waves; ++w) s += red[w][k];
+    return s;
+}
+// a workgroup maximum (which does not depend on the order); readable by thread 0 after the call
+__device__ inline double block_max(double x, double* smax, bool keep_nan) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double y = __shfl_down(x, o, 64);
+        x = keep_nan ? max_nan(x, y) : fmax(x, y);
+    }
+    __syncthreads();                           // the last reader of smax is done
+    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = x;
+    __syncthreads();
+    double m = smax[0];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = keep_nan ? max_nan(m, smax[w]) : fmax(m, smax[w]);
+    return m;
+}
+
+}  // namespace skimi

@@ -12,10 +12,13 @@
 // accumulates per thread in point order (thread i takes the points i, i + threads, ...), then a fixed shuffle tree per
 // wave, then the waves in order, so every sum depends only on a point's index within its group.  A point's workspace
 // entries are written and read by the same thread only.  All arithmetic is float64.  Rules: DESIGN §2 "Camera + points
-// refinement"; restated in tests/refine_restated.py.  The mask, the residual and the acceptance rule are resect.hip's.
+// refinement"; restated in tests/refine_restated.py.  The projection and `packed` are camera_lm.h's, shared with
+// resect.hip; the workgroup sums are reduce.h's.  The mask, the loss and the acceptance rule are the resection's, written here again.
 #include <math.h>
 
+#include "camera_lm.h"
 #include "common.h"
+#include "reduce.h"
 #include "rodrigues.h"
 
 namespace skimi {
@@ -56,10 +59,8 @@ struct State {
     int evals, success, failed, next, first;
 };
 
-__device__ inline bool is_fin(double x) { return fabs(x) <= 1.79769313486231570815e308; }
-__device__ inline double max_nan(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : fmax(a, b); }
-
-// rule 1: is point i of the group at `base` used?  From the caller's X, which a masked point keeps.
+// rule 1: is point i of the group at `base` used?  From the caller's X, which a masked point keeps.  resect.hip's
+// load_point is the same mask and weight with the loads of one view fused in: a fix here belongs there too.
 __device__ inline bool point_used(const RefineArgs& a, long base, int i) {
     const double* Xg = a.X + 3 * base;
     bool used = is_fin(Xg[3 * i]) && is_fin(Xg[3 * i + 1]) && is_fin(Xg[3 * i + 2]);
@@ -67,8 +68,7 @@ __device__ inline bool point_used(const RefineArgs& a, long base, int i) {
         const double* xg = a.x2d + 2 * (v * a.N + base);
         used = used && is_fin(xg[2 * i]) && is_fin(xg[2 * i + 1]);
         if (a.conf) {
-            double w = (a.conf + (v * a.N + base))[i];
-            w = is_fin(w) ? fmin(fmax(w, 0.0), 1.0) : 0.0;
+            const double w = clamp_conf((a.conf + (v * a.N + base))[i]);
             used = used && w >= a.min_conf;
         }
     }
@@ -80,10 +80,7 @@ __device__ inline void load_obs(const RefineArgs& a, long base, int i, int v, do
     x[0] = xg[2 * i];
     x[1] = xg[2 * i + 1];
     w = 1.0;
-    if (a.conf) {
-        w = (a.conf + (v * a.N + base))[i];
-        w = is_fin(w) ? fmin(fmax(w, 0.0), 1.0) : 0.0;
-    }
+    if (a.conf) w = clamp_conf((a.conf + (v * a.N + base))[i]);
 }
 __device__ inline void load3(const double* p, int i, double* X) {
     X[0] = p[3 * i];
@@ -91,77 +88,22 @@ __device__ inline void load3(const double* p, int i, double* X) {
     X[2] = p[3 * i + 2];
 }
 
-// fixed-order workgroup sums (resect.hip's): `red` alternates between two buffers, so a total stays readable until the
-// next-but-one reduction
-template <int N>
-__device__ inline void block_sum(const double (&v)[N], double (*red)[kRed]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        double x = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-        if (lane == 0) red[wave][k] = x;
-    }
-    __syncthreads();
-}
-__device__ inline double total(const double (*red)[kRed], int k) {
-    const int waves = blockDim.x >> 6;
-    double s = red[0][k];
-    for (int w = 1; w < waves; ++w) s += red[w][k];
-    return s;
-}
-// a workgroup maximum (which does not depend on the order); readable by thread 0 after the call
-__device__ inline double block_max(double x, double* smax, bool keep_nan) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double y = __shfl_down(x, o, 64);
-        x = keep_nan ? max_nan(x, y) : fmax(x, y);
-    }
-    __syncthreads();                           // the last reader of smax is done
-    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = x;
-    __syncthreads();
-    double m = smax[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = keep_nan ? max_nan(m, smax[w]) : fmax(m, smax[w]);
-    return m;
-}
-
-// q = R X, the camera point's depth and ray, and the weighted residual with the principal point folded into the keypoint
-struct Proj {
-    double q[3], z, u, v, pu, r[2];
-};
-__device__ inline void residual(const Cam& s, const double* X, const double* x, double w, Proj& p) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) p.q[k] = s.R[3 * k] * X[0] + s.R[3 * k + 1] * X[1] + s.R[3 * k + 2] * X[2];
-    p.z = p.q[2] + s.t[2];
-    p.u = (p.q[0] + s.t[0]) / p.z;
-    p.v = (p.q[1] + s.t[1]) / p.z;
-    p.pu = s.K[0] * p.u + s.K[1] * p.v;
-    p.r[0] = w * (p.pu + (s.K[2] - x[0]));
-    p.r[1] = w * (s.K[3] * p.v + (s.K[4] - x[1]));
-}
-
-__device__ inline void cross3(const double* a, const double* b, double* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// rule 4's loss of one residual component: rho' and the cost's summand (before the factor 1/2 or 1/2 f^2)
-__device__ inline double rho1_of(const RefineArgs& a, double r, double& summand) {
-    if (a.soft) {
-        const double sq = sqrt(1.0 + (r / a.f_scale) * (r / a.f_scale));
+// rule 4's loss of one residual component: rho' and the cost's summand (before the factor 1/2 or 1/2 f^2).  resect.hip has
+// the same arithmetic inline in its linearisation, and summand_change's in its trial pass: a fix here belongs there too.
+__device__ inline double rho1_of(int soft, double f_scale, double r, double& summand) {
+    if (soft) {
+        const double sq = sqrt(1.0 + (r / f_scale) * (r / f_scale));
         summand = 2.0 * (sq - 1.0);
         return 1.0 / sq;
     }
     summand = r * r;
     return 1.0;
 }
-// rule 7: the change of a component's summand when its residual r changes by dr
-__device__ inline double summand_change(const RefineArgs& a, double r, double dr) {
+// the change of a component's summand when its residual r changes by dr, formed from dr itself
+__device__ inline double summand_change(int soft, double f_scale, double r, double dr) {
     const double e = dr * (2.0 * r + dr);
-    if (!a.soft) return e;
-    const double z0 = (r / a.f_scale) * (r / a.f_scale), dz = e / (a.f_scale * a.f_scale);
+    if (!soft) return e;
+    const double z0 = (r / f_scale) * (r / f_scale), dz = e / (f_scale * f_scale);
     return 2.0 * dz / (sqrt(1.0 + (z0 + dz)) + sqrt(1.0 + z0));
 }
 
@@ -183,8 +125,6 @@ __device__ inline void solve3(const Ldl3& f, const double* b, double* x) {
     x[1] = y1 / f.d1 - f.l21 * x[2];
     x[0] = (y0 / f.d0 - f.l10 * x[1]) - f.l20 * x[2];
 }
-
-__device__ constexpr int packed(int i, int j) { return i <= j ? i * 6 - i * (i - 1) / 2 + (j - i) : j * 6 - j * (j - 1) / 2 + (i - j); }
 
 // One pass of the linearisation of view v over the group's used points.  kPoint: the point blocks (V_i and g_i gain this
 // view's part, W_iv is written), the camera gradient and the cost (7 sums); rows kRow0 .. kRow1 - 1 of the upper
@@ -223,7 +163,7 @@ __device__ inline double linearise_pass(const RefineArgs& a, State& s, long base
         for (int c = 0; c < 2; ++c) {
             cross3(pr.q, Jc[c] + 3, Jc[c]);
             double summand;
-            rho1[c] = rho1_of(a, pr.r[c], summand);
+            rho1[c] = rho1_of(a.soft, a.f_scale, pr.r[c], summand);
             if (kPoint) acc[kG + 6] += summand;
             if (kRow1 > kRow0) {
 #pragma unroll
@@ -253,7 +193,7 @@ __device__ inline double linearise_pass(const RefineArgs& a, State& s, long base
                     for (int k = 0; k < 3; ++k) {
                         const double rp = a.sqrt_lx * (X[k] - X0[k]);
                         double summand;
-                        const double rh = rho1_of(a, rp, summand);
+                        const double rh = rho1_of(a.soft, a.f_scale, rp, summand);
                         acc[kG + 6] += summand;
                         Vp[k == 0 ? 0 : k == 1 ? 3 : 5] = rh * (a.sqrt_lx * a.sqrt_lx);
                         gp[k] = rh * (a.sqrt_lx * rp);
@@ -437,7 +377,7 @@ __device__ inline void trial_pass(const RefineArgs& a, State& s, long base, int 
             double X0[3];
             load3(a.X + 3 * base, i, X0);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) acc[0] += summand_change(a, a.sqrt_lx * (X[k] - X0[k]), a.sqrt_lx * dX[k]);
+            for (int k = 0; k < 3; ++k) acc[0] += summand_change(a.soft, a.f_scale, a.sqrt_lx * (X[k] - X0[k]), a.sqrt_lx * dX[k]);
         }
         for (int v = 0; v < a.V; ++v) {
             const Cam& cam = s.cam[v];
@@ -452,8 +392,8 @@ __device__ inline void trial_pass(const RefineArgs& a, State& s, long base, int 
                 d[k] = ((cam.A * c1[k] + cam.B * c2[k]) + ((cam.R1[3 * k] * dX[0] + cam.R1[3 * k + 1] * dX[1]) + cam.R1[3 * k + 2] * dX[2])) + cam.d[3 + k];
             const double z1 = pr.z + d[2];
             const double du = (d[0] - pr.u * d[2]) / z1, dv = (d[1] - pr.v * d[2]) / z1;
-            acc[0] += summand_change(a, pr.r[0], w * (cam.K[0] * du + cam.K[1] * dv));
-            acc[0] += summand_change(a, pr.r[1], w * (cam.K[3] * dv));
+            acc[0] += summand_change(a.soft, a.f_scale, pr.r[0], w * (cam.K[0] * du + cam.K[1] * dv));
+            acc[0] += summand_change(a.soft, a.f_scale, pr.r[1], w * (cam.K[3] * dv));
         }
     }
     block_sum<3>(acc, red);
@@ -469,7 +409,7 @@ __global__ __launch_bounds__(kThreads) void refine_kernel(RefineArgs a) {
     const long base = g * a.gs;
     const int gs = (int)a.gs;
     const int V = a.V;
-    const double nan = __builtin_nan("");
+    const double nan = qnan();
 
     // ---- X_opt starts as X, bit for bit (an unused point and a failed group keep it); rule 1's count ----
     {

@@ -10,10 +10,14 @@
 // sits and whatever else is in the call.  Thread 0 is the controller between passes (6 x 6 LDL^T, Exp, the accept / stop
 // rules); its state (R, t, H, g, the step) lives in LDS, as do the 12 x 12 DLT matrix and its eigenvectors, whose cyclic
 // Jacobi runs over 12 lanes.  All arithmetic is float64.  Rules: DESIGN §2 "Resection"; restated in
-// tests/resect_restated.py.
+// tests/resect_restated.py.  The projection and `packed` are camera_lm.h's, shared with refine.hip; the workgroup sums are
+// reduce.h's.  The mask (load_point), the soft-L1 loss (inline in both passes) and the final maximum are written here and
+// again in refine.hip: each spot says so.
 #include <math.h>
 
+#include "camera_lm.h"
 #include "common.h"
+#include "reduce.h"
 #include "rodrigues.h"
 
 namespace skimi {
@@ -44,12 +48,11 @@ struct State {
     int evals, success, failed, next, first;
 };
 
-__device__ inline bool is_fin(double x) { return fabs(x) <= 1.79769313486231570815e308; }
-// max that keeps a NaN, as NumPy's max does (fmax drops it)
-__device__ inline double max_nan(double a, double b) { return (a != a || b != b) ? __builtin_nan("") : fmax(a, b); }
-
 // rule 1: point i of the group at `base` with view v's keypoint and weight; false if any view masks it.  The group's
-// bases are uniform and i is a 32-bit index, so the addresses cost no 64-bit vector registers.
+// bases are uniform and i is a 32-bit index, so the addresses cost no 64-bit vector registers.  The same mask and weight
+// as refine.hip's point_used + load_obs, kept as a second copy: built from that pair this kernel's assembly changes, and
+// its bits and time have not been compared against this form (profiles/shared_device_helpers.md).  A fix here belongs
+// there too.
 __device__ inline bool load_point(const ResectArgs& a, long base, int i, int v, double* X, double* x, double& w) {
     const double* Xg = a.X + 3 * base;
     X[0] = Xg[3 * i];
@@ -64,7 +67,7 @@ __device__ inline bool load_point(const ResectArgs& a, long base, int i, int v, 
         double ww = 1.0;
         if (a.conf) {
             ww = (a.conf + (vv * a.N + base))[i];
-            ww = is_fin(ww) ? fmin(fmax(ww, 0.0), 1.0) : 0.0;
+            ww = clamp_conf(ww);
             used = used && ww >= a.min_conf;
         }
         if (vv == v) {
@@ -74,27 +77,6 @@ __device__ inline bool load_point(const ResectArgs& a, long base, int i, int v, 
         }
     }
     return used;
-}
-
-// fixed-order workgroup sums (ba.hip's scheme with a run-time wave count): `red` alternates between two buffers, so a
-// total stays readable until the next-but-one reduction
-template <int N>
-__device__ inline void block_sum(const double (&v)[N], double (*red)[kRed]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        double x = v[k];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-        if (lane == 0) red[wave][k] = x;
-    }
-    __syncthreads();
-}
-__device__ inline double total(const double (*red)[kRed], int k) {
-    const int waves = blockDim.x >> 6;
-    double s = red[0][k];
-    for (int w = 1; w < waves; ++w) s += red[w][k];
-    return s;
 }
 
 // cyclic Jacobi of the symmetric n x n M (LDS, row stride n) to convergence, eigenvectors into the columns of Q; lane k
@@ -138,30 +120,8 @@ __device__ void jacobi_lds(double* M, double* Q, int n) {
     __syncthreads();
 }
 
-// q = R X, the camera point's depth and ray, and the weighted residual with the principal point folded into the keypoint
-struct Proj {
-    double q[3], z, u, v, pu, r[2];
-};
-__device__ inline void residual(const State& s, const double* X, const double* x, double w, Proj& p) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) p.q[k] = s.R[3 * k] * X[0] + s.R[3 * k + 1] * X[1] + s.R[3 * k + 2] * X[2];
-    p.z = p.q[2] + s.t[2];
-    p.u = (p.q[0] + s.t[0]) / p.z;
-    p.v = (p.q[1] + s.t[1]) / p.z;
-    p.pu = s.K[0] * p.u + s.K[1] * p.v;
-    p.r[0] = w * (p.pu + (s.K[2] - x[0]));
-    p.r[1] = w * (s.K[3] * p.v + (s.K[4] - x[1]));
-}
-
-__device__ inline void cross3(const double* a, const double* b, double* c) {
-    c[0] = a[1] * b[2] - a[2] * b[1];
-    c[1] = a[2] * b[0] - a[0] * b[2];
-    c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 // rule 5's solve: x with (H + lam I) x = -g, LDL^T without pivoting; H packed by rows of the upper triangle.  Every loop
 // is unrolled, so the arrays are indexed by constants and stay in registers.
-__device__ constexpr int packed(int i, int j) { return i <= j ? i * 6 - i * (i - 1) / 2 + (j - i) : j * 6 - j * (j - 1) / 2 + (i - j); }
 __device__ inline void ldl_solve(const double* Hp, const double* g, double lam, double* x) {
     double L[6][6], D[6], y[6];
 #pragma unroll
@@ -208,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void resect_kernel(ResectArgs a) {
     const int gs = (int)a.gs;
     const long p = blockIdx.x;                 // problem index of the [G, V] outputs
     double* err = a.err + v * a.N + base;
-    const double nan = __builtin_nan("");
+    const double nan = qnan();
 
     // ---- rule 1: the count, and the sums of rule 2 and of the centroid ----
     double X[3], x[2], w;
@@ -375,6 +335,7 @@ __global__ __launch_bounds__(kThreads) void resect_kernel(ResectArgs a) {
                             }
                             cross3(pr.q, J + 3, J);
                             const double r = pr.r[comp];
+                            // refine.hip's rho1_of, inline (a second copy, kept for the same reason as load_point)
                             double rho1 = 1.0;
                             if (a.soft) {
                                 const double sq = sqrt(1.0 + (r / a.f_scale) * (r / a.f_scale));
@@ -409,6 +370,8 @@ __global__ __launch_bounds__(kThreads) void resect_kernel(ResectArgs a) {
                         const double z1 = pr.z + dZ;
                         const double du = (dX - pr.u * dZ) / z1, dv = (dY - pr.v * dZ) / z1;
                         const double drx = w * (s.K[0] * du + s.K[1] * dv), dry = w * (s.K[3] * dv);
+                        // refine.hip's summand_change for both components, inline (a second copy, as above); the two
+                        // summands are added to each other first, then to acc[0]
                         const double ex = drx * (2.0 * pr.r[0] + drx), ey = dry * (2.0 * pr.r[1] + dry);
                         if (a.soft) {
                             const double zx = (pr.r[0] / a.f_scale) * (pr.r[0] / a.f_scale), zy = (pr.r[1] / a.f_scale) * (pr.r[1] / a.f_scale);
@@ -513,6 +476,7 @@ __global__ __launch_bounds__(kThreads) void resect_kernel(ResectArgs a) {
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) emax = max_nan(emax, __shfl_down(emax, o, 64));
+    // reduce.h's block_max by hand, in red's spare column: block_max needs an LDS array of its own and one more barrier
     __syncthreads();                           // the controller's last reads of red are done
     if ((tid & 63) == 0) red[0][tid >> 6][2] = emax;
     block_sum<2>(acc, red[0]);

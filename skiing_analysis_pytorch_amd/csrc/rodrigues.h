@@ -1,5 +1,5 @@
-// Rodrigues' formula with a Taylor branch at small angles, shared by the bundle adjustment (ba.hip) and the camera
-// resection (resect.hip).  float64, device only.
+// Rodrigues' formula with a Taylor branch at small angles, shared by the bundle adjustment (ba.hip), the camera
+// resection (resect.hip) and the camera-and-points refinement (refine.hip).  float64, device only.
 #pragma once
 #include <math.h>
 

@@ -9,7 +9,7 @@
 //
 // A scene is n = S H W pixels; all B scenes go through every launch (scene = blockIdx.y), a workgroup owns `tile`
 // consecutive pixels of one scene.  Every percentile is an exact selection: a radix select over the order-preserving
-// 32-bit key (person.hip's), four passes of 8 bits, one launch per pass.  A pass histograms in LDS and adds its bins
+// 32-bit key (fp64_util.h's key32), four passes of 8 bits, one launch per pass.  A pass histograms in LDS and adds its bins
 // to the scene's global histogram; the NEXT launch starts by resolving that histogram (every workgroup does it for
 // itself and gets the same digit), so there is no launch between passes.  Both order statistics of a percentile (ranks
 // i and i + 1) and, for the scale, both percentiles of an axis are selected in the same passes: selections of one key
@@ -20,6 +20,8 @@
 #include <math.h>
 
 #include "common.h"
+#include "fp64_util.h"
+#include "reduce.h"
 
 namespace skimi {
 
@@ -49,32 +51,6 @@ struct SceneWs {
 static_assert(sizeof(SceneWs) % 8 == 0, "scenes are laid out back to back");
 
 static inline size_t scene_ws_stride(long n) { return align_up(sizeof(SceneWs) + (size_t)cdiv(n, scene_tile(n)) * 4, 8); }
-
-// monotone map float -> uint32 (person.hip: -0.0 just below +0.0, +-inf ordered)
-__device__ inline unsigned scene_key(float z) {
-    const unsigned u = __float_as_uint(z);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float scene_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
-
-// NumPy's `linear` percentile on m >= 1 sorted values, in float64: v = q / 100 (m - 1), i = floor(v), gamma = v - i
-struct PctPos {
-    unsigned i0, i1;
-    double gamma;
-};
-__device__ inline PctPos pct_pos(double q, unsigned m) {
-    const double v = q / 100.0 * (double)(m - 1);
-    const double fl = floor(v);
-    PctPos p;
-    p.i0 = (unsigned)fl;
-    p.i1 = min(p.i0 + 1u, m - 1u);
-    p.gamma = v - fl;
-    return p;
-}
-__device__ inline double pct_lerp(double lo, double hi, double g) {
-    const double d = hi - lo;
-    return g < 0.5 ? lo + d * g : hi - d * (1.0 - g);
-}
 
 __device__ inline unsigned char colour_u8(float v) {
     const float p = v * 255.0f;
@@ -182,12 +158,6 @@ __device__ inline void sel_flush(const unsigned* h, unsigned* ghist_pass) {
         if (h[i]) atomicAdd(&ghist_pass[i], h[i]);
 }
 
-__device__ inline unsigned wave_sum_u32(unsigned v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
-    return v;
-}
-
 // ---- launch 1: clear the workspace, A = E0^-1 diag(-1, -1, 1, 1) ----
 __global__ __launch_bounds__(kSceneThreads) void scene_init_kernel(const float* __restrict__ extrinsic, int S, char* ws,
                                                                    size_t ws_stride, double* __restrict__ transform) {
@@ -250,11 +220,11 @@ __global__ __launch_bounds__(kSceneThreads) void scene_conf_pass_kernel(const fl
     for (long i = beg + tid; i < end; i += kSceneThreads) {
         const float v = c[i];
         if (P == 0 && v != v) ++n_nan;
-        sel_add<kConfSel>(P, scene_key(v), 0, h, s_prefix, s_leader);
+        sel_add<kConfSel>(P, key32(v), 0, h, s_prefix, s_leader);
     }
     sel_flush<kConfSel>(h, &w->conf_hist[P][0][0]);
     if (P == 0) {
-        n_nan = wave_sum_u32(n_nan);
+        n_nan = wave_sum(n_nan);
         if ((tid & 63) == 0 && n_nan) atomicAdd(&w->n_nan_conf, n_nan);
     }
 }
@@ -274,8 +244,8 @@ __global__ __launch_bounds__(kSceneThreads) void scene_mask_kernel(const float* 
     unsigned* block_count = reinterpret_cast<unsigned*>(w + 1);
     sel_begin<kConfSel, kConfSel>(4, &w->conf_hist[0][0][0], &w->conf_state[0][0][0], g == 0, h, s_prefix, s_rank, s_leader);
     if (tid == 0) {
-        const double nan = __longlong_as_double(0x7FF8000000000000LL);
-        double lo = (double)scene_unkey(s_prefix[0]), hi = (double)scene_unkey(s_prefix[1]);
+        const double nan = qnan();
+        double lo = (double)unkey32(s_prefix[0]), hi = (double)unkey32(s_prefix[1]);
         double thr = pct_lerp(lo, hi, pct_pos(q, (unsigned)n).gamma);
         if (w->n_nan_conf) thr = lo = hi = nan;   // np.percentile of an array with a NaN
         if (q == 0.0) thr = 0.0;                  // conf_thres == 0: no percentile is taken
@@ -309,14 +279,14 @@ __global__ __launch_bounds__(kSceneThreads) void scene_mask_kernel(const float* 
             const float v = pts[i * 3 + a];
             finite = finite && isfinite(v);
             if (v != v) ++cnt[2 + a];
-            sel_add<kXyzGroup>(0, scene_key(v), a * kXyzGroup, h, s_prefix, s_leader);
+            sel_add<kXyzGroup>(0, key32(v), a * kXyzGroup, h, s_prefix, s_leader);
         }
         if (!finite) ++cnt[1];
     }
     sel_flush<kXyzSel>(h, &w->xyz_hist[0][0][0]);
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
-        const unsigned v = wave_sum_u32(cnt[k]);
+        const unsigned v = wave_sum(cnt[k]);
         if ((tid & 63) == 0 && v) atomicAdd(&s_cnt[k], v);
     }
     __syncthreads();
@@ -358,8 +328,8 @@ __global__ __launch_bounds__(kSceneThreads) void scene_xyz_pass_kernel(const flo
             tot += v;
             if (i < g) off += v;
         }
-        tot = wave_sum_u32(tot);
-        off = wave_sum_u32(off);
+        tot = wave_sum(tot);
+        off = wave_sum(off);
         if (lane == 0) {
             atomicAdd(&s_total, tot);
             atomicAdd(&s_offset, off);
@@ -395,7 +365,7 @@ __global__ __launch_bounds__(kSceneThreads) void scene_xyz_pass_kernel(const flo
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
                 v[a] = pts[i * 3 + a];
-                sel_add<kXyzGroup>(P, scene_key(v[a]), a * kXyzGroup, h, s_prefix, s_leader);
+                sel_add<kXyzGroup>(P, key32(v[a]), a * kXyzGroup, h, s_prefix, s_leader);
             }
         }
         if (P == 1) {
@@ -448,7 +418,7 @@ __global__ __launch_bounds__(kSceneThreads) void scene_finish_kernel(char* ws, s
     SceneWs* w = reinterpret_cast<SceneWs*>(ws + b * ws_stride);
     sel_begin<kXyzSel, kXyzGroup>(4, &w->xyz_hist[0][0][0], &w->xyz_state[0][0][0], true, h, s_prefix, s_rank, s_leader);
     if (threadIdx.x != 0) return;
-    const double nan = __longlong_as_double(0x7FF8000000000000LL);
+    const double nan = qnan();
     const unsigned count = w->count;
     double* out = stats + b * 16;
     out[0] = w->thr[0];
@@ -461,8 +431,8 @@ __global__ __launch_bounds__(kSceneThreads) void scene_finish_kernel(char* ws, s
         double lower = nan, upper = nan;
         if (count > 0 && w->n_nan_axis[a] == 0) {
             const unsigned* p = s_prefix + a * kXyzGroup;
-            lower = pct_lerp((double)scene_unkey(p[0]), (double)scene_unkey(p[1]), pct_pos(5.0, count).gamma);
-            upper = pct_lerp((double)scene_unkey(p[2]), (double)scene_unkey(p[3]), pct_pos(95.0, count).gamma);
+            lower = pct_lerp((double)unkey32(p[0]), (double)unkey32(p[1]), pct_pos(5.0, count).gamma);
+            upper = pct_lerp((double)unkey32(p[2]), (double)unkey32(p[3]), pct_pos(95.0, count).gamma);
         }
         out[5 + a] = lower;
         out[8 + a] = upper;

@@ -2,11 +2,11 @@
 #pragma once
 #include <math.h>
 
+#include "fp64_util.h"
+
 namespace skimi {
 
 constexpr int kSvd3Sweeps = 40;
-
-__device__ inline double svd3_norm(double a, double b, double c) { return sqrt(a * a + b * b + c * c); }
 
 // A (row-major 3 x 3) = U S V^T by one-sided Jacobi on the columns -> Q = u1 v1^T + u2 v2^T + (u1 x u2)(v1 x v2)^T over the
 // two largest singular values, and ssum = the sum of the three.  Q is the polar factor U V^T with the singular vector of
@@ -50,7 +50,7 @@ __device__ inline void polar3_signed(const double* A, double* Q, double& ssum, d
     }
     double sg[3];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) sg[c] = svd3_norm(a[c][0], a[c][1], a[c][2]);
+    for (int c = 0; c < 3; ++c) sg[c] = norm3(a[c][0], a[c][1], a[c][2]);
     ssum = sg[0] + sg[1] + sg[2];
     const int k = (sg[0] <= sg[1] && sg[0] <= sg[2]) ? 0 : (sg[1] <= sg[2] ? 1 : 2);      // the smallest
     double u1[3], u2[3], v1[3], v2[3];

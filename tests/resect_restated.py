@@ -107,7 +107,7 @@ def dlt_init(K, X, x):
 
 # ---- rules 4 and 5 ----------------------------------------------------------------------------------------------------
 def exp_so3(w):
-    """ba.hip's Rodrigues with the Taylor branch"""
+    """rodrigues.h's Rodrigues with the Taylor branch"""
     A, B = exp_coefficients(w)
     Kx = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
     return np.eye(3) + A * Kx + B * (Kx @ Kx)
@@ -154,7 +154,7 @@ def normal_equations(K, R, t, X, x, w, loss, f_scale):
 
 
 def exp_coefficients(w):
-    """A = sin(th)/th, B = (1 - cos(th))/th^2 of ba.hip's Rodrigues, with its Taylor branch"""
+    """A = sin(th)/th, B = (1 - cos(th))/th^2 of rodrigues.h's Rodrigues, with its Taylor branch"""
     s = w[0] * w[0] + w[1] * w[1] + w[2] * w[2]
     if s < SMALL_ANGLE2:
         return 1.0 - s / 6.0 + s * s / 120.0, 0.5 - s / 24.0 + s * s / 720.0
