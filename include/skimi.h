@@ -1005,6 +1005,51 @@ int skimi_clip_quality(const double* X, const int32_t* lengths, int64_t clips, i
                        const int32_t* lr_pairs, int32_t n_pairs, void* workspace, size_t workspace_bytes, double* scalars,
                        double* bone_cv_edge, double* bone_len, void* stream);
 
+/* ---- lens distortion: OpenCV's rational + tangential + thin-prism model on points and frames (csrc/lens.hip) ----
+ * Everything is float64 on the device, one launch per call, bitwise reproducible (no data-dependent exit, no atomics).
+ * Rules (DESIGN §2 "Lens distortion"; tests/lens_restated.py evaluates the same expressions in the same order):
+ *  1. Parameters are HOST arrays, one set per camera, 1 <= C <= SKIMI_LENS_MAX_CAMERAS, and reach the kernel by value.
+ *     K, P, new_K [C, 3, 3] are read as fx = [0][0], fy = [1][1], cx = [0][2], cy = [1][2]; the other entries are not part of
+ *     the model.  dist [C, 12] = k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 (shorter OpenCV vectors zero-padded by the caller; the
+ *     tilt terms are not supported); NULL: all zero.  A zero or non-finite focal length, a non-finite principal point or
+ *     coefficient: SKIMI_ERR_ARG.
+ *  2. The model on normalised (x, y): r2 = x x + y y, c = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3),
+ *     x_d = x c + 2 p1 x y + p2 (r2 + 2 x x) + s1 r2 + s2 r2^2, y_d = y c + p1 (r2 + 2 y y) + 2 p2 x y + s3 r2 + s4 r2^2.
+ *  3. Points are [outer, C, n, 2] (dev): camera c owns the rows (o, c, .) of every o; outer = 1 is the plain [C, n, 2].
+ *     outer * n <= 2^31; an empty call launches nothing.  K_steps (dev, or NULL) [outer, C, 3, 3]: the K of every
+ *     (o, c), read from memory in place of the by-value K, with P = K (P must then be NULL and K may be).
+ *  4. skimi_distort_points: undistorted points -> distorted pixels of K.  The input is pixels of P (NULL: K), or normalised
+ *     coordinates when normalized != 0.
+ *  5. skimi_undistort_points: distorted pixels of K -> undistorted points, as pixels of P (NULL: K) or, normalized != 0, as
+ *     normalised coordinates.  OpenCV's fixed-point iteration from the distorted point: each of exactly `iters` rounds
+ *     (0 .. SKIMI_LENS_MAX_ITERS; cv2.undistortPoints runs 5) subtracts the tangential and prism terms and multiplies by 1 / c.
+ *     resid_px [outer, C, n] = the distance, in pixels of K, between the input and the re-distorted result: large where the
+ *     iteration did not converge or the point lies outside the model's invertible range.  A non-finite result or residual
+ *     (a NaN keypoint included) makes the point's two coordinates and its residual NaN; no other row is affected.
+ *  6. skimi_project_points = cv2.projectPoints with rotation matrices: X [outer, C, n, 3] (dev), R [C, 3, 3], t [C, 3] (host)
+ *     -> Xc = R X + t, (x, y) = (Xc_x, Xc_y) / Xc_z, rule 2, px [outer, C, n, 2] = pixels of K, depth [outer, C, n] = Xc_z.
+ *     Points at or behind the camera are projected as the formula says (inf / NaN at Xc_z = 0), as cv2 does.
+ *  7. skimi_undistort_u8 = cv2.undistort with a constant (0) border: in [C, F, H, W, ch] u8 -> out [C, F, OH, OW, ch] u8 (dev),
+ *     ch 1, 3 or 4, sides 1 .. SKIMI_LENS_MAX_SIDE, C * F <= 65535.  Output pixel (u, v) -> x = (u - cx') / fx', y = (v - cy') /
+ *     fy' through new_K (NULL: K) -> rule 2 -> (su, sv) = (fx x_d + cx, fy y_d + cy), computed on the fly (no stored map).
+ *     Unless -1 < su < W and -1 < sv < H (a NaN fails) the pixel is 0.  Else x0 = floor(su), y0 = floor(sv), a = su - x0,
+ *     b = sv - y0, taps outside the source count 0, value = (1 - b) ((1 - a) p00 + a p01) + b ((1 - a) p10 + a p11) in that
+ *     order, out = floor(value + 0.5).  cv2.remap quantises (su, sv) to 1/32 px and uses integer weights: its grey levels
+ *     may differ from these by a small amount; this rule is the contract.  The input is only read; nothing beyond the
+ *     C F OH OW ch output bytes is written (dword stores when OW * ch % 4 == 0 and out is 4-byte aligned, else bytes). */
+#define SKIMI_LENS_MAX_CAMERAS 8
+#define SKIMI_LENS_MAX_ITERS 1000
+#define SKIMI_LENS_MAX_SIDE 32768
+int skimi_distort_points(const double* x, const double* K, const double* dist, const double* P, const double* K_steps,
+                         int64_t outer, int32_t C, int64_t n, int32_t normalized, double* out, void* stream);
+int skimi_undistort_points(const double* x, const double* K, const double* dist, const double* P, const double* K_steps,
+                           int64_t outer, int32_t C, int64_t n, int32_t iters, int32_t normalized, double* out, double* resid_px,
+                           void* stream);
+int skimi_project_points(const double* X, const double* R, const double* t, const double* K, const double* dist, int64_t outer,
+                         int32_t C, int64_t n, double* px, double* depth, void* stream);
+int skimi_undistort_u8(const uint8_t* in, uint8_t* out, const double* K, const double* dist, const double* new_K, int32_t C,
+                       int32_t F, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t ch, void* stream);
+
 /* ---- VGGT head and track-head helper kernels, one launch each ----
  * The kernels skimi_vggt_forward runs between its GEMMs, exposed singly so that each can be tested against a float64
  * restatement.  All maps are channels-last and dense; dtype / out_dtype are SKIMI_F32, SKIMI_BF16 or SKIMI_F16.  Every

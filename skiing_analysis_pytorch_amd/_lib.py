@@ -162,6 +162,12 @@ _SIGNATURES = {
     "skimi_clip_quality": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32),
                                      C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_int32), C.c_int32, _vp, C.c_size_t, _vp,
                                      _vp, _vp, _vp]),
+    "skimi_distort_points": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, _vp, _vp]),
+    "skimi_undistort_points": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _vp, _vp,
+                                         _vp]),
+    "skimi_project_points": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int64, _vp, _vp, _vp]),
+    "skimi_undistort_u8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, _vp]),
     "skimi_resize_bilinear": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_float, _vp]),
     "skimi_resize_bilinear_planes": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
     "skimi_add_uv_pos": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),

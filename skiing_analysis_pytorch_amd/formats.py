@@ -14,6 +14,7 @@ VGGT stage (vggt/save.py:84-110, `infer.save_camera_info`) and the per-step scen
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from pathlib import Path
 from typing import Optional, Tuple
 
@@ -269,3 +270,81 @@ def read_glb_points(path) -> Tuple[np.ndarray, np.ndarray]:
     xyz = view(prim["attributes"]["POSITION"], "<f4", (3,)).astype(np.float32)
     rgb = view(prim["attributes"]["COLOR_0"], "u1", (3, 4))[:, :3].copy()
     return xyz, rgb
+
+
+# ---- camera calibration files (camera_calibration/calibration_parameters.{npz,yml}) ---------------------------------------
+@dataclass(frozen=True)
+class Calibration:
+    """One camera's calibration as camera_calibration writes it."""
+    K: np.ndarray               # float64 [3, 3]
+    dist: np.ndarray            # float64 [14]: k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 tx ty (OpenCV's order), zero-padded
+    image_size: Tuple[int, int]  # (width, height) of the frames it was solved on
+
+    def scaled_to(self, width: int, height: int) -> "Calibration":
+        """The same lens on frames of another size with the same aspect ratio: fx, cx scale with the width, fy, cy with the
+        height; the coefficients act on normalised coordinates and stay as they are.  Another aspect ratio means a crop or an
+        anamorphic resize that the file does not describe, and is refused."""
+        w0, h0 = self.image_size
+        width, height = int(width), int(height)
+        if width < 1 or height < 1 or width * h0 != height * w0:
+            raise ValueError(f"calibration of {w0} x {h0} frames cannot be rescaled to {width} x {height}: another aspect ratio")
+        K = self.K.copy()
+        K[0, 0] *= width / w0
+        K[0, 2] *= width / w0
+        K[1, 1] *= height / h0
+        K[1, 2] *= height / h0
+        return Calibration(K, self.dist.copy(), (width, height))
+
+
+def _opencv_yaml(text: str) -> dict:
+    """The subset of OpenCV's FileStorage YAML that calibration files use: `key: scalar` lines and `key: !!opencv-matrix`
+    nodes (rows, cols, dt, data: [ ... ] over several lines), after the `%YAML:1.0` header.  Parsed by hand: the header is
+    not valid YAML 1.1, and the package does not depend on a YAML library."""
+    import re
+
+    if not text.lstrip().startswith("%YAML"):
+        raise ValueError("not an OpenCV YAML file (no %YAML header)")
+    out = {}
+    for m in re.finditer(r"^(\w+):[ \t]*!!opencv-matrix\s*\n((?:[ \t]+.*\n?)+)", text, flags=re.M):
+        body = m.group(2)
+        rows, cols = (int(re.search(rf"^\s+{k}:\s*(\d+)", body, flags=re.M).group(1)) for k in ("rows", "cols"))
+        dt = re.search(r"^\s+dt:\s*\"?(\w+)\"?", body, flags=re.M).group(1)
+        data = re.search(r"data:\s*\[(.*?)\]", body, flags=re.S)
+        if dt not in ("d", "f", "i") or data is None:
+            raise ValueError(f"opencv-matrix {m.group(1)}: unsupported dt {dt!r} or no data")
+        vals = [float(v) for v in data.group(1).replace("\n", " ").split(",") if v.strip()]
+        if len(vals) != rows * cols:
+            raise ValueError(f"opencv-matrix {m.group(1)}: {len(vals)} values for {rows} x {cols}")
+        out[m.group(1)] = np.array(vals, np.float64).reshape(rows, cols)
+    for m in re.finditer(r"^(\w+):[ \t]*([-+0-9.eE]+)[ \t]*$", text, flags=re.M):
+        out.setdefault(m.group(1), float(m.group(2)))
+    return out
+
+
+def load_calibration(path) -> Calibration:
+    """calibration_parameters.npz (keys camera_matrix, dist_coeffs, image_size; the file's pickled object arrays are never
+    touched: allow_pickle stays False) or calibration_parameters.yml (OpenCV FileStorage: image_width, image_height,
+    camera_matrix, distortion_coefficients) -> Calibration.  4, 5, 8, 12 or 14 coefficients, zero-padded to 14."""
+    path = Path(path)
+    if path.suffix.lower() == ".npz":
+        with np.load(str(path), allow_pickle=False) as z:
+            missing = [k for k in ("camera_matrix", "dist_coeffs", "image_size") if k not in z.files]
+            if missing:
+                raise ValueError(f"{path}: no {missing[0]} entry")
+            K, d, size = z["camera_matrix"], z["dist_coeffs"], z["image_size"]
+    elif path.suffix.lower() in (".yml", ".yaml"):
+        y = _opencv_yaml(path.read_text())
+        try:
+            K, d, size = y["camera_matrix"], y["distortion_coefficients"], (y["image_width"], y["image_height"])
+        except KeyError as e:
+            raise ValueError(f"{path}: no {e.args[0]} entry") from None
+    else:
+        raise ValueError(f"{path}: a calibration file is .npz or OpenCV .yml")
+    K = np.array(K, dtype=np.float64)
+    d = np.array(d, dtype=np.float64).reshape(-1)
+    size = np.asarray(size).reshape(-1)
+    if K.shape != (3, 3) or d.size not in (4, 5, 8, 12, 14) or size.size != 2:
+        raise ValueError(f"{path}: camera_matrix {list(K.shape)}, {d.size} coefficients, image_size of {size.size} numbers")
+    dist = np.zeros(14, np.float64)
+    dist[:d.size] = d
+    return Calibration(K, dist, (int(size[0]), int(size[1])))

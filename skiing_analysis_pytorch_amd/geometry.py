@@ -3,7 +3,8 @@ skimi_triangulate_dlt, skimi_triangulate_triage, skimi_triangulate_robust, the p
 and the point-to-plane ICP: skimi_estimate_normals, skimi_icp_correspondences,
 skimi_icp_point_to_plane; the bundle adjustment: skimi_bundle_adjust; the camera resection: skimi_resect_cameras, the camera-and-points refinement: skimi_refine_cameras_points,
 skimi_relative_pose; the essential matrix: skimi_essential_ransac, skimi_five_point; the fusion and smoothing of a clip:
-skimi_fuse_h36m, skimi_fuse_views, skimi_smooth_ema, skimi_smooth_savgol; the kinematic analysis of clips: skimi_kinematics)
+skimi_fuse_h36m, skimi_fuse_views, skimi_smooth_ema, skimi_smooth_savgol; the kinematic analysis of clips: skimi_kinematics;
+the lens model on points: skimi_distort_points, skimi_undistort_points, skimi_project_points)
 plus the small host helpers of the reference's VGGT wrapper.
 
 Reference: vggt/vggt/utils/pose_enc.py:62-124, rotation.py:14-44, geometry.py:15-117,
@@ -11,7 +12,8 @@ vggt/triangulate.py:13-71, vggt/reproject.py:108-144 + triangulation/postprocess
 vggt/multi_view_process.py:195-217 + :356-395 (person origin), vggt/vggt/infer.py:107-155, vggt/multi_view_process.py:427-520 (ICP),
 :523-564 + bundle_adjustment/loss.py (bundle adjustment), VideoPose3D/slove_rt_from_3d.py (resection),
 VideoPose3D/fuse/fuse.py, fuse/main_raw.py:194-250, fuse/fuse.py:289-412 (fusion and smoothing; host form: fuse.py),
-angle/main.py (kinematics; entry points: angle.py).
+angle/main.py (kinematics; entry points: angle.py), camera_calibration/calibration_parameters.* + triangulation/postprocess.py:89-97
+(lens distortion, from OpenCV's documented model).
 """
 from __future__ import annotations
 
@@ -114,12 +116,15 @@ def triage_launch(K, R, t, kp, conf, conf_thr, err_thresh_px):
 
 
 def triangulate_triage(K: torch.Tensor, R: torch.Tensor, t: torch.Tensor, keypoints: torch.Tensor, conf=None,
-                       conf_thr: float = 0.3, err_thresh_px: float = 2.0) -> TriageResult:
+                       conf_thr: float = 0.3, err_thresh_px: float = 2.0, dist=None) -> TriageResult:
     """triangulate_joints with a verdict, in one launch: K, R [T, V, 3, 3], t [T, V, 3], keypoints [T, V, J, 2] (pixels),
     conf [T, V, J] detector scores or None -> TriageResult (unpacks as X, X_clean, err, depth, keep, view_stats, report).
     Every view is projected through its own (K, R, t): err = ||K (R X + t) / depth - keypoint||, em = mean over the views;
     a joint is kept iff every depth > 0, em is finite and <= err_thresh_px, and every score >= conf_thr
-    (post_triage_single, triangulation/postprocess.py:70-121, from two views to V).  2 <= V <= 8, 1 <= J <= 32."""
+    (post_triage_single, triangulation/postprocess.py:70-121, from two views to V).  2 <= V <= 8, 1 <= J <= 32.
+    dist: None, or the lens coefficients of the views ([k] or [V, k], host; lens_coeffs): the keypoints are first undistorted
+    with their view's K, undistortPoints(x, K, d, P=K) as post_triage_single's dist1 / dist2 (one more launch in front;
+    the triage kernel is the same).  None or all-zero coefficients: exactly the call without dist."""
     for a in (K, R, t, keypoints) + (() if conf is None else (conf,)):
         if not a.is_cuda:
             raise _lib.SkimiError("triangulate_triage needs device tensors")
@@ -127,6 +132,7 @@ def triangulate_triage(K: torch.Tensor, R: torch.Tensor, t: torch.Tensor, keypoi
     kp = keypoints.contiguous().to(torch.float32)
     if conf is not None:
         conf = conf.contiguous().to(torch.float32)
+    kp = _undistorted_f32(kp, K, dist)
     X, Xc, err, depth, keep, vs, rep = triage_launch(K, R, t, kp, conf, conf_thr, err_thresh_px)
     return TriageResult(X, Xc, err, depth, keep.bool(), vs, rep)
 
@@ -189,7 +195,7 @@ def robust_launch(K, R, t, kp, conf, conf_thr, inlier_px, min_inliers, refine_it
 
 def triangulate_robust(K: torch.Tensor, R: torch.Tensor, t: torch.Tensor, keypoints: torch.Tensor, conf=None,
                        conf_thr: float = 0.3, inlier_px: float = 2.0, min_inliers: int = 2, refine_iters: int = 5,
-                       weighted: bool = False) -> RobustResult:
+                       weighted: bool = False, dist=None) -> RobustResult:
     """Outlier-robust triangulation in one launch: K, R [T, V, 3, 3], t [T, V, 3], keypoints [T, V, J, 2] (pixels), conf
     [T, V, J] detector scores or None -> RobustResult.  Per joint: every pair of eligible views (finite keypoint, score >=
     conf_thr) gives a two-view DLT hypothesis; the one with the most views within inlier_px (then the smaller truncated
@@ -197,7 +203,9 @@ def triangulate_robust(K: torch.Tensor, R: torch.Tensor, t: torch.Tensor, keypoi
     the reprojection error of that set.  weighted=True weights refit and refinement by the scores clipped to [0, 1].  A
     joint with fewer than two agreeing views fails (NaN); `ok` also asks for min_inliers views in the final set.  With
     every view an inlier, refine_iters=0 and no weighting the result is triangulate_joints'.  Rules: DESIGN §2 "Robust
-    triangulation".  2 <= V <= 8, 1 <= J <= 32, 2 <= min_inliers <= V, 0 <= refine_iters <= 32."""
+    triangulation".  2 <= V <= 8, 1 <= J <= 32, 2 <= min_inliers <= V, 0 <= refine_iters <= 32.  dist: None, or the views'
+    lens coefficients ([k] or [V, k], host): the keypoints are first undistorted with their view's K, as in
+    triangulate_triage; None or all-zero coefficients: exactly the call without dist."""
     for a in (K, R, t, keypoints) + (() if conf is None else (conf,)):
         if not a.is_cuda:
             raise _lib.SkimiError("triangulate_robust needs device tensors")
@@ -205,6 +213,7 @@ def triangulate_robust(K: torch.Tensor, R: torch.Tensor, t: torch.Tensor, keypoi
     kp = keypoints.contiguous().to(torch.float32)
     if conf is not None:
         conf = conf.contiguous().to(torch.float32)
+    kp = _undistorted_f32(kp, K, dist)
     X, err, inl, rms, ok, Xok, ratio, rep = robust_launch(K, R, t, kp, conf, conf_thr, inlier_px, min_inliers, refine_iters,
                                                           weighted)
     return RobustResult(X, err, inl, rms, ok.bool(), Xok, ratio, rep)
@@ -1153,6 +1162,188 @@ def clip_quality(X: torch.Tensor, lengths=None, edges=H36M_EDGES, left_edges=H36
     check(lib().skimi_clip_quality(ptr(X), ptr(len_t), B, T, J, e_c, E, l_c, EL, r_c, ER, p_c, NP, ptr(ws), ws_bytes, ptr(scalars),
                                    ptr(cv_edge), ptr(bone_len), _lib.current_stream()), "skimi_clip_quality")
     return ClipQualityResult(*(scalars[:, k] for k in range(8)), cv_edge, bone_len, scalars)
+
+
+# ---- lens distortion of points (csrc/lens.hip; rules: include/skimi.h, DESIGN §2 "Lens distortion") -----------------------
+# OpenCV's rational + tangential + thin-prism model.  Calibrations are small HOST arrays (NumPy, lists or CPU tensors; a
+# device tensor is copied back): they reach the kernels by value.  Batch rule of the three point functions: K [3, 3] is
+# one camera for every point of x [..., 2]; K [C, 3, 3] is one camera per entry of the axis before the points' own,
+# x [..., C, n, 2], and everything in front of that axis is batch (keypoints [T, V, J, 2] with a calibration per view:
+# one launch).  dist is [k] (shared) or [C, k], k in LENS_COEFF_COUNTS.
+LENS_MAX_CAMERAS, LENS_MAX_ITERS = 8, 1000
+LENS_COEFF_COUNTS = (4, 5, 8, 12, 14)
+
+
+class UndistortResult(NamedTuple):
+    """undistort_points' outputs (float64 device tensors unless the call was the identity)."""
+    x: torch.Tensor          # [..., 2]: undistorted points, pixels of P (default K) or normalised coordinates
+    resid_px: torch.Tensor   # [...]: pixel distance between the input and the re-distorted result; NaN with a NaN point
+
+
+class ProjectResult(NamedTuple):
+    """project_points' outputs (float64 device tensors)."""
+    x: torch.Tensor          # [..., 2]: pixels of K
+    depth: torch.Tensor      # [...]: z in the camera frame
+
+
+def _host_f64(a) -> np.ndarray:
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+
+
+def lens_coeffs(dist) -> np.ndarray:
+    """OpenCV coefficient vectors [..., k], k = 4, 5, 8, 12 or 14 in cv2's order (k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 tx ty) ->
+    float64 [..., 12], zero-padded.  None: twelve zeros.  Non-zero tx / ty (the tilt model) is refused."""
+    if dist is None:
+        return np.zeros(12, np.float64)
+    d = _host_f64(dist)
+    if d.ndim == 2 and d.shape[0] == 1 and d.shape[1] in LENS_COEFF_COUNTS:
+        d = d[0]                     # cv2 hands its vectors out as [1, k]
+    if d.ndim < 1 or d.shape[-1] not in LENS_COEFF_COUNTS:
+        raise ValueError(f"distortion coefficients must come as 4, 5, 8, 12 or 14 numbers, got shape {list(d.shape)}")
+    if d.shape[-1] == 14:
+        if np.any(d[..., 12:] != 0):
+            raise ValueError("the tilt model (non-zero tx, ty) is not supported")
+        d = d[..., :12]
+    if not np.isfinite(d).all():
+        raise ValueError("distortion coefficients must be finite")
+    out = np.zeros(d.shape[:-1] + (12,), np.float64)
+    out[..., :d.shape[-1]] = d
+    return out
+
+
+def _lens_matrix(name, what, M, C):
+    """[3, 3] or [C, 3, 3] host matrix -> float64 [C or 1, 3, 3]; only fx, fy, cx, cy are part of the model"""
+    M = _host_f64(M)
+    if M.shape[-2:] != (3, 3) or M.ndim not in (2, 3):
+        raise ValueError(f"{name}: {what} must be [3, 3] or [C, 3, 3], got {list(M.shape)}")
+    M = M.reshape(-1, 3, 3)
+    if C is not None and M.shape[0] != C:
+        if M.shape[0] != 1:
+            raise ValueError(f"{name}: {what} holds {M.shape[0]} cameras, K holds {C}")
+        M = np.ascontiguousarray(np.broadcast_to(M, (C, 3, 3)))
+    if not (np.isfinite(M[:, [0, 1, 0, 1], [0, 1, 2, 2]]).all() and (M[:, 0, 0] != 0).all() and (M[:, 1, 1] != 0).all()):
+        raise ValueError(f"{name}: {what} needs finite, non-zero focal lengths and a finite principal point")
+    return M
+
+
+def _lens_setup(name, x, K, dist, last):
+    """-> (K [C, 3, 3], dist [C, 12], per_camera, outer, C, n) for points x [..., last] under the batch rule above"""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise _lib.SkimiError(f"{name} needs a device tensor of points")
+    if x.dim() < 1 or x.shape[-1] != last:
+        raise ValueError(f"{name}: points must be [..., {last}], got {list(x.shape)}")
+    per_camera = _host_f64(K).ndim == 3
+    Kh = _lens_matrix(name, "K", K, None)
+    C = Kh.shape[0]
+    if C > LENS_MAX_CAMERAS:
+        raise ValueError(f"{name}: at most {LENS_MAX_CAMERAS} cameras a call, got {C}")
+    d = lens_coeffs(dist)
+    if d.ndim > 2 or (d.ndim == 2 and d.shape[0] not in (1, C)):
+        raise ValueError(f"{name}: dist must be [k] or [{C}, k], got {list(d.shape)}")
+    d = np.ascontiguousarray(np.broadcast_to(d.reshape(-1, 12), (C, 12)))
+    if per_camera:
+        if x.dim() < 3 or x.shape[-3] != C:
+            raise ValueError(f"{name}: K holds {C} cameras, so points must be [..., {C}, n, {last}], got {list(x.shape)}")
+        outer, n = int(np.prod(x.shape[:-3], dtype=np.int64)), int(x.shape[-2])
+    else:
+        outer, n = 1, int(np.prod(x.shape[:-1], dtype=np.int64))
+    return Kh, d, per_camera, outer, C, n
+
+
+def _hp(a):
+    return None if a is None else a.ctypes.data
+
+
+def distort_points(x: torch.Tensor, K, dist, P=None, normalized: bool = False) -> torch.Tensor:
+    """Undistorted points -> where the real lens images them, in one launch: x [..., 2] device tensor, as pixels of P
+    (default K) or, normalized=True, as normalised coordinates -> float64 pixels of K.  The exact inverse direction of
+    undistort_points with the same arguments.  All-zero coefficients with P equal to K and pixels in: the input object is
+    returned unchanged."""
+    Kh, d, _pc, outer, C, n = _lens_setup("distort_points", x, K, dist, 2)
+    Ph = None if P is None else _lens_matrix("distort_points", "P", P, C)
+    if not normalized and not d.any() and (Ph is None or np.array_equal(Ph, Kh)):
+        return x
+    xi = x.contiguous().to(torch.float64)
+    out = torch.empty_like(xi)
+    check(lib().skimi_distort_points(ptr(xi), _hp(Kh), _hp(d), _hp(Ph), None, outer, C, n, 1 if normalized else 0, ptr(out),
+                                     _lib.current_stream()), "skimi_distort_points")
+    return out
+
+
+def undistort_points(x: torch.Tensor, K, dist, P=None, iters: int = 20, normalized: bool = False) -> UndistortResult:
+    """cv2.undistortPoints(x, K, dist, P=P) in one launch: distorted pixels x [..., 2] (device) of K -> UndistortResult(x,
+    resid_px), the points as pixels of P (default K) or, normalized=True, as normalised coordinates (cv2's result without
+    P).  OpenCV's fixed-point iteration with exactly `iters` rounds (cv2 runs 5; no early exit: bitwise reproducible).
+    resid_px is the pixel distance between the input and the re-distorted result: it exposes a point that did not converge
+    or lies beyond the model's invertible range.  A NaN keypoint gives NaN in its own row only.  All-zero coefficients
+    with P equal to K and pixels out: the input object is returned unchanged, with a zero residual."""
+    Kh, d, _pc, outer, C, n = _lens_setup("undistort_points", x, K, dist, 2)
+    Ph = None if P is None else _lens_matrix("undistort_points", "P", P, C)
+    iters = int(iters)
+    if not 0 <= iters <= LENS_MAX_ITERS:
+        raise ValueError(f"undistort_points: iters must be in 0..{LENS_MAX_ITERS}, got {iters}")
+    if not normalized and not d.any() and (Ph is None or np.array_equal(Ph, Kh)):
+        return UndistortResult(x, torch.zeros(x.shape[:-1], dtype=torch.float64, device=x.device))
+    xi = x.contiguous().to(torch.float64)
+    out = torch.empty_like(xi)
+    resid = torch.empty(xi.shape[:-1], dtype=torch.float64, device=xi.device)
+    check(lib().skimi_undistort_points(ptr(xi), _hp(Kh), _hp(d), _hp(Ph), None, outer, C, n, iters, 1 if normalized else 0,
+                                       ptr(out), ptr(resid), _lib.current_stream()), "skimi_undistort_points")
+    return UndistortResult(out, resid)
+
+
+def undistort_keypoints_steps(keypoints: torch.Tensor, K: torch.Tensor, dist, iters: int = 20) -> UndistortResult:
+    """post_triage_single's rule, undistortPoints(x, K, d, P=K), for keypoints [T, V, J, 2] whose K [T, V, 3, 3] is a DEVICE
+    tensor with one matrix per step and view (the model's own intrinsics): the kernel reads K from memory, the per-view
+    coefficients dist ([k] or [V, k]) travel by value.  One launch; float64 out."""
+    if keypoints.dim() != 4 or keypoints.shape[-1] != 2 or tuple(K.shape) != tuple(keypoints.shape[:2]) + (3, 3):
+        raise ValueError(f"undistort_keypoints_steps: need keypoints [T, V, J, 2] and K [T, V, 3, 3], got {list(keypoints.shape)}, "
+                         f"{list(K.shape)}")
+    if not keypoints.is_cuda or K.device != keypoints.device:
+        raise _lib.SkimiError("undistort_keypoints_steps needs keypoints and K on one device")
+    T, V, J, _ = keypoints.shape
+    if V > LENS_MAX_CAMERAS:
+        raise ValueError(f"undistort_keypoints_steps: at most {LENS_MAX_CAMERAS} views, got {V}")
+    d = lens_coeffs(dist)
+    if d.ndim > 2 or (d.ndim == 2 and d.shape[0] not in (1, V)):
+        raise ValueError(f"undistort_keypoints_steps: dist must be [k] or [{V}, k], got {list(d.shape)}")
+    d = np.ascontiguousarray(np.broadcast_to(d.reshape(-1, 12), (V, 12)))
+    xi = keypoints.contiguous().to(torch.float64)
+    Kd = K.contiguous().to(torch.float64)
+    out = torch.empty_like(xi)
+    resid = torch.empty((T, V, J), dtype=torch.float64, device=xi.device)
+    check(lib().skimi_undistort_points(ptr(xi), None, _hp(d), None, ptr(Kd), T, V, J, int(iters), 0, ptr(out), ptr(resid),
+                                       _lib.current_stream()), "skimi_undistort_points")
+    return UndistortResult(out, resid)
+
+
+def _undistorted_f32(keypoints, K, dist):
+    """the keypoints the triangulations see under dist=: unchanged (the same object) for None or all-zero coefficients"""
+    if dist is None or not lens_coeffs(dist).any():
+        return keypoints
+    return undistort_keypoints_steps(keypoints, K, dist).x.to(torch.float32)
+
+
+def project_points(X: torch.Tensor, R, t, K, dist=None) -> ProjectResult:
+    """cv2.projectPoints with rotation matrices in place of rvec, in one launch: X [..., 3] device tensor in the world frame,
+    R [3, 3] / t [3] (or [C, 3, 3] / [C, 3] with K [C, 3, 3] and X [..., C, n, 3]) host arrays, dist None or coefficients ->
+    ProjectResult(x float64 [..., 2] pixels of K, depth float64 [...] = z in the camera frame).  Points behind the camera
+    are projected as the formula says, as cv2 does."""
+    Kh, d, per_camera, outer, C, n = _lens_setup("project_points", X, K, dist, 3)
+    Rh, th = _host_f64(R), _host_f64(t)
+    if tuple(Rh.shape) != ((C, 3, 3) if per_camera else (3, 3)) or tuple(th.shape) != ((C, 3) if per_camera else (3,)):
+        raise ValueError(f"project_points: R / t must match K ({'[C, 3, 3] / [C, 3]' if per_camera else '[3, 3] / [3]'}), got "
+                         f"{list(Rh.shape)}, {list(th.shape)}")
+    if not (np.isfinite(Rh).all() and np.isfinite(th).all()):
+        raise ValueError("project_points: R and t must be finite")
+    Xi = X.contiguous().to(torch.float64)
+    px = torch.empty(Xi.shape[:-1] + (2,), dtype=torch.float64, device=Xi.device)
+    depth = torch.empty(Xi.shape[:-1], dtype=torch.float64, device=Xi.device)
+    check(lib().skimi_project_points(ptr(Xi), _hp(Rh), _hp(th), _hp(Kh), _hp(d), outer, C, n, ptr(px), ptr(depth),
+                                     _lib.current_stream()), "skimi_project_points")
+    return ProjectResult(px, depth)
 
 
 # ---- host helpers of the wrapper (small arrays, NumPy as in the reference) -----------------

@@ -110,6 +110,45 @@ def cfg_get(cfg, dotted: str, default=None):
     return cur
 
 
+def lens_from_cfg(cfg, cameras: int, frame_size):
+    """The lens stage of the entry points: None unless cfg.infer.undistort is true (default false), else (K [cameras, 3, 3],
+    dist [cameras, 14]) float64 from cfg.infer.calibration -- one calibration file for every camera (the reference's single
+    K_dist) or a list of one per camera -- each rescaled to frame_size = (width, height) (formats.Calibration.scaled_to).
+    A calibration whose coefficients are all zero describes a pinhole: with only such cameras the answer is None as well,
+    so that "calibrated, no distortion" runs exactly what "no calibration" runs."""
+    if not cfg_get(cfg, "infer.undistort", False):
+        return None
+    from . import formats
+    paths = cfg_get(cfg, "infer.calibration", None)
+    if paths is None:
+        raise ValueError("cfg.infer.undistort is set but cfg.infer.calibration names no calibration file")
+    paths = [paths] * cameras if isinstance(paths, (str, Path)) else [p for p in paths]
+    if len(paths) != cameras:
+        raise ValueError(f"cfg.infer.calibration: one path, or one per camera ({cameras}), got {len(paths)}")
+    cals = [formats.load_calibration(p).scaled_to(*frame_size) for p in paths]
+    K, dist = np.stack([c.K for c in cals]), np.stack([c.dist for c in cals])
+    geometry.lens_coeffs(dist)   # refuses the tilt model before any frame is touched
+    return (K, dist) if dist.any() else None
+
+
+def undistort_detections(keypoints: np.ndarray, boxes: np.ndarray, K, dist, device):
+    """One camera's detector output in source pixels under a lens: keypoints [..., 2] undistorted (geometry.undistort_points,
+    P = K), boxes [..., 4] = (x1, y1, x2, y2) replaced by the bounding box of their four undistorted corners -> (keypoints,
+    boxes, the largest finite resid_px, the number of finite points the inverse lost to NaN) with the inputs' dtypes."""
+    with torch.cuda.device(device):
+        kp_in = torch.from_numpy(np.ascontiguousarray(keypoints)).to(device)
+        kp = geometry.undistort_points(kp_in, K, dist)
+        b = torch.from_numpy(np.ascontiguousarray(boxes)).to(device)
+        corners = torch.stack([b[..., [0, 1]], b[..., [2, 1]], b[..., [0, 3]], b[..., [2, 3]]], dim=-2)      # [..., 4, 2]
+        c = geometry.undistort_points(corners, K, dist)
+        nb = torch.cat([c.x.amin(dim=-2), c.x.amax(dim=-2)], dim=-1)
+        resid = torch.cat([kp.resid_px.reshape(-1), c.resid_px.reshape(-1)])
+        worst = float(torch.nan_to_num(resid, nan=0.0).max()) if resid.numel() else 0.0
+        finite_in = torch.cat([torch.isfinite(kp_in).all(-1).reshape(-1), torch.isfinite(corners).all(-1).reshape(-1)])
+        lost = int((finite_in & torch.isnan(resid)).sum())
+        return kp.x.cpu().numpy().astype(keypoints.dtype), nb.cpu().numpy().astype(boxes.dtype), worst, lost
+
+
 def predictions_to_glb_points(preds: dict, conf_thres=50.0, prediction_mode: str = "Predicted Pointmap", filter_by_frames="all",
                               mask_black_bg: bool = False, mask_white_bg: bool = False, mask_sky: bool = False):
     """The point cloud of the reference's predictions_to_glb (vggt/visual_util.py:39-236) from a prediction dict of DEVICE

@@ -41,6 +41,12 @@ single views got wrong): the NPZ gains x3d_robust, x3d_robust_ok, robust_inlier_
 robust_view_inlier_ratio.  `cfg.triangulation.inlier_px` (default: err_thresh_px), `.min_inliers` (2), `.refine_iters` (5)
 and `.weighted` (false) are its parameters; x3d and the triage arrays are not touched.  Off by default: the NPZ is unchanged.
 
+With `cfg.infer.undistort` true and `cfg.infer.calibration` naming a calibration file (one for both cameras, as the
+reference's single K_dist, or a list of two; formats.load_calibration) the lens is taken out first: each call's source frames
+are undistorted on the device (preprocess.undistort_images), the source-pixel keypoints are undistorted
+(geometry.undistort_points) and the detector boxes become the bounding boxes of their four undistorted corners; the largest
+resid_px is logged.  The NPZ keeps its keys.  Off by default, and with all-zero coefficients: exactly the run without it.
+
 What it leaves out (out of scope): video decode (frames come from the `.pt` files, which
 `prepare_dataset` can embed; the video paths only name the subject), PNG / matplotlib output, the camera cones and
 sky mask of the scene GLB (its point cloud is written per step with `cfg.infer.scene_glb` true, default false:
@@ -57,8 +63,8 @@ from typing import List, Optional
 import numpy as np
 import torch
 
-from . import formats, fuse, geometry, parallel
-from .infer import CameraHead, cfg_get, save_camera_info
+from . import formats, fuse, geometry, parallel, preprocess
+from .infer import CameraHead, cfg_get, lens_from_cfg, save_camera_info, undistort_detections
 
 logger = logging.getLogger(__name__)
 
@@ -208,18 +214,28 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
     for frames_, pt_, vid_ in ((lf, left_pt_path, left_video_path), (rf, right_pt_path, right_video_path)):
         if frames_ is None:
             raise RuntimeError(f"{pt_} embeds no frames and {vid_} cannot be decoded here (formats.read_video_frames)")
-    if cfg_get(cfg, "infer.hflip", False):       # multi_view_process.py:116-127
+    head = camera_head if camera_head is not None else CameraHead(cfg, out_dir / "vggt_infer")
+    if head.outdir is None:
+        head.outdir = out_dir / "vggt_infer"
+    hflip = bool(cfg_get(cfg, "infer.hflip", False))
+    # opt-in lens stage (DESIGN §2 "Lens distortion"): the detections are undistorted here, the frames chunk by chunk on the
+    # device below; both belong to the sensor's own pixels, so they come before the mirror of hflip
+    lens = lens_from_cfg(cfg, 2, (int(lf.shape[2]), int(lf.shape[1])))
+    if lens is not None:
+        lk, lb, worst_l, lost_l = undistort_detections(lk, lb, lens[0][0], lens[1][0], head.device)
+        rk, rb, worst_r, lost_r = undistort_detections(rk, rb, lens[0][1], lens[1][1], head.device)
+        logger.info(f"[Run-MV] lens: keypoints and boxes undistorted, largest resid_px {max(worst_l, worst_r):.3g}, "
+                    f"{lost_l + lost_r} points lost to the inverse")
+    if hflip:       # multi_view_process.py:116-127
         W0 = lf[0].shape[1]
-        rf = torch.flip(rf, [2])
+        if lens is None:
+            rf = torch.flip(rf, [2])
         rk = rk.copy()
         rk[..., 0] = W0 - rk[..., 0]
         rb = rb.copy()
         x1, x2 = rb[..., 0].copy(), rb[..., 2].copy()
         rb[..., 0], rb[..., 2] = W0 - x2, W0 - x1
 
-    head = camera_head if camera_head is not None else CameraHead(cfg, out_dir / "vggt_infer")
-    if head.outdir is None:
-        head.outdir = out_dir / "vggt_infer"
     T = min(len(lf), len(rf))
     lo, hi, _T_pad = parallel.shard_range(T)
     source_size = tuple(lf.shape[1:3])
@@ -238,18 +254,30 @@ def process_multi_view_video(left_video_path: Path, left_pt_path: Path, right_vi
     x3d_l, K_l, R_l, t_l, C_l = [], [], [], [], []
     triage_l = []   # per call: X_clean, err, keep (uint8), view_stats, report on the device
     robust_l = []   # per call: geometry.robust_launch's eight outputs on the device
+
+    def step_frames(idx):
+        """the [left, right] frames of the steps idx; with the lens stage on, undistorted on the device in one launch"""
+        if lens is None:
+            return [[lf[i], rf[i]] for i in idx]
+        with torch.cuda.device(head.device):
+            src = torch.stack([lf[idx], rf[idx]]).to(head.device)                    # [2, n, H, W, 3] raw sensor frames
+            und = preprocess.undistort_images(src, lens[0], lens[1])
+            if hflip:
+                und[1] = torch.flip(und[1], [2])
+        return [[und[0, b], und[1, b]] for b in range(len(idx))]
+
     for a in range(lo, hi, steps_per_call):
         idx = [min(i, T - 1) for i in range(a, min(a + steps_per_call, hi))]     # padded steps repeat the last one
         # a padded step (index >= T on the last ranks) is computed to keep the collective uniform, but does not
         # write frame_{T-1}/predictions.npz a second time
         write = [i < T for i in range(a, min(a + steps_per_call, hi))]
         if device_origin:
-            recs = head.reconstruct_batch(idx, [[lf[i], rf[i]] for i in idx], write=write, dense_to_host=False, scene=scene_glb)
+            recs = head.reconstruct_batch(idx, step_frames(idx), write=write, dense_to_host=False, scene=scene_glb)
             bx = np.stack([np.stack([_bbox_of(lb, i), _bbox_of(rb, i)]) for i in idx]).astype(np.float32)
             po = geometry.person_origin(head.last_world_points[:, :2], torch.from_numpy(bx).to(head.device), source_size)
             po_stats = po.stats.cpu().numpy()   # [n, 2, 8]: the only numbers of the dense maps that reach the host
         else:
-            recs = head.reconstruct_batch(idx, [[lf[i], rf[i]] for i in idx], write=write, scene=scene_glb)
+            recs = head.reconstruct_batch(idx, step_frames(idx), write=write, scene=scene_glb)
         Ks, Rs, ts = [], [], []
         for b, (i, (_E, K_res, R, t, C, wp)) in enumerate(zip(idx, recs)):
             if device_origin:

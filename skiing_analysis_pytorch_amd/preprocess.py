@@ -17,7 +17,7 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, geometry
 from ._lib import check, lib, ptr
 
 PRECISION_BITS = 32 - 8 - 2   # Resample.c: 8-bit pixels, 2 bits of headroom for the overshoot of the cubic
@@ -132,4 +132,41 @@ def load_and_preprocess_images_device(image_list: Sequence, mode: str = "crop", 
         x_off -= (mw - ow) // 2
         check(lib().skimi_u8_hwc_to_f32_chw(ptr(r), new_h, new_w, ptr(out[i]), mh, mw, y_off, x_off, 1.0, st),
               "skimi_u8_hwc_to_f32_chw")
+    return out
+
+
+def undistort_images(frames: torch.Tensor, K, dist, new_K=None, out_size=None, out=None) -> torch.Tensor:
+    """cv2.undistort of whole frames in one launch (csrc/lens.hip; rules: include/skimi.h, DESIGN §2 "Lens distortion"):
+    frames uint8 [F, H, W, ch] or [C, F, H, W, ch] on the device, ch 1, 3 or 4; K, new_K [3, 3] (or [C, 3, 3], one per camera
+    of the five-axis form) and dist (OpenCV's 4, 5, 8, 12 or 14 coefficients, [k] or [C, k]) on the host; new_K defaults to K,
+    out_size = (width, height) to the input's.  Output pixel (u, v) maps through new_K to a normalised point, that point is
+    distorted and mapped through K to a source position, computed on the fly in float64 and sampled bilinearly with a zero
+    border; the value is rounded half up.  out: a contiguous uint8 device tensor of the result's shape to write into.
+    The input is not modified."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() not in (4, 5):
+        raise _lib.SkimiError("undistort_images needs a uint8 [F, H, W, ch] or [C, F, H, W, ch] device tensor")
+    five = frames.dim() == 5
+    fr = frames.contiguous() if five else frames.contiguous()[None]
+    C, F, H, W, ch = (int(s) for s in fr.shape)
+    if ch not in (1, 3, 4):
+        raise ValueError(f"undistort_images: 1, 3 or 4 channels, got {ch}")
+    if C > geometry.LENS_MAX_CAMERAS:
+        raise ValueError(f"undistort_images: at most {geometry.LENS_MAX_CAMERAS} cameras a call, got {C}")
+    Kh = geometry._lens_matrix("undistort_images", "K", K, C)
+    Nh = None if new_K is None else geometry._lens_matrix("undistort_images", "new_K", new_K, C)
+    d = geometry.lens_coeffs(dist)
+    if d.ndim > 2 or (d.ndim == 2 and d.shape[0] not in (1, C)):
+        raise ValueError(f"undistort_images: dist must be [k] or [{C}, k], got {list(d.shape)}")
+    d = np.ascontiguousarray(np.broadcast_to(d.reshape(-1, 12), (C, 12)))
+    ow, oh = (W, H) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    if ow < 1 or oh < 1 or H < 1 or W < 1:
+        raise ValueError(f"undistort_images: empty frame ({W} x {H} -> {ow} x {oh})")
+    shape = (C, F, oh, ow, ch) if five else (F, oh, ow, ch)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=fr.device)
+    elif (not out.is_cuda or out.device != fr.device or out.dtype != torch.uint8 or tuple(out.shape) != shape
+          or not out.is_contiguous()):
+        raise ValueError(f"undistort_images: out must be a contiguous uint8 device tensor {list(shape)}")
+    check(lib().skimi_undistort_u8(ptr(fr), ptr(out), geometry._hp(Kh), geometry._hp(d), geometry._hp(Nh), C, F, H, W, oh, ow, ch,
+                                   _lib.current_stream()), "skimi_undistort_u8")
     return out

@@ -7,7 +7,9 @@ Every 30th frame of ONE camera forms a single S = ceil(T / 30) view stack (singl
 which goes through `CameraHead.reconstruct_from_frames` once (:152-163); the cameras of those frames are
 written with `save_camera_info` (:171-178, vggt/save.py:84-110).  Left out: the video decode
 (frames come from the `.pt` file when embedded), the per-frame skeleton PNGs.  The scene GLB (vggt/save.py:58-73; point
-cloud only) is written with `cfg.infer.scene_glb` true (default false).
+cloud only) is written with `cfg.infer.scene_glb` true (default false).  With `cfg.infer.undistort` true and
+`cfg.infer.calibration` naming a calibration file the view stack is undistorted on the device first
+(preprocess.undistort_images); off by default, and with all-zero coefficients: exactly the run without it.
 """
 from __future__ import annotations
 
@@ -15,8 +17,10 @@ import logging
 from pathlib import Path
 from typing import Optional
 
-from . import formats
-from .infer import CameraHead, cfg_get, save_camera_info
+import torch
+
+from . import formats, preprocess
+from .infer import CameraHead, cfg_get, lens_from_cfg, save_camera_info
 
 logger = logging.getLogger(__name__)
 
@@ -40,6 +44,14 @@ def process_single_view_video(video_path: Path, pt_path: Path, out_root: Path, i
     if head.outdir is None:
         head.outdir = out_dir / "vggt_infer"
     inference_imgs = [frames[idx] for idx in range(0, len(frames), FRAME_STRIDE)]
+    # opt-in lens stage (cfg.infer.undistort + cfg.infer.calibration; DESIGN §2 "Lens distortion"): the view stack is
+    # undistorted on the device in one launch.  This entry point reads no keypoints or boxes, so there are none to move.
+    lens = lens_from_cfg(cfg, 1, (int(frames.shape[2]), int(frames.shape[1])))
+    if lens is not None:
+        with torch.cuda.device(head.device):
+            und = preprocess.undistort_images(torch.stack(inference_imgs).to(head.device), lens[0][0], lens[1][0])
+        inference_imgs = list(und)
+        logger.info(f"[Run-SV] lens: {len(inference_imgs)} frames undistorted on the device")
     scene_glb = bool(cfg_get(cfg, "infer.scene_glb", False))
     _E, K_resized, R, t, C, _wp = head.reconstruct_batch([0], [inference_imgs], scene=scene_glb)[0]
     # the reference keeps the "multi_view" file name here too (single_view_process.py:172)

@@ -853,6 +853,50 @@ def gen_evaluate():
 GENERATORS["evaluate"] = gen_evaluate
 
 
+def gen_lens():
+    """DESIGN §2 "Lens distortion": the calibration the reference ships (camera_calibration/calibration_parameters.{npz,yml})
+    as two small fixtures -- the .yml as it is (settings only) and a pickle-free calibration.npz with camera_matrix,
+    dist_coeffs, image_size -- and lens.npz, the outputs of the reference's OWN cv2-free vggt/vggt/dependency/distortion.py
+    (apply_distortion on 1, 2 and 4 parameters; iterative_undistortion inside the 4-parameter model's invertible range) on
+    the points of tests/lens_cases.py, in float64.  inv_ref_err is the reference's own round-trip error: truth ->
+    apply_distortion -> iterative_undistortion against the truth (it stops at a step of 1e-5).  Only inputs and results are
+    stored."""
+    import importlib.util
+    import shutil
+
+    sys.path.insert(0, str(ROOT / "tests"))
+    import lens_cases as lc
+
+    src = Path(REF) / "camera_calibration"
+    shutil.copyfile(src / "calibration_parameters.yml", GOLD / "calibration_parameters.yml")
+    with np.load(src / "calibration_parameters.npz", allow_pickle=False) as z:
+        np.savez(GOLD / "calibration.npz", camera_matrix=z["camera_matrix"].astype(np.float64),
+                 dist_coeffs=z["dist_coeffs"].astype(np.float64), image_size=z["image_size"].astype(np.int64))
+    spec = importlib.util.spec_from_file_location("ref_distortion", os.path.join(REF, "vggt", "vggt", "dependency", "distortion.py"))
+    ref = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(ref)
+    tt = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64))      # noqa: E731
+    u, v = lc.ref_forward_points()
+    out = {"fwd_u": u, "fwd_v": v}
+    for name, params in (("p1", lc.REF_P1), ("p2", lc.REF_P2), ("p4", lc.REF_P4)):
+        ud, vd = ref.apply_distortion(tt(params), tt(u), tt(v))
+        out[f"fwd_{name}_params"] = params
+        out[f"fwd_{name}"] = np.stack([ud.numpy(), vd.numpy()], -1)
+    truth = lc.ref_inverse_truth()
+    p4 = tt(lc.REF_P4[:1])
+    xd, yd = ref.apply_distortion(p4, tt(truth[..., 0]), tt(truth[..., 1]))
+    dist_pts = torch.stack([xd, yd], -1)
+    und = ref.iterative_undistortion(p4, dist_pts).numpy()
+    out |= {"inv_params": lc.REF_P4[:1], "inv_truth": truth, "inv_distorted": dist_pts.numpy(), "inv_undistorted": und,
+            "inv_ref_err": np.array(np.abs(und - truth).max())}
+    path = GOLD / "lens.npz"
+    np.savez_compressed(path, **out)
+    print("wrote", path.name, path.stat().st_size, "bytes; the reference's round-trip error:", float(out["inv_ref_err"]))
+
+
+GENERATORS["lens"] = gen_lens
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GENERATORS)
     for w in which:
