@@ -1050,6 +1050,74 @@ int skimi_project_points(const double* X, const double* R, const double* t, cons
 int skimi_undistort_u8(const uint8_t* in, uint8_t* out, const double* K, const double* dist, const double* new_K, int32_t C,
                        int32_t F, int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t ch, void* stream);
 
+/* ---- bird's-eye view of the front camera: homography, frame warp, skeleton on the plan, ground track (csrc/bev.hip) ----
+ * front_side/front/bev_utils.py (cv2.findHomography(method=0), image_points_to_bev, cv2.warpPerspective), front_side/run.py
+ * (project_world_to_bev_centered + the centre of merge).  Everything is float64 on the device, one launch per call, no
+ * atomics, no host synchronisation, no allocation, bitwise reproducible; a group's result is the same bits alone and inside
+ * a batch.  Rules (DESIGN §2 "Bird's-eye view"; tests/bev_restated.py evaluates the same expressions in the same order):
+ *
+ * skimi_homography_fit: src, dst [G, n, 2] (dev), 4 <= n, G >= 1, G n <= 2^31; post [9] (HOST, NULL: identity, finite) ->
+ * H, Hinv [G, 9], Hn [G, 9] (or NULL), err [G, n], stats [G, 4], status [G] i32 (dev).  One wave per group; every sum over the points is one lane's,
+ * in point order.
+ *  1. A correspondence is used iff its four numbers are finite; fewer than 4 used: the group fails.
+ *  2. Hartley normalisation per side over the used points: centroid c, mean distance d, s = sqrt(2) / d, point -> (x - c) s.
+ *     d = 0 or non-finite: the group fails.
+ *  3. Each used pair (x, y) -> (u, v), normalised, gives the rows [-x, -y, -1, 0, 0, 0, u x, u y, u] and [0, 0, 0, -x, -y, -1,
+ *     v x, v y, v]; the 9 x 9 A^T A is summed in point order.
+ *  4. Cyclic Jacobi to convergence (csrc/jacobi.h: the stopping rule and zeroing of the essential matrix's null space); h =
+ *     the eigenvector of the smallest eigenvalue, the lower index on a tie.
+ *  5. Hn = T_dst^-1 h T_src.  |Hn[2][2]| >= 1e-12 ||Hn||_F: Hn /= Hn[2][2]; else Hn is scaled to ||Hn||_F = 1 with its entry
+ *     of largest magnitude positive.
+ *  6. status = 1 iff Hn is finite and |det Hn| >= 1e-12 (the reference's check_homography on H_m); else the group fails.
+ *  7. H = post Hn, not renormalised (post = the canvas matrix S keeps h22 = 1: its last row is (0, 0, 1)).  The Hn output is
+ *     rule 5's matrix itself (the reference's H_m beside its H_px = S H_m), NaN for a failed group.
+ *  8. Hinv = adj(H) / det(H), every cofactor a b - c d in written order.
+ *  9. A failed group: H, Hinv, err, rms and max all NaN, status 0; its neighbours are untouched.
+ * 10. err = || pi(H x) - pi(post x') || per used point, NaN for an unused one; stats = n_used, rms err, max err, det Hn (NaN
+ *     when the group failed before rule 5).
+ *     For n > 4 this is the algebraic least-squares solution: cv2's Levenberg-Marquardt polish, RANSAC and LMedS are out.  The
+ *     eigenvalue gap is not thresholded: three of four points exactly collinear are caught only by rule 6.
+ *
+ * skimi_homography_points: x [G, n, 2], H [G, 9] (dev; shared != 0: one H [9] for every group) -> out [G, n, 2].  w = (h6 x +
+ * h7 y) + h8, X and Y alike; out = (X / w, Y / w), NaN in both coordinates when the input or w is non-finite or |w| < eps
+ * (the reference raises there; a batch cannot).  G n <= 2^31; an empty call launches nothing.
+ *
+ * skimi_warp_perspective_u8 = cv2.warpPerspective(INTER_LINEAR, constant border 0): in [C, F, H, W, ch] u8 -> out [C, F, OH, OW,
+ * ch] u8 (dev), ch 1, 3 or 4, sides 1 .. SKIMI_LENS_MAX_SIDE, C F <= 65535.  Hinv (DEV) [C, 9], or [C F, 9] when per_frame != 0,
+ * maps output pixels to source positions: for output pixel (u, v), X = (g0 u + g1 v) + g2, Y and w alike, su = X / w, sv = Y / w
+ * by plain division with no test of w's sign, as cv2: what lies beyond the horizon line is mirrored as cv2 mirrors it.  Then
+ * rule 7 of the lens block verbatim (csrc/warp_u8.h is the one copy of it): 0 unless -1 < su < W and -1 < sv < H (any
+ * non-finite value fails: a failed fit's NaN matrix gives a black frame), floor, a, b, taps outside count 0, the same
+ * bilinear expression, floor(value + 0.5), the same stores.  cv2 quantises positions to 1/32 px with integer weights; this
+ * rule is the contract.  The input is only read; nothing beyond the C F OH OW ch output bytes is written.
+ *
+ * skimi_bev_skeleton = project_world_to_bev_centered + the centre of merge: X [T, J, 3], center_px [T, 2] (dev) -> uv [T, J, 2]
+ * f64, px [T, J, 2] i32, valid [T, J] u8, center_world [T, 3] (dev).  ax0, ax1 in 0 .. 2 (the reference's use_axes).
+ *  1. center_world = np.nanmean over the joints PER COORDINATE (NaN skipped, an infinity is not); an all-NaN column: NaN.
+ *     Lane l of the step's wave adds its joints l, l + 64, .. in order, then reduce.h's wave_sum.  center_world_in [T, 3]
+ *     (dev, or NULL): the caller's centre, taken in place of the mean (project_world_to_bev_centered's own argument).
+ *  2. A joint is valid iff its three coordinates, the two centre coordinates used and the step's center_px are finite.
+ *  3. dx = x[ax0] - c[ax0], dz = x[ax1] - c[ax1], swapped when rot90_left != 0; du = dx / mpp, dv = -dz / mpp; (u0, v0) = rint
+ *     of center_px; uv = (u0 + du, v0 + dv); px = rint(uv), rounding half to even as Python's round (saturating at int32).
+ *  4. An invalid joint: NaN in uv, 0 in px.
+ *
+ * skimi_ground_track: p [P, T, 2] metres (dev), fps > 0 -> out [P, T, 6] = step, path, vx, vy, speed, heading.
+ *  1. step_t = || p_t - p_(t-1) ||, 0 at t = 0, NaN if either end is non-finite.  path_t = the sum of the finite steps up to t,
+ *     in time order (one thread per person).
+ *  2. v_t = ((p_(t+1) - p_(t-1)) fps) / 2, one-sided (p_1 - p_0) fps and (p_(T-1) - p_(T-2)) fps at the ends; NaN in both
+ *     components where a needed sample is non-finite or T = 1.  speed = || v ||, heading = atan2(vx, vy).
+ *  3. Nothing is smoothed: callers smooth the track first. */
+int skimi_homography_fit(const double* src, const double* dst, const double* post, int64_t G, int32_t n, double* H, double* Hinv,
+                         double* Hn, double* err, double* stats, int32_t* status, void* stream);
+int skimi_homography_points(const double* x, const double* H, int64_t G, int64_t n, int32_t shared, double eps, double* out,
+                            void* stream);
+int skimi_warp_perspective_u8(const uint8_t* in, uint8_t* out, const double* Hinv, int32_t per_frame, int32_t C, int32_t F,
+                              int32_t H, int32_t W, int32_t OH, int32_t OW, int32_t ch, void* stream);
+int skimi_bev_skeleton(const double* X, const double* center_px, const double* center_world_in, int64_t T, int32_t J,
+                       double metres_per_pixel, int32_t ax0, int32_t ax1, int32_t rot90_left, double* uv, int32_t* px, uint8_t* valid,
+                       double* center_world, void* stream);
+int skimi_ground_track(const double* p, int64_t P, int64_t T, double fps, double* out, void* stream);
+
 /* ---- VGGT head and track-head helper kernels, one launch each ----
  * The kernels skimi_vggt_forward runs between its GEMMs, exposed singly so that each can be tested against a float64
  * restatement.  All maps are channels-last and dense; dtype / out_dtype are SKIMI_F32, SKIMI_BF16 or SKIMI_F16.  Every

@@ -168,6 +168,13 @@ _SIGNATURES = {
     "skimi_project_points": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int64, _vp, _vp, _vp]),
     "skimi_undistort_u8": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, _vp]),
+    "skimi_homography_fit": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "skimi_homography_points": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_double, _vp, _vp]),
+    "skimi_warp_perspective_u8": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, C.c_int32, _vp]),
+    "skimi_bev_skeleton": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp,
+                                     _vp, _vp]),
+    "skimi_ground_track": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_double, _vp, _vp]),
     "skimi_resize_bilinear": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_float, _vp]),
     "skimi_resize_bilinear_planes": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
     "skimi_add_uv_pos": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "fp64_util.h"
+#include "jacobi.h"   // jacobi_serial: the nine-vector null space (rule 4) and the 3 x 3 of the decomposition
 
 namespace skimi {
 namespace {
@@ -28,7 +29,6 @@ namespace {
 
 constexpr int kSol = 10;                     // solutions per sample
 constexpr int kMinPoints = 5;
-constexpr int kJacobiSweeps = 60;
 constexpr int kPolishSteps = 3;              // DESIGN: the step after which the restatement's iterate is at its rounding floor
 constexpr double kResidualBound = 1e-10;     // on max |M mon| / (1 + x^2 + y^2 + z^2)^(3/2) after the polish
 constexpr double kPivotTol = 1e-14;
@@ -61,45 +61,6 @@ HD void draw_sample(uint64_t seed, uint64_t group, uint64_t h, int m, int* sampl
         bool seen = false;
         for (int k = 0; k < n; ++k) seen = seen || sample[k] == r;
         if (!seen) sample[n++] = r;
-    }
-}
-
-// ---- cyclic Jacobi of a symmetric n x n (row-major), eigenvectors into the columns of Q: resect.hip's jacobi_lds, one
-// thread doing every lane's part, the same rotations in the same order -------------------------------------------------
-template <int n>
-HD void jacobi_serial(double* M, double* Q) {
-    for (int i = 0; i < n * n; ++i) Q[i] = (i / n == i % n) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < kJacobiSweeps; ++sweep) {
-        double off = 0.0, diag = 0.0;
-        for (int a = 0; a < n; ++a) {
-            diag += M[a * n + a] * M[a * n + a];
-            for (int b = a + 1; b < n; ++b) off += M[a * n + b] * M[a * n + b];
-        }
-        if (!is_fin(off) || off <= 1e-40 * diag || off == 0.0) break;
-        for (int p = 0; p < n - 1; ++p)
-            for (int q = p + 1; q < n; ++q) {
-                const double mpq = M[p * n + q];
-                if (mpq == 0.0) continue;
-                const double theta = (M[q * n + q] - M[p * n + p]) / (2.0 * mpq);
-                const double tn = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                const double cs = 1.0 / sqrt(tn * tn + 1.0), sn = tn * cs;
-                for (int k = 0; k < n; ++k) {
-                    const double mkp = M[k * n + p], mkq = M[k * n + q];
-                    M[k * n + p] = cs * mkp - sn * mkq;
-                    M[k * n + q] = sn * mkp + cs * mkq;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double mpk = M[p * n + k], mqk = M[q * n + k];
-                    M[p * n + k] = cs * mpk - sn * mqk;
-                    M[q * n + k] = sn * mpk + cs * mqk;
-                }
-                M[p * n + q] = M[q * n + p] = 0.0;
-                for (int k = 0; k < n; ++k) {
-                    const double qkp = Q[k * n + p], qkq = Q[k * n + q];
-                    Q[k * n + p] = cs * qkp - sn * qkq;
-                    Q[k * n + q] = sn * qkp + cs * qkq;
-                }
-            }
     }
 }
 

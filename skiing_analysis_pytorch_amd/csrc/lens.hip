@@ -11,6 +11,7 @@
 // model output that never left the device (geometry.triangulate_triage(dist=)).
 #include "common.h"
 #include "fp64_util.h"
+#include "warp_u8.h"
 
 namespace skimi {
 
@@ -151,13 +152,10 @@ __global__ __launch_bounds__(kPtThreads) void project_points_kernel(const double
 }
 
 // ---- the frame warp ------------------------------------------------------------------------------------------------
-// in [C, F, H, W, CH] -> out [C, F, OH, OW, CH].  A thread owns kPix adjacent output pixels of one row: kPix * CH bytes,
-// a whole number of dwords, which it packs in registers and writes as dwords when the output rows are dword-aligned
-// (OW * CH % 4 == 0 and an aligned base), byte by byte otherwise and at a row's ragged end.  A wave covers 64 * kPix = 256
+// in [C, F, H, W, CH] -> out [C, F, OH, OW, CH].  The thread shape, the taps, the rounding and the stores are warp_u8.h's
+// (shared with bev.hip's perspective warp); this kernel supplies the source position.  A wave covers 64 * kPix = 256
 // adjacent pixels of a row, so its gathers fall into the two source rows around the (gently curved) preimage of that
-// span: a few cache lines a row.  Block = 64 x 4 threads = 256 x 4 output pixels; blockIdx.z = (camera, frame).
-constexpr int kPix = 4, kWarpX = 64, kWarpY = 4;
-
+// span: a few cache lines a row.  blockIdx.z = (camera, frame).
 template <int CH>
 __global__ __launch_bounds__(kWarpX* kWarpY) void undistort_u8_kernel(const unsigned char* __restrict__ in,
                                                                      unsigned char* __restrict__ out, LensCams cams, int F, int H,
@@ -180,38 +178,10 @@ __global__ __launch_bounds__(kWarpX* kWarpY) void undistort_u8_kernel(const unsi
         double xd, yd;
         distort(d, x, y, xd, yd);
         const double su = lc.fx * xd + lc.cx, sv = lc.fy * yd + lc.cy;
-        const bool inside = u < OW && su > -1.0 && su < (double)W && sv > -1.0 && sv < (double)H;   // false for a NaN
-        if (!inside) continue;   // the bytes stay 0: the constant border
-        const double x0f = floor(su), y0f = floor(sv);
-        const double a = su - x0f, b = sv - y0f;
-        const int x0 = (int)x0f, y0 = (int)y0f;   // -1 .. W - 1, -1 .. H - 1
-        const bool l = x0 >= 0, r = x0 + 1 < W, t = y0 >= 0, bt = y0 + 1 < H;
-        const unsigned char* s00 = src + ((size_t)max(y0, 0) * W + max(x0, 0)) * CH;
-        const size_t dx = (l && r) ? CH : 0, dy = (t && bt) ? (size_t)W * CH : 0;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-            // every address lies inside the frame; a tap outside it counts 0
-            const double p00 = (l && t) ? (double)s00[c] : 0.0;
-            const double p01 = (r && t) ? (double)s00[(l ? dx : 0) + c] : 0.0;
-            const double p10 = (l && bt) ? (double)s00[(t ? dy : 0) + c] : 0.0;
-            const double p11 = (r && bt) ? (double)s00[(l ? dx : 0) + (t ? dy : 0) + c] : 0.0;
-            const double val = (1.0 - b) * ((1.0 - a) * p00 + a * p01) + b * ((1.0 - a) * p10 + a * p11);
-            const unsigned int q = (unsigned int)floor(val + 0.5);   // 0 .. 255
-            const int byte = p * CH + c;
-            words[byte >> 2] |= q << (8 * (byte & 3));
-        }
+        if (!(u < OW && warp_inside(su, sv, H, W))) continue;   // the bytes stay 0: the constant border
+        warp_tap_pack<CH>(src, H, W, su, sv, p, words);
     }
-    unsigned char* dst = out + (((size_t)img * OH + v) * OW + u0) * CH;
-    if (aligned && u0 + kPix <= OW) {
-        unsigned int* dw = reinterpret_cast<unsigned int*>(dst);
-#pragma unroll
-        for (int w = 0; w < CH; ++w) dw[w] = words[w];
-    } else {
-        const int nb = min(kPix, OW - u0) * CH;
-#pragma unroll
-        for (int byte = 0; byte < kPix * CH; ++byte)
-            if (byte < nb) dst[byte] = (unsigned char)(words[byte >> 2] >> (8 * (byte & 3)));
-    }
+    warp_store<CH>(out + (((size_t)img * OH + v) * OW + u0) * CH, words, aligned, u0, OW);
 }
 
 // host side: K [C, 3, 3], the second matrix (NULL: K), dist [C, 12] -> the by-value records

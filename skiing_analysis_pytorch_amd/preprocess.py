@@ -170,3 +170,40 @@ def undistort_images(frames: torch.Tensor, K, dist, new_K=None, out_size=None, o
     check(lib().skimi_undistort_u8(ptr(fr), ptr(out), geometry._hp(Kh), geometry._hp(d), geometry._hp(Nh), C, F, H, W, oh, ow, ch,
                                    _lib.current_stream()), "skimi_undistort_u8")
     return out
+
+
+def warp_perspective(frames: torch.Tensor, Hinv: torch.Tensor, out_size, per_frame: bool = False, out=None) -> torch.Tensor:
+    """cv2.warpPerspective(frame, H, out_size, flags=INTER_LINEAR) with a constant 0 border for whole clips in one launch
+    (csrc/bev.hip; rules: include/skimi.h, DESIGN §2 "Bird's-eye view"): frames uint8 [F, H, W, ch] or [C, F, H, W, ch] on the
+    device, ch 1, 3 or 4; out_size = (width, height).  Hinv is the INVERSE of cv2's H (output pixel -> source position:
+    geometry.homography_fit's Hinv) and lives on the DEVICE: [3, 3] for a four-axis clip, [C, 3, 3] one per camera, or with
+    per_frame=True [F, 3, 3] / [C, F, 3, 3], one per frame (a panning camera), so a fit, its inverse and the warp run back to
+    back without a host round trip.  The source position is computed on the fly in float64 by plain division (what lies
+    beyond the horizon line is mirrored as cv2 mirrors it), sampled bilinearly, rounded half up; a non-finite matrix (a
+    failed fit) gives a black frame.  out: a contiguous uint8 device tensor of the result's shape to write into.  The
+    input is not modified."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() not in (4, 5):
+        raise _lib.SkimiError("warp_perspective needs a uint8 [F, H, W, ch] or [C, F, H, W, ch] device tensor")
+    if not isinstance(Hinv, torch.Tensor) or not Hinv.is_cuda:
+        raise _lib.SkimiError("warp_perspective needs Hinv on the device")
+    five = frames.dim() == 5
+    fr = frames.contiguous() if five else frames.contiguous()[None]
+    C, F, H, W, ch = (int(s) for s in fr.shape)
+    if ch not in (1, 3, 4):
+        raise ValueError(f"warp_perspective: 1, 3 or 4 channels, got {ch}")
+    lead = ((C, F) if five else (F,)) if per_frame else ((C,) if five else ())
+    g = Hinv.to(fr.device, torch.float64).contiguous()
+    if tuple(g.shape) != (*lead, 3, 3):
+        raise ValueError(f"warp_perspective: Hinv must be {[*lead, 3, 3]} (per_frame={bool(per_frame)}), got {list(g.shape)}")
+    ow, oh = int(out_size[0]), int(out_size[1])
+    if ow < 1 or oh < 1 or H < 1 or W < 1:
+        raise ValueError(f"warp_perspective: empty frame ({W} x {H} -> {ow} x {oh})")
+    shape = (C, F, oh, ow, ch) if five else (F, oh, ow, ch)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=fr.device)
+    elif (not out.is_cuda or out.device != fr.device or out.dtype != torch.uint8 or tuple(out.shape) != shape
+          or not out.is_contiguous()):
+        raise ValueError(f"warp_perspective: out must be a contiguous uint8 device tensor {list(shape)}")
+    check(lib().skimi_warp_perspective_u8(ptr(fr), ptr(out), ptr(g), int(bool(per_frame)), C, F, H, W, oh, ow, ch,
+                                          _lib.current_stream()), "skimi_warp_perspective_u8")
+    return out

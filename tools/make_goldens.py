@@ -897,6 +897,97 @@ def gen_lens():
 GENERATORS["lens"] = gen_lens
 
 
+def gen_bev():
+    """DESIGN §2 "Bird's-eye view": the reference's OWN cv2-free functions of front_side/front/bev_utils.py (make_bev_canvas,
+    foot_from_bbox_xyxy, image_points_to_bev), front_side/front/run.py (_convert_xywh_to_xyxy, _unnormalize_bbox) and
+    front_side/run.py (project_world_to_bev_centered) on seeded inputs, inputs and outputs only.  The modules import cv2,
+    tqdm and their sibling loaders at the top and use none of them on these paths: empty stand-in modules satisfy the
+    imports.  cv2.findHomography and cv2.warpPerspective are NOT recorded (cv2 is not installed where this runs): they are
+    pinned by the restatement and the checks of tests/test_bev_cpu.py."""
+    import importlib
+    import types
+
+    def stand_in(name, **attrs):
+        m = types.ModuleType(name)
+        for k, v in attrs.items():
+            setattr(m, k, v)
+        return m
+
+    nothing = lambda *a, **k: None      # noqa: E731
+    fs = os.path.join(REF, "front_side")
+    stubs = {
+        "front_side": stand_in("front_side", __path__=[fs]),
+        "front_side.load": stand_in("front_side.load", load_sam3_results=nothing, load_sam_3d_body_results=nothing),
+        "front_side.side": stand_in("front_side.side", __path__=[]),
+        "front_side.side.run": stand_in("front_side.side.run", process_side_frame=nothing),
+        "front_side.utils": stand_in("front_side.utils", __path__=[]),
+        "front_side.utils.merge": stand_in("front_side.utils.merge", merge_frame_to_video=nothing),
+        "front_side.side.visualization": stand_in("front_side.side.visualization", __path__=[]),
+        "front_side.side.visualization.utils": stand_in("front_side.side.visualization.utils", parse_pose_metainfo=nothing),
+    }
+    for name in ("cv2", "tqdm"):
+        try:
+            __import__(name)
+        except ImportError:
+            stubs[name] = stand_in(name, tqdm=lambda it, **k: it)
+    saved = {name: sys.modules.get(name) for name in stubs}
+    sys.modules.update(stubs)
+    try:
+        bu = importlib.import_module("front_side.front.bev_utils")
+        fr = importlib.import_module("front_side.front.run")
+        top = importlib.import_module("front_side.run")
+    finally:
+        for name, mod in saved.items():
+            if mod is None:
+                sys.modules.pop(name, None)
+            else:
+                sys.modules[name] = mod
+        for name in [n for n in sys.modules if n == "front_side" or n.startswith("front_side.")]:
+            sys.modules.pop(name, None)
+
+    rng = np.random.default_rng(11)
+    out = {}
+    cfgs = np.array([[30.0, 60.0, 20.0, 5.0, 10.0], [12.5, 33.3, 7.5, 1.25, 0.7], [30.0, 60.0, 0.9, 5.0, 10.0]])
+    sizes, mats = [], []
+    for c in cfgs:
+        size, S = bu.make_bev_canvas(bu.BeVConfig(*map(float, c)))
+        sizes.append(size), mats.append(S)
+    out |= {"canvas_cfg": cfgs, "canvas_size": np.array(sizes, np.int64), "canvas_S": np.array(mats)}
+    boxes = rng.uniform(0, 1000, (9, 4))
+    out |= {"foot_boxes": boxes, "foot_out": np.stack([bu.foot_from_bbox_xyxy(b) for b in boxes])}
+    H = np.array([[0.96, 0.81, -920.0], [0.01, -3.7, 4008.0], [1e-5, 0.00268, 1.0]])
+    uv = rng.uniform([0, 150], [1920, 1080], (33, 2))
+    out |= {"pts_H": H, "pts_uv": uv, "pts_out": bu.image_points_to_bev(uv, H)}
+    xywh = rng.uniform(0, 0.5, (7, 4))
+    xyxy = fr._convert_xywh_to_xyxy(xywh)
+    out |= {"xywh": xywh, "xyxy": xyxy, "unnorm_size": np.array([1080, 1920], np.int64),
+            "unnorm_out": fr._unnormalize_bbox(xyxy, (1080, 1920))}
+    # the skeleton on the plan: seeded joints with NaN joints; a 1/8 m grid at 0.25 m / px meets exact halves
+    cases = []
+    for k, (mpp, grid, rot, axes) in enumerate(((0.02, False, True, (0, 2)), (0.25, True, True, (0, 2)), (0.25, True, False, (0, 2)),
+                                                 (0.02, False, False, (0, 1)), (0.5, True, True, (2, 1)))):
+        J = 21 if k % 2 == 0 else 17
+        X = rng.integers(-40, 41, (J, 3)).astype(np.float64) / 8.0 if grid else rng.normal(size=(J, 3)) + [0.5, 1.0, 6.0]
+        X[3] = np.nan
+        X[7, 1] = np.nan
+        center_world = np.array([0.125, -0.25, 0.375]) if grid else np.nanmean(X, axis=0)
+        center_px = (int(rng.integers(100, 700)), int(rng.integers(100, 1500)))
+        pts = top.project_world_to_bev_centered(X, center_world, center_px, mpp, use_axes=axes, rot90_left=rot)
+        valid = np.array([p is not None for p in pts])
+        px = np.array([p if p is not None else (0, 0) for p in pts], np.int64)
+        cases.append((X, center_world, np.array(center_px, np.int64), np.array(mpp), np.array(axes, np.int64), np.array(rot), px, valid))
+    for k, vals in enumerate(cases):
+        for key, v in zip(("X", "center_world", "center_px", "mpp", "axes", "rot", "px", "valid"), vals):
+            out[f"skel{k}_{key}"] = v
+    out["skel_count"] = np.array(len(cases))
+    path = GOLD / "bev.npz"
+    np.savez_compressed(path, **out)
+    print("wrote", path.name, path.stat().st_size, "bytes")
+
+
+GENERATORS["bev"] = gen_bev
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GENERATORS)
     for w in which:
