@@ -12,18 +12,18 @@
 //   O^T[d, q]  += V^T P^T A = V^T from LDS via ds_read_b64_tr_b16 (hardware transpose of a
 //                          row-major [key][d] tile), B = P: the S^T accumulator converted to bf16
 //                          in place (k order inside a step: key = 16s + 8(j>>2) + 4h + (j&3)).
-// blockIdx -> (batch, head, q-block) is XCD-contiguous so one XCD's L2 holds a head's K/V.
+// blockIdx -> (batch, head, q-block) is XCD-contiguous (gfx950.h) so one XCD's L2 holds a head's K/V.
 #include <stdlib.h>
 
+#include "attention_tile.h"
 #include "common.h"
+#include "env.h"
 #include "kernels.h"
 
 namespace skimi {
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
+using namespace att;   // the K / V tile layout shared with attention_q64.hip and attention_x3.hip
+
 
 __device__ __forceinline__ bf16x8 pack8(const f32x16& p, int s) {
     bf16x8 r;
@@ -34,22 +34,12 @@ __device__ __forceinline__ bf16x8 pack8(const f32x16& p, int s) {
 
 template <int dbg>   // dbg != 0: timing ablations only (SKIMI_ATTN_ABL), results are wrong
 __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(const AttnArgs a, int nqb) {
-    constexpr int KV = 64;                 // keys per tile
-    constexpr int TILE = KV * 64 * 2;      // bytes of one K (or V) tile
     __shared__ __attribute__((aligned(16))) char smem[4 * TILE];   // [buf][K|V]
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    // XCD-contiguous remap of the 1-D grid
-    int id;
-    {
-        const int nblk = gridDim.x;
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7;
-        const int q = nblk >> 3, r = nblk & 7;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int id = xcd_contiguous_id();   // one XCD's L2 holds a head's K/V
     const int qb = id % nqb;
     const int bh = id / nqb;
     const int head = bh % a.heads, b = bh / a.heads;
@@ -69,10 +59,7 @@ __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(const AttnArgs a, int
         for (int s = 0; s < 4; ++s) qf[s] = *reinterpret_cast<const bf16x8*>(qp + 16 * s);
     }
 
-    // K/V staging by LDS-DMA (global_load_lds_dwordx4): one wave-instruction lands 8 rows x 128 B
-    // linearly in LDS, so both bank swizzles are applied to the per-lane SOURCE chunk:
-    //   K rows: chunk ^= (row>>1)&7          (conflict-free ds_read_b128 of 32 rows at one chunk)
-    //   V rows: chunk ^= ((row>>1)&1)<<2     (conflict-free ds_read_b64_tr_b16 of 4-row blocks)
+    // K/V staging by LDS-DMA (global_load_lds_dwordx4), bank swizzles on the per-lane SOURCE chunk: attention_tile.h.
     // Rows past the end are clamped to the last valid row (finite data; their scores are masked
     // to -inf, so their P is exactly 0).  No staging registers, no ds_write pass.
     const int nkt = (a.seq_k + KV - 1) / KV;
@@ -83,14 +70,12 @@ __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(const AttnArgs a, int
         char* vb = kb + TILE;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int row = 8 * (2 * wave + j) + srow;                 // tile row 0..63
+            const int row = DMA_ROWS * (2 * wave + j) + srow;          // tile row 0..63
             const int key = min(kt * KV + row, a.seq_k - 1);
-            const int kc = sch ^ ((row >> 1) & 7);
+            const int kc = sch ^ ((row >> 1) & 7);                      // the source swizzles of attention_tile.h
             const int vc = sch ^ (((row >> 1) & 1) << 2);
-            __builtin_amdgcn_global_load_lds((gbl_void*)(K + (long)key * a.k_row + kc * 8),
-                                             (lds_void*)(kb + (2 * wave + j) * 8 * 128), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gbl_void*)(V + (long)key * a.v_row + vc * 8),
-                                             (lds_void*)(vb + (2 * wave + j) * 8 * 128), 16, 0, 0);
+            lds_dma16(K + (long)key * a.k_row + kc * 8, kb + (2 * wave + j) * DMA_ROWS * ROW);
+            lds_dma16(V + (long)key * a.v_row + vc * 8, vb + (2 * wave + j) * DMA_ROWS * ROW);
         }
     };
 
@@ -108,7 +93,7 @@ __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(const AttnArgs a, int
     const float c2 = a.scale * 1.44269504088896340736f;   // softmax scale folded into exp2
 
     issue(0, 0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): own LDS-DMA landed, then the barrier (protocol: attention_q64.hip)
+    wait_vmcnt<0>();   // own LDS-DMA landed, then the barrier (protocol: gfx950.h)
     __syncthreads();
 
     for (int kt = 0; kt < nkt; ++kt) {
@@ -126,7 +111,7 @@ __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(const AttnArgs a, int
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
                 const bf16x8 kf = (dbg & 1) ? qf[ks] :
-                    *reinterpret_cast<const bf16x8*>(kb + row * 128 + (((2 * ks + lh) ^ ((row >> 1) & 7)) << 4));
+                    *reinterpret_cast<const bf16x8*>(kb + k_frag_off(row, ks, lh));
                 // the first k-step takes the constant 0 as C (inline operand: no 16-register clear)
                 s[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[ks], ks == 0 ? zero16 : s[t], 0, 0, 0);
             }
@@ -137,7 +122,7 @@ __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(const AttnArgs a, int
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int key = kt * KV + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int key = acc_key(kt * KV + t * 32, r, lh);
                     if (key >= a.seq_k) s[t][r] = -INFINITY;
                 }
         }
@@ -180,16 +165,11 @@ __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(const AttnArgs a, int
                 if (!(dbg & 8)) lacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pf, lacc, 0, 0, 0);
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
-                    // tr-read block: rows key0 + q (q = (lane&15)>>2), cols dcol0 + 4p (p = lane&3)
-                    const int q4 = (lane & 15) >> 2, p4 = lane & 3;
-                    const int dcol = dt * 32 + 16 * ((lane >> 4) & 1) + 4 * p4;   // first of 4 d columns
-                    bf16x8 vf = qf[0];
+                    bf16x8 vf = qf[0];   // the read mirrors read_vt of attention_tile.h
                     if (!(dbg & 2))
 #pragma unroll
                     for (int half = 0; half < 2; ++half) {
-                        const int row = t * 32 + 16 * ks + 8 * half + 4 * lh + q4;
-                        const int chunk = (dcol >> 3) ^ (((row >> 1) & 1) << 2);
-                        const char* addr = vb + row * 128 + (chunk << 4) + ((dcol & 7) << 1);
+                        const char* addr = vt_ptr(vb, t, ks, dt, half, lane, lh);
                         const s16x4 v4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)addr);
                         vf[4 * half + 0] = v4[0];
                         vf[4 * half + 1] = v4[1];
@@ -201,7 +181,7 @@ __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(const AttnArgs a, int
             }
         }
 
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) ahead of the barrier, written out
+        wait_vmcnt<0>();   // ahead of the barrier, written out
         __syncthreads();
     }
 
@@ -216,21 +196,18 @@ __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(const AttnArgs a, int
                 bf16x4 v;
 #pragma unroll
                 for (int j = 0; j < 4; ++j) v[j] = (short)f2x16(o[dt][4 * g + j] * inv, a.out_f16 != 0);
-                *reinterpret_cast<bf16x4*>(op + dt * 32 + 8 * g + 4 * lh) = v;
+                *reinterpret_cast<bf16x4*>(out_ptr(op, dt, g, lh)) = v;
             }
     }
 }
 
 static int q64_enabled() {   // SKIMI_ATTN_Q64: 1 (default) the 64-query-per-wave kernel; 0 this file's 32-query kernel
-    static const int q64 = getenv("SKIMI_ATTN_Q64") ? atoi(getenv("SKIMI_ATTN_Q64")) : 1;
-    return q64;
+    return (int)env_once("SKIMI_ATTN_Q64", 1);
 }
 
 // SKIMI_ATTN_MX=0: SKIMI_PREC_FP8 quantises the bf16 output rows in a separate pass instead (A/B timing, tests)
 bool attention_mx_output_ok(int dtype, int heads, int head_dim) {
-    static const bool dyn = getenv("SKIMI_ENV_DYNAMIC") && atoi(getenv("SKIMI_ENV_DYNAMIC"));
-    static int use_mx = -1;
-    if (use_mx < 0 || dyn) use_mx = getenv("SKIMI_ATTN_MX") ? atoi(getenv("SKIMI_ATTN_MX")) : 1;
+    const int use_mx = (int)env_switch("SKIMI_ATTN_MX", 1);
     return use_mx && dtype == SKIMI_BF16 && head_dim == 64 && heads % 2 == 0 && q64_enabled() != 0;
 }
 
@@ -251,7 +228,7 @@ int attention_bf16_launch(const AttnArgs& a, hipStream_t st) {
     if (prof) prof_before(st);
     // timing ablations (wrong results) exist only in a -DSKIMI_ABLATIONS build (SKIMI_ABLATIONS=1 python -m ...build)
 #ifdef SKIMI_ABLATIONS
-    static const int dbg = getenv("SKIMI_ATTN_ABL") ? atoi(getenv("SKIMI_ATTN_ABL")) : 0;
+    const int dbg = (int)env_once("SKIMI_ATTN_ABL", 0);
 #else
     const int dbg = 0;
 #endif
@@ -318,9 +295,7 @@ int attention_launch(const void* qkv, void* out, int dtype, int batch, int seq, 
     if (dtype == SKIMI_F32) {
         // fp32-accurate mode: the bf16x3 kernel when the caller lends scratch for the hi / lo planes (SKIMI_ATTN_X3=0: the
         // exact-fp32 MFMA kernel, A/B timing and a cross-check in the tests)
-        static const bool dyn = getenv("SKIMI_ENV_DYNAMIC") && atoi(getenv("SKIMI_ENV_DYNAMIC"));
-        static int use_x3 = -1;
-        if (use_x3 < 0 || dyn) use_x3 = getenv("SKIMI_ATTN_X3") ? atoi(getenv("SKIMI_ATTN_X3")) : 1;
+        const int use_x3 = (int)env_switch("SKIMI_ATTN_X3", 1);
         const long tokens = (long)batch * seq;
         if (use_x3 && head_dim == 64 && x3_scratch && x3_scratch_bytes >= attention_x3_scratch_bytes(tokens, 3 * C)) {
             const bool rec = want_rec && ((uintptr_t)out & 127) == 0;

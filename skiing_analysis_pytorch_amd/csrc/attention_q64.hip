@@ -37,44 +37,26 @@
 // (zero operands: 1144-1218 TFLOP/s, tools/mb_attn_power.py), not short of MFMA / VALU overlap.
 #include <stdlib.h>
 
+#include "attention_tile.h"
 #include "common.h"
+#include "env.h"
 #include "kernels.h"
 
 namespace skimi {
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
 typedef __attribute__((ext_vector_type(2))) float f32x2;
 
-__device__ __forceinline__ float xhalf_max(float x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __builtin_fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float xhalf_sum(float x) {
-    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
+using namespace att;   // the K / V tile layout shared with attention_bf16.hip and attention_x3.hip
 
 template <int dbg>   // dbg != 0: timing ablations (SKIMI_ATTN_ABL), results are wrong
 __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int nqb) {
-    constexpr int KV = 64;                 // keys per tile
-    constexpr int TILE = KV * 64 * 2;      // bytes of one K (or V) tile
     __shared__ __attribute__((aligned(16))) char smem[4 * TILE];   // [buf][K|V]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
 
-    int id;
-    {
-        const int nblk = gridDim.x;
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7;
-        const int q = nblk >> 3, r = nblk & 7;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int id = xcd_contiguous_id();   // one XCD's L2 holds a head's K/V
     const int qb = id % nqb;
     const int bh = id / nqb;
     const int head = bh % a.heads, b = bh / a.heads;
@@ -104,9 +86,7 @@ __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int 
                 for (int j = 0; j < 8; ++j) qf[qi][s][j] = (short)f2bf(bf2f((unsigned short)qf[qi][s][j]) * c2q);
     }
 
-    // K/V staging by LDS-DMA: one wave-instruction lands 8 rows x 128 B linearly, bank swizzles on
-    // the per-lane SOURCE chunk (K: chunk ^= (row>>1)&7; V: chunk ^= ((row>>1)&1)<<2), rows past
-    // the end clamped (their scores are masked to -inf)
+    // K/V staging by LDS-DMA, source-side bank swizzles, rows past the end clamped: attention_tile.h
     const int nkt = (a.seq_k + KV - 1) / KV;
     const bool ragged = (a.seq_k & (KV - 1)) != 0;
     const int srow = lane >> 3, sch = lane & 7;
@@ -115,14 +95,12 @@ __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int 
         char* vb = kb + TILE;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int row = 8 * (2 * wave + j) + srow;                 // tile row 0..63
+            const int row = DMA_ROWS * (2 * wave + j) + srow;          // tile row 0..63
             const int key = min(kt * KV + row, a.seq_k - 1);
-            const int kc = sch ^ ((row >> 1) & 7);
+            const int kc = sch ^ ((row >> 1) & 7);                      // the source swizzles of attention_tile.h
             const int vc = sch ^ (((row >> 1) & 1) << 2);
-            __builtin_amdgcn_global_load_lds((gbl_void*)(K + (long)key * a.k_row + kc * 8),
-                                             (lds_void*)(kb + (2 * wave + j) * 8 * 128), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gbl_void*)(V + (long)key * a.v_row + vc * 8),
-                                             (lds_void*)(vb + (2 * wave + j) * 8 * 128), 16, 0, 0);
+            lds_dma16(K + (long)key * a.k_row + kc * 8, kb + (2 * wave + j) * DMA_ROWS * ROW);
+            lds_dma16(V + (long)key * a.v_row + vc * 8, vb + (2 * wave + j) * DMA_ROWS * ROW);
         }
     };
 
@@ -141,13 +119,9 @@ __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int 
     if (lh == 0) kone[0] = (short)0x3F80;
     bf16x8 qneg[2] = {{0, 0, 0, 0, 0, 0, 0, 0}, {0, 0, 0, 0, 0, 0, 0, 0}};
 
-    // LDS-DMA double buffer, visibility protocol: a wave's global_load_lds writes land in LDS when ITS vmcnt
-    // reaches 0, so every wave waits vmcnt(0) on its own DMA and only then enters the workgroup barrier; after
-    // the barrier all four waves' shares of the tile are in LDS.  The wait is written out (not left to how
-    // hipcc lowers __syncthreads(); gfx950 barriers do not wait for memory counters by themselves), and
-    // tests/test_abi.py greps the emitted ISA for `s_waitcnt vmcnt(0)` ahead of every s_barrier of this kernel.
+    // LDS-DMA double buffer: own wait_vmcnt<0>(), then the workgroup barrier (the visibility protocol: gfx950.h)
     issue(0, 0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+    wait_vmcnt<0>();
     __syncthreads();
 
     for (int kt = 0; kt < nkt; ++kt) {
@@ -163,7 +137,7 @@ __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int 
             const int row = t * 32 + l31;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks)
-                kf[t][ks] = *reinterpret_cast<const bf16x8*>(kb + row * 128 + (((2 * ks + lh) ^ ((row >> 1) & 7)) << 4));
+                kf[t][ks] = *reinterpret_cast<const bf16x8*>(kb + k_frag_off(row, ks, lh));
         }
         __builtin_amdgcn_sched_barrier(0);   // all 8 reads in flight before the first MFMA waits (counted lgkmcnt)
 #pragma unroll
@@ -179,6 +153,7 @@ __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int 
         }
 
         // ---- V^T fragments (ds_read_b64_tr_b16 of the row-major [key][d] tile), shared by both blocks ----
+        // (the loop body mirrors read_vt of attention_tile.h)
         bf16x8 vf[2][2][2];   // [32-key block][16-key step][d tile]
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -186,13 +161,9 @@ __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int 
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
-                    const int q4 = (lane & 15) >> 2, p4 = lane & 3;
-                    const int dcol = dt * 32 + 16 * ((lane >> 4) & 1) + 4 * p4;   // first of 4 d columns
 #pragma unroll
                     for (int half = 0; half < 2; ++half) {
-                        const int row = t * 32 + 16 * ks + 8 * half + 4 * lh + q4;
-                        const int chunk = (dcol >> 3) ^ (((row >> 1) & 1) << 2);
-                        const char* addr = vb + row * 128 + (chunk << 4) + ((dcol & 7) << 1);
+                        const char* addr = vt_ptr(vb, t, ks, dt, half, lane, lh);
                         const s16x4 v4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)addr);
                         vf[t][ks][dt][4 * half + 0] = v4[0];
                         vf[t][ks][dt][4 * half + 1] = v4[1];
@@ -215,7 +186,7 @@ __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int 
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int key = kt * KV + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                        const int key = acc_key(kt * KV + t * 32, r, lh);
                         if (key >= a.seq_k) s[qi][t][r] = -INFINITY;
                     }
         }
@@ -261,13 +232,13 @@ __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int 
                         s[qi][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kone, qneg[qi], zero16, 0, 0, 0);
 #pragma unroll
                         for (int ks = 0; ks < 4; ++ks) {
-                            const bf16x8 kr = *reinterpret_cast<const bf16x8*>(kb + row * 128 + (((2 * ks + lh) ^ ((row >> 1) & 7)) << 4));
+                            const bf16x8 kr = *reinterpret_cast<const bf16x8*>(kb + k_frag_off(row, ks, lh));
                             s[qi][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kr, qf[qi][ks], s[qi][t], 0, 0, 0);
                         }
                         if (ragged && kt == nkt - 1) {
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
-                                const int key = kt * KV + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                                const int key = acc_key(kt * KV + t * 32, r, lh);
                                 if (key >= a.seq_k) s[qi][t][r] = -INFINITY;
                             }
                         }
@@ -327,7 +298,7 @@ __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int 
                 }
         }
 
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's share of tile kt+1 has landed in LDS
+        wait_vmcnt<0>();   // this wave's share of tile kt+1 has landed in LDS
         if (!(dbg & 1)) __syncthreads();
     }
 
@@ -355,7 +326,7 @@ __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int 
                 if (q < a.seq_q) {
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
-                        *reinterpret_cast<int*>(pq + dt * 32 + 8 * g + 4 * lh) =
+                        *reinterpret_cast<int*>(out_ptr(pq, dt, g, lh)) =
                             mx_pack4(o[qi][dt][4 * g] * inv, o[qi][dt][4 * g + 1] * inv, o[qi][dt][4 * g + 2] * inv,
                                      o[qi][dt][4 * g + 3] * inv, si);
                 }
@@ -372,7 +343,7 @@ __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int 
                     bf16x4 v;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) v[j] = (short)f2x16(o[qi][dt][4 * g + j] * inv, a.out_f16 != 0);
-                    *reinterpret_cast<bf16x4*>(op + dt * 32 + 8 * g + 4 * lh) = v;
+                    *reinterpret_cast<bf16x4*>(out_ptr(op, dt, g, lh)) = v;
                 }
         }
     }
@@ -382,12 +353,12 @@ void attention_q64_dispatch(const AttnArgs& a, hipStream_t st) {
     const int nqb = (int)cdiv(a.seq_q, 256);
     const long nblk = (long)nqb * a.heads * a.batch;
 #ifdef SKIMI_ABLATIONS   // timing ablations (wrong results): only in a -DSKIMI_ABLATIONS build
-    static const int dbg = getenv("SKIMI_ATTN_ABL") ? atoi(getenv("SKIMI_ATTN_ABL")) : 0;
+    const int dbg = (int)env_once("SKIMI_ATTN_ABL", 0);
 #else
     const int dbg = 0;
 #endif
     // SKIMI_ATTN_LDSPAD (bytes of unused dynamic LDS): occupancy experiments, e.g. 65536 -> one workgroup per CU
-    static const size_t pad = getenv("SKIMI_ATTN_LDSPAD") ? (size_t)atol(getenv("SKIMI_ATTN_LDSPAD")) : 0;
+    const size_t pad = (size_t)env_once("SKIMI_ATTN_LDSPAD", 0);
     if (pad) {
         static bool once = false;
         if (!once) {

@@ -14,16 +14,12 @@
 // row sums are fp32 VALU adds of the unsplit p.  Output fp32.
 #include <stdlib.h>
 
+#include "attention_tile.h"
 #include "common.h"
 #include "gemm_epilogue.h"
 #include "kernels.h"
 
 namespace skimi {
-
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
 
 struct AttnX3Args {
     const float* q;                       // fp32, AttnArgs strides (elements)
@@ -36,39 +32,15 @@ struct AttnX3Args {
     float scale;
 };
 
-__device__ __forceinline__ bf16x8 read_tr(const char* vb, int t, int ks, int dt, int lane, int lh) {
-    // V^T fragment of the row-major [key][d] tile by ds_read_b64_tr_b16 (attention_bf16.hip)
-    const int q4 = (lane & 15) >> 2, p4 = lane & 3;
-    const int dcol = dt * 32 + 16 * ((lane >> 4) & 1) + 4 * p4;
-    bf16x8 vf;
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        const int row = t * 32 + 16 * ks + 8 * half + 4 * lh + q4;
-        const int chunk = (dcol >> 3) ^ (((row >> 1) & 1) << 2);
-        const char* addr = vb + row * 128 + (chunk << 4) + ((dcol & 7) << 1);
-        const s16x4 v4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)addr);
-        vf[4 * half + 0] = v4[0];
-        vf[4 * half + 1] = v4[1];
-        vf[4 * half + 2] = v4[2];
-        vf[4 * half + 3] = v4[3];
-    }
-    return vf;
-}
+using namespace att;   // the K / V tile layout shared with attention_bf16.hip and attention_q64.hip
 
 __global__ __launch_bounds__(256, 2) void attn_x3_kernel(const AttnX3Args a, int nqb) {
-    constexpr int KV = 64;
-    constexpr int TILE = KV * 64 * 2;      // bytes of one bf16 tile
     __shared__ __attribute__((aligned(16))) char smem[8 * TILE];   // [buf][K hi | K lo | V hi | V lo]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l31 = lane & 31, lh = lane >> 5;
-    int id;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x, xcd = bid & 7;
-        const int q = nblk >> 3, r = nblk & 7;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int id = xcd_contiguous_id();   // one XCD's L2 holds a head's K/V planes
     const int qb = id % nqb;
     const int bh = id / nqb;
     const int head = bh % a.heads, b = bh / a.heads;
@@ -105,15 +77,15 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(const AttnX3Args a, int
         char* base = smem + buf * 4 * TILE;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            const int row = 8 * (2 * wave + j) + srow;
+            const int row = DMA_ROWS * (2 * wave + j) + srow;
             const int key = min(kt * KV + row, a.seq_k - 1);
-            const int kc = sch ^ ((row >> 1) & 7);
+            const int kc = sch ^ ((row >> 1) & 7);                      // the source swizzles of attention_tile.h
             const int vc = sch ^ (((row >> 1) & 1) << 2);
-            const int dst = (2 * wave + j) * 8 * 128;
-            __builtin_amdgcn_global_load_lds((gbl_void*)(Kh + (long)key * a.k_row + kc * 8), (lds_void*)(base + dst), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gbl_void*)(Kl + (long)key * a.k_row + kc * 8), (lds_void*)(base + TILE + dst), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gbl_void*)(Vh + (long)key * a.v_row + vc * 8), (lds_void*)(base + 2 * TILE + dst), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gbl_void*)(Vl + (long)key * a.v_row + vc * 8), (lds_void*)(base + 3 * TILE + dst), 16, 0, 0);
+            const int dst = (2 * wave + j) * DMA_ROWS * ROW;
+            lds_dma16(Kh + (long)key * a.k_row + kc * 8, base + dst);
+            lds_dma16(Kl + (long)key * a.k_row + kc * 8, base + TILE + dst);
+            lds_dma16(Vh + (long)key * a.v_row + vc * 8, base + 2 * TILE + dst);
+            lds_dma16(Vl + (long)key * a.v_row + vc * 8, base + 3 * TILE + dst);
         }
     };
 
@@ -127,7 +99,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(const AttnX3Args a, int
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
     issue(0, 0);
-    __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): own LDS-DMA landed, then the barrier (protocol: attention_q64.hip)
+    wait_vmcnt<0>();   // own LDS-DMA landed, then the barrier (protocol: gfx950.h)
     __syncthreads();
 
     for (int kt = 0; kt < nkt; ++kt) {
@@ -145,7 +117,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(const AttnX3Args a, int
             const int row = t * 32 + l31;
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
-                const int off = row * 128 + (((2 * ks + lh) ^ ((row >> 1) & 7)) << 4);
+                const int off = k_frag_off(row, ks, lh);
                 const bf16x8 kfh = *reinterpret_cast<const bf16x8*>(kbh + off);
                 const bf16x8 kfl = *reinterpret_cast<const bf16x8*>(kbl + off);
                 s[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfl, qh[ks], ks == 0 ? zero16 : s[t], 0, 0, 0);
@@ -158,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(const AttnX3Args a, int
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int key = kt * KV + t * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                    const int key = acc_key(kt * KV + t * 32, r, lh);
                     if (key >= a.seq_k) s[t][r] = -INFINITY;
                 }
         }
@@ -205,15 +177,15 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(const AttnX3Args a, int
                 }
 #pragma unroll
                 for (int dt = 0; dt < 2; ++dt) {
-                    const bf16x8 vfh = read_tr(vbh, t, ks, dt, lane, lh);
-                    const bf16x8 vfl = read_tr(vbl, t, ks, dt, lane, lh);
+                    const bf16x8 vfh = read_vt(vbh, t, ks, dt, lane, lh);
+                    const bf16x8 vfl = read_vt(vbl, t, ks, dt, lane, lh);
                     o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfl, ph, o[dt], 0, 0, 0);
                     o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfh, pl, o[dt], 0, 0, 0);
                     o[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfh, ph, o[dt], 0, 0, 0);
                 }
             }
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) ahead of the barrier, written out
+        wait_vmcnt<0>();   // ahead of the barrier, written out
         __syncthreads();
     }
 
@@ -258,7 +230,7 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(const AttnX3Args a, int
         for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
             for (int g = 0; g < 4; ++g)
-                *reinterpret_cast<float4*>(op + dt * 32 + 8 * g + 4 * lh) =
+                *reinterpret_cast<float4*>(out_ptr(op, dt, g, lh)) =
                     make_float4(o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv, o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv);
     }
 }

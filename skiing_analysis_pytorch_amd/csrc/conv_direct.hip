@@ -18,12 +18,10 @@
 //   * the epilogue stores straight from the accumulator layout: for every register 32 lanes hold
 //     the 32 output channels of one pixel = one full 128-B line.
 #include "common.h"
+#include "gfx950.h"
 #include "kernels.h"
 
 namespace skimi {
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
 
 __device__ uint4 g_conv_zero_page[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 
@@ -115,7 +113,7 @@ __global__ __launch_bounds__(512, 2) void conv_direct_n32_kernel(const ConvDirec
             w_off[j] = row * 32 + sc * 8;
         }
     }
-    auto stage = [&](int buf, int s) {
+    auto stage = [&](int buf, int s) {   // the bare builtin = lds_dma16 of gfx950.h, which moves this kernel's m0 writes
         char* base = smem + buf * CD_BUF;
 #pragma unroll
         for (int j = 0; j < 3; ++j) {

@@ -23,13 +23,12 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "env.h"
 #include "gemm_epilogue.h"
+#include "gfx950.h"
 #include "kernels.h"
 
 namespace skimi {
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
 
 __device__ uint4 g_cw_zero_page[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
 
@@ -43,14 +42,6 @@ constexpr int CW_RING = 4;
 constexpr int CW_LDS = 2 * CW_WIN + CW_RING * CW_TAP;    // 79872 B: two workgroups per CU
 constexpr int CW_STG_ROW = 72;                           // epilogue staging: floats per pixel row (64 + pad: the two lane halves hit different banks)
 
-#define CW_BAR()                              \
-    do {                                      \
-        __builtin_amdgcn_sched_barrier(0);    \
-        __builtin_amdgcn_s_barrier();         \
-        __builtin_amdgcn_sched_barrier(0);    \
-    } while (0)
-// s_waitcnt vmcnt(N) only (expcnt / lgkmcnt fields at their maxima)
-#define CW_VMCNT(N) __builtin_amdgcn_s_waitcnt(0x0F70 | ((N) & 15) | (((N) >> 4) << 14))
 
 // DMA instructions a wave issues in the step of tap t: two weight pieces, and a window piece while t < 6
 __host__ __device__ constexpr int cw_ops(int t) { return 2 + (t < 6 ? 1 : 0); }
@@ -73,13 +64,7 @@ __global__ __launch_bounds__(256, 2) void conv_win128_kernel(const GemmArgs p, i
     const int l31 = lane & 31, lh = lane >> 5;
     const int ph = wave >> 1, ch = wave & 1;   // pixel half (tile rows 8 ph ..), cout half
 
-    // tile id contiguous per XCD (blocks b and b + 8 share an XCD): neighbouring tiles share their halo rows in one L2
-    int bid;
-    {
-        const int nblk = gridDim.x, b = blockIdx.x, xcd = b & 7;
-        const int qn = nblk >> 3, rn = nblk & 7;
-        bid = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
-    }
+    int bid = xcd_contiguous_id();   // neighbouring tiles share their halo rows in one L2
     const int tx = bid % tiles_x;
     bid /= tiles_x;
     const int ty = bid % tiles_y;
@@ -111,6 +96,7 @@ __global__ __launch_bounds__(256, 2) void conv_win128_kernel(const GemmArgs p, i
         w_off[j] = row * (int)p.ldw + (((lane & 3) ^ ((row >> 2) & 3)) << 3);
     }
     char* const ring = smem + 2 * CW_WIN;
+    // (the bare builtin = lds_dma16 of gfx950.h, which changes this kernel's schedule)
     auto issue_w = [&](int s, int tap, int slot) {   // (slice, tap) -> ring slot
         const unsigned short* src = Wt + tap * C + s * 32;
 #pragma unroll
@@ -159,12 +145,12 @@ __global__ __launch_bounds__(256, 2) void conv_win128_kernel(const GemmArgs p, i
         for (int t = 0; t < 9; ++t) {
             // this wave's pieces of tap t (and, at t = 0, of the window) have landed: vmcnt(cw_allowed(t)), an immediate
             switch (t) {
-                case 0: CW_VMCNT(4); break;
-                case 1: case 8: CW_VMCNT(5); break;
-                case 2: case 7: CW_VMCNT(6); break;
-                default: CW_VMCNT(7); break;
+                case 0: wait_vmcnt<4>(); break;
+                case 1: case 8: wait_vmcnt<5>(); break;
+                case 2: case 7: wait_vmcnt<6>(); break;
+                default: wait_vmcnt<7>(); break;
             }
-            if constexpr (!(ABL & 16)) CW_BAR();                          // ... and everybody else's; all waves are done with step q - 1
+            if constexpr (!(ABL & 16)) fenced_barrier();                          // ... and everybody else's; all waves are done with step q - 1
             {
                 const int t3 = (t + 3) % 9;
                 const int s3 = min(s + (t + 3 >= 9 ? 1 : 0), nsl - 1);
@@ -211,8 +197,8 @@ __global__ __launch_bounds__(256, 2) void conv_win128_kernel(const GemmArgs p, i
             __builtin_amdgcn_sched_group_barrier(0x008, 10, 0);
         }
     }
-    CW_VMCNT(0);   // the clamped tail reloads
-    CW_BAR();      // every wave is past its last fragment read: the whole LDS is free
+    wait_vmcnt<0>();   // the clamped tail reloads
+    fenced_barrier();      // every wave is past its last fragment read: the whole LDS is free
 
     // ---- epilogue: 32 pixels x 64 couts at a time through a wave-private LDS tile -> row-contiguous 16-B accesses ----
     float* stg = reinterpret_cast<float*>(smem) + wave * (32 * CW_STG_ROW);
@@ -224,7 +210,7 @@ __global__ __launch_bounds__(256, 2) void conv_win128_kernel(const GemmArgs p, i
 #pragma unroll
             for (int r = 0; r < 16; ++r) stg[((r & 3) + 8 * (r >> 2) + 4 * lh) * CW_STG_ROW + j * 32 + l31] = acc[i][j][r];
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the tile is written (one wave: LDS executes its accesses in order)
+        wait_lgkmcnt0();   // lgkmcnt(0): the tile is written (one wave: LDS executes its accesses in order)
 #pragma unroll 1
         for (int it = 0; it < 8; ++it) {
             const int row_l = it * 4 + (lane >> 4);
@@ -236,15 +222,13 @@ __global__ __launch_bounds__(256, 2) void conv_win128_kernel(const GemmArgs p, i
                 store_four(p, rm, n, v);
             }
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);   // the reads are done before the next pass overwrites the tile
+        wait_lgkmcnt0();   // the reads are done before the next pass overwrites the tile
     }
 }
 
 // SKIMI_CONV_WIN: 1 (default) where the shape pays, 0 never (A/B timing), 2 wherever the kernel applies (tests)
 static int conv_win_mode() {
-    static const bool dyn = getenv("SKIMI_ENV_DYNAMIC") && atoi(getenv("SKIMI_ENV_DYNAMIC"));
-    static int mode = -1;
-    if (mode < 0 || dyn) mode = getenv("SKIMI_CONV_WIN") ? atoi(getenv("SKIMI_CONV_WIN")) : 1;
+    const int mode = (int)env_switch("SKIMI_CONV_WIN", 1);
     return mode;
 }
 
@@ -280,7 +264,7 @@ int conv_win_launch(GemmArgs& a, hipStream_t st) {
     a.splitk = 1;
     a.partial = nullptr;
     // SKIMI_CONV_WIN_LDSPAD (bytes of unused dynamic LDS): occupancy experiments, e.g. 8192 -> one workgroup per CU
-    static const int pad = getenv("SKIMI_CONV_WIN_LDSPAD") ? atoi(getenv("SKIMI_CONV_WIN_LDSPAD")) : 0;
+    const int pad = (int)env_once("SKIMI_CONV_WIN_LDSPAD", 0);
     const int lds = CW_LDS + pad;
 #define CW_GO(F16_, ABL_)                                                                                                      \
     do {                                                                                                                       \

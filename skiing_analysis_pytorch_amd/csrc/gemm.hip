@@ -19,14 +19,13 @@
 //   * blockIdx -> tile map is XCD-aware: each XCD walks a contiguous run of tiles that share
 //     an A row panel, so the panel and W stay in that XCD's L2.
 #include "common.h"
+#include "env.h"
 #include "gemm_epilogue.h"
+#include "gfx950.h"
 #include <algorithm>
 #include <stdlib.h>
 
 namespace skimi {
-
-// 0 / 1 environment switch, read once
-#define SKIMI_ENV_FLAG(NAME) ([]() { static const bool v = getenv(NAME) && atoi(getenv(NAME)); return v; }())
 
 // ---- staging helpers ------------------------------------------------------------------
 template <typename T> struct Stage;
@@ -110,19 +109,17 @@ __global__ __launch_bounds__(256) void gemm_kernel(const GemmArgs p) {
     const int wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
 
-    // XCD-aware, bijective workgroup -> (K split, tile) map.  Workgroups are dealt to the 8 XCDs round-robin
-    // in launch order (x fastest, then y), so linear ids l and l + 8 share an L2.  Each XCD takes a contiguous
-    // run of the split-major order (split, tile): with split-K it owns whole K ranges, so every byte of W and
-    // of A is pulled through ONE L2 instead of through the L2 of every XCD that holds a tile of that row /
-    // column (measured on the B = 1 lifter convs: FETCH_SIZE 51 MB for 14.5 MB of operands before).
+    // workgroup -> (K split, tile), XCD-contiguous (gfx950.h) over the 2-D grid in launch order (x fastest, then
+    // y).  Each XCD takes a contiguous run of the split-major order (split, tile): with split-K it owns whole K
+    // ranges, so every byte of W and of A is pulled through ONE L2 instead of through the L2 of every XCD that
+    // holds a tile of that row / column (measured on the B = 1 lifter convs: FETCH_SIZE 51 MB for 14.5 MB of
+    // operands before).
     int id, ks;
     {
         const int ntile = p.ntm * p.ntn;
         const int nblk = ntile * (int)gridDim.y;
         const int lin = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
-        const int xcd = lin & 7;
-        const int q = nblk >> 3, r = nblk & 7;
-        const int ord = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
+        const int ord = xcd_contiguous_id(lin, nblk);
         ks = ord / ntile;
         id = ord - ks * ntile;
     }
@@ -565,7 +562,7 @@ int gemm_dispatch(const skimi_gemm_desc* d, hipStream_t st, void* scratch, size_
     // every mode: a fixed summation order over the K splits (one slab plane per split, added in order by the epilogue)
     // instead of global float atomics, whose arrival order changes the last bits from run to run -- and, through the
     // track head's iterations, its tracks by up to a fifth of a pixel.  SKIMI_SPLITK_ATOMIC=1: atomics (A/B timing).
-    bool ordered = !SKIMI_ENV_FLAG("SKIMI_SPLITK_ATOMIC");
+    bool ordered = !(int)env_once("SKIMI_SPLITK_ATOMIC", 0);
     const size_t plane = (size_t)d->M * d->N * sizeof(float);
     if (force_splitk > 0) {
         splitk = force_splitk;

@@ -21,25 +21,19 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "env.h"
 #include "gemm_epilogue.h"
+#include "gfx950.h"
 
 namespace skimi {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
-
-// blockIdx -> output tile.  Workgroups are dealt to the 8 XCDs round-robin, so the blocks with equal
-// blockIdx & 7 share an L2: give each XCD a contiguous run of tile ids (bijective for any count),
-// and order the ids so that the ~32 tiles an XCD runs at once form an 8-row x 4-column patch
+// blockIdx -> output tile: XCD-contiguous tile ids (gfx950.h), ordered so that the ~32 tiles an XCD runs at once
+// form an 8-row x 4-column patch
 // (groups of 8 tile rows, column-major inside a group): per K-step that patch pulls 8 A panels and
 // 4 W panels through the L2 instead of 2-3 A panels and every W panel (row-major order), which is
 // what bounds the LDS-DMA stream.
 __device__ __forceinline__ void tile_coords256(const GemmArgs& p, int& tm, int& tn) {
-    const int nblk = p.ntm * p.ntn;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7;
-    const int q = nblk >> 3, r = nblk & 7;
-    const int id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+    const int id = xcd_contiguous_id(blockIdx.x, p.ntm * p.ntn);
     constexpr int GM = 8;
     const int per_group = GM * p.ntn;
     const int group = id / per_group, within = id - group * per_group;
@@ -117,7 +111,7 @@ __device__ __forceinline__ void epilogue256(const GemmArgs& p, ACC& acc, char* s
     do {                                                                                                        \
         acc_to_slab<MT>(stg, acc, i, lane);                                                                     \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                  \
-        __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0) */                                                    \
+        wait_lgkmcnt0(); /* lgkmcnt(0) */                                                                       \
     } while (0)
 
     if (EPI == 2 && interior) {
@@ -149,7 +143,7 @@ __device__ __forceinline__ void epilogue256(const GemmArgs& p, ACC& acc, char* s
                     r[i % PF][it] =
                         *reinterpret_cast<const float4*>((const float*)p.resid + (long)(mrow + PF * 32 + it * 4) * p.ldr + n);
             }
-            __builtin_amdgcn_s_waitcnt(0xC07F);   // slab reads retired before the next pass overwrites it
+            wait_lgkmcnt0();   // slab reads retired before the next pass overwrites it
         }
         return;
     }
@@ -181,7 +175,7 @@ __device__ __forceinline__ void epilogue256(const GemmArgs& p, ACC& acc, char* s
                 }
                 *reinterpret_cast<bf16x4*>((unsigned short*)p.out + (long)(mrow + it * 4) * p.ldo + n) = pack4_16<H16>(y0, y1, y2, y3);
             }
-            __builtin_amdgcn_s_waitcnt(0xC07F);   // slab reads retired before the next pass overwrites it
+            wait_lgkmcnt0();   // slab reads retired before the next pass overwrites it
         }
         return;
     }
@@ -229,7 +223,7 @@ __device__ __forceinline__ void epilogue256(const GemmArgs& p, ACC& acc, char* s
                 }
             }
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        wait_lgkmcnt0();
     }
 #undef SKIMI_ACC_TO_SLAB
 }
@@ -284,10 +278,10 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
         char* wb = smem + buf * BUF + A_TILE + (4 * wave) * 8 * RB;
 #pragma unroll
         for (int j = 0; j < MT; ++j)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(a_src[j] + kt * BK), (lds_void*)(ab + j * 8 * RB), 16, 0, 0);
+            lds_dma16(a_src[j] + kt * BK, ab + j * 8 * RB);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(w_src[j] + kt * BK), (lds_void*)(wb + j * 8 * RB), 16, 0, 0);
+            lds_dma16(w_src[j] + kt * BK, wb + j * 8 * RB);
     };
 
     f32x16 acc[MT][2];
@@ -362,14 +356,6 @@ __global__ __launch_bounds__(512, 2) void gemm256_kernel(const GemmArgs p) {
 // P2 -> P4, HA[1] P3 -> next P1, HW[0] P1 -> next P2.
 // M16: a quadrant is 4 x 2 tiles of 16x16 in 2 k-steps of 32 (16 v_mfma_f32_16x16x32 instead of 8 of 32x32x16: the
 // same MFMA cycles), with the same 8 + 4 fragment reads per phase (rows l & 15, 16-B chunk 4 s + (l >> 4)).
-#define SKIMI_BAR()                           \
-    do {                                      \
-        __builtin_amdgcn_sched_barrier(0);    \
-        __builtin_amdgcn_s_barrier();         \
-        __builtin_amdgcn_sched_barrier(0);    \
-    } while (0)
-// s_waitcnt vmcnt(N) only (expcnt / lgkmcnt fields at their maxima)
-#define SKIMI_VMCNT(N) __builtin_amdgcn_s_waitcnt(0x0F70 | ((N) & 15) | (((N) >> 4) << 14))
 
 template <int EPI, int DEEP, bool F16 = false, bool M16 = false>
 __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
@@ -416,16 +402,14 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
         char* base = smem + (kt & 1) * BUF;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(a_src[h][j] + kt * BK), (lds_void*)(base + a_row0[h][j] * RB), 16,
-                                             0, 0);
+            lds_dma16(a_src[h][j] + kt * BK, base + a_row0[h][j] * RB);
     };
     auto issue_w = [&](int h, int kt) {
         if (no_dma) return;
         char* base = smem + (kt & 1) * BUF + A_TILE;
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(w_src[h][j] + kt * BK), (lds_void*)(base + w_row0[h][j] * RB), 16,
-                                             0, 0);
+            lds_dma16(w_src[h][j] + kt * BK, base + w_row0[h][j] * RB);
     };
 
     f32x16 acc[MT][2];           // 32x32 tiles
@@ -447,12 +431,12 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
         issue_a(0, 1);
         if (DEEP) issue_w(0, 1);
         issue_w(1, 1);
-        if (DEEP) SKIMI_VMCNT(6); else SKIMI_VMCNT(4);
+        if (DEEP) wait_vmcnt<6>(); else wait_vmcnt<4>();
     } else {
-        SKIMI_VMCNT(0);
+        wait_vmcnt<0>();
     }
-    SKIMI_BAR();
-    if (wr == 1) SKIMI_BAR();   // wave row 1 runs one barrier behind wave row 0
+    fenced_barrier();
+    if (wr == 1) fenced_barrier();   // wave row 1 runs one barrier behind wave row 0
 
     bf16x8 af[2][4], wf[2][4];   // A: [row block within the quadrant][k-step]; W: [jh][k-step]
     bf16x8 af16[4][2], wf16[2][2][2];   // M16: A [16-row block][k-step]; W [jh][16-column block][k-step]
@@ -505,7 +489,7 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
         };
 #define SKIMI_QUADRANT(IH, JH)                                                                                  \
     do {                                                                                                         \
-        SKIMI_BAR();                                                                                             \
+        fenced_barrier();                                                                                        \
         __builtin_amdgcn_s_setprio(1);                                                                           \
         if (no_mfma) {                                                                                           \
         } else if constexpr (M16) {                                                                              \
@@ -519,7 +503,7 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
             }                                                                                                    \
         }                                                                                                        \
         __builtin_amdgcn_s_setprio(0);                                                                           \
-        SKIMI_BAR();                                                                                             \
+        fenced_barrier();                                                                                        \
     } while (0)
 
         // P1
@@ -541,14 +525,14 @@ __global__ __launch_bounds__(512, 2) void gemm256pp_kernel(const GemmArgs p) {
         // P4
         if (kt + 2 < nkt) {
             issue_w(1, kt + 2);
-            if (DEEP) SKIMI_VMCNT(6); else SKIMI_VMCNT(4);
+            if (DEEP) wait_vmcnt<6>(); else wait_vmcnt<4>();
         } else {
-            SKIMI_VMCNT(0);
+            wait_vmcnt<0>();
         }
         SKIMI_QUADRANT(1, 0);
 #undef SKIMI_QUADRANT
     }
-    if (wr == 0) SKIMI_BAR();   // re-align the two wave rows: nobody reads operand tiles any more
+    if (wr == 0) fenced_barrier();   // re-align the two wave rows: nobody reads operand tiles any more
 
     if constexpr (M16) epilogue256<MT, EPI, 2, F16 && EPI == 3>(p, acc16, smem, wave, lane, wr, wc, m0, n0);
     else epilogue256<MT, EPI, 2, F16 && EPI == 3>(p, acc, smem, wave, lane, wr, wc, m0, n0);
@@ -604,7 +588,7 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
         char* base = smem + slot * PIECE + (4 * wave) * 8 * RB;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(src[q][j] + kt * BK), (lds_void*)(base + j * 8 * RB), 16, 0, 0);
+            lds_dma16(src[q][j] + kt * BK, base + j * 8 * RB);
     };
 
     if constexpr (M16) {
@@ -622,8 +606,7 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
         else fb[n - 8] = *reinterpret_cast<const bf16x8*>(smem + sw * PIECE + off);
     };
     auto issue_one = [&](int q, int j, int kt, int slot) {
-        __builtin_amdgcn_global_load_lds((gbl_void*)(src[q][j] + kt * BK), (lds_void*)(smem + slot * PIECE + (4 * wave + j) * 8 * RB),
-                                         16, 0, 0);
+        lds_dma16(src[q][j] + kt * BK, smem + slot * PIECE + (4 * wave + j) * 8 * RB);
     };
 
     // [column half h][16-row block i][16-column block c]: columns 64 h + 16 c.  The MFMAs are inline asm on accumulators
@@ -664,11 +647,11 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
     if (nkt > 1) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) issue(q, 1, 4 + q);
-        SKIMI_VMCNT(16);
+        wait_vmcnt<16>();
     } else {
-        SKIMI_VMCNT(0);
+        wait_vmcnt<0>();
     }
-    SKIMI_BAR();
+    fenced_barrier();
     int sb = 0;   // slot of piece 0 of K-tile kt
 #pragma unroll
     for (int n = 0; n < 16; ++n) read_one(sb, 0, n, fa0, fb0);
@@ -677,7 +660,7 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
     // (an MFMA holds the SIMD for 16 cycles here instead of 32); the rest run back to back.
 #define SKIMI_W4_HEAD()                       \
     do {                                      \
-        __builtin_amdgcn_s_waitcnt(0xC07F);   \
+        wait_lgkmcnt0();                      \
         __builtin_amdgcn_sched_barrier(0);    \
     } while (0)
 #define SKIMI_W4_KTILE(N1, N2)                                                                       \
@@ -700,8 +683,8 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
            read (kt+1, k-step 0), issue (kt+2; q = 2, 3) into K-tile kt's A slots */                 \
         SKIMI_W4_HEAD();                                                                             \
         if (N1) {                                                                                    \
-            if (N2) SKIMI_VMCNT(8); else SKIMI_VMCNT(0);                                             \
-            SKIMI_BAR();                                                                             \
+            if (N2) wait_vmcnt<8>(); else wait_vmcnt<0>();                                           \
+            fenced_barrier();                                                                        \
         }                                                                                            \
         kstep(fa1, fb1, [&](int g) {                                                                 \
             if (N1 && g < 16) read_one(nsb, 0, g, fa0, fb0);                                         \
@@ -730,8 +713,8 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int c = 0; c < 4; ++c) asm volatile("" : "+a"(acc[h][i][c]));
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    SKIMI_BAR();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0 and 1
+    wait_lgkmcnt0();
+    fenced_barrier();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0 and 1
 
     epilogue256<4, EPI, 4, F16 && EPI == 3>(p, acc[0], smem, wave, lane, wr, 2 * wc, m0, n0);
     epilogue256<4, EPI, 4, F16 && EPI == 3>(p, acc[1], smem, wave, lane, wr, 2 * wc + 1, m0, n0);
@@ -771,11 +754,11 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
     if (nkt > 1) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) issue(q, 1, 4 + q);
-        SKIMI_VMCNT(16);
+        wait_vmcnt<16>();
     } else {
-        SKIMI_VMCNT(0);
+        wait_vmcnt<0>();
     }
-    SKIMI_BAR();
+    fenced_barrier();
     int sb = 0;   // slot of piece 0 of K-tile kt
     read(sb, 0, fa0, fb0);
     // One k-step: the fragments it multiplies were requested a whole k-step ago, so the lgkmcnt(0)
@@ -783,7 +766,7 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
     // dealt out between the first MFMAs (2 reads or 1 DMA per MFMA), the rest run back to back.
 #define SKIMI_W4_HEAD()                       \
     do {                                      \
-        __builtin_amdgcn_s_waitcnt(0xC07F);   \
+        wait_lgkmcnt0();                      \
         __builtin_amdgcn_sched_barrier(0);    \
     } while (0)
 #define SKIMI_W4_TAIL(NDMA)                                                        \
@@ -828,8 +811,8 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
         /* k-step 3 */                                                              \
         SKIMI_W4_HEAD();                                                            \
         if (N1) {                                                                   \
-            if (N2) SKIMI_VMCNT(8); else SKIMI_VMCNT(0);                            \
-            SKIMI_BAR();                                                            \
+            if (N2) wait_vmcnt<8>(); else wait_vmcnt<0>();                          \
+            fenced_barrier();                                                       \
             read(nsb, 0, fa0, fb0);                                                 \
             if (N2) {                                                               \
                 issue(2, kt + 2, sb);                                               \
@@ -851,8 +834,8 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_kernel(const GemmArgs p) {
 #undef SKIMI_W4_HEAD
 #undef SKIMI_W4_TAIL
 #undef SKIMI_W4_MFMA
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    SKIMI_BAR();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0 and 1
+    wait_lgkmcnt0();
+    fenced_barrier();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0 and 1
 
     epilogue256<4, EPI, 4, F16 && EPI == 3>(p, acc[0], smem, wave, lane, wr, 2 * wc, m0, n0);
     epilogue256<4, EPI, 4, F16 && EPI == 3>(p, acc[1], smem, wave, lane, wr, 2 * wc + 1, m0, n0);
@@ -902,7 +885,7 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_fp8_kernel(const GemmArgs p)
         char* base = smem + slot * PIECE + (4 * wave) * 8 * RB;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-            __builtin_amdgcn_global_load_lds((gbl_void*)(src[q][j] + (long)kt * BK), (lds_void*)(base + j * 8 * RB), 16, 0, 0);
+            lds_dma16(src[q][j] + (long)kt * BK, base + j * 8 * RB);
     };
     // E8M0 dwords (4 scale blocks of a K-tile) of this lane's rows: A rows 128 wr + 32 i + l31, W rows 128 wc + 32 j + l31
     const unsigned* asc[4];
@@ -970,17 +953,17 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_fp8_kernel(const GemmArgs p)
     if (nkt > 1) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) issue(q, 1, 4 + q);
-        SKIMI_VMCNT(16);
+        wait_vmcnt<16>();
     } else {
-        SKIMI_VMCNT(0);
+        wait_vmcnt<0>();
     }
     take_scales();
-    SKIMI_BAR();
+    fenced_barrier();
     int sb = 0;   // slot of piece 0 of K-tile kt
     readp(sb, 0, fa0, fb0);
 #define SKIMI_F8_HEAD()                       \
     do {                                      \
-        __builtin_amdgcn_s_waitcnt(0xC07F);   \
+        wait_lgkmcnt0();                      \
         __builtin_amdgcn_sched_barrier(0);    \
     } while (0)
     // 16 MFMAs with the next k-step's 16 fragment reads (2 per MFMA) and NV vector-memory instructions behind them
@@ -1016,8 +999,8 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_fp8_kernel(const GemmArgs p)
         /* k-step 1: scale blocks 2 / 3 */                                          \
         SKIMI_F8_HEAD();                                                            \
         if (N1) {                                                                   \
-            if (N2) SKIMI_VMCNT(8); else SKIMI_VMCNT(0);                            \
-            SKIMI_BAR();                                                            \
+            if (N2) wait_vmcnt<8>(); else wait_vmcnt<0>();                          \
+            fenced_barrier();                                                       \
             readp(nsb, 0, fa0, fb0);                                                \
             load_scales(kt + 1);                                                    \
             if (N2) {                                                               \
@@ -1028,7 +1011,7 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_fp8_kernel(const GemmArgs p)
         SKIMI_F8_MFMA(fa1, fb1, 2);                                                 \
         if (N1) SKIMI_F8_TAIL((N2 ? 16 : 8)); else __builtin_amdgcn_sched_barrier(0); \
         if (N1) {                                                                   \
-            SKIMI_VMCNT(PW);   /* the scales of K-tile kt + 1 have landed */         \
+            wait_vmcnt<PW>();   /* the scales of K-tile kt + 1 have landed */        \
             take_scales();                                                          \
         }                                                                           \
         sb = nsb;                                                                   \
@@ -1045,25 +1028,12 @@ __global__ __launch_bounds__(256, 1) void gemm256w4_fp8_kernel(const GemmArgs p)
 #undef SKIMI_F8_TAIL
 #undef SKIMI_F8_MFMA
 #undef SKIMI_F8_CAT
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    SKIMI_BAR();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0 and 1
+    wait_lgkmcnt0();
+    fenced_barrier();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0 and 1
 
     epilogue256<4, EPI, 4>(p, acc[0], smem, wave, lane, wr, 2 * wc, m0, n0);
     epilogue256<4, EPI, 4>(p, acc[1], smem, wave, lane, wr, 2 * wc + 1, m0, n0);
 }
-
-// integer environment switch; read once, or on every call under SKIMI_ENV_DYNAMIC=1 (lets a timing
-// script alternate variants inside one process: boxes and thermal state differ by several percent)
-static int env_int(const char* name, int dflt, int& cache, bool& have) {
-    static const bool dynamic = getenv("SKIMI_ENV_DYNAMIC") && atoi(getenv("SKIMI_ENV_DYNAMIC"));
-    if (!have || dynamic) {
-        const char* v = getenv(name);
-        cache = v ? atoi(v) : dflt;
-        have = true;
-    }
-    return cache;
-}
-#define SKIMI_ENV_INT(NAME, DFLT) ([]() { static int c; static bool h = false; return env_int(NAME, DFLT, c, h); }())
 
 // which compile-time epilogue serves this launch (0 = generic)
 static int epi_kind(const GemmArgs& a) {
@@ -1120,7 +1090,7 @@ static int launch256pp_(GemmArgs& a, hipStream_t st) {
 template <int EPI, bool F16, bool M16>
 static int launch256pp(GemmArgs& a, hipStream_t st) {
     if constexpr (F16) return launch256pp_<EPI, 1, true, M16>(a, st);
-    const int deep = SKIMI_ENV_INT("SKIMI_GEMM256_DEEP", 1);
+    const int deep = (int)env_switch("SKIMI_GEMM256_DEEP", 1);
     return deep ? launch256pp_<EPI, 1, false, M16>(a, st) : launch256pp_<EPI, 0, false, M16>(a, st);
 }
 
@@ -1173,7 +1143,7 @@ static int gemm256_pick(GemmArgs& a, hipStream_t st, int epi, bool mt3, bool w4,
 // one workgroup per CU, so time ~ ceil(tiles / 256) * (rows per tile)
 int gemm256_launch(GemmArgs& a, hipStream_t st) {
 #ifdef SKIMI_ABLATIONS   // timing ablations (wrong results): only in a -DSKIMI_ABLATIONS build
-    a.dbg = SKIMI_ENV_INT("SKIMI_GEMM256_ABL", 0);
+    a.dbg = (int)env_switch("SKIMI_GEMM256_ABL", 0);
 #else
     a.dbg = 0;
 #endif
@@ -1191,10 +1161,10 @@ int gemm256_launch(GemmArgs& a, hipStream_t st) {
     // SKIMI_GEMM256_MT3 / _W4 / _PP = 0 / 1 force a choice (A/B timing).
     // MFMA shape of the single-stream and ping-pong loops (SKIMI_GEMM256_MFMA = 16 | 32): v_mfma_f32_16x16x32 by
     // default, measured against 32x32x16 interleaved on one box
-    const bool m16 = SKIMI_ENV_INT("SKIMI_GEMM256_MFMA", 16) != 32;
-    const int use_pp = SKIMI_ENV_INT("SKIMI_GEMM256_PP", 1);
-    const int use_mt3 = SKIMI_ENV_INT("SKIMI_GEMM256_MT3", -1);
-    const int use_w4 = SKIMI_ENV_INT("SKIMI_GEMM256_W4", -1);
+    const bool m16 = (int)env_switch("SKIMI_GEMM256_MFMA", 16) != 32;
+    const int use_pp = (int)env_switch("SKIMI_GEMM256_PP", 1);
+    const int use_mt3 = (int)env_switch("SKIMI_GEMM256_MT3", -1);
+    const int use_w4 = (int)env_switch("SKIMI_GEMM256_W4", -1);
     const bool mt3 = use_mt3 == 1 || (use_mt3 < 0 && cost(192) < 0.8 * cost(256));
     const bool w4 = use_w4 >= 0 ? use_w4 != 0 : (epi == 1 || (epi == 2 && a.K > 1024));
     // the loop gemm256_pick takes (the fp16 build has no two-phase 256-row loop: ping-pong in its place)

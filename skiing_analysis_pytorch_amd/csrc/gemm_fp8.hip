@@ -26,13 +26,13 @@
 #include <algorithm>
 
 #include "common.h"
+#include "env.h"
 #include "gemm_epilogue.h"
+#include "gfx950.h"
 #include "kernels.h"
 
 namespace skimi {
 
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
@@ -136,12 +136,7 @@ __global__ __launch_bounds__(256, TW == 2 ? 2 : 1) void gemm_fp8_kernel(const Fp
     const int l31 = lane & 31, lh = lane >> 5;
     const int wn = wave & 1, wm = wave >> 1;
     // tile order: XCD-contiguous ids, column-of-tiles-major inside (the 8 M-tiles next to each other share a W panel)
-    int id;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x, xcd = bid & 7;
-        const int q = nblk >> 3, r = nblk & 7;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int id = xcd_contiguous_id();
     constexpr int GM = 8;
     const int per_group = GM * p.ntn;
     const int group = id / per_group, within = id - group * per_group;
@@ -172,8 +167,8 @@ __global__ __launch_bounds__(256, TW == 2 ? 2 : 1) void gemm_fp8_kernel(const Fp
         const unsigned char* ak = abase + (long)kt * BK;
 #pragma unroll
         for (int j = 0; j < SR / 8; ++j) {
-            __builtin_amdgcn_global_load_lds((gbl_void*)(wk + woff[j]), (lds_void*)(wb + (SR * wave + 8 * j) * 128), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((gbl_void*)(ak + aoff[j]), (lds_void*)(ab + (SR * wave + 8 * j) * 128), 16, 0, 0);
+            lds_dma16(wk + woff[j], wb + (SR * wave + 8 * j) * 128);
+            lds_dma16(ak + aoff[j], ab + (SR * wave + 8 * j) * 128);
         }
     };
     // E8M0 dwords of this lane's rows: [tile i of W, tile j of A], one dword per K-tile
@@ -207,7 +202,7 @@ __global__ __launch_bounds__(256, TW == 2 ? 2 : 1) void gemm_fp8_kernel(const Fp
             sw[i] = swn[i] >> (8 * lh);
             sa[i] = san[i] >> (8 * lh);
         }
-        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): this wave's share of tile kt (and the scales) has landed
+        wait_vmcnt<0>();   // vmcnt(0): this wave's share of tile kt (and the scales) has landed
         __syncthreads();                      // ... everybody's; and everybody is done reading buffer cur ^ 1
         if (kt + 1 < nkt) {
             issue(cur ^ 1, kt + 1);
@@ -288,9 +283,7 @@ __global__ __launch_bounds__(256, TW == 2 ? 2 : 1) void gemm_fp8_kernel(const Fp
 
 // large launches go to the single-stream 256-row loop (gemm256w4_fp8_kernel); SKIMI_FP8_W4=0 keeps them here (A/B timing)
 static bool fp8_w4_shape(int M, int N) {
-    static const bool dyn = getenv("SKIMI_ENV_DYNAMIC") && atoi(getenv("SKIMI_ENV_DYNAMIC"));
-    static int use_w4 = -1;
-    if (use_w4 < 0 || dyn) use_w4 = getenv("SKIMI_FP8_W4") ? atoi(getenv("SKIMI_FP8_W4")) : 1;
+    const int use_w4 = (int)env_switch("SKIMI_FP8_W4", 1);
     return use_w4 && M >= 2048 && N >= 512 && N % 4 == 0 && cdiv(M, 256) * cdiv(N, 256) >= 160;
 }
 // whether a bias + GELU launch of this shape can write its result as MXFP8 (out_dtype SKIMI_FP8MX)
@@ -339,7 +332,7 @@ int gemm_fp8_launch(const void* A, const void* As, const void* W, const void* Ws
     // 256 x 256 tiles where the K loop is long enough to pay for the larger epilogue and they fill most of the chip
     // (measured at M = 43968, tools/mb_fp8.py: K = 4096 -> 1207 vs 1071 TFLOP/s, K = 1024 -> 736-803 vs 828-865),
     // else 128 x 128 (two workgroups per CU).  SKIMI_FP8_TILE=128|256 forces a choice (A/B timing).
-    static const int force_tile = getenv("SKIMI_FP8_TILE") ? atoi(getenv("SKIMI_FP8_TILE")) : 0;
+    const int force_tile = (int)env_once("SKIMI_FP8_TILE", 0);
     const bool big = force_tile ? force_tile == 256 : (K >= 2048 && cdiv(M, 256) * cdiv(N, 256) >= 200);
     const int bt = big ? 256 : 128;
     p.ntm = (int)cdiv(M, bt); p.ntn = (int)cdiv(N, bt);

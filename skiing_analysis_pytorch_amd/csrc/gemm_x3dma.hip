@@ -13,12 +13,11 @@
 #include <algorithm>
 
 #include "common.h"
+#include "env.h"
 #include "gemm_epilogue.h"
+#include "gfx950.h"
 
 namespace skimi {
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef __attribute__((address_space(1))) const void gbl_void;
 
 // fp32 [rows, C] (row stride ld) -> hi, lo bf16 planes [rows, C] contiguous
 __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restrict__ x, long ld, long rows, int C,
@@ -120,14 +119,6 @@ struct X3Rec {
 // half of a fragment is the hi half's address ^ 64.  Staging addresses are (wave-uniform 64-bit
 // base) + (per-lane unsigned 32-bit offset): the K-tile / tap part goes into the base on the
 // scalar unit, a padding-tap lane only swaps its offset for the zero page's.
-#define SKIMI_X3_BAR()                        \
-    do {                                      \
-        __builtin_amdgcn_sched_barrier(0);    \
-        __builtin_amdgcn_s_barrier();         \
-        __builtin_amdgcn_sched_barrier(0);    \
-    } while (0)
-#define SKIMI_X3_VMCNT(N) __builtin_amdgcn_s_waitcnt(0x0F70 | ((N) & 15) | (((N) >> 4) << 14))
-
 //
 // M16 (SKIMI_X3_MFMA=16, the default): the quadrant is 8 x 8 tiles of 16x16 (256 accumulator registers again) and a
 // K-tile is ONE k-step of 32 = 192 v_mfma_f32_16x16x32_bf16, the same MFMA cycles: on this shape the chip holds a
@@ -155,14 +146,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
     const int wr = wave >> 1, wc = wave & 1;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    int id;
-    {
-        const int nblk = p.ntm * p.ntn;
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7;
-        const int q = nblk >> 3, r = nblk & 7;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int id = xcd_contiguous_id(blockIdx.x, p.ntm * p.ntn);
     const int tm = id / p.ntn, tn = id - tm * p.ntn;
     const int m0 = tm * BM;
     int n0 = tn * BN;
@@ -259,13 +243,11 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
         if (ABL & 1) return;
         const bool ok = AMODE == 0 || ((a_ok[q][j] >> at.tap) & 1u) != 0;
         const unsigned o = ok ? a_off[q][j] : at.z + ((lane & 7) << 4);
-        __builtin_amdgcn_global_load_lds((gbl_void*)(at.base + (size_t)o),
-                                         (lds_void*)(smem + slot * PIECE + (4 * wave + j) * 8 * RB), 16, 0, 0);
+        lds_dma16(at.base + (size_t)o, smem + slot * PIECE + (4 * wave + j) * 8 * RB);
     };
     auto dma_w = [&](int kt, int q, int j, int slot) {
         if (ABL & 1) return;
-        __builtin_amdgcn_global_load_lds((gbl_void*)(wbase + (long)kt * 128 + (size_t)w_off[q][j]),
-                                         (lds_void*)(smem + slot * PIECE + (4 * wave + j) * 8 * RB), 16, 0, 0);
+        lds_dma16(wbase + (long)kt * 128 + (size_t)w_off[q][j], smem + slot * PIECE + (4 * wave + j) * 8 * RB);
     };
     auto issue_a = [&](int kt, int slot0, int slot1) {
         const ATile at = a_tile(kt);
@@ -333,11 +315,11 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
     if (nkt > 1) {
         issue_a(1, 4, 5);
         issue_w(1, 6, 7);
-        SKIMI_X3_VMCNT(16);
+        wait_vmcnt<16>();
     } else {
-        SKIMI_X3_VMCNT(0);
+        wait_vmcnt<0>();
     }
-    SKIMI_X3_BAR();
+    fenced_barrier();
     int sb = 0;   // slot of piece 0 of K-tile kt
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
@@ -346,7 +328,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
     }
 #define SKIMI_X3_HEAD()                       \
     do {                                      \
-        __builtin_amdgcn_s_waitcnt(0xC07F);   \
+        wait_lgkmcnt0();                      \
         __builtin_amdgcn_sched_barrier(0);    \
     } while (0)
     // one K-tile: the fragment reads go one behind each of a phase's first MFMAs, the 8 staging instructions one behind
@@ -369,8 +351,8 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
         /* phase 2: AH.WH; kt+1 landed, barrier; read AL of kt+1; W pieces of kt+2 */              \
         SKIMI_X3_HEAD();                                                                           \
         if (N1) {                                                                                  \
-            if (N2) SKIMI_X3_VMCNT(8); else SKIMI_X3_VMCNT(0);                                     \
-            SKIMI_X3_BAR();                                                                        \
+            if (N2) wait_vmcnt<8>(); else wait_vmcnt<0>();                                         \
+            fenced_barrier();                                                                      \
         }                                                                                          \
         phase(ah, wh, [&](int g) {                                                                 \
             if (N1 && g < 8) rd(nsb, false, true, g, al[g]);                                       \
@@ -449,7 +431,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
     } while (0)
 #define SKIMI_X3_HEAD()                       \
     do {                                      \
-        __builtin_amdgcn_s_waitcnt(0xC07F);   \
+        wait_lgkmcnt0();                      \
         __builtin_amdgcn_sched_barrier(0);    \
     } while (0)
     // 16 fragment reads behind the first 8 MFMAs, NDMA staging instructions behind the next 2 NDMA
@@ -473,11 +455,11 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
     if (nkt > 1) {
         issue_a(1, 4, 5);
         issue_w(1, 6, 7);
-        SKIMI_X3_VMCNT(16);
+        wait_vmcnt<16>();
     } else {
-        SKIMI_X3_VMCNT(0);
+        wait_vmcnt<0>();
     }
-    SKIMI_X3_BAR();
+    fenced_barrier();
     int sb = 0;   // slot of piece 0 of K-tile kt
     read(sb, 0, ah0, al0, wh0, wl0);
 #define SKIMI_X3_KTILE(N1, N2)                                                      \
@@ -492,8 +474,8 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
         /* k-step 1 */                                                              \
         SKIMI_X3_HEAD();                                                            \
         if (N1) {                                                                   \
-            if (N2) SKIMI_X3_VMCNT(8); else SKIMI_X3_VMCNT(0);                      \
-            SKIMI_X3_BAR();                                                         \
+            if (N2) wait_vmcnt<8>(); else wait_vmcnt<0>();                          \
+            fenced_barrier();                                                       \
             read(nsb, 0, ah0, al0, wh0, wl0);                                       \
             if (N2) issue_w(kt + 2, sb, slot(sb + 1));                              \
         }                                                                           \
@@ -513,8 +495,8 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
 #undef SKIMI_X3_HEAD
 #undef SKIMI_X3_MFMA
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    SKIMI_X3_BAR();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0..4
+    wait_lgkmcnt0();
+    fenced_barrier();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0..4
 
     // ---- epilogue: per-wave 32-row x 128-column passes through a private LDS slab (row pitch SP) ----
     float* stg = reinterpret_cast<float*>(smem) + wave * (32 * SP);
@@ -568,7 +550,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                \
         to_slab(i);                                                                                                \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                     \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                                                        \
+        wait_lgkmcnt0();                                                                                           \
         _Pragma("unroll") for (int half = 0; half < 2; ++half) {                                                   \
             float4 v[8], bs[8];                                                                                    \
             long orow[8];                                                                                          \
@@ -591,7 +573,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
                 if (HAS_REC) store_rec4(p, orow[it], n, y.x, y.y, y.z, y.w);                                       \
             }                                                                                                      \
         }                                                                                                          \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                                                        \
+        wait_lgkmcnt0();                                                                                           \
     }
             // compile-time variants, as below: a uniform branch inside the unrolled passes costs a vmcnt(0) per store
             switch ((out ? 2 : 0) | (p.out_rec ? 1 : 0)) {
@@ -607,7 +589,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
         for (int i = 0; i < 4; ++i) {
             to_slab(i);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_s_waitcnt(0xC07F);
+            wait_lgkmcnt0();
 #pragma unroll 1
             for (int it = 0; it < 16; ++it) {
                 const int row_l = it * 2 + lh;
@@ -621,7 +603,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
                 if (out) *reinterpret_cast<float4*>(out + orow * p.ldo + n) = y;
                 if (p.out_rec) store_rec4(p, orow, n, y.x, y.y, y.z, y.w);
             }
-            __builtin_amdgcn_s_waitcnt(0xC07F);
+            wait_lgkmcnt0();
         }
         return;
     }
@@ -653,7 +635,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                \
         to_slab(i);                                                                                                \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                     \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                                                        \
+        wait_lgkmcnt0();                                                                                           \
         _Pragma("unroll") for (int half = 0; half < 2; ++half) {                                                   \
             const long mrow = m0 + wr * 128 + i * 32 + half * 16 + lh;                                             \
             float4 v[8], rr[8], r2[8];                                                                             \
@@ -673,7 +655,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
                 if (HAS_REC) store_rec4(p, mrow + it * 2, n, y.x, y.y, y.z, y.w);                                  \
             }                                                                                                      \
         }                                                                                                          \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                                                        \
+        wait_lgkmcnt0();                                                                                           \
     }
         // compile-time variants: a uniform branch inside the unrolled passes would cost a vmcnt(0) per store
         const int variant = (rs2 ? 8 : rs ? 4 : 0) | (out ? 2 : 0) | (p.out_rec ? 1 : 0);
@@ -696,7 +678,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
     for (int i = 0; i < 4; ++i) {
         to_slab(i);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        wait_lgkmcnt0();
 #pragma unroll 1
         for (int it = 0; it < 16; ++it) {
             const int row_l = it * 2 + lh;
@@ -713,7 +695,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4_kernel(const GemmArgs p, con
                 if (n + 3 < p.N) store_one(p, rm, n + 3, v.w);
             }
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        wait_lgkmcnt0();
     }
 }
 
@@ -733,14 +715,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
     const int wr = wave >> 1, wc = wave & 1;
     const int l31 = lane & 31, lh = lane >> 5;
 
-    int id;
-    {
-        const int nblk = p.ntm * p.ntn;
-        const int bid = blockIdx.x;
-        const int xcd = bid & 7;
-        const int q = nblk >> 3, r = nblk & 7;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int id = xcd_contiguous_id(blockIdx.x, p.ntm * p.ntn);
     const int tm = id / p.ntn, tn = id - tm * p.ntn;
     const int m0 = tm * BM, n0 = tn * BN;
     const int nkt = (p.K + BK - 1) / BK;
@@ -806,12 +781,10 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
     auto dma_a = [&](const ATile& at, int q, int j, int slot) {
         const bool ok = AMODE == 0 || ((a_ok[q][j] >> at.tap) & 1u) != 0;
         const unsigned o = ok ? a_off[q][j] : at.z + ((lane & 7) << 4);
-        __builtin_amdgcn_global_load_lds((gbl_void*)(at.base + (size_t)o),
-                                         (lds_void*)(smem + slot * PIECE + (4 * wave + j) * 8 * RB), 16, 0, 0);
+        lds_dma16(at.base + (size_t)o, smem + slot * PIECE + (4 * wave + j) * 8 * RB);
     };
     auto dma_w = [&](int kt, int j, int slot) {
-        __builtin_amdgcn_global_load_lds((gbl_void*)(pl.w + (long)kt * 128 + (size_t)w_off[j]),
-                                         (lds_void*)(smem + slot * PIECE + (4 * wave + j) * 8 * RB), 16, 0, 0);
+        lds_dma16(pl.w + (long)kt * 128 + (size_t)w_off[j], smem + slot * PIECE + (4 * wave + j) * 8 * RB);
     };
     // all three pieces of K-tile kt -> slots s0 (A rows 0..127), s1 (A rows 128..255), s2 (W rows)
     auto issue = [&](int kt, int s0, int s1, int s2) {
@@ -864,8 +837,8 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
     issue(0, 0, 1, 2);
     if (nkt > 1) issue(1, 3, 4, 5);
     if (nkt > 2) issue(2, 6, 7, 8);
-    if (nkt > 2) SKIMI_X3_VMCNT(24); else if (nkt > 1) SKIMI_X3_VMCNT(12); else SKIMI_X3_VMCNT(0);
-    SKIMI_X3_BAR();
+    if (nkt > 2) wait_vmcnt<24>(); else if (nkt > 1) wait_vmcnt<12>(); else wait_vmcnt<0>();
+    fenced_barrier();
     int sb = 0;   // slot of piece 0 of K-tile kt
 #pragma unroll
     for (int i = 0; i < 8; ++i) rd_a(sb, true, i, al[i]);
@@ -873,7 +846,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
     for (int j = 0; j < 4; ++j) rd_w(sb, false, j, wh[j]);
 #define SKIMI_X3N_HEAD()                      \
     do {                                      \
-        __builtin_amdgcn_s_waitcnt(0xC07F);   \
+        wait_lgkmcnt0();                      \
         __builtin_amdgcn_sched_barrier(0);    \
     } while (0)
     // N1 / N2 / N3: K-tiles kt+1 / kt+2 / kt+3 exist (literals; the last three K-tiles are peeled)
@@ -890,8 +863,8 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
         SKIMI_X3N_HEAD();                                                                          \
         ATile at{};                                                                                \
         if (N1) {                                                                                  \
-            if (N2) SKIMI_X3_VMCNT(12); else SKIMI_X3_VMCNT(0);                                    \
-            SKIMI_X3_BAR();                                                                        \
+            if (N2) wait_vmcnt<12>(); else wait_vmcnt<0>();                                        \
+            fenced_barrier();                                                                      \
             if (N3) at = a_tile(kt + 3);                                                           \
         }                                                                                          \
         phase(ah, wh, [&](int g) {                                                                 \
@@ -965,7 +938,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
     } while (0)
 #define SKIMI_X3N_HEAD()                      \
     do {                                      \
-        __builtin_amdgcn_s_waitcnt(0xC07F);   \
+        wait_lgkmcnt0();                      \
         __builtin_amdgcn_sched_barrier(0);    \
     } while (0)
     // 12 fragment reads behind the first 6 MFMAs, NDMA staging instructions one per MFMA after them
@@ -987,8 +960,8 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
     issue(0, 0, 1, 2);
     if (nkt > 1) issue(1, 3, 4, 5);
     if (nkt > 2) issue(2, 6, 7, 8);
-    if (nkt > 2) SKIMI_X3_VMCNT(24); else if (nkt > 1) SKIMI_X3_VMCNT(12); else SKIMI_X3_VMCNT(0);
-    SKIMI_X3_BAR();
+    if (nkt > 2) wait_vmcnt<24>(); else if (nkt > 1) wait_vmcnt<12>(); else wait_vmcnt<0>();
+    fenced_barrier();
     int sb = 0;   // slot of piece 0 of K-tile kt
     read(sb, 0, ah0, al0, wh0, wl0);
     // N1 / N2 / N3: K-tiles kt+1 / kt+2 / kt+3 exist (literals; the last three K-tiles are peeled)
@@ -1003,8 +976,8 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
         /* k-step 1 */                                                              \
         SKIMI_X3N_HEAD();                                                           \
         if (N1) {                                                                   \
-            if (N2) SKIMI_X3_VMCNT(12); else SKIMI_X3_VMCNT(0);                     \
-            SKIMI_X3_BAR();                                                         \
+            if (N2) wait_vmcnt<12>(); else wait_vmcnt<0>();                         \
+            fenced_barrier();                                                       \
             read(nsb, 0, ah0, al0, wh0, wl0);                                       \
             if (N3) issue(kt + 3, sb, slot(sb + 1), slot(sb + 2));                  \
         }                                                                           \
@@ -1028,8 +1001,8 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
 #undef SKIMI_X3N_HEAD
 #undef SKIMI_X3N_MFMA
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    SKIMI_X3_BAR();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0..2
+    wait_lgkmcnt0();
+    fenced_barrier();   // nobody reads operand pieces any more: the epilogue slabs alias slots 0..2
 
     // ---- epilogue: per-wave 32-row x 64-column passes through a private LDS slab (row pitch SP) ----
     float* stg = reinterpret_cast<float*>(smem) + wave * (32 * SP);
@@ -1078,7 +1051,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
     _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                                \
         to_slab(i);                                                                                                \
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                                                     \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                                                        \
+        wait_lgkmcnt0();                                                                                           \
         const long mrow = m0 + wr * 128 + i * 32 + (lane >> 4);                                                    \
         float4 v[8], rr[8], r2[8];                                                                                 \
         _Pragma("unroll") for (int it = 0; it < 8; ++it)                                                           \
@@ -1096,7 +1069,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
             if (HAS_OUT) *reinterpret_cast<float4*>(out + (mrow + it * 4) * p.ldo + n) = y;                        \
             if (HAS_REC) store_rec4(p, mrow + it * 4, n, y.x, y.y, y.z, y.w);                                      \
         }                                                                                                          \
-        __builtin_amdgcn_s_waitcnt(0xC07F);                                                                        \
+        wait_lgkmcnt0();                                                                                           \
     }
         const int variant = (rs2 ? 8 : rs ? 4 : 0) | (out ? 2 : 0) | (p.out_rec ? 1 : 0);
         switch (variant) {
@@ -1118,7 +1091,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
     for (int i = 0; i < 4; ++i) {
         to_slab(i);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        wait_lgkmcnt0();
 #pragma unroll 1
         for (int it = 0; it < 8; ++it) {
             const int row_l = it * 4 + (lane >> 4);
@@ -1135,7 +1108,7 @@ __global__ __launch_bounds__(256, 1) void gemm_x3w4n_kernel(const GemmArgs p, co
                 if (n + 3 < p.N) store_one(p, rm, n + 3, v.w);
             }
         }
-        __builtin_amdgcn_s_waitcnt(0xC07F);
+        wait_lgkmcnt0();
     }
 }
 
@@ -1184,9 +1157,7 @@ bool gemm_x3dma_eligible(const skimi_gemm_desc* d) {
     // with 172 tiles (M = 43808) is already faster here than on the generic 128x128 kernel (17.38 vs
     // 17.18 frames/s at a threshold of 160 vs 200); below that the generic kernel's smaller tiles win.
     // (SKIMI_X3_MIN_TILES overrides the threshold: the tests run small shapes through these kernels)
-    static const bool dyn = getenv("SKIMI_ENV_DYNAMIC") && atoi(getenv("SKIMI_ENV_DYNAMIC"));
-    static long min_tiles = -1;
-    if (min_tiles < 0 || dyn) min_tiles = getenv("SKIMI_X3_MIN_TILES") ? atol(getenv("SKIMI_X3_MIN_TILES")) : 160;
+    const long min_tiles = env_switch("SKIMI_X3_MIN_TILES", 160);
     const long tiles = cdiv(d->M, 256) * (d->N > 128 ? cdiv(d->N, 256) : 1) * (fold ? d->ps_s * d->ps_s : 1);
     return d->M >= (min_tiles <= 1 ? 256 : 4096) && d->N >= 96 && tiles >= min_tiles;
 }
@@ -1218,9 +1189,7 @@ static int launch_x3w4n_(GemmArgs& a, const X3Rec& pl, hipStream_t st) {
 // MFMA shape of both loops (SKIMI_X3_MFMA = 16 | 32): v_mfma_f32_16x16x32_bf16 by default; read once, or per launch
 // under SKIMI_ENV_DYNAMIC=1 (interleaved A/B timing in one process)
 static bool x3_m16() {
-    static const bool dyn = getenv("SKIMI_ENV_DYNAMIC") && atoi(getenv("SKIMI_ENV_DYNAMIC"));
-    static int shape = -1;
-    if (shape < 0 || dyn) shape = getenv("SKIMI_X3_MFMA") ? atoi(getenv("SKIMI_X3_MFMA")) : 16;
+    const int shape = (int)env_switch("SKIMI_X3_MFMA", 16);
     return shape != 32;
 }
 
@@ -1264,7 +1233,7 @@ int gemm_x3dma_launch(GemmArgs& a, const skimi_gemm_desc* d, hipStream_t st) {
     }
 #ifdef SKIMI_ABLATIONS   // timing ablations (wrong results): only in a -DSKIMI_ABLATIONS build
     if (a.a_mode == 0) {
-        static const int abl = getenv("SKIMI_X3_ABL") ? atoi(getenv("SKIMI_X3_ABL")) : 0;
+        const int abl = (int)env_once("SKIMI_X3_ABL", 0);
         switch (abl) {
             case 1: return launch_x3w4<0, 1>(a, pl, st);
             case 2: return launch_x3w4<0, 2>(a, pl, st);
@@ -1275,7 +1244,7 @@ int gemm_x3dma_launch(GemmArgs& a, const skimi_gemm_desc* d, hipStream_t st) {
         }
     }
     if (a.a_mode == 2) {
-        static const int abl = getenv("SKIMI_X3_ABL") ? atoi(getenv("SKIMI_X3_ABL")) : 0;
+        const int abl = (int)env_once("SKIMI_X3_ABL", 0);
         switch (abl) {
             case 1: return launch_x3w4<2, 1>(a, pl, st);
             case 2: return launch_x3w4<2, 2>(a, pl, st);

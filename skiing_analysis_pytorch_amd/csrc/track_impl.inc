@@ -31,7 +31,7 @@ struct TrackW {
 // (BF16, F16, FP8) its Linears and convolutions take that mode's 16-bit operands (weights packed once, fp32
 // activations rounded while staged), one MFMA per product; under BF16X3 it is fp32-accurate like everything else.
 static int track_prec(const skimi_vggt_config& cfg) {
-    static const bool force_x3 = getenv("SKIMI_TRACK_X3") && atoi(getenv("SKIMI_TRACK_X3"));   // A/B timing: round 2's fp32-accurate track head
+    const bool force_x3 = (int)env_once("SKIMI_TRACK_X3", 0) != 0;   // A/B timing: round 2's fp32-accurate track head
     if (cfg.prec == SKIMI_PREC_BF16X3 || force_x3) return SKIMI_PREC_BF16X3;
     return cfg.prec == SKIMI_PREC_F16 ? SKIMI_PREC_F16 : SKIMI_PREC_BF16;
 }

@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "env.h"
 #include "gemm_epilogue.h"
 #include "kernels.h"
 #include "track_kernels.h"
@@ -248,7 +249,7 @@ struct Packer {
         float* tmp = nullptr;
         if (k > 1) {
             // fp32-accurate convs run on K-tiles of 32: order K slice-major there (see permute_conv_kernel)
-            static const int force_tap_major = getenv("SKIMI_CONV_TAP_MAJOR") ? atoi(getenv("SKIMI_CONV_TAP_MAJOR")) : 0;   // A/B timing
+            const int force_tap_major = (int)env_once("SKIMI_CONV_TAP_MAJOR", 0);   // A/B timing
             c.kmode = (prec == SKIMI_PREC_BF16X3 && Ci % 32 == 0 && !force_tap_major) ? 2 : 1;
             if (hipMalloc((void**)&tmp, (size_t)Co * Ci * k * k * 4) != hipSuccess) { rc = SKIMI_ERR_HIP; return c; }
             if ((rc = permute_conv_launch(src, tmp, Co, Ci, k, k, st, c.kmode == 2))) return c;
@@ -597,7 +598,7 @@ const UvTab* find_uv(const ShapeTabs* h, int w, int hh, int C) {
 
 // whether a feature_only head's last upsample also applies the consumer's LayerNorm (SKIMI_TRACK_LN_FUSED=0: separate pass)
 bool dpt_fused_ln(const DptW& w, int f2, int udt) {
-    static const bool off = getenv("SKIMI_TRACK_LN_FUSED") && !atoi(getenv("SKIMI_TRACK_LN_FUSED"));
+    const bool off = !(int)env_once("SKIMI_TRACK_LN_FUSED", 1);
     return !off && w.feature_only && w.out_ln != nullptr && w.out_ln->g != nullptr && w.out_ln->b != nullptr && f2 == 128 && udt == SKIMI_F32;
 }
 
@@ -830,7 +831,7 @@ void* run_dpt(Ctx& c, const DptW& w, float* const* sf, float* const* sg, int F, 
     const int Ho = ph * c.h->cfg.patch_size / w.down_ratio, Wo = pw * c.h->cfg.patch_size / w.down_ratio;
     const UvTab* uvt = w.pos_embed ? find_uv(c.tabs, Wo, Ho, f2) : nullptr;
     if (w.pos_embed && !uvt && !c.rc && !c.dry()) { set_error("uv table missing"); c.rc = SKIMI_ERR_STATE; }
-    static const int no_direct = getenv("SKIMI_CONV_DIRECT") ? !atoi(getenv("SKIMI_CONV_DIRECT")) : 0;   // A/B timing
+    const int no_direct = !(int)env_once("SKIMI_CONV_DIRECT", 1);   // A/B timing
     const bool direct = !w.feature_only && w.oc2a_direct != nullptr && adt == SKIMI_F32 && !no_direct;
     void* c2 = nullptr;
     if (direct) {

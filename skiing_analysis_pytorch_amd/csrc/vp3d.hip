@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.h"
+#include "env.h"
 #include "gemm_epilogue.h"
 #include "kernels.h"
 
@@ -348,13 +349,13 @@ int skimi_vp3d_forward(skimi_vp3d* h, const float* x, float* out, int32_t batch,
     // SKIMI_VP3D_STREAM_ROWS moves the switch-over (rows of the first layer; larger batches are MFMA-bound and
     // run on the LDS-DMA kernels below).
     {
-        static const int use_stream = getenv("SKIMI_VP3D_STREAM") ? atoi(getenv("SKIMI_VP3D_STREAM")) : 1;
-        static const long max_rows = getenv("SKIMI_VP3D_STREAM_ROWS") ? atol(getenv("SKIMI_VP3D_STREAM_ROWS")) : 2048;
+        const int use_stream = (int)env_once("SKIMI_VP3D_STREAM", 1);
+        const long max_rows = env_once("SKIMI_VP3D_STREAM_ROWS", 2048);
         const bool ok = use_stream && h->prec == SKIMI_PREC_BF16X3 && h->w_shrink_frag != nullptr && (long)rows0 <= max_rows &&
                         h->w_frag.size() == 2 * (h->fw.size() - 1);
         if (ok) {
             // expand_conv: on the MFMA kernel (bf16x3 like the other layers; SKIMI_VP3D_EXPAND_VALU=1: the exact-fp32 VALU kernel)
-            static const int expand_valu = getenv("SKIMI_VP3D_EXPAND_VALU") ? atoi(getenv("SKIMI_VP3D_EXPAND_VALU")) : 0;
+            const int expand_valu = (int)env_once("SKIMI_VP3D_EXPAND_VALU", 0);
             if (expand_valu || h->w_expand_frag == nullptr)
                 rc = vp3d_expand_launch(x, (const float*)h->w_expand, h->k0pad, h->b_expand, bufX, recX, batch, frames_in, cin0,
                                         h->fw[0], C, st);

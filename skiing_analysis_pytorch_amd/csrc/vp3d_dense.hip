@@ -35,6 +35,8 @@
 #include <algorithm>
 
 #include "common.h"
+#include "env.h"
+#include "gfx950.h"
 #include "kernels.h"
 
 namespace skimi {
@@ -64,12 +66,7 @@ __global__ __launch_bounds__(512) void vp3d_win_kernel(const Vp3dWin p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kg = lane >> 4;
     // tile id: contiguous per XCD, as in vp3d_mm_kernel (the row splits of a channel tile share its weight slice)
-    int id;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x, xcd = bid & 7;
-        const int q = nblk >> 3, r = nblk & 7;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int id = xcd_contiguous_id();
     const int per = p.B * p.msc;
     const int ct = id / per, rem = id - ct * per;
     const int b = rem / p.msc, rs = rem - b * p.msc;
@@ -228,11 +225,7 @@ static int launch_win(const Vp3dWin& p, int grid, size_t lds, hipStream_t st) {
 // SKIMI_VP3D_WINDOW=0 sends the dense blocks to the per-tap kernel (vp3d_mm_kernel) instead (A/B timing; re-read on
 // every forward under SKIMI_ENV_DYNAMIC=1, so that one process can alternate the two)
 bool vp3d_window_enabled() {
-    static const bool dynamic = getenv("SKIMI_ENV_DYNAMIC") && atoi(getenv("SKIMI_ENV_DYNAMIC"));
-    static const int fixed = getenv("SKIMI_VP3D_WINDOW") ? atoi(getenv("SKIMI_VP3D_WINDOW")) : 1;
-    if (!dynamic) return fixed != 0;
-    const char* v = getenv("SKIMI_VP3D_WINDOW");
-    return v ? atoi(v) != 0 : true;
+    return (int)env_switch("SKIMI_VP3D_WINDOW", 1) != 0;
 }
 
 // One dense conv (dilation 1, `taps` taps) + BN (folded) + ReLU: records in, records (and optionally fp32) out.

@@ -37,6 +37,8 @@
 #include <algorithm>
 
 #include "common.h"
+#include "env.h"
+#include "gfx950.h"
 #include "kernels.h"
 
 namespace skimi {
@@ -77,14 +79,9 @@ __global__ __launch_bounds__(512) void vp3d_mm_kernel(const Vp3dMM p) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kg = lane >> 4;
     VP3D_TS(0);
-    // tile id: contiguous per XCD (blocks b and b + 8 share an XCD), so the ms partners of a channel tile
+    // tile id: contiguous per XCD, so the ms partners of a channel tile
     // (consecutive ids) sit on one XCD whenever ms divides the per-XCD count
-    int id;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x, xcd = bid & 7;
-        const int q = nblk >> 3, r = nblk & 7;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int id = xcd_contiguous_id();
     const int ct = id / p.ms, rs = id - ct * p.ms;
     const int c0 = ct * CT, r0 = rs * p.R;
     const int SC = p.C >> 5;                 // slices per tap
@@ -261,7 +258,7 @@ __global__ __launch_bounds__(512) void vp3d_mm_kernel(const Vp3dMM p) {
     }
     VP3D_TS(5);
 #ifdef SKIMI_ABLATIONS
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    wait_vmcnt<0>();
     VP3D_TS(6);
 #endif
 }
@@ -312,12 +309,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) void vp3d_conv_kernel(con
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, kg = lane >> 4;
-    int id;
-    {
-        const int nblk = gridDim.x, bid = blockIdx.x, xcd = bid & 7;
-        const int q = nblk >> 3, r = nblk & 7;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-    }
+    const int id = xcd_contiguous_id();
     const int per = p.B * p.msc;
     const int ct = id / per, rem = id - ct * per;
     const int b = rem / p.msc, rs = rem - b * p.msc;
@@ -615,8 +607,8 @@ int vp3d_mm_launch(const void* wrec, int Npad, const void* xrec, const float* bi
     const long K = (long)taps * C, halo = (long)(taps - 1) * dil;
     // First choice: vp3d_conv_kernel (activations loaded once for all taps).  Candidates: taps = 1 -> CT 16 or 32, up to
     // 4 row tiles; taps = 3 -> CT 16, up to 5 row tiles INCLUDING the 2 d halo.  Cost = bytes a workgroup loads x rounds.
-    static const int use_conv = getenv("SKIMI_VP3D_TAPREUSE") ? atoi(getenv("SKIMI_VP3D_TAPREUSE")) : 1;
-    static const int use_pairs = getenv("SKIMI_VP3D_PAIRS") ? atoi(getenv("SKIMI_VP3D_PAIRS")) : 1;   // 0: 8-wave workgroups only (A/B timing)
+    const int use_conv = (int)env_once("SKIMI_VP3D_TAPREUSE", 1);
+    const int use_pairs = (int)env_once("SKIMI_VP3D_PAIRS", 1);   // 0: 8-wave workgroups only (A/B timing)
     // cost of a candidate = rounds x (elements the workgroups of one CU load in a round + FIXED), FIXED = the in-kernel fixed cost
     // of a round (first loads out, K-partials through LDS, store drain: ~8 us against ~5.5 us for 131 K elements,
     // profiles/r02_vp3d_summary.md).  4-wave workgroups sit two to a CU: a round holds 512 of them and loads twice the elements.
