@@ -1118,6 +1118,60 @@ int skimi_bev_skeleton(const double* X, const double* center_px, const double* c
                        double* center_world, void* stream);
 int skimi_ground_track(const double* p, int64_t P, int64_t T, double fps, double* out, void* stream);
 
+/* ---- camera calibration from the corners of a plane target: Zhang's start + Levenberg-Marquardt (csrc/calibrate.hip) ----
+ * camera_calibration/main.py (cv2.calibrateCamera on chessboard corners, its prune step and standard deviations), corners
+ * given as arrays.  obj [n, 2] (dev): the target's corners in its own plane (z = 0), shared by all boards; img [V, n, 2]
+ * (dev) pixels; use [G, V] u8 (dev, or NULL: every view in every group); K0 [G, 3, 3] and dist0 [G, 12] (dev, or NULL);
+ * width, height, free_mask (12 bits over fx fy cx cy k1 k2 p1 p2 k3 k4 k5 k6: bit i frees parameter i; dist's order is
+ * the lens block's, so dist[0 .. 7] = parameters 4 .. 11 and dist[8 .. 11], the thin-prism terms, are always 0) and
+ * max_evals are host scalars.  Each of the G groups is one calibration problem over the same V views under its own `use`
+ * row, solved by one workgroup.  Everything is float64.  A call is the copy of obj once per board into the workspace, the
+ * homography fit above on the V boards (shared by all groups) and the solver kernel: no host synchronisation, no
+ * allocation, no atomics.  Every sum has a fixed order that depends only on (view, corner) indices: a group is bitwise what
+ * it is alone, inside a batch and on a rerun.  Limits: 1 <= G <= 2^20 - 16, 1 <= V <= 1024, 4 <= n <= 4096; the workspace
+ * is skimi_calibrate_workspace_bytes(G, V, n) bytes (0 for sizes the call refuses), 8-byte aligned.  Bad arguments:
+ * SKIMI_ERR_ARG before any launch, outputs untouched.  Rules (DESIGN §2 "Calibration"; tests/calibrate_restated.py):
+ *  1. Masks.  A corner is used iff its two image coordinates (and its two object coordinates) are finite.  A view is used in
+ *     group g iff use[g, v] != 0, it has >= 4 used corners and its homography has status 1.  Fewer than 3 used views, or
+ *     fewer residuals than parameters (2 x used corners < free intrinsics + 6 x used views), fails the group: every float
+ *     output NaN, success 0, n_evals 0 (n_views and n_corners still count); its neighbours are untouched.  An unused view of
+ *     a good group has NaN pose and NaN errors.
+ *  2. Start of the intrinsics.  K0 NULL (cv2's initCameraMatrix2D): cx = (width - 1) / 2, cy = (height - 1) / 2; per used
+ *     view, in view order, Hc = T Hn with T the translation by (-cx, -cy), h = column 0, v = column 1, d1 = (h + v) / 2,
+ *     d2 = (h - v) / 2, each of the four scaled to unit length, giving the rows [h0 v0, h1 v1 | -h2 v2] and [d1_0 d2_0,
+ *     d1_1 d2_1 | -d1_2 d2_2]; the 2 x 2 normal equations N (a, b) = r over all rows, det = N00 N11 - N01 N01, a = (N11 r0 -
+ *     N01 r1) / det, b = (N00 r1 - N01 r0) / det; fx = sqrt|1 / a|, fy = sqrt|1 / b|.  K0 given (cv2's USE_INTRINSIC_GUESS):
+ *     fx fy cx cy from K0.  The coefficients start at dist0[0 .. 7], or zero.  A zero or non-finite focal length, a non-finite
+ *     principal point or coefficient fails the group.
+ *  3. Start of each pose.  M = K^-1 Hn, negated when M22 < 0; s = 1 / ||M col 0||, r1 = s M col 0, r2 = s M col 1, r3 = r1 x
+ *     r2, R = the nearest rotation to [r1 r2 r3] (csrc/svd3.h), t = s M col 2.
+ *  4. Residual.  Xc = R (X, Y, 0) + t, (x, y) = Xc.xy / Xc.z, rule 2 of the lens block with s1 .. s4 = 0, r = (fx x_d + cx,
+ *     fy y_d + cy) - corner.  cost = sum r^2 over the used corners of the used views: plain least squares, as cv2.
+ *  5. Parameters.  The free intrinsics are additive; per view R <- Exp(w) R, t <- t + dt.  A fixed intrinsic keeps its start:
+ *     its Jacobian column is zero and its row and column of the reduced system are the identity with a zero right side.
+ *  6. Step (Marquardt's scaling, as cv2's CvLevMarq and MINPACK): (H + lam diag H) d = -g, H = J^T J from the analytic
+ *     Jacobian, solved exactly through the Schur complement on the views: B*_v = B_v + lam diag B_v (6 x 6, LDL^T), S = A +
+ *     lam diag A - sum_v C_v B*_v^-1 C_v^T (12 x 12), d_intr = S^-1 (-g_a + sum_v C_v B*_v^-1 g_v) by LDL^T without
+ *     pivoting, d_v = -B*_v^-1 (g_v + C_v^T d_intr).  lam0 = 1e-3.
+ *  7. Accept iff the trial's cost, evaluated from the trial parameters, is finite and <= c (1 + 1e-14): lam <- max(lam / 10,
+ *     1e-16); else lam <- 10 lam and the step is solved again from the stored blocks.
+ *  8. Stop on an accepted step with ||d|| <= 3e-8 (1 + ||x||) (success 1), d over the free intrinsics and every used view's
+ *     (w, dt), x the free intrinsics and the used views' t after the step; on lam >= 1e30; after max_evals cost evaluations
+ *     (the start and every trial count).
+ *  9. Finish.  The blocks are re-linearised at the stopping point; S0 = the Schur complement at lam = 0; std[i] = sqrt((S0^-1)_ii
+ *     cost / (m - p)) for the free intrinsics, m = 2 x used corners, p = free intrinsics + 6 x used views (cv2's
+ *     stdDeviationsIntrinsics); NaN for a fixed intrinsic, where m <= p and where a factorisation
+ *     (a view's B_v or S0) meets a pivot that is not positive.
+ * 10. Outputs (dev): K [G, 3, 3], dist [G, 12], R [G, V, 3, 3], t [G, V, 3], rvec [G, V, 3] (cv2.Rodrigues of R), err [G, V, n]
+ *     pixel distance (NaN where unused), view_stats [G, V, 3] = mean, rms, max, rms [G] = sqrt(cost / used corners) (cv2's
+ *     return value), cost0, cost [G], std [G, 12] (free_mask's order), n_evals, n_views, n_corners, success [G] i32. */
+size_t skimi_calibrate_workspace_bytes(int64_t G, int32_t V, int32_t n);
+int skimi_calibrate_camera(const double* obj, const double* img, const uint8_t* use, const double* K0, const double* dist0, int64_t G,
+                           int32_t V, int32_t n, int32_t width, int32_t height, int32_t free_mask, int32_t max_evals, double* K,
+                           double* dist, double* R, double* t, double* rvec, double* err, double* view_stats, double* rms,
+                           double* cost0, double* cost, double* std, int32_t* n_evals, int32_t* n_views, int32_t* n_corners,
+                           int32_t* success, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- VGGT head and track-head helper kernels, one launch each ----
  * The kernels skimi_vggt_forward runs between its GEMMs, exposed singly so that each can be tested against a float64
  * restatement.  All maps are channels-last and dense; dtype / out_dtype are SKIMI_F32, SKIMI_BF16 or SKIMI_F16.  Every

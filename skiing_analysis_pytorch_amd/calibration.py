@@ -1,14 +1,122 @@
-"""Ground-truth-free checks of a camera calibration (camera_calibration/main.py:192-237), on top of the device lens model.
+"""Camera calibration from chessboard corners and its ground-truth-free checks (camera_calibration/main.py), on top of the
+device solver and the device lens model.
 
-The calibration solver itself (cv2.calibrateCamera) is outside this build; what a calibration file holds is read by
-`formats.load_calibration`.  Host module: small arrays, NumPy; the one heavy step, undistorting the detected corners, is
-`geometry.undistort_points` on the device.
+The solver (cv2.calibrateCamera in the reference) is `geometry.calibrate_camera` on the device: Zhang's start and a
+Levenberg-Marquardt over the intrinsics and every board's pose, many view subsets in one call.  This module is the rest of
+the reference's script without its pictures and files: the object points, the prune step, the reprojection and coverage
+statistics, and the leave-one-out spread that a batch makes cheap.  Corners arrive as arrays: detecting them
+(findChessboardCorners / cornerSubPix), sampling videos, getOptimalNewCameraMatrix / valid_roi_fraction and stereo
+calibration are outside this build.  `formats.save_calibration` / `formats.load_calibration` write and read the files.
+Host module: small arrays, NumPy; the heavy steps run on the device.
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Callable, Optional, Sequence, Tuple
 
 import numpy as np
+
+
+@dataclass
+class CalibConfig:
+    """The reference's CalibConfig without its picture, video and file fields, plus the frame size (the reference reads it
+    off its first picture)."""
+    board_cols: int = 9           # inner corners along columns
+    board_rows: int = 6           # inner corners along rows
+    square_size: float = 25.0     # same unit across all boards
+    rational_model: bool = True   # frees k4 .. k6
+    zero_tangent: bool = False    # holds p1 = p2 = 0
+    prune_top_ratio: float = 0.1  # drop the worst share of the views once; 0 disables
+    image_size: Optional[Tuple[int, int]] = None   # (width, height)
+    max_evals: int = 200
+
+    @property
+    def board_size(self) -> Tuple[int, int]:
+        return (self.board_cols, self.board_rows)
+
+    @property
+    def flags(self) -> int:
+        """cv2's flags for the .yml: CALIB_RATIONAL_MODEL = 1 << 14, CALIB_ZERO_TANGENT_DIST = 1 << 3"""
+        return (16384 if self.rational_model else 0) | (8 if self.zero_tangent else 0)
+
+
+def prepare_object_points(board_size: Tuple[int, int], square_size: float) -> np.ndarray:
+    """prepare_object_points (main.py:73-77): [cols * rows, 3] float32, x fastest, z = 0, scaled by the square's size."""
+    cols, rows = board_size
+    objp = np.zeros((cols * rows, 3), np.float32)
+    objp[:, :2] = np.mgrid[0:cols, 0:rows].T.reshape(-1, 2)
+    return objp * float(square_size)
+
+
+def reproj_stats(err) -> Tuple[list, dict]:
+    """compute_reproj_stats (main.py:154-167) from the solver's err [V, n] (NaN where unused; an all-NaN view is skipped):
+    per view mean / median / 95th percentile, and the three over all corners together, with np.percentile's semantics."""
+    err = np.asarray(err, np.float64)
+    per_img, every = [], []
+    for e in err:
+        e = e[~np.isnan(e)]
+        if e.size == 0:
+            continue
+        per_img.append({"mean_px": float(e.mean()), "median_px": float(np.median(e)), "p95_px": float(np.percentile(e, 95))})
+        every.append(e)
+    if not every:
+        return per_img, {"global_mean_px": None, "global_median_px": None, "global_p95_px": None}
+    cat = np.concatenate(every)
+    return per_img, {"global_mean_px": float(cat.mean()), "global_median_px": float(np.median(cat)),
+                     "global_p95_px": float(np.percentile(cat, 95))}
+
+
+def convex_hull_area(points) -> float:
+    """Area of the convex hull of points [N, 2] (cv2.convexHull + cv2.contourArea): Andrew's monotone chain, then the
+    shoelace formula.  Fewer than 3 distinct points, or all collinear: 0."""
+    pts = np.unique(np.asarray(points, np.float64).reshape(-1, 2), axis=0)     # sorted by x, then y
+    if len(pts) < 3:
+        return 0.0
+
+    def chain(seq):
+        out = []
+        for q in seq:
+            while len(out) >= 2 and ((out[-1][0] - out[-2][0]) * (q[1] - out[-2][1])
+                                     - (out[-1][1] - out[-2][1]) * (q[0] - out[-2][0])) <= 0:
+                out.pop()
+            out.append(q)
+        return out
+
+    hull = np.array(chain(pts)[:-1] + chain(pts[::-1])[:-1])
+    if len(hull) < 3:
+        return 0.0
+    x, y = hull[:, 0], hull[:, 1]
+    return float(0.5 * abs(np.dot(x, np.roll(y, -1)) - np.dot(y, np.roll(x, -1))))
+
+
+def edge_center_ratio(imgpoints: Sequence, image_size: Tuple[int, int], border_ratio: float = 0.2) -> dict:
+    """compute_edge_center_ratio (main.py:170-189): the share of the w h frame that the convex hull of all corners covers,
+    and the share of corners within border_ratio of a frame edge.  Non-finite corners are skipped; float64 throughout (the
+    reference rounds the hull's input to float32)."""
+    w, h = image_size
+    pts = [np.asarray(p, np.float64).reshape(-1, 2) for p in imgpoints]
+    if not pts:
+        return {"coverage_ratio": 0.0, "edge_points_ratio": 0.0}
+    pts = np.concatenate(pts)
+    pts = pts[np.isfinite(pts).all(axis=1)]
+    if len(pts) == 0:
+        return {"coverage_ratio": 0.0, "edge_points_ratio": 0.0}
+    xs, ys = pts[:, 0], pts[:, 1]
+    at_edge = ((xs < w * border_ratio) | (xs > w * (1 - border_ratio)) | (ys < h * border_ratio) | (ys > h * (1 - border_ratio))).mean()
+    return {"coverage_ratio": float(convex_hull_area(pts) / (w * h)), "edge_points_ratio": float(at_edge)}
+
+
+def prune_mask(mean_err, prune_top_ratio: float) -> Optional[np.ndarray]:
+    """The reference's prune rule (main.py:303-308) on the per-view mean errors: with prune_top_ratio > 0 and >= 20 views, the
+    views whose mean exceeds the 1 - ratio quantile are dropped, provided some are and >= 10 remain -> the keep mask, or None
+    when nothing is to be pruned."""
+    means = np.asarray(mean_err, np.float64)
+    if not (prune_top_ratio > 0 and len(means) >= 20):
+        return None
+    keep = means <= np.quantile(means, 1 - prune_top_ratio)
+    if (~keep).sum() == 0 or keep.sum() < 10:
+        return None
+    return keep
 
 
 def fov_and_principal(K, image_size: Tuple[int, int]) -> dict:
@@ -58,3 +166,79 @@ def line_straightness(imgpoints: Sequence, board_size: Tuple[int, int], K, dist,
     und = np.asarray((undistort or _undistort_on_device)(np.ascontiguousarray(pts), K, dist), np.float64)
     return {"straightness_rms_before_px": line_fit_rms(pts, cols, rows),
             "straightness_rms_after_px": line_fit_rms(und, cols, rows)}
+
+
+def _solve(corners, cfg: CalibConfig, image_size, use=None):
+    """corners [V, n, 2] -> geometry.calibrate_camera's result as NumPy arrays (one read-back, after the call)"""
+    import torch
+
+    from . import geometry
+    size = image_size or cfg.image_size
+    if size is None:
+        raise ValueError("calibration needs the frame's (width, height): image_size, or CalibConfig.image_size")
+    img = np.ascontiguousarray(np.asarray(corners, np.float64).reshape(len(corners), -1, 2))
+    obj = prepare_object_points(cfg.board_size, cfg.square_size)[:, :2].astype(np.float64)
+    if img.shape[1] != obj.shape[0]:
+        raise ValueError(f"every board needs {obj.shape[0]} corners ({cfg.board_cols} x {cfg.board_rows}), got {img.shape[1]}")
+    r = geometry.calibrate_camera(torch.from_numpy(obj).cuda(), torch.from_numpy(img).cuda(), size,
+                                  use=None if use is None else torch.from_numpy(np.ascontiguousarray(use, dtype=np.uint8)).cuda(),
+                                  rational_model=cfg.rational_model, zero_tangent=cfg.zero_tangent, max_evals=cfg.max_evals)
+    return img, tuple(int(x) for x in size), {k: getattr(r, k).cpu().numpy() for k in r._fields}
+
+
+def calibrate_camera(corners, cfg: CalibConfig, image_size: Optional[Tuple[int, int]] = None, names: Optional[Sequence[str]] = None,
+                     undistort: Optional[Callable] = None) -> dict:
+    """calibrate_camera (main.py:250-380) from detected corners: corners [V, n, 2] (or cv2's [V, n, 1, 2]), every board
+    row-major with cfg.board_cols corners a row; names: one per view (default view_0000 ..) -> the reference's result dict
+    (status, rms_reproj_error, camera_matrix, dist_coeffs, num_images, image_size, used_names, dropped_names, the global
+    reprojection, coverage, field-of-view and straightness figures; the last over the boards with every corner finite), without per_image_csv and the valid-ROI figures, plus
+    rvecs, tvecs [num_images, 3], per_image (the CSV's rows), std_intrinsics (geometry.CALIB_PARAMS' order) and
+    rms_before_prune.  The prune step is the reference's: the second calibration runs through the solver's `use` mask and is
+    accepted iff its rms fell.  dist_coeffs holds 5 coefficients, or 8 with the rational model."""
+    img, size, r = _solve(corners, cfg, image_size)
+    V = img.shape[0]
+    names = [f"view_{i:04d}" for i in range(V)] if names is None else list(names)
+    if len(names) != V:
+        raise ValueError(f"{len(names)} names for {V} views")
+    if not np.isfinite(r["rms"][0]):
+        return {"status": "Failed", "reason": "fewer than 3 usable views", "num_images": int(r["n_views"][0])}
+    used = ~np.isnan(r["mean_err"][0])
+    rms_first = float(r["rms"][0])
+    dropped = []
+    keep = prune_mask(r["mean_err"][0][used], cfg.prune_top_ratio)
+    if keep is not None:
+        idx = np.flatnonzero(used)
+        use = np.zeros((1, V), np.uint8)
+        use[0, idx[keep]] = 1
+        _, _, r2 = _solve(corners, cfg, size, use=use)
+        if r2["rms"][0] < r["rms"][0]:                     # accept iff the rms fell (a NaN fails)
+            dropped = [names[i] for i in idx[~keep]]
+            r, used = r2, ~np.isnan(r2["mean_err"][0])
+    K, n_coef = r["K"][0], 8 if cfg.rational_model else 5
+    dist = r["dist"][0][:n_coef].copy()
+    per_img, global_stats = reproj_stats(r["err"][0])
+    kept = [names[i] for i in np.flatnonzero(used)]
+    for row, name in zip(per_img, kept):
+        row["image_name"] = name
+    return {"status": "Success", "rms_reproj_error": float(r["rms"][0]), "camera_matrix": K, "dist_coeffs": dist,
+            "num_images": len(kept), "image_size": size, "used_names": kept, "dropped_names": dropped, **global_stats,
+            **edge_center_ratio(img[used], size, border_ratio=0.2), **fov_and_principal(K, size),
+            **line_straightness(img[used & np.isfinite(img).all(axis=(1, 2))], cfg.board_size, K, dist, undistort=undistort),
+            "rvecs": r["rvec"][0][used], "tvecs": r["t"][0][used], "per_image": per_img, "std_intrinsics": r["std"][0],
+            "rms_before_prune": rms_first, "n_evals": int(r["n_evals"][0]), "converged": bool(r["success"][0])}
+
+
+def leave_one_out(corners, cfg: CalibConfig, image_size: Optional[Tuple[int, int]] = None) -> dict:
+    """The V calibrations that each leave one view out, in one device call (group v omits view v) -> K [V, 3, 3], dist [V, 12],
+    rms [V], success [V] and spread: per parameter (geometry.CALIB_PARAMS' order) the mean, std, min and max over the
+    groups that succeeded in stopping on a finite result.  A parameter whose spread is large against its std_intrinsics
+    depends on single views."""
+    from . import geometry
+    V = len(corners)
+    _, _, r = _solve(corners, cfg, image_size, use=1 - np.eye(V, dtype=np.uint8))
+    p = np.concatenate([r["K"][:, [0, 1, 0, 1], [0, 1, 2, 2]], r["dist"][:, :8]], axis=1)
+    ok = np.isfinite(p).all(axis=1)
+    q = p[ok] if ok.any() else np.full((1, 12), np.nan)
+    return {"K": r["K"], "dist": r["dist"], "rms": r["rms"], "success": r["success"], "n_evals": r["n_evals"],
+            "spread": {"names": list(geometry.CALIB_PARAMS), "mean": q.mean(axis=0), "std": q.std(axis=0), "min": q.min(axis=0),
+                       "max": q.max(axis=0)}}

@@ -348,3 +348,43 @@ def load_calibration(path) -> Calibration:
     dist = np.zeros(14, np.float64)
     dist[:d.size] = d
     return Calibration(K, dist, (int(size[0]), int(size[1])))
+
+
+def _opencv_matrix(name: str, a: np.ndarray) -> str:
+    vals = [repr(float(v)) for v in a.reshape(-1)]
+    lines, line = [], "   data: ["
+    for k, v in enumerate(vals):
+        piece = v + (", " if k + 1 < len(vals) else " ]")
+        if len(line) + len(piece) > 76:
+            lines.append(line.rstrip())
+            line = "       "
+        line += piece
+    lines.append(line)
+    return f"{name}: !!opencv-matrix\n   rows: {a.shape[0]}\n   cols: {a.shape[1]}\n   dt: d\n" + "\n".join(lines) + "\n"
+
+
+def save_calibration(npz_path, yml_path, K, dist, image_size, rvecs=None, tvecs=None, used=(), used_full=None, dropped=(),
+                     flags: int = 0) -> None:
+    """What camera_calibration/main.py saves (:325-349) and `load_calibration` reads.  npz_path: camera_matrix [3, 3],
+    dist_coeffs [1, k] (k = 4, 5, 8, 12 or 14), image_size (width, height), rvecs / tvecs [V, 3, 1], used, used_full,
+    dropped as fixed-width string arrays -- no pickled object arrays, and no `config` entry (the reference pickles a dict).
+    yml_path: OpenCV FileStorage with image_width, image_height, camera_matrix, distortion_coefficients, and flags.  Either
+    path may be None.  Every float is written with repr, so both files read back to the same bits."""
+    K = np.asarray(K, np.float64)
+    d = np.asarray(dist, np.float64).reshape(-1)
+    w, h = (int(x) for x in image_size)
+    if K.shape != (3, 3) or d.size not in (4, 5, 8, 12, 14):
+        raise ValueError(f"save_calibration: camera_matrix {list(K.shape)}, {d.size} coefficients (4, 5, 8, 12 or 14)")
+    strs = lambda names: np.array([str(x) for x in names], dtype=np.str_).reshape(-1)      # noqa: E731
+    if npz_path is not None:
+        npz_path = Path(npz_path)
+        npz_path.parent.mkdir(parents=True, exist_ok=True)
+        vec = lambda a: np.zeros((0, 3, 1)) if a is None else np.asarray(a, np.float64).reshape(-1, 3, 1)     # noqa: E731
+        np.savez(str(npz_path), camera_matrix=K, dist_coeffs=d[None], rvecs=vec(rvecs), tvecs=vec(tvecs),
+                 image_size=np.array([w, h], np.int64), used=strs(used), used_full=strs(used if used_full is None else used_full),
+                 dropped=strs(dropped))
+    if yml_path is not None:
+        yml_path = Path(yml_path)
+        yml_path.parent.mkdir(parents=True, exist_ok=True)
+        yml_path.write_text(f"%YAML:1.0\n---\nimage_width: {w}\nimage_height: {h}\n" + _opencv_matrix("camera_matrix", K)
+                            + _opencv_matrix("distortion_coefficients", d[None]) + f"flags: {int(flags)}\n")

@@ -988,6 +988,25 @@ def gen_bev():
 GENERATORS["bev"] = gen_bev
 
 
+def gen_calibrate():
+    """DESIGN §2 "Calibration": recorded results of the calibration the reference ships (camera_calibration/
+    calibration_parameters.npz): its camera matrix, its first eight coefficients, the frame size and 24 of its 181 board
+    poses (indices linspace(0, 180, 24) truncated), with the board's geometry (9 x 6 inner corners, squares of 25).  The tests
+    synthesise corners from these by projecting the board.  The file's pickled object arrays are never touched."""
+    with np.load(Path(REF) / "camera_calibration" / "calibration_parameters.npz", allow_pickle=False) as z:
+        idx = np.linspace(0, 180, 24).astype(np.int64)
+        out = {"camera_matrix": z["camera_matrix"].astype(np.float64), "dist_coeffs": z["dist_coeffs"].astype(np.float64).reshape(-1)[:8],
+               "image_size": z["image_size"].astype(np.int64), "rvecs": z["rvecs"].astype(np.float64).reshape(-1, 3)[idx],
+               "tvecs": z["tvecs"].astype(np.float64).reshape(-1, 3)[idx], "view_index": idx,
+               "board": np.array([9, 6], np.int64), "square": np.array(25.0)}
+    path = GOLD / "calibrate.npz"
+    np.savez_compressed(path, **out)
+    print("wrote", path.name, path.stat().st_size, "bytes")
+
+
+GENERATORS["calibrate"] = gen_calibrate
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GENERATORS)
     for w in which:
