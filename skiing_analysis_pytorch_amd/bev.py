@@ -25,7 +25,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _lib, geometry, preprocess
+from . import geometry, preprocess
+from ._args import device_tensor
 
 # the reference's marked ground points of the 1920 x 1080 front frame and their places on the ground, in metres
 DEFAULT_IMG_PTS = np.array([[0.0, 1080.0], [1920.0, 1080.0], [1336.0, 130.0], [600.0, 130.0]], dtype=np.float64)
@@ -54,15 +55,9 @@ def make_bev_canvas(cfg: BeVConfig = BeVConfig()) -> Tuple[Tuple[int, int], np.n
     return (w, h), np.array([[s, 0, -x_min * s], [0, -s, y_max * s], [0, 0, 1]], dtype=np.float64)
 
 
-def _dev(name, a) -> torch.Tensor:
-    if not isinstance(a, torch.Tensor) or not a.is_cuda:
-        raise _lib.SkimiError(f"{name} needs device tensors")
-    return a
-
-
 def convert_xywh_to_xyxy(bboxes_xywh: torch.Tensor) -> torch.Tensor:
     """[..., 4] (x, y, w, h) -> (x1, y1, x2, y2) = (x, y, x + w, y + h)."""
-    b = _dev("convert_xywh_to_xyxy", bboxes_xywh)
+    b = device_tensor("convert_xywh_to_xyxy", bboxes_xywh)
     if b.dim() < 1 or b.shape[-1] != 4:
         raise ValueError(f"Invalid bbox shape for xywh to xyxy: {list(b.shape)}")
     return torch.stack([b[..., 0], b[..., 1], b[..., 0] + b[..., 2], b[..., 1] + b[..., 3]], dim=-1)
@@ -70,7 +65,7 @@ def convert_xywh_to_xyxy(bboxes_xywh: torch.Tensor) -> torch.Tensor:
 
 def unnormalize_bbox(bbox: torch.Tensor, img_size: Tuple[int, int]) -> torch.Tensor:
     """[..., 4] (x1, y1, x2, y2) in [0, 1] -> float64 pixels of img_size = (H, W)."""
-    b = _dev("unnormalize_bbox", bbox).to(torch.float64)
+    b = device_tensor("unnormalize_bbox", bbox).to(torch.float64)
     if b.dim() < 1 or b.shape[-1] != 4:
         raise ValueError(f"bbox last dim must be 4, got {list(b.shape)}")
     H, W = img_size
@@ -79,7 +74,7 @@ def unnormalize_bbox(bbox: torch.Tensor, img_size: Tuple[int, int]) -> torch.Ten
 
 def foot_from_bbox_xyxy(bbox: torch.Tensor) -> torch.Tensor:
     """[..., 4] (x1, y1, x2, y2) -> float64 [..., 2]: the middle of the box's lower edge, ((x1 + x2) * 0.5, y2)."""
-    b = _dev("foot_from_bbox_xyxy", bbox).to(torch.float64)
+    b = device_tensor("foot_from_bbox_xyxy", bbox).to(torch.float64)
     if b.dim() < 1 or b.shape[-1] != 4:
         raise ValueError(f"bbox must have 4 numbers, got {list(b.shape)}")
     return torch.stack([(b[..., 0] + b[..., 2]) * 0.5, b[..., 3]], dim=-1)
@@ -106,8 +101,8 @@ def inverse3(H: torch.Tensor) -> torch.Tensor:
 def warp_image_to_bev(image: torch.Tensor, H: torch.Tensor, bev_size: Tuple[int, int]) -> torch.Tensor:
     """cv2.warpPerspective(image, H, bev_size, flags=INTER_LINEAR): image uint8 [h, w, ch] or [F, h, w, ch], H [3, 3] the
     FORWARD matrix (image -> plan) as cv2 takes it, both on the device; bev_size = (width, height)."""
-    img = _dev("warp_image_to_bev", image)
-    Hd = _dev("warp_image_to_bev", H).to(torch.float64)
+    img = device_tensor("warp_image_to_bev", image)
+    Hd = device_tensor("warp_image_to_bev", H).to(torch.float64)
     if tuple(Hd.shape) != (3, 3):
         raise ValueError(f"H shape must be (3,3), got {list(Hd.shape)}")
     out = preprocess.warp_perspective(img if img.dim() == 4 else img[None], inverse3(Hd), bev_size)
@@ -148,8 +143,8 @@ def make_bev(img: torch.Tensor, bboxes_xyxy: torch.Tensor, img_pts=None, cfg: Be
     (foot_xy_px float64 [N, 2] plan pixels, src = img as it came, bev_img uint8 [bev_h, bev_w, 3]).  blank_bev: the plan is
     the flat colour bev_bg and nothing is warped.  A degenerate img_pts raises ValueError as the reference (one read-back
     of the fit's status; process_front_clip reads nothing back)."""
-    img = _dev("make_bev", img)
-    boxes = _dev("make_bev", bboxes_xyxy).to(torch.float64)
+    img = device_tensor("make_bev", img)
+    boxes = device_tensor("make_bev", bboxes_xyxy).to(torch.float64)
     if boxes.dim() == 1:
         boxes = boxes[None]
     if boxes.dim() != 2 or boxes.shape[1] != 4:
@@ -170,7 +165,7 @@ def project_world_to_bev_centered(kpts_world: torch.Tensor, center_world, center
                                   rot90_left: bool = False) -> geometry.BevSkeletonResult:
     """kpts_world [J, 3] (or [T, J, 3]), center_world [3] ([T, 3]; None: merge's np.nanmean over the joints), center_px [2]
     ([T, 2]), device tensors -> BevSkeletonResult.  The reference's list of (u, v) tuples and None is px with valid."""
-    k = _dev("project_world_to_bev_centered", kpts_world)
+    k = device_tensor("project_world_to_bev_centered", kpts_world)
     c = center_px if isinstance(center_px, torch.Tensor) else torch.tensor([float(v) for v in center_px], dtype=torch.float64,
                                                                           device=k.device)
     return geometry.bev_skeleton(k, c, meters_per_pixel, use_axes, rot90_left, center_world=center_world)
@@ -209,10 +204,10 @@ def process_front_clip(frames: torch.Tensor, boxes_xywh: torch.Tensor, img_pts=N
     H_px A^-1: the second group of the fit takes the ground points A img_pts, in the frame's own pixels, and its Hinv is
     what the warp reads the frame with.  For frames already of calib_size A is the identity, the two groups are the same
     bits and the result is the reference's rule exactly."""
-    fr = _dev("process_front_clip", frames)
+    fr = device_tensor("process_front_clip", frames)
     if fr.dtype != torch.uint8 or fr.dim() != 4 or fr.shape[3] != 3:
         raise ValueError(f"process_front_clip: frames must be uint8 [T, h, w, 3], got {fr.dtype} {list(fr.shape)}")
-    boxes = _dev("process_front_clip", boxes_xywh)
+    boxes = device_tensor("process_front_clip", boxes_xywh)
     T, h, w = int(fr.shape[0]), int(fr.shape[1]), int(fr.shape[2])
     if boxes.dim() != 3 or boxes.shape[0] != T or boxes.shape[2] != 4:
         raise ValueError(f"process_front_clip: boxes_xywh must be [{T}, N, 4], got {list(boxes.shape)}")

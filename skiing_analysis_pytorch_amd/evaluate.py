@@ -16,10 +16,10 @@ from __future__ import annotations
 import math
 from pathlib import Path
 
-import numpy as np
 import torch
 
 from . import geometry
+from ._args import upload_f64
 
 FUSED_METRICS_HEADER = "Fused Pose Evaluation Metrics:"       # VideoPose3D/main.py:100
 
@@ -28,9 +28,7 @@ def _dev(a, like=None):
     """a device float64 tensor of a host array or tensor (a device tensor stays where it is)"""
     if isinstance(a, torch.Tensor) and a.is_cuda:
         return a.to(torch.float64)
-    dev = like.device if like is not None else torch.device("cuda", torch.cuda.current_device())
-    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
-    return t.to(dev, torch.float64)
+    return upload_f64(a, like.device if like is not None else torch.device("cuda", torch.cuda.current_device()))
 
 
 def _frames(name, a, like=None):

@@ -17,8 +17,10 @@ from typing import Sequence
 import numpy as np
 import torch
 
-from . import _lib, geometry
+from . import _lib
+from ._args import camera_matrices, frame_clip, frame_out, host_ptr, on_device, per_camera_coeffs, shapes, to_dev
 from ._lib import check, lib, ptr
+from .device.lens import LENS_MAX_CAMERAS, lens_coeffs
 
 PRECISION_BITS = 32 - 8 - 2   # Resample.c: 8-bit pixels, 2 bits of headroom for the overshoot of the cubic
 
@@ -143,31 +145,16 @@ def undistort_images(frames: torch.Tensor, K, dist, new_K=None, out_size=None, o
     distorted and mapped through K to a source position, computed on the fly in float64 and sampled bilinearly with a zero
     border; the value is rounded half up.  out: a contiguous uint8 device tensor of the result's shape to write into.
     The input is not modified."""
-    if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() not in (4, 5):
-        raise _lib.SkimiError("undistort_images needs a uint8 [F, H, W, ch] or [C, F, H, W, ch] device tensor")
-    five = frames.dim() == 5
-    fr = frames.contiguous() if five else frames.contiguous()[None]
+    fr, five = frame_clip("undistort_images", frames)
     C, F, H, W, ch = (int(s) for s in fr.shape)
-    if ch not in (1, 3, 4):
-        raise ValueError(f"undistort_images: 1, 3 or 4 channels, got {ch}")
-    if C > geometry.LENS_MAX_CAMERAS:
-        raise ValueError(f"undistort_images: at most {geometry.LENS_MAX_CAMERAS} cameras a call, got {C}")
-    Kh = geometry._lens_matrix("undistort_images", "K", K, C)
-    Nh = None if new_K is None else geometry._lens_matrix("undistort_images", "new_K", new_K, C)
-    d = geometry.lens_coeffs(dist)
-    if d.ndim > 2 or (d.ndim == 2 and d.shape[0] not in (1, C)):
-        raise ValueError(f"undistort_images: dist must be [k] or [{C}, k], got {list(d.shape)}")
-    d = np.ascontiguousarray(np.broadcast_to(d.reshape(-1, 12), (C, 12)))
+    if C > LENS_MAX_CAMERAS:
+        raise ValueError(f"undistort_images: at most {LENS_MAX_CAMERAS} cameras a call, got {C}")
+    Kh = camera_matrices("undistort_images", "K", K, C)
+    Nh = None if new_K is None else camera_matrices("undistort_images", "new_K", new_K, C)
+    d = per_camera_coeffs("undistort_images", lens_coeffs(dist), C)
     ow, oh = (W, H) if out_size is None else (int(out_size[0]), int(out_size[1]))
-    if ow < 1 or oh < 1 or H < 1 or W < 1:
-        raise ValueError(f"undistort_images: empty frame ({W} x {H} -> {ow} x {oh})")
-    shape = (C, F, oh, ow, ch) if five else (F, oh, ow, ch)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=fr.device)
-    elif (not out.is_cuda or out.device != fr.device or out.dtype != torch.uint8 or tuple(out.shape) != shape
-          or not out.is_contiguous()):
-        raise ValueError(f"undistort_images: out must be a contiguous uint8 device tensor {list(shape)}")
-    check(lib().skimi_undistort_u8(ptr(fr), ptr(out), geometry._hp(Kh), geometry._hp(d), geometry._hp(Nh), C, F, H, W, oh, ow, ch,
+    out = frame_out("undistort_images", fr, five, ow, oh, out)
+    check(lib().skimi_undistort_u8(ptr(fr), ptr(out), host_ptr(Kh), host_ptr(d), host_ptr(Nh), C, F, H, W, oh, ow, ch,
                                    _lib.current_stream()), "skimi_undistort_u8")
     return out
 
@@ -182,28 +169,14 @@ def warp_perspective(frames: torch.Tensor, Hinv: torch.Tensor, out_size, per_fra
     beyond the horizon line is mirrored as cv2 mirrors it), sampled bilinearly, rounded half up; a non-finite matrix (a
     failed fit) gives a black frame.  out: a contiguous uint8 device tensor of the result's shape to write into.  The
     input is not modified."""
-    if not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() not in (4, 5):
-        raise _lib.SkimiError("warp_perspective needs a uint8 [F, H, W, ch] or [C, F, H, W, ch] device tensor")
-    if not isinstance(Hinv, torch.Tensor) or not Hinv.is_cuda:
-        raise _lib.SkimiError("warp_perspective needs Hinv on the device")
-    five = frames.dim() == 5
-    fr = frames.contiguous() if five else frames.contiguous()[None]
+    on_device("warp_perspective", Hinv, what="Hinv on the device")
+    fr, five = frame_clip("warp_perspective", frames)
     C, F, H, W, ch = (int(s) for s in fr.shape)
-    if ch not in (1, 3, 4):
-        raise ValueError(f"warp_perspective: 1, 3 or 4 channels, got {ch}")
     lead = ((C, F) if five else (F,)) if per_frame else ((C,) if five else ())
-    g = Hinv.to(fr.device, torch.float64).contiguous()
-    if tuple(g.shape) != (*lead, 3, 3):
-        raise ValueError(f"warp_perspective: Hinv must be {[*lead, 3, 3]} (per_frame={bool(per_frame)}), got {list(g.shape)}")
+    g = to_dev(Hinv, dev=fr.device)
+    shapes("warp_perspective", ((f"Hinv (per_frame={bool(per_frame)})", g, (*lead, 3, 3)),))
     ow, oh = int(out_size[0]), int(out_size[1])
-    if ow < 1 or oh < 1 or H < 1 or W < 1:
-        raise ValueError(f"warp_perspective: empty frame ({W} x {H} -> {ow} x {oh})")
-    shape = (C, F, oh, ow, ch) if five else (F, oh, ow, ch)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.uint8, device=fr.device)
-    elif (not out.is_cuda or out.device != fr.device or out.dtype != torch.uint8 or tuple(out.shape) != shape
-          or not out.is_contiguous()):
-        raise ValueError(f"warp_perspective: out must be a contiguous uint8 device tensor {list(shape)}")
+    out = frame_out("warp_perspective", fr, five, ow, oh, out)
     check(lib().skimi_warp_perspective_u8(ptr(fr), ptr(out), ptr(g), int(bool(per_frame)), C, F, H, W, oh, ow, ch,
                                           _lib.current_stream()), "skimi_warp_perspective_u8")
     return out
