@@ -332,6 +332,32 @@ int skimi_attention_ex(const void* qkv, void* out, int32_t dtype, int32_t out_dt
 /* bytes of x3_scratch the bf16x3 attention kernel needs for `tokens` packed qkv rows of `row_elems` f32 each */
 uint64_t skimi_attention_x3_scratch_bytes(int64_t tokens, int64_t row_elems);
 
+/* The LayerNorm and fp32 attention launches with every argument the forward gives them (vggt.hip's DPT heads, the track
+ * head's run_mha), for kernel-level tests.
+ *
+ * skimi_layernorm_ex: skimi_layernorm plus
+ *   grp_rows, grp_stride, grp_off   input row gather: output row r reads input row
+ *                (r / grp_rows) * grp_stride + grp_off + r % grp_rows (grp_rows = 0: row r).  The DPT heads drop the
+ *                special tokens of every frame with it.  grp_rows > 0 needs grp_off >= 0 and
+ *                grp_stride >= grp_off + grp_rows;
+ *   in_rows      rows the input buffers hold: every row index read must be below it;
+ *   out_dtype    SKIMI_F32 / SKIMI_BF16 / SKIMI_F16 with row stride ldo >= C, or SKIMI_BF16X3_REC: bf16x3 records
+ *                [rows][C/32][hi 32 | lo 32] followed by a 256-byte zero page (`out` 128-byte aligned, rows * C * 4 + 256
+ *                bytes; C % 256 == 0 with C/256 in {1, 2, 3, 4, 6, 8}, 16-byte aligned operands, ldx % 4 == 0; ldo unused).
+ *
+ * skimi_attention_f32_strided: softmax(scale q k^T) v in fp32 on four separate streams.  Element (g, head, token, d)
+ * of stream s sits at s + go * s_strides[3] + gi * s_strides[2] + head * s_strides[1] + token * s_strides[0] + d with
+ * g = go * batch_inner + gi (batch_inner = 0: one level, gi = g).  *_strides = {token, head, batch, outer batch} in
+ * elements, every one a multiple of 4, every pointer 16-byte aligned; head_dim a multiple of 4 up to 128;
+ * batch <= 65535 (a grid dimension), batch_inner > 0 divides batch. */
+int skimi_layernorm_ex(const float* x, const float* x2, int64_t ldx, int64_t in_rows, int64_t rows, int32_t C,
+                       const float* gamma, const float* beta, float eps, void* out, int32_t out_dtype, int64_t ldo,
+                       int64_t grp_rows, int64_t grp_stride, int64_t grp_off, void* stream);
+int skimi_attention_f32_strided(const float* q, const float* k, const float* v, float* out, const int64_t* q_strides,
+                                const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
+                                int32_t batch, int32_t batch_inner, int32_t heads, int32_t seq_q, int32_t seq_k,
+                                int32_t head_dim, float scale, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* VideoPose3D TemporalModel lifter  (VideoPose3D/common/model.py:79-138)     */
 /* ------------------------------------------------------------------------- */

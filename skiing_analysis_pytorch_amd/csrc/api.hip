@@ -259,10 +259,56 @@ uint64_t skimi_attention_x3_scratch_bytes(int64_t tokens, int64_t row_elems) {
     return (uint64_t)attention_x3_scratch_bytes((long)tokens, (long)row_elems);
 }
 
-// ---- VGGT head / track-head helper kernels, one launch each (vggt_kernels.hip, track_kernels.hip): the forward
-// calls the launches directly with sizes it derived itself; here every scalar a caller supplies is checked first ----
 static inline bool is_elem_dtype(int32_t d) { return d == SKIMI_F32 || d == SKIMI_BF16 || d == SKIMI_F16; }
 static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// the LayerNorm launch of the DPT heads (vggt.hip) and the attention launch of the track head (track_impl.inc's
+// run_mha), with their arguments, for kernel-level tests.  The forward derives the gather and the strides itself; here
+// what the kernels cannot notice is checked first.
+int skimi_layernorm_ex(const float* x, const float* x2, int64_t ldx, int64_t in_rows, int64_t rows, int32_t C,
+                       const float* gamma, const float* beta, float eps, void* out, int32_t out_dtype, int64_t ldo,
+                       int64_t grp_rows, int64_t grp_stride, int64_t grp_off, void* stream) {
+    SKIMI_CHECK_ARG(rows > 0 && in_rows > 0 && ldx >= 0, "skimi_layernorm_ex: rows, in_rows must be positive, ldx not negative");
+    SKIMI_CHECK_ARG(grp_rows >= 0, "skimi_layernorm_ex: grp_rows = %ld is negative", (long)grp_rows);
+    int64_t last = rows - 1;   // the largest input row read
+    if (grp_rows > 0) {
+        SKIMI_CHECK_ARG(grp_off >= 0 && grp_stride >= grp_off + grp_rows,
+                        "skimi_layernorm_ex: the gather needs grp_off >= 0 and grp_stride >= grp_off + grp_rows (got %ld, %ld, %ld)",
+                        (long)grp_rows, (long)grp_stride, (long)grp_off);
+        last = (rows - 1) / grp_rows * grp_stride + grp_off + (rows - 1) % grp_rows;
+    }
+    SKIMI_CHECK_ARG(last < in_rows, "skimi_layernorm_ex: input row %ld is read, the input has %ld rows", (long)last, (long)in_rows);
+    SKIMI_CHECK_ARG(out_dtype == SKIMI_BF16X3_REC || ldo >= C, "skimi_layernorm_ex: ldo = %ld is below C = %d", (long)ldo, C);
+    return layernorm_launch(x, x2, ldx, rows, C, gamma, beta, eps, out, out_dtype, ldo, (hipStream_t)stream, grp_rows,
+                            grp_stride, grp_off);
+}
+
+int skimi_attention_f32_strided(const float* q, const float* k, const float* v, float* out, const int64_t* q_strides,
+                                const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
+                                int32_t batch, int32_t batch_inner, int32_t heads, int32_t seq_q, int32_t seq_k,
+                                int32_t head_dim, float scale, void* stream) {
+    SKIMI_CHECK_ARG(q_strides && k_strides && v_strides && o_strides, "skimi_attention_f32_strided: null stride list");
+    SKIMI_CHECK_ARG(batch <= 65535 && heads <= 65535, "skimi_attention_f32_strided: batch %d and heads %d are grid dimensions (<= 65535)",
+                    batch, heads);
+    SKIMI_CHECK_ARG(batch_inner >= 0 && (batch_inner == 0 || batch % batch_inner == 0),
+                    "skimi_attention_f32_strided: batch_inner %d must divide batch %d", batch_inner, batch);
+    for (int i = 0; i < 4; ++i)
+        SKIMI_CHECK_ARG(q_strides[i] % 4 == 0 && k_strides[i] % 4 == 0 && v_strides[i] % 4 == 0 && o_strides[i] % 4 == 0,
+                        "skimi_attention_f32_strided: every stride must be a multiple of 4 elements (16-B loads)");
+    SKIMI_CHECK_ARG(al16(q) && al16(k) && al16(v) && al16(out), "skimi_attention_f32_strided: 16-byte aligned buffers");
+    AttnArgs a;
+    a.q = q; a.k = k; a.v = v; a.out = out;
+    a.q_row = q_strides[0]; a.k_row = k_strides[0]; a.v_row = v_strides[0]; a.o_row = o_strides[0];
+    a.q_head = q_strides[1]; a.k_head = k_strides[1]; a.v_head = v_strides[1]; a.o_head = o_strides[1];
+    a.q_batch = q_strides[2]; a.k_batch = k_strides[2]; a.v_batch = v_strides[2]; a.o_batch = o_strides[2];
+    a.q_batch2 = q_strides[3]; a.k_batch2 = k_strides[3]; a.v_batch2 = v_strides[3]; a.o_batch2 = o_strides[3];
+    a.batch = batch; a.batch_inner = batch_inner; a.heads = heads; a.seq_q = seq_q; a.seq_k = seq_k; a.head_dim = head_dim;
+    a.scale = scale;
+    return attention_f32_launch(a, (hipStream_t)stream);   // its own checks: null buffers, empty shape, head_dim
+}
+
+// ---- VGGT head / track-head helper kernels, one launch each (vggt_kernels.hip, track_kernels.hip): the forward
+// calls the launches directly with sizes it derived itself; here every scalar a caller supplies is checked first ----
 
 int skimi_resize_bilinear(const void* in, void* out, int32_t dtype, int32_t out_dtype, int32_t N, int32_t h, int32_t w,
                           int32_t H, int32_t W, int32_t C, const float* tabx, const float* taby, const float* ln_g,

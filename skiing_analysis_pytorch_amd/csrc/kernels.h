@@ -11,6 +11,10 @@ int layernorm_launch(const float* x, const float* x2, int64_t ldx, int64_t rows,
                      const float* gamma, const float* beta, float eps, void* out, int out_dtype,
                      int64_t ldo, hipStream_t st, int64_t grp_rows = 0, int64_t grp_stride = 0,
                      int64_t grp_off = 0);
+// out_dtype SKIMI_BF16X3_REC is written by the vector kernel only: C / 256 must be one of its instantiations
+static inline bool layernorm_records_ok(int C) {
+    return C % 256 == 0 && (C / 256 <= 4 || C / 256 == 6 || C / 256 == 8);
+}
 
 int qknorm_rope_launch(void* qkv, int dtype, int64_t tokens, int heads, const float* qn_w,
                        const float* qn_b, const float* kn_w, const float* kn_b, float eps,

@@ -144,8 +144,8 @@ int layernorm_launch(const float* x, const float* x2, int64_t ldx, int64_t rows,
     SKIMI_CHECK_ARG(out_dtype == SKIMI_F32 || out_dtype == SKIMI_BF16 || out_dtype == SKIMI_F16 || out_dtype == SKIMI_BF16X3_REC,
                     "skimi_layernorm: bad out_dtype %d", out_dtype);
     dim3 grid((unsigned)cdiv(rows, 4)), block(256);
-    SKIMI_CHECK_ARG(out_dtype != SKIMI_BF16X3_REC || (C % 256 == 0 && ((uintptr_t)out & 127) == 0),
-                    "skimi_layernorm: records output needs C %% 256 == 0 and a 128-byte aligned buffer");
+    SKIMI_CHECK_ARG(out_dtype != SKIMI_BF16X3_REC || (layernorm_records_ok(C) && ((uintptr_t)out & 127) == 0),
+                    "skimi_layernorm: records output needs C = 256 * {1, 2, 3, 4, 6, 8} and a 128-byte aligned buffer");
     {
         auto al16 = [](const void* p) { return p == nullptr || ((uintptr_t)p & 15) == 0; };
         const bool vec = C % 256 == 0 && (x2 == nullptr || (C / 2) % 256 == 0) && ldx % 4 == 0 && ldo % 4 == 0 &&

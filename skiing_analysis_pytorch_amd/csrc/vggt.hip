@@ -646,7 +646,7 @@ void* run_dpt(Ctx& c, const DptW& w, float* const* sf, float* const* sg, int F, 
                 // wide projections run on the LDS-DMA bf16x3 kernel: the LayerNorm writes their operand records
                 auto d = c.desc(w.proj[i], lnb, adt, D, F * np, t0, adt, w.oc[i]);
                 bool rec_in = false;
-                if (adt == SKIMI_F32 && D % 256 == 0 && w.proj[i].w_split != nullptr) {
+                if (adt == SKIMI_F32 && layernorm_records_ok(D) && w.proj[i].w_split != nullptr) {
                     auto q = d;
                     q.a_dtype = SKIMI_BF16X3_REC;
                     q.x3_scratch = (char*)lnb_rec + (size_t)F * np * D * 4;

@@ -154,13 +154,48 @@ def gemm_last_path() -> GemmPath:
                     mfma={1: 16, 2: 32}.get((v >> 8) & 15), epi=(v >> 12) & 15, splitk=(v >> 16) & 255, raw=v)
 
 
-def layernorm(x, gamma=None, beta=None, eps=1e-5, *, x2=None, out_dtype=torch.float32):
-    _require_cuda(x, x2, gamma, beta)
-    rows = x.numel() // x.shape[-1]
+def layernorm(x, gamma=None, beta=None, eps=1e-5, *, x2=None, out_dtype=torch.float32, out=None, rows=None, ldo=None,
+              grp_rows=0, grp_stride=0, grp_off=0):
+    """LayerNorm over the last dim of x (with x2: of the concatenation [x | x2], x2 on x's row stride).
+
+    The keyword arguments after out_dtype make the launches of the forward (skimi_layernorm_ex); x is [in_rows, C] then,
+    on any row stride.  grp_rows / grp_stride / grp_off: output row r reads input row (r // grp_rows) * grp_stride +
+    grp_off + r % grp_rows; rows: output rows (default: every input row, or every whole group of the gather);
+    out_dtype="records": bf16x3 records + zero page (a `records_buffer`); out: the destination -- for records any buffer of
+    rows * C * 4 + 256 bytes, 128-byte aligned, else [rows, >= C] whose row stride is ldo (ldo= overrides it)."""
+    _require_cuda(x, x2, gamma, beta, out)
     Cc = x.shape[-1] * (2 if x2 is not None else 1)
-    out = torch.empty((*x.shape[:-1], Cc), dtype=out_dtype, device=x.device)
-    check(lib().skimi_layernorm(ptr(x), ptr(x2), x.stride(-2), rows, Cc, ptr(gamma), ptr(beta), eps, ptr(out),
-                                _dt(out), Cc, _lib.current_stream()), "skimi_layernorm")
+    if out is None and rows is None and ldo is None and not grp_rows and not isinstance(out_dtype, str):
+        rows = x.numel() // x.shape[-1]
+        out = torch.empty((*x.shape[:-1], Cc), dtype=out_dtype, device=x.device)
+        check(lib().skimi_layernorm(ptr(x), ptr(x2), x.stride(-2), rows, Cc, ptr(gamma), ptr(beta), eps, ptr(out),
+                                    _dt(out), Cc, _lib.current_stream()), "skimi_layernorm")
+        return out
+    if x.dim() != 2 or x.stride(-1) != 1 or (x2 is not None and (x2.shape != x.shape or x2.stride() != x.stride())):
+        raise _lib.SkimiError("layernorm: the strided form takes x [in_rows, C] with unit column stride, x2 laid out like x")
+    in_rows = x.shape[0]
+    if rows is None:
+        rows = in_rows // grp_stride * grp_rows if grp_rows else in_rows
+    records = isinstance(out_dtype, str)
+    if records:
+        assert out_dtype == "records", out_dtype
+        if out is None:
+            out = records_buffer(rows, Cc, x.device)
+        if out.numel() * out.element_size() < rows * Cc * 4 + 256:
+            raise _lib.SkimiError("layernorm: `out` is too small for the records and their zero page")
+        odt, ldo = _lib.BF16X3_REC, Cc
+    else:
+        if out is None:
+            out = torch.empty((rows, ldo or Cc), dtype=out_dtype, device=x.device)
+        odt = _dt(out)
+        if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] < rows or out.shape[1] < Cc:
+            raise _lib.SkimiError("layernorm: `out` is [>= rows, >= C] with unit column stride")
+        if ldo is None:
+            ldo = out.stride(0)
+        elif ldo != out.stride(0):
+            raise _lib.SkimiError("layernorm: ldo is the row stride of `out`")
+    check(lib().skimi_layernorm_ex(ptr(x), ptr(x2), x.stride(0), in_rows, rows, Cc, ptr(gamma), ptr(beta), eps, ptr(out), odt,
+                                   ldo, grp_rows, grp_stride, grp_off, _lib.current_stream()), "skimi_layernorm_ex")
     return out
 
 
@@ -215,6 +250,31 @@ def attention(qkv, batch, seq, heads, head_dim, out_dtype=None, *, q_prescaled=0
     else:
         check(lib().skimi_attention_out(ptr(qkv), ptr(out), _dt(qkv), _dt(out), batch, seq, heads, head_dim,
                                         _lib.current_stream()), "skimi_attention_out")
+    return out
+
+
+def attention_f32_strided(q, k, v, out, *, q_strides, k_strides, v_strides, o_strides, batch, heads, seq_q, seq_k, head_dim,
+                          scale=None, batch_inner=0):
+    """The exact-fp32 attention kernel on four separate streams, as the track head launches it (skimi_attention_f32_strided).
+    q / k / v / out: fp32 device tensors whose first element is the stream's origin (views into one buffer are fine);
+    *_strides = (token, head, batch, outer batch) in elements; batch index g = go * batch_inner + gi (batch_inner = 0: one
+    level).  scale defaults to 1 / sqrt(head_dim).  Every stream must fit the storage behind its tensor."""
+    _require_cuda(q, k, v, out)
+    no, ni = (batch // batch_inner, batch_inner) if batch_inner > 0 else (1, batch)
+    for name, t, s, seq in (("q", q, q_strides, seq_q), ("k", k, k_strides, seq_k), ("v", v, v_strides, seq_k),
+                            ("out", out, o_strides, seq_q)):
+        if t.dtype != torch.float32:
+            raise _lib.SkimiError(f"attention_f32_strided: {name} must be fp32")
+        if len(s) != 4 or min(s) < 0:
+            raise _lib.SkimiError(f"attention_f32_strided: {name}_strides = (token, head, batch, outer batch), not negative")
+        room = t.untyped_storage().nbytes() // 4 - t.storage_offset()
+        last = (seq - 1) * s[0] + (heads - 1) * s[1] + (ni - 1) * s[2] + (no - 1) * s[3] + head_dim
+        if min(batch, heads, seq, head_dim) > 0 and last > room:
+            raise _lib.SkimiError(f"attention_f32_strided: the {name} stream ends {last - room} elements past its buffer")
+    arr = [(C.c_int64 * 4)(*map(int, s)) for s in (q_strides, k_strides, v_strides, o_strides)]
+    sc = float(scale) if scale is not None else (1.0 / head_dim ** 0.5 if head_dim > 0 else 0.0)
+    check(lib().skimi_attention_f32_strided(ptr(q), ptr(k), ptr(v), ptr(out), *arr, batch, batch_inner, heads, seq_q, seq_k,
+                                            head_dim, sc, _lib.current_stream()), "skimi_attention_f32_strided")
     return out
 
 

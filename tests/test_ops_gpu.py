@@ -160,6 +160,7 @@ def test_layernorm(C):
     assert (out - ref).abs().max().item() < 2e-5
     assert (ops.layernorm(x, None, None, 1e-6) - F.layer_norm(x, (C,), None, None, 1e-6)).abs().max().item() < 2e-5
     ob = ops.layernorm(x, g, b, 1e-5, out_dtype=torch.bfloat16)
+    # superseded by test_rowops_gpu.py's bound (the fp32 bound + half a bf16 ulp of the float64 reference); kept as it was
     assert (ob.float() - ref).abs().max().item() < 4e-2
 
 
