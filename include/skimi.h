@@ -866,6 +866,75 @@ int skimi_fuse_views(const double* X_l, const double* X_r, const double* U_l, co
 int skimi_smooth_ema(const double* X, int64_t frames, int64_t joints, const double* base, int32_t adaptive, double alpha_min,
                      double alpha_max, double speed_gain, double* Y, void* stream);
 
+/* skimi_smooth_ema_batch = skimi_smooth_ema on `clips` clips at once: X, Y [clips, frames, joints, 3], one base [joints] for
+ * all of them.  One launch, one thread per (clip, joint) running skimi_smooth_ema's walk: clip b's result is that call's on
+ * X[b] bit for bit.  clips == 0 is valid and launches nothing. */
+int skimi_smooth_ema_batch(const double* X, int64_t clips, int64_t frames, int64_t joints, const double* base, int32_t adaptive,
+                           double alpha_min, double alpha_max, double speed_gain, double* Y, void* stream);
+
+/* skimi_fuse_group = fuse/main_unity.py:98-132 (align == 0) or the per-frame body of fuse/main_raw.py:194-240 (align != 0) for
+ * every pair (a, b), a < b, of `views` views, pairs in the order of itertools.combinations: pair p of P = views (views - 1)
+ * / 2.  X [views, frames, joints, 3]; U [views, frames, joints, 2].  Rules (DESIGN §2 "Group fusion"): those of
+ * skimi_fuse_views with X_l = X[a], X_r = X[b], through the same device code:
+ *  1. quality == NULL: rule 2 (conf, err [views, frames, joints], fit_ok [views, frames]) and the canonical pose of rule 3
+ *     (workspace, skimi_fuse_group_workspace_bytes) once per (view, frame) in a first launch; then per (pair, frame) rule 1
+ *     if align, else aligned = X[b]; dist and conf_x of rule 3; q_a = sqrt(conf[a] conf_x), q_b = sqrt(conf[b] conf_x);
+ *     rule 4.  (main_unity's clip(conf conf_x, 0, 1) changes nothing: both factors lie in [0, 1].)  With align != 0 every
+ *     output of pair (a, b) equals skimi_fuse_views' on (X[a], X[b], U[a], U[b]) bit for bit.
+ *  2. quality [views, frames, joints] given: q_a = quality[a], q_b = quality[b]; one launch; U, workspace, conf, err,
+ *     fit_ok, conf_x and dist are not touched and may be NULL.
+ * Outputs per pair: fused, aligned [P, frames, joints, 3]; q_a, q_b, conf_x, dist [P, frames, joints].  views <= 4096, views *
+ * frames and P * frames below 2^31.  views < 2 gives no pair (views == 1 still fills conf, err, fit_ok).  A pair's results
+ * depend on its two views alone. */
+size_t skimi_fuse_group_workspace_bytes(int64_t views, int64_t frames, int32_t joints);
+int skimi_fuse_group(const double* X, const double* U, const double* quality, int64_t views, int64_t frames, int32_t joints,
+                     int32_t root_idx, int32_t left_hip_idx, int32_t right_hip_idx, int32_t left_shoulder_idx,
+                     int32_t right_shoulder_idx, double sigma_px, double sigma_3d, int32_t scale_mode, int32_t min_points,
+                     int32_t align, void* workspace, size_t workspace_bytes, double* fused, double* aligned, double* q_a, double* q_b,
+                     double* conf_x, double* dist, double* conf, double* err, int32_t* fit_ok, void* stream);
+
+/* skimi_joint_quality = the ground-truth-free joint quality of fuse/fuse.py:124-285 (estimate_bone_median_lengths,
+ * q_from_bone_deviation, q_from_temporal, q_2d_sanity, combine_q) for `views` clips.  X [views, frames, joints, 3] (NaN rows =
+ * missing joints); U [views, frames, joints, 2] or NULL; edges [n_edges, 2] dev i32, positions on the joint axis; size [views,
+ * 2] dev f64 (width, height), needed with U; bias NULL, [joints] (bias_stride 0) or [views, joints] (bias_stride joints);
+ * med_lens [views, n_edges]: written, or read when med_given.  Two launches (one when med_given or n_edges == 0), no
+ * atomics, bitwise reproducible; a view's results depend on that view alone, and with med_given a frame's on that frame
+ * and the one before it.  Rules (DESIGN §2 "Joint quality"):
+ *  - a row is finite when its three coordinates are.  len[v, t, e] = ||X[a] - X[b]|| when both rows are finite, else NaN.
+ *    An edge with an endpoint outside 0 .. joints - 1 is ignored everywhere (its median is NaN); edges act in their order,
+ *    a repeated edge counts twice, a self-edge is counted twice for its joint.
+ *  - med[v, e]: the median of the non-NaN len[v, :, e], an exact selection on order-preserving keys (one wave per (view,
+ *    edge)); (lo + hi) / 2 for an even count; NaN without a sample (frames == 0 included).
+ *  - q_bone: -1e9 for a row that is not finite; else over the edges at j with a finite median and two finite rows, dev_sum
+ *    += |len - med| in edge order and cnt of them: -100 for cnt == 0, else -(dev_sum / (cnt + 1e-8)).
+ *  - q_temp: -1e9 for a row that is not finite; 0 for t == 0 or a row at t - 1 that is not finite; else -beta_temp ||X[t] -
+ *    X[t-1]||.
+ *  - q_san: 0 where U is given, u and v are finite and 0 <= u < width, 0 <= v < height; else -50.
+ *  - q = (w_bone q_bone + w_temp q_temp) + w_san q_san, then + bias if given, in this order, no fused multiply-add.
+ * q, q_bone, q_temp, q_san [views, frames, joints].  1 <= joints <= 128, views <= 4096, n_edges <= 65536, views * frames
+ * below 2^31. */
+int skimi_joint_quality(const double* X, const double* U, int64_t views, int64_t frames, int32_t joints, const int32_t* edges,
+                        int32_t n_edges, const double* size, double beta_temp, double w_bone, double w_temp, double w_san,
+                        int32_t med_given, const double* bias, int64_t bias_stride, double* med_lens, double* q, double* q_bone,
+                        double* q_temp, double* q_san, void* stream);
+
+/* skimi_convert_skeleton = VideoPose3D/coco_hm36.py (coco_to_h36m, h36m_to_coco) on the device.  X, Y [frames, 17, coords],
+ * coords 2 or 3 (Y must not be X); one launch, one thread per frame; NaN propagates through the arithmetic.  frames <= 2^34,
+ * but <= 2^20 for SKIMI_SKELETON_H36M_TO_COCO with synthesize: every workgroup of 256 frames sums the clip mean below
+ * itself, frames^2 / 256 reads in all, the price of one launch and of the same bits in every frame.  Rules (DESIGN
+ * §2 "Skeleton conversion"):
+ *  - SKIMI_SKELETON_COCO_TO_H36M: pelvis = (l_hip + r_hip) 0.5, thorax = (l_sho + r_sho) 0.5, spine = (pelvis + thorax) 0.5,
+ *    neck = nose, head = nose + 0.5 (nose - (l_eye + r_eye) 0.5) if synthesize else nose; the 12 limb joints are copied.
+ *  - SKIMI_SKELETON_H36M_TO_COCO: nose = neck, the 12 limb joints are copied, eyes and ears NaN unless synthesize.  With
+ *    synthesize: sv = l_sho - r_sho, but the first `coords` entries of (1, 0, 0) in EVERY frame when the clip mean of ||sv||
+ *    (summed in a fixed order; a NaN mean does not count) is < 1e-8, the reference's quirk; w = ||sv||, side = sv / (w +
+ *    1e-9), up = (head - neck) / (||head - neck|| + 1e-9); l_eye, r_eye = (head +- 0.25 w side) - 0.15 w up; l_ear, r_ear =
+ *    (head +- 0.35 w side) - 0.10 w up. */
+#define SKIMI_SKELETON_COCO_TO_H36M 0
+#define SKIMI_SKELETON_H36M_TO_COCO 1
+int skimi_convert_skeleton(const double* X, int64_t frames, int32_t coords, int32_t direction, int32_t synthesize, double* Y,
+                           void* stream);
+
 /* skimi_smooth_savgol = smooth_skeleton with the window already chosen.  X, Y [frames, joints, 3] (Y must not be X); win odd
  * in 1..33, 0 <= poly < win (poly is only checked); fir [win]; first, last [win / 2, win] (fuse.savgol_operators).  One thread
  * per (joint, coordinate) series: its finite samples in time order form the sequence x_0 .. x_{n-1}; with n >= win, y_k =

@@ -156,6 +156,15 @@ _SIGNATURES = {
                                    C.c_double, C.c_double, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _vp, _vp]),
     "skimi_smooth_ema": (C.c_int, [_vp, C.c_int64, C.c_int64, _vp, C.c_int32, C.c_double, C.c_double, C.c_double, _vp, _vp]),
+    "skimi_smooth_ema_batch": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _vp, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                         _vp, _vp]),
+    "skimi_fuse_group_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32]),
+    "skimi_fuse_group": (C.c_int, [_vp, _vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                   C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_size_t, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "skimi_joint_quality": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, _vp, C.c_int32, _vp, C.c_double, C.c_double,
+                                      C.c_double, C.c_double, C.c_int32, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "skimi_convert_skeleton": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "skimi_smooth_savgol": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "skimi_kin_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
     "skimi_kinematics": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32,

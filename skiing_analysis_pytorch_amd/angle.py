@@ -7,7 +7,8 @@ order.  No PNG is written: not the series plots, not the skeleton pictures, not 
 
 The tables below restate the reference's as data.  A layout names the joint of each role (geometry.KIN_ROLES order, -1 for
 absent) in a clip's joint axis: MHR70_15 is the reference's own 15-joint order, H36M_17 this build's fused VideoPose3D joints
-with the thorax as the neck.  The COCO-17 joints of the VGGT clip path have no neck and are not wired up."""
+with the thorax as the neck.  COCO_17 stands for the COCO-17 joints of the VGGT clip path: they have no neck, so analyze and
+process_person_pair convert them on the device (geometry.convert_skeleton, "coco_to_h36m") and run the H36M_17 layout."""
 from __future__ import annotations
 
 import csv
@@ -32,6 +33,7 @@ ROLE_IDS = (5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 62, 41, 69)
 
 MHR70_15 = tuple(ID_TO_INDEX[i] for i in ROLE_IDS)
 H36M_17 = (11, 14, 12, 15, 4, 1, 5, 2, 6, 3, 13, 16, 8)     # Human3.6M: hips 4 / 1, knees 5 / 2, feet 6 / 3, thorax 8, arms 11-13 / 14-16
+COCO_17 = ("coco17",)                                       # not a role table: _role_layout converts to H36M-17 first
 assert MHR70_15 == geometry.KIN_LAYOUT_MHR70_15
 
 SERIES = geometry.KIN_SERIES
@@ -74,12 +76,24 @@ def analysis_from(result, clip: int = 0, length: int | None = None) -> Analysis:
                     host("turn_counts")[:n])
 
 
+def _role_layout(kpts: torch.Tensor, layout):
+    """(device joints (..., J, 3), layout) as geometry.kinematics takes them: COCO_17 joints are converted to H36M-17 frame by
+    frame (geometry.convert_skeleton, "coco_to_h36m") and get the H36M_17 roles; any other layout passes through"""
+    if tuple(layout) != COCO_17:
+        return kpts, layout
+    if kpts.shape[-2] != 17:
+        raise ValueError(f"layout COCO_17 needs 17 joints, got {kpts.shape[-2]}")
+    return geometry.convert_skeleton(kpts.reshape(-1, 17, 3), "coco_to_h36m").reshape(kpts.shape), H36M_17
+
+
 def analyze(kpts, up_axis=UP_Y_DOWN, layout=MHR70_15, **kw) -> Analysis:
-    """kpts (T, J, 3), a host array or a device tensor -> Analysis, from one device call."""
+    """kpts (T, J, 3), a host array or a device tensor -> Analysis, from one device call (two for layout=COCO_17: the
+    conversion to H36M-17 comes first)."""
     if not isinstance(kpts, torch.Tensor):
         kpts = torch.from_numpy(np.ascontiguousarray(np.asarray(kpts, dtype=np.float64))).to(torch.device("cuda", torch.cuda.current_device()))
     if kpts.dim() != 3 or kpts.shape[2] != 3:
         raise ValueError("kpts must be (T,J,3)")
+    kpts, layout = _role_layout(kpts, layout)
     return analysis_from(geometry.kinematics(kpts, layout=layout, up_axis=up_axis, **kw))
 
 
@@ -213,7 +227,8 @@ def process_person_pair(smoothed_path: Path, fused_path: Path, output_dir: Path,
     for b, c in enumerate(clips):
         X[b, :lengths[b]] = c
     dev = torch.device("cuda", torch.cuda.current_device())
-    res = geometry.kinematics(torch.from_numpy(X).to(dev), lengths=lengths, layout=layout, up_axis=up_axis)
+    Xd, layout = _role_layout(torch.from_numpy(X).to(dev), layout)
+    res = geometry.kinematics(Xd, lengths=lengths, layout=layout, up_axis=up_axis)
     before, after = (analysis_from(res, b, lengths[b]) for b in range(2))
     write_person_pair(before, after, output_dir)
     return before, after

@@ -320,22 +320,13 @@ __global__ __launch_bounds__(kThreads) void pe_joint_kernel(PeArgs a) {
         }
         sd = sqrt(wave_sum(ss) / (double)cnt);
         // the two middle order statistics (the same one for an odd count)
-        unsigned k0 = (unsigned)(cnt - 1) / 2, k1 = (unsigned)cnt / 2;
-        unsigned long long p0 = 0, p1 = 0;
-        for (int bit = 63; bit >= 0; --bit) {
-            int c0 = 0, c1 = 0;
+        unsigned long long p0, p1;
+        wave_select2((unsigned)(cnt - 1) / 2, (unsigned)cnt / 2, [&](auto&& f) {
             for (int i = lane; i < n; i += 64) {
                 const double v = x[(long)i * J];
-                if (is_fin(v)) {
-                    const unsigned long long key = key64(v);
-                    c0 += ((key ^ p0) >> bit) == 0;    // the bits above agree with the prefix and this one is 0
-                    c1 += ((key ^ p1) >> bit) == 0;
-                }
+                if (is_fin(v)) f(key64(v));
             }
-            c0 = wave_sum(c0), c1 = wave_sum(c1);
-            if (k0 >= (unsigned)c0) k0 -= (unsigned)c0, p0 |= 1ULL << bit;
-            if (k1 >= (unsigned)c1) k1 -= (unsigned)c1, p1 |= 1ULL << bit;
-        }
+        }, p0, p1);
         med = (unkey64(p0) + unkey64(p1)) / 2.0;
     }
     if (lane == 0) {

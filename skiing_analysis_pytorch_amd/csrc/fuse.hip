@@ -1,8 +1,10 @@
 // The consumers of the gathered [T, J, 3] joints on the device: the VideoPose3D left/right fusion without extrinsics
 // (fuse.fuse_pose_no_extrinsics_h36m), the two-view fusion with its confidences (the per-frame body of fuse/main_raw.py:
 // align_right_to_left, weakpersp_reproj_confidence, crossview_consistency_confidence, fuse_frame_3d), the adaptive EMA
-// (fuse.temporal_smooth_ema) and the NaN-aware Savitzky-Golay filter (fuse.smooth_skeleton).  The host functions of fuse.py
-// are the restatement; rules: DESIGN §2 "Fusion + smoothing on the device".
+// (fuse.temporal_smooth_ema) and the NaN-aware Savitzky-Golay filter (fuse.smooth_skeleton); the fusion of every pair of a
+// camera group (fuse/main_unity.py) through the two-view kernel's device functions, the EMA of a batch of clips, and the
+// ground-truth-free joint quality (fuse/fuse.py:124-285).  The host functions of fuse.py are the restatement; rules: DESIGN
+// §2 "Fusion + smoothing on the device", "Group fusion", "Joint quality".
 //
 // Fusion: one wave per frame (four frames per workgroup, no LDS, no barrier), lanes over joints (two joints per lane above
 // 64).  Every sum is a per-lane sum over the lane's joints followed by a fixed xor-butterfly over the 64 lanes, so it
@@ -243,36 +245,30 @@ __device__ inline void canonicalize(const double* F, const int* key, int torso, 
     }
 }
 
-__global__ __launch_bounds__(256) void fuse_views_kernel(ViewsArgs a) {
-    const int lane = threadIdx.x & 63;
-    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (t >= a.T) return;                      // the whole wave leaves: no barrier in this kernel
+// the lane's rows (joints lane and lane + 64) of frame `row0 / J` of one view: NaN beyond J; U may be NULL (then not read)
+__device__ inline void load_rows(const double* X, const double* U, long row0, int J, int lane, bool* act, double (*Xo)[3],
+                                 double (*Uo)[2]) {
     const double nan = qnan();
-    const int J = a.J;
-    bool act[2];
-    double Xl[2][3], Xr[2][3], Ul[2][2], Ur[2][2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         const int j = lane + 64 * k;
         act[k] = j < J;
-        const long row = t * J + (act[k] ? j : 0);
+        const long row = row0 + (act[k] ? j : 0);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            Xl[k][c] = act[k] ? a.Xl[row * 3 + c] : nan;
-            Xr[k][c] = act[k] ? a.Xr[row * 3 + c] : nan;
-        }
+        for (int c = 0; c < 3; ++c) Xo[k][c] = act[k] ? X[row * 3 + c] : nan;
+        if (U) {
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            Ul[k][c] = act[k] ? a.Ul[row * 2 + c] : nan;
-            Ur[k][c] = act[k] ? a.Ur[row * 2 + c] : nan;
+            for (int c = 0; c < 2; ++c) Uo[k][c] = act[k] ? U[row * 2 + c] : nan;
         }
     }
-    // align_right_to_left: Kabsch right -> left on the joints finite in both; fewer than 3: the right view unchanged
+}
+
+// align_right_to_left: Kabsch right -> left on the joints finite in both; fewer than 3: the right view unchanged
+__device__ inline void kabsch_align(const double (*Xl)[3], const double (*Xr)[3], const bool* act, double (*Al)[3]) {
     bool both[2];
 #pragma unroll
     for (int k = 0; k < 2; ++k) both[k] = act[k] && fin3(Xl[k]) && fin3(Xr[k]);
     const double nb = wave_sum((both[0] ? 1.0 : 0.0) + (both[1] ? 1.0 : 0.0));
-    double Al[2][3];
 #pragma unroll
     for (int k = 0; k < 2; ++k)
 #pragma unroll
@@ -299,6 +295,40 @@ __global__ __launch_bounds__(256) void fuse_views_kernel(ViewsArgs a) {
             for (int r = 0; r < 3; ++r)
                 if (both[k]) Al[k][r] = (Xr[k][0] * P[r] + Xr[k][1] * P[3 + r] + Xr[k][2] * P[6 + r]) + tv[r];
     }
+}
+
+// crossview_consistency_confidence of one joint from its two canonical rows -> dist (NaN where either is), conf_x
+__device__ inline void cross_conf(const double* Ca, const double* Cb, double var3, double& d, double& cx) {
+    const bool ok = fin3(Ca) && fin3(Cb);
+    const double d0 = Ca[0] - Cb[0], d1 = Ca[1] - Cb[1], d2 = Ca[2] - Cb[2];
+    d = ok ? sqrt(d0 * d0 + d1 * d1 + d2 * d2) : qnan();
+    cx = is_fin(d) ? exp(-(d * d) / (2.0 * var3)) : 0.0;
+}
+
+// fuse_frame_3d of one joint: softmax2 of the qualities, then (left present) + 2 (right present)
+__device__ inline void fuse_row(double ql, double qr, const double* Xl, const double* Al, double* F) {
+    const double nan = qnan();
+    const double m = (ql != ql || qr != qr) ? nan : fmax(ql, qr);
+    const double ea = exp(ql - m), eb = exp(qr - m), se = ea + eb + 1e-8;
+    const double wl = ea / se, wr = eb / se;
+    const bool lok = fin3(Xl), rok = fin3(Al);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const double blend = (wl * Xl[c] + wr * Al[c]) / (wl + wr + 1e-8);
+        F[c] = lok ? (rok ? blend : Xl[c]) : (rok ? Al[c] : nan);
+    }
+}
+
+__global__ __launch_bounds__(256) void fuse_views_kernel(ViewsArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long t = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= a.T) return;                      // the whole wave leaves: no barrier in this kernel
+    const int J = a.J;
+    bool act[2];
+    double Xl[2][3], Xr[2][3], Ul[2][2], Ur[2][2], Al[2][3];
+    load_rows(a.Xl, a.Ul, t * J, J, lane, act, Xl, Ul);
+    load_rows(a.Xr, a.Ur, t * J, J, lane, act, Xr, Ur);
+    kabsch_align(Xl, Xr, act, Al);
     // the confidences, each view on its raw 3D
     double cl[2], cr[2], el[2], er[2], Ca[2][3], Cb[2][3];
     const bool okl = weakpersp(Xl, Ul, act, a.min_points, a.sigma_px, cl, el);
@@ -309,21 +339,14 @@ __global__ __launch_bounds__(256) void fuse_views_kernel(ViewsArgs a) {
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
         if (!act[k]) continue;
-        const bool ok = fin3(Ca[k]) && fin3(Cb[k]);
-        const double d0 = Ca[k][0] - Cb[k][0], d1 = Ca[k][1] - Cb[k][1], d2 = Ca[k][2] - Cb[k][2];
-        const double d = ok ? sqrt(d0 * d0 + d1 * d1 + d2 * d2) : nan;
-        const double cx = is_fin(d) ? exp(-(d * d) / (2.0 * var3)) : 0.0;
+        double d, cx, F[3];
+        cross_conf(Ca[k], Cb[k], var3, d, cx);
         const double ql = sqrt(cl[k] * cx), qr = sqrt(cr[k] * cx);
-        // fuse_frame_3d: softmax2 of the qualities, then (left present) + 2 (right present)
-        const double m = (ql != ql || qr != qr) ? nan : fmax(ql, qr);
-        const double ea = exp(ql - m), eb = exp(qr - m), se = ea + eb + 1e-8;
-        const double wl = ea / se, wr = eb / se;
-        const bool lok = fin3(Xl[k]), rok = fin3(Al[k]);
+        fuse_row(ql, qr, Xl[k], Al[k], F);
         const long row = t * J + lane + 64 * k;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            const double blend = (wl * Xl[k][c] + wr * Al[k][c]) / (wl + wr + 1e-8);
-            a.fused[row * 3 + c] = lok ? (rok ? blend : Xl[k][c]) : (rok ? Al[k][c] : nan);
+            a.fused[row * 3 + c] = F[c];
             a.aligned[row * 3 + c] = Al[k][c];
         }
         a.q_l[row] = ql, a.q_r[row] = qr;
@@ -336,11 +359,205 @@ __global__ __launch_bounds__(256) void fuse_views_kernel(ViewsArgs a) {
     }
 }
 
+// ---- fusion of a camera group (fuse/main_unity.py:98-132, fuse/main_raw.py:194-240): every pair of V views ------------
+// Two kernels.  group_views_kernel, one wave per (view, frame): the view's weak-perspective confidence and its canonical
+// pose (workspace), once each.  group_pairs_kernel, one wave per (pair, frame), pairs in itertools.combinations order: the
+// Kabsch alignment (align), the cross-view confidence from the two canonical poses, fuse_frame_3d.  The arithmetic is
+// fuse_views_kernel's, through the same device functions, so a pair's results are that kernel's bit for bit.
+struct GroupArgs {
+    const double *X, *U, *Q;                   // [V, T, J, 3], [V, T, J, 2], given qualities [V, T, J] or NULL
+    double *canon, *conf, *err;                // workspace [V, T, J, 3]; [V, T, J]
+    int32_t* fit_ok;                           // [V, T]
+    double *fused, *aligned, *q_a, *q_b, *conf_x, *dist;
+    long V, T, P;
+    int J, key[5], torso, min_points, align;
+    double sigma_px, sigma_3d;
+};
+
+__global__ __launch_bounds__(256) void group_views_kernel(GroupArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6);        // = view * T + frame
+    if (w >= a.V * a.T) return;
+    const int J = a.J;
+    bool act[2];
+    double X[2][3], U[2][2], cf[2], er[2], Cn[2][3];
+    load_rows(a.X, a.U, w * J, J, lane, act, X, U);
+    const bool ok = weakpersp(X, U, act, a.min_points, a.sigma_px, cf, er);
+    canonicalize(a.X + w * J * 3, a.key, a.torso, X, Cn);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (!act[k]) continue;
+        const long row = w * J + lane + 64 * k;
+        a.conf[row] = cf[k], a.err[row] = er[k];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) a.canon[row * 3 + c] = Cn[k][c];
+    }
+    if (lane == 0) a.fit_ok[w] = ok ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void group_pairs_kernel(GroupArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6);        // = pair * T + frame
+    if (w >= a.P * a.T) return;
+    const long p = w / a.T, t = w - p * a.T;
+    long va = 0, rem = p;                      // pair p of combinations(range(V), 2)
+    while (rem >= a.V - 1 - va) rem -= a.V - 1 - va, ++va;
+    const long vb = va + 1 + rem;
+    const int J = a.J;
+    const long ra = (va * a.T + t) * J, rb = (vb * a.T + t) * J;
+    bool act[2];
+    double Xa[2][3], Xb[2][3], Al[2][3];
+    load_rows(a.X, nullptr, ra, J, lane, act, Xa, nullptr);
+    load_rows(a.X, nullptr, rb, J, lane, act, Xb, nullptr);
+    if (a.align) {
+        kabsch_align(Xa, Xb, act, Al);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Al[k][c] = Xb[k][c];
+    }
+    const double s3 = fmax(a.sigma_3d, 1e-12), var3 = s3 * s3;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        if (!act[k]) continue;
+        const int j = lane + 64 * k;
+        const long row = w * J + j;
+        double qa, qb, F[3];
+        if (a.Q) {
+            qa = a.Q[ra + j], qb = a.Q[rb + j];
+        } else {
+            double d, cx;
+            cross_conf(a.canon + (ra + j) * 3, a.canon + (rb + j) * 3, var3, d, cx);
+            qa = sqrt(a.conf[ra + j] * cx), qb = sqrt(a.conf[rb + j] * cx);
+            a.conf_x[row] = cx, a.dist[row] = d;
+        }
+        fuse_row(qa, qb, Xa[k], Al[k], F);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            a.fused[row * 3 + c] = F[c];
+            a.aligned[row * 3 + c] = Al[k][c];
+        }
+        a.q_a[row] = qa, a.q_b[row] = qb;
+    }
+}
+
+// ---- ground-truth-free joint quality (fuse/fuse.py:124-285) -----------------------------------------------------------
+struct QualityArgs {
+    const double *X, *U, *size, *bias;         // [V, T, J, 3]; [V, T, J, 2] or NULL; [V, 2] (width, height); [J] / [V, J] or NULL
+    const int32_t* edges;                      // [E, 2]
+    double *med, *q, *q_bone, *q_temp, *q_san; // [V, E]; [V, T, J] each
+    long V, T, bias_stride;
+    int J, E;
+    double beta, w_bone, w_temp, w_san;
+};
+
+// the order-preserving key of edge (ia, ib)'s length in the frame whose first row is row0; 0 where a row is not finite
+// (a length is >= +0, so every real key has its top bit set)
+__device__ inline unsigned long long edge_key(const double* X, long row0, int ia, int ib) {
+    const double *pa = X + (row0 + ia) * 3, *pb = X + (row0 + ib) * 3;
+    if (!(fin3(pa) && fin3(pb))) return 0ULL;
+    return key64(norm3(pa[0] - pb[0], pa[1] - pb[1], pa[2] - pb[2]));
+}
+
+// NaN-ignoring median of an edge's lengths over the clip: one wave per (view, edge), lanes over frames, the exact selection
+// of the two middle ranks over the keys (reduce.h: wave_select2, shared with evaluate.hip's per-joint medians).  The first
+// kKeyCache keys of a lane stay in registers; longer clips recompute the rest in every pass.
+constexpr int kKeyCache = 4;
+__global__ __launch_bounds__(256) void bone_median_kernel(QualityArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6);        // = view * E + edge
+    if (w >= a.V * a.E) return;
+    const long v = w / a.E;
+    const int e = (int)(w - v * a.E), J = a.J;
+    const int ia = a.edges[2 * e], ib = a.edges[2 * e + 1];
+    if (ia < 0 || ia >= J || ib < 0 || ib >= J) {                    // the reference's `a not in idx`: no sample at all
+        if (lane == 0) a.med[w] = qnan();
+        return;
+    }
+    const long T = a.T, f0 = v * T;
+    unsigned long long kc[kKeyCache];
+    unsigned cnt = 0;
+#pragma unroll
+    for (int k = 0; k < kKeyCache; ++k) {
+        const long t = lane + 64 * k;
+        kc[k] = t < T ? edge_key(a.X, (f0 + t) * J, ia, ib) : 0ULL;
+        cnt += (unsigned)(kc[k] >> 63);
+    }
+    for (long t = lane + 64 * kKeyCache; t < T; t += 64) cnt += (unsigned)(edge_key(a.X, (f0 + t) * J, ia, ib) >> 63);
+    const unsigned n = wave_sum(cnt);
+    if (n == 0) {
+        if (lane == 0) a.med[w] = qnan();
+        return;
+    }
+    unsigned long long p0, p1;               // a missing sample's key is 0 and takes no part
+    wave_select2((n - 1) / 2, n / 2, [&](auto&& f) {
+#pragma unroll
+        for (int k = 0; k < kKeyCache; ++k)
+            if (kc[k] >> 63) f(kc[k]);
+        for (long t = lane + 64 * kKeyCache; t < T; t += 64) {
+            const unsigned long long key = edge_key(a.X, (f0 + t) * J, ia, ib);
+            if (key >> 63) f(key);
+        }
+    }, p0, p1);
+    const double lo = unkey64(p0), hi = unkey64(p1);
+    if (lane == 0) a.med[w] = (n & 1u) ? lo : (lo + hi) / 2.0;
+}
+
+// one wave per (view, frame), lanes over joints: a lane walks the edge list in its order for each of its joints
+__global__ __launch_bounds__(256) void joint_quality_kernel(QualityArgs a) {
+    const int lane = threadIdx.x & 63;
+    const long w = (long)blockIdx.x * 4 + (threadIdx.x >> 6);        // = view * T + frame
+    if (w >= a.V * a.T) return;
+    const long v = w / a.T, t = w - v * a.T;
+    const int J = a.J;
+    const double* F = a.X + w * J * 3;
+    const double* med = a.med + v * a.E;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int j = lane + 64 * k;
+        if (j >= J) continue;
+        const double* x = F + 3 * j;
+        const bool ok = fin3(x);
+        double qb = -1e9, qt = -1e9, qs = -50.0;
+        if (ok) {
+            double dev = 0.0;
+            int cnt = 0;
+            for (int e = 0; e < a.E; ++e) {
+                const int ia = a.edges[2 * e], ib = a.edges[2 * e + 1];
+                if (ia < 0 || ia >= J || ib < 0 || ib >= J || !is_fin(med[e])) continue;
+                if (ia == j) {
+                    const double* o = F + 3 * ib;
+                    if (fin3(o)) dev += fabs(norm3(x[0] - o[0], x[1] - o[1], x[2] - o[2]) - med[e]), ++cnt;
+                }
+                if (ib == j) {                                       // a self-edge counts twice, as in the reference
+                    const double* o = F + 3 * ia;
+                    if (fin3(o)) dev += fabs(norm3(x[0] - o[0], x[1] - o[1], x[2] - o[2]) - med[e]), ++cnt;
+                }
+            }
+            qb = cnt == 0 ? -100.0 : -(dev / ((double)cnt + 1e-8));
+            qt = 0.0;
+            if (t > 0) {
+                const double* p = x - (long)J * 3;
+                if (fin3(p)) qt = -a.beta * norm3(x[0] - p[0], x[1] - p[1], x[2] - p[2]);
+            }
+        }
+        if (a.U) {
+            const double u0 = a.U[(w * J + j) * 2], u1 = a.U[(w * J + j) * 2 + 1];
+            const double W = a.size[2 * v], H = a.size[2 * v + 1];
+            if (is_fin(u0) && is_fin(u1) && 0.0 <= u0 && u0 < W && 0.0 <= u1 && u1 < H) qs = 0.0;
+        }
+        double q = (a.w_bone * qb + a.w_temp * qt) + a.w_san * qs;
+        if (a.bias) q = q + a.bias[v * a.bias_stride + j];
+        const long row = w * J + j;
+        a.q[row] = q, a.q_bone[row] = qb, a.q_temp[row] = qt, a.q_san[row] = qs;
+    }
+}
+
 // ---- temporal_smooth_ema: one thread per joint ----------------------------------------------------------------------
-__global__ __launch_bounds__(64) void smooth_ema_kernel(const double* __restrict__ X, long T, long J, const double* __restrict__ base,
-                                                        int adaptive, double amin, double amax, double gain, double* __restrict__ Y) {
-    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= J) return;
+// the walk of joint j over the clip X [T, J, 3] -> Y
+__device__ inline void ema_walk(const double* __restrict__ X, long T, long J, long j, const double* __restrict__ base, int adaptive,
+                                double amin, double amax, double gain, double* __restrict__ Y) {
     const double nan = qnan();
     const double b = base[j];
     double st[3];
@@ -373,6 +590,23 @@ __global__ __launch_bounds__(64) void smooth_ema_kernel(const double* __restrict
             has = fin3(st);
         }
     }
+}
+
+__global__ __launch_bounds__(64) void smooth_ema_kernel(const double* __restrict__ X, long T, long J, const double* __restrict__ base,
+                                                        int adaptive, double amin, double amax, double gain, double* __restrict__ Y) {
+    const long j = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= J) return;
+    ema_walk(X, T, J, j, base, adaptive, amin, amax, gain, Y);
+}
+
+// B clips [B, T, J, 3] with one base [J]: one thread per (clip, joint), the same walk
+__global__ __launch_bounds__(64) void smooth_ema_batch_kernel(const double* __restrict__ X, long B, long T, long J,
+                                                              const double* __restrict__ base, int adaptive, double amin, double amax,
+                                                              double gain, double* __restrict__ Y) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * J) return;
+    const long b = i / J;
+    ema_walk(X + b * T * J * 3, T, J, i - b * J, base, adaptive, amin, amax, gain, Y + b * T * J * 3);
 }
 
 // ---- smooth_skeleton: one thread per (joint, coordinate) series -----------------------------------------------------
@@ -528,6 +762,99 @@ int skimi_smooth_ema(const double* X, int64_t frames, int64_t joints, const doub
     SKIMI_CHECK_ARG(X && base && Y && X != Y, "skimi_smooth_ema: NULL input or output, or Y is X");
     hipLaunchKernelGGL(smooth_ema_kernel, dim3((unsigned)cdiv(joints, 64)), dim3(64), 0, (hipStream_t)stream, X, (long)frames,
                        (long)joints, base, adaptive != 0, alpha_min, alpha_max, speed_gain, Y);
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
+int skimi_smooth_ema_batch(const double* X, int64_t clips, int64_t frames, int64_t joints, const double* base, int32_t adaptive,
+                           double alpha_min, double alpha_max, double speed_gain, double* Y, void* stream) {
+    SKIMI_CHECK_ARG(clips >= 0 && frames >= 0 && joints >= 0 && joints <= 0x7fffffffLL && clips <= 0x7fffffffLL &&
+                        (joints == 0 || clips == 0 || frames <= kMaxElems / joints / clips),
+                    "skimi_smooth_ema_batch: clips = %lld, frames = %lld, joints = %lld outside clips, frames, joints >= 0, clips * "
+                    "frames * joints <= 2^40", (long long)clips, (long long)frames, (long long)joints);
+    if (clips == 0 || frames == 0 || joints == 0) return SKIMI_OK;
+    SKIMI_CHECK_ARG(X && base && Y && X != Y, "skimi_smooth_ema_batch: NULL input or output, or Y is X");
+    hipLaunchKernelGGL(smooth_ema_batch_kernel, dim3((unsigned)cdiv(clips * joints, 64)), dim3(64), 0, (hipStream_t)stream, X,
+                       (long)clips, (long)frames, (long)joints, base, adaptive != 0, alpha_min, alpha_max, speed_gain, Y);
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
+size_t skimi_fuse_group_workspace_bytes(int64_t views, int64_t frames, int32_t joints) {
+    if (views < 0 || frames < 0 || joints < 1 || joints > kMaxJoints) return 0;
+    if (views > 0 && frames > 0x7fffffffLL / views) return 0;
+    return (size_t)views * (size_t)frames * (size_t)joints * 3 * sizeof(double);
+}
+
+int skimi_fuse_group(const double* X, const double* U, const double* quality, int64_t views, int64_t frames, int32_t joints,
+                     int32_t root_idx, int32_t left_hip_idx, int32_t right_hip_idx, int32_t left_shoulder_idx,
+                     int32_t right_shoulder_idx, double sigma_px, double sigma_3d, int32_t scale_mode, int32_t min_points,
+                     int32_t align, void* workspace, size_t workspace_bytes, double* fused, double* aligned, double* q_a, double* q_b,
+                     double* conf_x, double* dist, double* conf, double* err, int32_t* fit_ok, void* stream) {
+    SKIMI_CHECK_ARG(joints >= 1 && joints <= kMaxJoints, "skimi_fuse_group: joints = %d outside 1..%d", joints, kMaxJoints);
+    SKIMI_CHECK_ARG(views >= 0 && views <= 4096, "skimi_fuse_group: views = %lld outside 0..4096", (long long)views);
+    const int64_t pairs = views * (views - 1) / 2;
+    SKIMI_CHECK_ARG(frames >= 0 && (pairs == 0 || frames <= 0x7fffffffLL / pairs) && (views == 0 || frames <= 0x7fffffffLL / views),
+                    "skimi_fuse_group: frames = %lld: frames * views and frames * pairs must stay below 2^31", (long long)frames);
+    const int32_t key[5] = {root_idx, left_hip_idx, right_hip_idx, left_shoulder_idx, right_shoulder_idx};
+    for (int i = 0; i < 5; ++i)
+        SKIMI_CHECK_ARG(key[i] >= 0 && key[i] < joints, "skimi_fuse_group: key joint %d = %d outside 0..%d", i, key[i], joints - 1);
+    SKIMI_CHECK_ARG(fabs(sigma_px) <= 1.79769313486231570815e308 && fabs(sigma_3d) <= 1.79769313486231570815e308,
+                    "skimi_fuse_group: sigma_px = %g, sigma_3d = %g must be finite", sigma_px, sigma_3d);
+    SKIMI_CHECK_ARG(scale_mode == SKIMI_FUSE_SCALE_HIP || scale_mode == SKIMI_FUSE_SCALE_TORSO, "skimi_fuse_group: unknown scale_mode %d",
+                    scale_mode);
+    SKIMI_CHECK_ARG(min_points >= 1, "skimi_fuse_group: min_points = %d < 1", min_points);
+    if (frames == 0 || views == 0) return SKIMI_OK;
+    SKIMI_CHECK_ARG(X, "skimi_fuse_group: NULL input");
+    GroupArgs a{};
+    a.X = X, a.U = U, a.Q = quality;
+    a.canon = (double*)workspace, a.conf = conf, a.err = err, a.fit_ok = fit_ok;
+    a.fused = fused, a.aligned = aligned, a.q_a = q_a, a.q_b = q_b, a.conf_x = conf_x, a.dist = dist;
+    a.V = views, a.T = frames, a.P = pairs, a.J = joints;
+    a.torso = scale_mode == SKIMI_FUSE_SCALE_TORSO, a.min_points = min_points, a.align = align != 0;
+    for (int i = 0; i < 5; ++i) a.key[i] = key[i];
+    a.sigma_px = sigma_px, a.sigma_3d = sigma_3d;
+    if (!quality) {
+        SKIMI_CHECK_ARG(U && conf && err && fit_ok, "skimi_fuse_group: without given qualities U, conf, err and fit_ok are needed");
+        SKIMI_CHECK_ARG(pairs == 0 || (conf_x && dist), "skimi_fuse_group: NULL conf_x or dist");
+        SKIMI_CHECK_ARG(workspace && workspace_bytes >= skimi_fuse_group_workspace_bytes(views, frames, joints),
+                        "skimi_fuse_group: the workspace is NULL or smaller than skimi_fuse_group_workspace_bytes");
+        hipLaunchKernelGGL(group_views_kernel, dim3((unsigned)cdiv(views * frames, 4)), dim3(256), 0, (hipStream_t)stream, a);
+        SKIMI_LAUNCH_CHECK();
+    }
+    if (pairs == 0) return SKIMI_OK;
+    SKIMI_CHECK_ARG(fused && aligned && q_a && q_b, "skimi_fuse_group: NULL pair output");
+    hipLaunchKernelGGL(group_pairs_kernel, dim3((unsigned)cdiv(pairs * frames, 4)), dim3(256), 0, (hipStream_t)stream, a);
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
+int skimi_joint_quality(const double* X, const double* U, int64_t views, int64_t frames, int32_t joints, const int32_t* edges,
+                        int32_t n_edges, const double* size, double beta_temp, double w_bone, double w_temp, double w_san,
+                        int32_t med_given, const double* bias, int64_t bias_stride, double* med_lens, double* q, double* q_bone,
+                        double* q_temp, double* q_san, void* stream) {
+    SKIMI_CHECK_ARG(joints >= 1 && joints <= kMaxJoints, "skimi_joint_quality: joints = %d outside 1..%d", joints, kMaxJoints);
+    SKIMI_CHECK_ARG(views >= 0 && views <= 4096 && n_edges >= 0 && n_edges <= 65536,
+                    "skimi_joint_quality: views = %lld, n_edges = %d outside 0..4096, 0..65536", (long long)views, n_edges);
+    SKIMI_CHECK_ARG(frames >= 0 && (views == 0 || frames <= 0x7fffffffLL / views),
+                    "skimi_joint_quality: frames = %lld: views * frames must stay below 2^31", (long long)frames);
+    SKIMI_CHECK_ARG(bias_stride == 0 || bias_stride == joints, "skimi_joint_quality: bias_stride = %lld is neither 0 ([joints]) nor joints "
+                    "([views, joints])", (long long)bias_stride);
+    if (views == 0) return SKIMI_OK;
+    SKIMI_CHECK_ARG(n_edges == 0 || (edges && med_lens), "skimi_joint_quality: NULL edges or med_lens");
+    QualityArgs a{};
+    a.X = X, a.U = U, a.size = size, a.bias = bias, a.edges = edges;
+    a.med = med_lens, a.q = q, a.q_bone = q_bone, a.q_temp = q_temp, a.q_san = q_san;
+    a.V = views, a.T = frames, a.bias_stride = bias_stride, a.J = joints, a.E = n_edges;
+    a.beta = beta_temp, a.w_bone = w_bone, a.w_temp = w_temp, a.w_san = w_san;
+    SKIMI_CHECK_ARG(frames == 0 || (X && q && q_bone && q_temp && q_san && (!U || size)),
+                    "skimi_joint_quality: NULL input or output, or U without size");
+    if (n_edges > 0 && !med_given) {           // frames == 0: every median is NaN, written by the same kernel
+        hipLaunchKernelGGL(bone_median_kernel, dim3((unsigned)cdiv(views * n_edges, 4)), dim3(256), 0, (hipStream_t)stream, a);
+        SKIMI_LAUNCH_CHECK();
+    }
+    if (frames == 0) return SKIMI_OK;
+    hipLaunchKernelGGL(joint_quality_kernel, dim3((unsigned)cdiv(views * frames, 4)), dim3(256), 0, (hipStream_t)stream, a);
     SKIMI_LAUNCH_CHECK();
     return SKIMI_OK;
 }

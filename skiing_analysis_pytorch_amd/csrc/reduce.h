@@ -24,6 +24,26 @@ __device__ __forceinline__ unsigned wave_sum(unsigned v) {
     return v;
 }
 
+// Exact selection of two ranks by one wave: the keys (order-preserving, key64) are spread over the lanes, for_keys(f) calls
+// f(key) for each of the calling lane's keys, k0 <= k1 are 0-based ranks below the number of keys.  64 passes from the top
+// bit down: count the keys that agree with the prefix above the bit and have the bit clear (wave_sum: every lane gets the
+// same count), then step past them or stay.  p0, p1: the keys of rank k0, k1, the same in every lane.  The two middle
+// ranks (n - 1) / 2, n / 2 give a median (evaluate.hip: per-joint error tables; fuse.hip: bone lengths over a clip).
+template <class ForKeys>
+__device__ inline void wave_select2(unsigned k0, unsigned k1, ForKeys&& for_keys, unsigned long long& p0, unsigned long long& p1) {
+    p0 = p1 = 0;
+    for (int bit = 63; bit >= 0; --bit) {
+        unsigned c0 = 0, c1 = 0;
+        for_keys([&](unsigned long long key) {
+            c0 += ((key ^ p0) >> bit) == 0;    // the bits above agree with the prefix and this one is 0
+            c1 += ((key ^ p1) >> bit) == 0;
+        });
+        c0 = wave_sum(c0), c1 = wave_sum(c1);
+        if (k0 >= c0) k0 -= c0, p0 |= 1ULL << bit;
+        if (k1 >= c1) k1 -= c1, p1 |= 1ULL << bit;
+    }
+}
+
 // fixed-order workgroup sums of N values per thread: a shuffle tree inside each wave, then `total` adds the waves in
 // order, so every thread that reads total k gets the same bits.  The caller alternates `red` between two buffers: one
 // barrier per reduction suffices, and a total stays readable until the next-but-one reduction.

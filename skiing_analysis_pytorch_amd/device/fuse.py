@@ -1,6 +1,8 @@
-"""Left/right pose fusion and temporal smoothing of a clip on the device (csrc/fuse.hip; C-ABI: skimi_fuse_h36m,
-skimi_fuse_views, skimi_smooth_ema, skimi_smooth_savgol): VideoPose3D/fuse/fuse.py, fuse/main_raw.py:194-250,
-fuse/fuse.py:289-412; the host form is the package's fuse.py; rules: DESIGN §2 "Fusion + smoothing on the device".
+"""Left/right pose fusion, camera-group fusion, joint quality and temporal smoothing of a clip on the device (csrc/fuse.hip;
+C-ABI: skimi_fuse_h36m, skimi_fuse_views, skimi_fuse_group, skimi_joint_quality, skimi_smooth_ema, skimi_smooth_ema_batch,
+skimi_smooth_savgol): VideoPose3D/fuse/fuse.py, fuse/main_raw.py:194-250, fuse/main_unity.py:98-132, fuse/fuse.py:124-412;
+the host form is the package's fuse.py; rules: DESIGN §2 "Fusion + smoothing on the device", "Group fusion", "Joint
+quality".
 """
 from __future__ import annotations
 
@@ -9,7 +11,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from .._args import add_lead, f64, f64_dev, i32, upload_f64
+from .._args import add_lead, f64, f64_dev, i32, strip_lead, upload_f64, workspace
 from .._lib import check, current_stream, lib, ptr
 
 FUSE_MAX_JOINTS = 128
@@ -127,10 +129,16 @@ def _clip(fn, X):
 def smooth_ema(X: torch.Tensor, target_ids=None, alpha: float = 0.7, adaptive: bool = True, alpha_min: float = 0.45,
                alpha_max: float = 0.92, speed_gain: float = 0.25) -> EmaResult:
     """fuse.temporal_smooth_ema on the device: X [T, J, 3] (NaN rows = missing joints) -> EmaResult.  One thread per joint
-    walks the clip; the per-joint base factors come from alpha, target_ids and fuse._ALPHA_FACTOR as on the host."""
+    walks the clip; the per-joint base factors come from alpha, target_ids and fuse._ALPHA_FACTOR as on the host.
+    X [B, T, J, 3] smooths B clips in one launch (skimi_smooth_ema_batch): clip b's result is the [T, J, 3] call's on X[b] bit
+    for bit; B = 0 is accepted."""
     from .. import fuse
 
-    X, T, J = _clip("smooth_ema", X)
+    X = f64_dev("smooth_ema", X)
+    batched = X.dim() == 4
+    if X.dim() not in (3, 4) or X.shape[-1] != 3:
+        raise ValueError(f"smooth_ema: need X [T, J, 3] or [B, T, J, 3], got {list(X.shape)}")
+    T, J = X.shape[-3], X.shape[-2]
     if adaptive:
         ids = np.arange(J) if target_ids is None else np.asarray(list(target_ids), dtype=np.int64)
         if ids.shape != (J,):
@@ -142,8 +150,12 @@ def smooth_ema(X: torch.Tensor, target_ids=None, alpha: float = 0.7, adaptive: b
         base = np.full(J, float(alpha))
     base = torch.from_numpy(np.ascontiguousarray(base, dtype=np.float64)).to(X.device)
     Y = torch.empty_like(X)
-    check(lib().skimi_smooth_ema(ptr(X), T, J, ptr(base), int(bool(adaptive)), float(alpha_min), float(alpha_max),
-                                 float(speed_gain), ptr(Y), current_stream()), "skimi_smooth_ema")
+    if batched:
+        check(lib().skimi_smooth_ema_batch(ptr(X), X.shape[0], T, J, ptr(base), int(bool(adaptive)), float(alpha_min),
+                                           float(alpha_max), float(speed_gain), ptr(Y), current_stream()), "skimi_smooth_ema_batch")
+    else:
+        check(lib().skimi_smooth_ema(ptr(X), T, J, ptr(base), int(bool(adaptive)), float(alpha_min), float(alpha_max),
+                                     float(speed_gain), ptr(Y), current_stream()), "skimi_smooth_ema")
     return EmaResult(Y, base)
 
 
@@ -167,3 +179,112 @@ def smooth_savgol(X: torch.Tensor, win: int = 9, poly: int = 2) -> SavgolResult:
     check(lib().skimi_smooth_savgol(ptr(X), T, J, w, int(poly), ptr(fir), ptr(first), ptr(last), ptr(Y), current_stream()),
           "skimi_smooth_savgol")
     return SavgolResult(Y, w)
+
+
+class FuseGroupResult(NamedTuple):
+    """fuse_group's outputs (device tensors; V views, P = V (V - 1) / 2 pairs, T frames, J joints).  With given qualities the
+    confidence outputs (conf_x, dist, conf, err, fit_ok) are None."""
+    pairs: torch.Tensor       # int32 [P, 2]: (a, b), a < b, in itertools.combinations order
+    fused: torch.Tensor       # float64 [P, T, J, 3]
+    aligned: torch.Tensor     # float64 [P, T, J, 3]: view b in view a's frame (align=True), else view b itself
+    q_a: torch.Tensor         # float64 [P, T, J]
+    q_b: torch.Tensor
+    conf_x: torch.Tensor      # float64 [P, T, J]: cross-view consistency confidence
+    dist: torch.Tensor        # float64 [P, T, J]
+    conf: torch.Tensor        # float64 [V, T, J]: weak-perspective reprojection confidence of each view
+    err: torch.Tensor         # float64 [V, T, J]
+    fit_ok: torch.Tensor      # bool [V, T]
+
+
+def fuse_group(X: torch.Tensor, U, *, root_idx: int, left_hip_idx: int, right_hip_idx: int, left_shoulder_idx: int,
+               right_shoulder_idx: int, sigma_px: float = 12.0, sigma_3d: float = 0.08, scale_mode: str = "hip", min_points: int = 8,
+               align: bool = False, quality="confidence") -> FuseGroupResult:
+    """Every pair of a camera group fused in one call: X [V, T, J, 3], U [V, T, J, 2] device tensors -> FuseGroupResult.
+    align=False is fuse/main_unity.py's _fuse_pair (fuse_frame_3d on the raw poses), align=True fuse/main_raw.py's frame body
+    (view b Kabsch-aligned onto view a first; pair (a, b) then equals fuse_views(X[a], X[b], U[a], U[b]) bit for bit).
+    quality="confidence": q = sqrt(conf conf_x), each view's weak-perspective fit and canonical pose computed once;
+    quality=<tensor [V, T, J]> (joint_quality(...).q, say): those qualities, U may be None, no confidences."""
+    X = f64_dev("fuse_group", X)
+    if scale_mode not in FUSE_SCALE_MODES:
+        raise ValueError("scale_mode must be 'hip' or 'torso'")
+    if X.dim() != 4 or X.shape[3] != 3:
+        raise ValueError(f"fuse_group: need X [V, T, J, 3], got {list(X.shape)}")
+    V, T, J, dev = X.shape[0], X.shape[1], X.shape[2], X.device
+    given = not isinstance(quality, str)
+    if not given and quality != "confidence":
+        raise ValueError("fuse_group: quality must be 'confidence' or a [V, T, J] tensor")
+    Q = f64_dev("fuse_group", quality, dev) if given else None
+    Ud = None if (given and U is None) else f64_dev("fuse_group", U, dev)
+    if Ud is not None and tuple(Ud.shape) != (V, T, J, 2):
+        raise ValueError(f"fuse_group: U must be [{V}, {T}, {J}, 2], got {list(Ud.shape)}")
+    if Q is not None and tuple(Q.shape) != (V, T, J):
+        raise ValueError(f"fuse_group: quality must be [{V}, {T}, {J}], got {list(Q.shape)}")
+    pairs = torch.tensor([(a, b) for a in range(V) for b in range(a + 1, V)], dtype=torch.int32).reshape(-1, 2).to(dev)
+    P = pairs.shape[0]
+    fused, aligned, q_a, q_b = f64(dev, P, T, J, 3), f64(dev, P, T, J, 3), f64(dev, P, T, J), f64(dev, P, T, J)
+    conf_x = dist = conf = err = fit_ok = ws = None
+    nbytes = 0
+    if not given:
+        conf_x, dist, conf, err, fit_ok = f64(dev, P, T, J), f64(dev, P, T, J), f64(dev, V, T, J), f64(dev, V, T, J), i32(dev, V, T)
+        nbytes = int(lib().skimi_fuse_group_workspace_bytes(V, T, J))
+        ws = workspace(dev, nbytes, at_least=8, as_f64=True)
+    check(lib().skimi_fuse_group(ptr(X), ptr(Ud), ptr(Q), V, T, J, int(root_idx), int(left_hip_idx), int(right_hip_idx),
+                                 int(left_shoulder_idx), int(right_shoulder_idx), float(sigma_px), float(sigma_3d),
+                                 FUSE_SCALE_MODES[scale_mode], int(min_points), int(bool(align)), ptr(ws), nbytes, ptr(fused),
+                                 ptr(aligned), ptr(q_a), ptr(q_b), ptr(conf_x), ptr(dist), ptr(conf), ptr(err), ptr(fit_ok),
+                                 current_stream()), "skimi_fuse_group")
+    return FuseGroupResult(pairs, fused, aligned, q_a, q_b, conf_x, dist, conf, err, None if given else fit_ok.bool())
+
+
+class JointQualityResult(NamedTuple):
+    """joint_quality's outputs (device tensors; V views, T frames, J joints, E edges; without the view axis for a [T, J, 3]
+    input)."""
+    q: torch.Tensor           # float64 [V, T, J]
+    q_bone: torch.Tensor      # float64 [V, T, J]: -1e9 missing joint, -100 no usable edge
+    q_temp: torch.Tensor      # float64 [V, T, J]
+    q_san: torch.Tensor       # float64 [V, T, J]: 0 or -50
+    med_lens: torch.Tensor    # float64 [V, E]
+
+
+def joint_quality(X: torch.Tensor, U=None, *, edges, size, beta_temp: float = 1.0, w_bone: float = 1.0, w_temp: float = 0.3,
+                  w_san: float = 0.2, med_lens=None, bias=None) -> JointQualityResult:
+    """The ground-truth-free joint quality of fuse/fuse.py:124-285 (fuse.compute_q_nogt on the host) for V clips: X [V, T, J,
+    3] ([T, J, 3]: V = 1) device tensor, NaN rows = missing joints; U [V, T, J, 2] or None; edges [E, 2] positions on the
+    joint axis; size (width, height), shared or one per view; med_lens [V, E]: used instead of the clips' medians; bias
+    [J] or [V, J]: added at the end (+b for the left camera, -b for the right one) -> JointQualityResult."""
+    X, single = add_lead(f64_dev("joint_quality", X), 4)
+    if X.dim() != 4 or X.shape[3] != 3:
+        raise ValueError(f"joint_quality: need X [V, T, J, 3] or [T, J, 3], got {list(X.shape)}")
+    V, T, J, dev = X.shape[0], X.shape[1], X.shape[2], X.device
+    Ud = None
+    if U is not None:
+        Ud = add_lead(f64_dev("joint_quality", U, dev), 4)[0] if single else f64_dev("joint_quality", U, dev)
+        if tuple(Ud.shape) != (V, T, J, 2):
+            raise ValueError(f"joint_quality: U must be [{V}, {T}, {J}, 2], got {list(Ud.shape)}")
+    ed = edges if isinstance(edges, torch.Tensor) else torch.as_tensor(np.asarray(list(edges), dtype=np.int64).reshape(-1, 2))
+    if ed.dim() != 2 or ed.shape[1] != 2:
+        raise ValueError(f"joint_quality: edges must be [E, 2], got {list(ed.shape)}")
+    ed = ed.to(dev, torch.int32).contiguous()
+    E = ed.shape[0]
+    sz = np.asarray(size, dtype=np.float64)
+    if sz.shape not in ((2,), (V, 2)):
+        raise ValueError(f"joint_quality: size must be (width, height) or [{V}, 2], got {list(sz.shape)}")
+    sz = torch.from_numpy(np.broadcast_to(sz, (V, 2)).copy(order="C")).to(dev).contiguous()      # broadcast views are read-only
+    if med_lens is None:
+        med = f64(dev, V, E)
+    else:
+        med = upload_f64(med_lens, dev)
+        med = med[None] if single and med.dim() == 1 else med
+        if tuple(med.shape) != (V, E):
+            raise ValueError(f"joint_quality: med_lens must be [{V}, {E}], got {list(med.shape)}")
+    b, bs = None, 0
+    if bias is not None:
+        b = upload_f64(bias, dev)
+        if tuple(b.shape) not in ((J,), (V, J)):
+            raise ValueError(f"joint_quality: bias must be [{J}] or [{V}, {J}], got {list(b.shape)}")
+        bs = J if b.dim() == 2 else 0
+    q, qb, qt, qs = (f64(dev, V, T, J) for _ in range(4))
+    check(lib().skimi_joint_quality(ptr(X), ptr(Ud), V, T, J, ptr(ed), E, ptr(sz), float(beta_temp), float(w_bone), float(w_temp),
+                                    float(w_san), int(med_lens is not None), ptr(b), bs, ptr(med), ptr(q), ptr(qb), ptr(qt), ptr(qs),
+                                    current_stream()), "skimi_joint_quality")
+    return JointQualityResult(*strip_lead((q, qb, qt, qs, med), single))

@@ -8,7 +8,8 @@ and the NaN-aware masks (missing joints) must be preserved bit-for-bit, so these
 gathered tensor on every rank rather than as GPU kernels.  Array form ([J,3] / [T,J,3] with NaN
 for missing joints) of the reference's dict form; `to_dicts` / `from_dicts` convert.
 
-Opt-in device counterparts (csrc/fuse.hip): geometry.fuse_h36m, fuse_views, smooth_ema, smooth_savgol.  The functions here
+Opt-in device counterparts (csrc/fuse.hip): geometry.fuse_h36m, fuse_views, fuse_group, joint_quality, smooth_ema,
+smooth_savgol.  The ground-truth-free joint quality of fuse/fuse.py:124-285 is at the end of the file.  The functions here
 stay as they are: pinned to the reference by tests/golden/fuse_*.npz, they are what the kernels are tested against."""
 from __future__ import annotations
 
@@ -420,3 +421,129 @@ def fuse_pose_no_extrinsics_h36m(left_3d: np.ndarray, right_3d: np.ndarray, tau:
         gains = [d["gain"] for d in diag["per_frame"]]
         diag["mean_gain"] = float(np.nanmean(gains)) if gains else np.nan
     return (fused_seq[0] if single else fused_seq), diag
+
+
+# ---- ground-truth-free joint quality (fuse/fuse.py:42-67, :124-285) in array form ----
+# Arrays [T, J, 3] / [T, J, 2] with NaN rows for missing joints; `edges` [E, 2] are positions on the joint axis (the
+# reference's ids looked up in target_ids; an id that is not in target_ids is a position outside 0 .. J - 1 here).
+# Device counterpart: geometry.joint_quality (csrc/fuse.hip); rules: DESIGN §2 "Joint quality".
+Q_MISSING, Q_NO_EDGE, Q_INSANE = -1e9, -100.0, -50.0
+
+
+def _edges_array(edges) -> np.ndarray:
+    return np.asarray(list(edges), dtype=np.int64).reshape(-1, 2)
+
+
+def q_2d_sanity(U, width, height, J: int = None) -> np.ndarray:
+    """fuse.py:124-148: U [..., J, 2] (or None with J given) -> [..., J]: 0 where u, v are finite and inside the image
+    (0 <= u < width, 0 <= v < height), -50 otherwise."""
+    if U is None:
+        if J is None:
+            raise ValueError("q_2d_sanity: without U the number of joints J is needed")
+        return np.full((int(J),), Q_INSANE, dtype=np.float64)
+    U = np.asarray(U, dtype=np.float64)
+    u, v = U[..., 0], U[..., 1]
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(u) & np.isfinite(v) & (0 <= u) & (u < width) & (0 <= v) & (v < height)
+    return np.where(ok, 0.0, Q_INSANE)
+
+
+def bone_lengths(X: np.ndarray, edges) -> np.ndarray:
+    """X [..., J, 3] -> [..., E]: ||X[a] - X[b]|| where both rows are finite, NaN elsewhere and for an edge with an
+    endpoint outside 0 .. J - 1."""
+    X = np.asarray(X, dtype=np.float64)
+    E, J = _edges_array(edges), X.shape[-2]
+    L = np.full(X.shape[:-2] + (E.shape[0],), np.nan, dtype=np.float64)
+    ok = _row_ok(X)
+    for e, (a, b) in enumerate(E):
+        if 0 <= a < J and 0 <= b < J:
+            both = ok[..., a] & ok[..., b]
+            d = np.where(both[..., None], X[..., a, :] - X[..., b, :], 0.0)
+            L[..., e] = np.where(both, np.sqrt((d * d).sum(axis=-1)), np.nan)
+    return L
+
+
+def bone_median_lengths(X: np.ndarray, edges) -> np.ndarray:
+    """fuse.py:151-177 estimate_bone_median_lengths: X [T, J, 3] -> [E], the NaN-ignoring median over the clip of every
+    edge's length; NaN for an edge without a single sample (where the reference's nanmedian warns) and for T = 0."""
+    L = bone_lengths(np.asarray(X, dtype=np.float64).reshape(-1, *np.shape(X)[-2:]), edges)
+    med = np.full(L.shape[1], np.nan, dtype=np.float64)
+    for e in range(L.shape[1]):
+        col = L[:, e]
+        col = col[~np.isnan(col)]
+        if col.size:
+            med[e] = np.median(col)
+    return med
+
+
+def q_from_bone_deviation(X: np.ndarray, edges, med_lens: np.ndarray) -> np.ndarray:
+    """fuse.py:180-221 on one frame X [J, 3]: -mean over the incident edges (finite median, both rows finite) of |len -
+    median|, the mean taken as dev_sum / (cnt + 1e-8); -100 without such an edge; -1e9 for a missing joint."""
+    X = np.asarray(X, dtype=np.float64)
+    J = X.shape[0]
+    ok = _row_ok(X)
+    dev, cnt = np.zeros(J), np.zeros(J, dtype=np.int64)
+    for e, (a, b) in enumerate(_edges_array(edges)):
+        if not (0 <= a < J and 0 <= b < J) or not np.isfinite(med_lens[e]) or not (ok[a] and ok[b]):
+            continue
+        d = abs(np.linalg.norm(X[a] - X[b]) - med_lens[e])
+        for j in (a, b):                                   # a self-edge counts twice
+            dev[j] += d
+            cnt[j] += 1
+    q = np.where(cnt > 0, -(dev / (cnt + EPS)), Q_NO_EDGE)
+    return np.where(ok, q, Q_MISSING)
+
+
+def q_from_temporal(prev, curr: np.ndarray, beta: float = 1.0) -> np.ndarray:
+    """fuse.py:224-246: -beta ||x_t - x_{t-1}|| per joint; 0 where there is no previous row; -1e9 for a missing joint."""
+    curr = np.asarray(curr, dtype=np.float64)
+    ok_c = _row_ok(curr)
+    q = np.where(ok_c, 0.0, Q_MISSING)
+    if prev is None:
+        return q
+    prev = np.asarray(prev, dtype=np.float64)
+    ok = ok_c & _row_ok(prev)
+    d = np.where(ok[:, None], curr - prev, 0.0)
+    return np.where(ok, -beta * np.sqrt((d * d).sum(axis=1)), q)
+
+
+def combine_q(q_bone, q_temp=None, q_sanity=None, w_bone: float = 1.0, w_temp: float = 0.3, w_san: float = 0.2) -> np.ndarray:
+    """fuse.py:249-262"""
+    q = w_bone * np.asarray(q_bone, dtype=np.float64)
+    if q_temp is not None:
+        q = q + w_temp * q_temp
+    if q_sanity is not None:
+        q = q + w_san * q_sanity
+    return q
+
+
+def compute_q_nogt(X: np.ndarray, U=None, *, edges, width, height, beta_temp: float = 1.0, w_bone: float = 1.0,
+                   w_temp: float = 0.3, w_san: float = 0.2, med_lens=None, bias=None):
+    """fuse.py:265-285 compute_q_nogt_frame for every frame of one view's clip X [T, J, 3] (U [T, J, 2] or None), with the
+    clip's own median bone lengths unless med_lens [E] is given; bias [J] is added at the end (+b for the left camera, -b
+    for the right one: DESIGN §2 "Joint quality") -> dict(q, q_bone, q_temp, q_san [T, J], med_lens [E])."""
+    X = np.asarray(X, dtype=np.float64)
+    T, J = X.shape[:2]
+    med = bone_median_lengths(X, edges) if med_lens is None else np.asarray(med_lens, dtype=np.float64)
+    qb, qt, qs = (np.empty((T, J), dtype=np.float64) for _ in range(3))
+    for t in range(T):
+        qb[t] = q_from_bone_deviation(X[t], edges, med)
+        qt[t] = q_from_temporal(X[t - 1] if t else None, X[t], beta=beta_temp)
+        qs[t] = q_2d_sanity(None if U is None else U[t], width, height, J=J)
+    q = combine_q(qb, qt, qs, w_bone=w_bone, w_temp=w_temp, w_san=w_san)
+    if bias is not None:
+        q = q + np.asarray(bias, dtype=np.float64)
+    return {"q": q, "q_bone": qb, "q_temp": qt, "q_san": qs, "med_lens": med}
+
+
+def body_side_bias(names_or_ids, id_to_name=None, bias_val: float = 1.0) -> np.ndarray:
+    """fuse.py:42-67: +bias_val for a joint whose name ends in _L / _l, -bias_val for _R / _r, 0 for the rest.
+    names_or_ids: joint names, or ids looked up in id_to_name."""
+    b = np.zeros(len(names_or_ids), dtype=np.float64)
+    for k, key in enumerate(names_or_ids):
+        name = key if id_to_name is None or isinstance(key, str) else id_to_name[key]
+        if name.endswith(("_L", "_l")):
+            b[k] = +bias_val
+        elif name.endswith(("_R", "_r")):
+            b[k] = -bias_val
+    return b

@@ -24,7 +24,9 @@ from .device.resect import (RESECT_LOSSES, ResectResult, relative_pose, resect_c
 from .device.refine import (RefineResult, refine_cameras_points)
 from .device.essential import (EssentialResult, essential_ransac, five_point)
 from .device.fuse import (FUSE_MAX_JOINTS, FUSE_SCALE_MODES, SAVGOL_MAX_WIN, FuseH36MResult, FUSE_DIAG_FIELDS,
-                          FuseViewsResult, EmaResult, SavgolResult, fuse_h36m, fuse_views, smooth_ema, smooth_savgol)
+                          FuseViewsResult, EmaResult, SavgolResult, fuse_h36m, fuse_views, smooth_ema, smooth_savgol,
+                          FuseGroupResult, JointQualityResult, fuse_group, joint_quality)
+from .device.skeleton import (SKELETON_DIRECTIONS, convert_skeleton)
 from .device.kinematics import (KIN_ROLES, KIN_BASE_SERIES, KIN_SERIES, KIN_STAT_FIELDS, KIN_LAYOUT_MHR70_15, KIN_LDS_FRAMES,
                                 KinematicsResult, kin_max_turns, kinematics)
 from .device.evaluate import (EVAL_MAX_JOINTS, EVAL_MAX_EDGES, EVAL_MAX_PAIRS, EVAL_LDS_ELEMS, JOINT_STAT_FIELDS, H36M_EDGES,

@@ -334,13 +334,29 @@ def _side_streams(dev, n):
     return pool[:n]
 
 
+_H36M_KEYS = ("joints3d", "joints3d_smoothed", "joints3d_clean", "joints3d_clean_smoothed", "joints3d_robust", "joints3d_robust_ok",
+              "joints3d_robust_smoothed")
+
+
+def _with_h36m(out, skeleton):
+    """process_multi_view_clip(skeleton="h36m"): the COCO-17 joint keys that are present, converted under <key>_h36m"""
+    if skeleton is None:
+        return out
+    for key in _H36M_KEYS:
+        if key in out:
+            x = out[key]
+            out[key + "_h36m"] = geometry.convert_skeleton(x if x.is_cuda else x.numpy(), "coco_to_h36m")
+    return out
+
+
 @torch.no_grad()
 def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.Tensor, steps_per_call: int = 4,
                             want_dense: bool = False, streams: int = 1, smooth: bool = False, boxes: Optional[torch.Tensor] = None,
                             scores: Optional[torch.Tensor] = None, source_size=None, triage: bool = False,
                             conf_thr: float = 0.3, err_thresh_px: float = 2.0, robust: bool = False,
                             inlier_px: Optional[float] = None, min_inliers: int = 2, refine_iters: int = 5,
-                            weighted: bool = False, device_smooth: bool = False) -> Dict[str, torch.Tensor]:
+                            weighted: bool = False, device_smooth: bool = False,
+                            skeleton: Optional[str] = None) -> Dict[str, torch.Tensor]:
     """The hot loop of process_multi_view_video (vggt/multi_view_process.py:133-309) for a clip
     already in memory: frames [T, S, 3, H, W] in [0,1] (device), keypoints [T, S, J, 2] in the
     pixels of the H x W frames.  Per time step: one S-view VGGT call -> cameras -> DLT
@@ -376,8 +392,20 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
     there), and the dict gains "joints3d_robust", "joints3d_robust_ok", "robust_err" [T, S, J], "inlier_views" [T, J]
     uint8, "robust_rms_px" [T, J], "robust_ok" [T, J] bool, "view_inlier_ratio" [T, S], "robust_report" [T, 4]; with
     smooth=True also "joints3d_robust_smoothed" = fuse.smooth_skeleton(joints3d_robust_ok).  "joints3d" and the triage
-    outputs stay what they are: robust and triage are independent and may both be on.  2 <= S <= 8, J <= 32."""
+    outputs stay what they are: robust and triage are independent and may both be on.  2 <= S <= 8, J <= 32.
+
+    skeleton="h36m" (default None: nothing changes): the keypoints are COCO-17 (J = 17, anything else is a ValueError before
+    the model is called) and the dict gains "joints3d_h36m" [T, 17, 3], the H36M-17 form of "joints3d" (geometry.
+    convert_skeleton, "coco_to_h36m"), float64 on the device, which geometry.kinematics (angle.H36M_17), geometry.fuse_h36m
+    and geometry.pose_errors take; the smoothed, clean and robust joint keys that are present are converted the same way
+    under "<key>_h36m".  Every other key is what it is without the argument."""
     T, S = frames.shape[:2]
+    if skeleton is not None:
+        if skeleton != "h36m":
+            raise ValueError(f"process_multi_view_clip: skeleton must be None or 'h36m', got {skeleton!r}")
+        if keypoints.dim() != 4 or keypoints.shape[2] != 17:
+            raise ValueError(f"process_multi_view_clip: skeleton='h36m' converts COCO-17 joints, keypoints are "
+                             f"{list(keypoints.shape)}")
     H, W = frames.shape[-2:]
     lo, hi, T_pad = parallel.shard_range(T)
     want = {"camera", "depth", "point"} if want_dense else {"camera"}
@@ -513,7 +541,7 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
                 out["joints3d_clean_smoothed"] = geometry.smooth_savgol(out["joints3d_clean"]).X
             if robust:
                 out["joints3d_robust_smoothed"] = geometry.smooth_savgol(out["joints3d_robust_ok"]).X
-            return out
+            return _with_h36m(out, skeleton)
         out["joints3d_smoothed"] = torch.from_numpy(fuse.temporal_smooth_ema(joints.cpu().numpy().astype(np.float64)))
         if triage:   # the reference's post_triage_sequence(smooth=True): Savitzky-Golay over the kept joints
             out["joints3d_clean_smoothed"] = torch.from_numpy(
@@ -521,7 +549,7 @@ def process_multi_view_clip(model: VGGT, frames: torch.Tensor, keypoints: torch.
         if robust:   # the same filter over the joints the consensus accepted
             out["joints3d_robust_smoothed"] = torch.from_numpy(
                 fuse.smooth_skeleton(out["joints3d_robust_ok"].cpu().numpy().astype(np.float64)))
-    return out
+    return _with_h36m(out, skeleton)
 
 
 @torch.no_grad()

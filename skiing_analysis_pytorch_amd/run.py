@@ -264,3 +264,117 @@ def solve_rt_from_essential(X3d, x2d_left, x2d_right, conf_left=None, conf_right
         Path(out).parent.mkdir(parents=True, exist_ok=True)
         np.savez(out, **res)
     return res
+
+
+# ---- fuse/main_unity.py run_batch for one camera group ---------------------------------------------------------------------
+GROUP_TARGET_IDS = (1, 2, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 41, 62, 69)      # fuse/main_unity.py: TARGET_IDS
+_CAMERA_SUFFIXES = ("_sam_3d_body_outputs", "_sam_3d_body_output", "_outputs")
+
+
+def camera_name_from_path(path) -> str:
+    """fuse/main_unity.py:62-68: the file's stem without the first of the known output suffixes it ends with"""
+    stem = Path(path).stem
+    for suffix in _CAMERA_SUFFIXES:
+        if stem.endswith(suffix):
+            return stem[: -len(suffix)]
+    return stem
+
+
+def load_camera_sequence(path, target_ids=GROUP_TARGET_IDS):
+    """fuse/main_unity.py:80-95 in array form: an .npz with the per-frame records under the key `outputs` (else under its
+    first key), each with pred_keypoints_2d [N, 2] and pred_keypoints_3d [N, 3] -> (p2d [T, J, 2], p3d [T, J, 3]) float64,
+    the rows `target_ids` of every frame."""
+    ids = list(target_ids)
+    with np.load(path, allow_pickle=True) as data:
+        frames = data["outputs" if "outputs" in data.files else data.files[0]]
+        p2d = np.full((len(frames), len(ids), 2), np.nan)
+        p3d = np.full((len(frames), len(ids), 3), np.nan)
+        for t, frame in enumerate(frames):
+            p2d[t] = np.asarray(frame["pred_keypoints_2d"], dtype=np.float64)[ids]
+            p3d[t] = np.asarray(frame["pred_keypoints_3d"], dtype=np.float64)[ids]
+    return p2d, p3d
+
+
+def group_inputs(inputs, names=None, target_ids=None):
+    """V paths or V (p2d, p3d) array pairs -> (names, U [V, T, J, 2], X [V, T, J, 3]) on the host, every sequence cut to the
+    shortest one (fuse/main_unity.py:104).  Paths are named by camera_name_from_path, array pairs cam0, cam1, ..."""
+    ids = GROUP_TARGET_IDS if target_ids is None else tuple(target_ids)
+    seqs, auto = [], []
+    for i, item in enumerate(inputs):
+        if isinstance(item, (str, Path)):
+            seqs.append(load_camera_sequence(item, ids))
+            auto.append(camera_name_from_path(item))
+        else:
+            p2d, p3d = (np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a, dtype=np.float64) for a in item)
+            seqs.append((p2d, p3d))
+            auto.append(f"cam{i}")
+    names = auto if names is None else [str(n) for n in names]
+    if len(names) != len(seqs):
+        raise ValueError(f"fuse_camera_group: {len(names)} names for {len(seqs)} cameras")
+    if len(seqs) < 2:
+        raise ValueError("fuse_camera_group: a group needs at least two cameras")
+    T = min(min(len(p2d), len(p3d)) for p2d, p3d in seqs)
+    U, X = np.stack([p2d[:T] for p2d, _ in seqs]), np.stack([p3d[:T] for _, p3d in seqs])
+    if X.ndim != 4 or X.shape[3] != 3 or U.shape != X.shape[:3] + (2,):
+        raise ValueError(f"fuse_camera_group: need p3d [T, J, 3] and p2d [T, J, 2] per camera, got {list(X.shape)}, {list(U.shape)}")
+    return names, U, X
+
+
+def save_group(out_dir, names, pairs, smoothed, fused=None):
+    """fuse/save.py for every pair: <a>__<b>_smoothed.npy (and _fused.npy when `fused` is given), [T, J, 3] float64 with NaN
+    for missing joints -> the paths written"""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    written = []
+    for p, (a, b) in enumerate(pairs):
+        stem = f"{names[int(a)]}__{names[int(b)]}"
+        for kind, arr in (("fused", fused), ("smoothed", smoothed)):
+            if arr is None:
+                continue
+            path = out_dir / f"{stem}_{kind}.npy"
+            np.save(path, np.ascontiguousarray(arr[p], dtype=np.float64))
+            written.append(path)
+    return written
+
+
+def _fuse_camera_group(layer, dev, inputs, out_dir, names, target_ids, fuse_kw, ema_kw, quality, size, edges, save_raw_fused):
+    """fuse_camera_group's body with the module the device calls are taken from (`layer`: geometry), the device the clips go
+    to and the keywords of the two calls"""
+    ids = GROUP_TARGET_IDS if target_ids is None else tuple(target_ids)
+    names, U, X = group_inputs(inputs, names, ids)
+    if X.shape[1] == 0:
+        raise ValueError("fuse_camera_group: the shortest sequence is empty; nothing to save")
+    Xd, Ud = torch.from_numpy(X).to(dev), torch.from_numpy(U).to(dev)
+    if isinstance(quality, str) and quality == "nogt":
+        from . import skeleton
+        if size is None:
+            raise ValueError('fuse_camera_group: quality="nogt" needs size=(width, height)')
+        quality = layer.joint_quality(Xd, Ud, edges=skeleton.MHR70_15_EDGES if edges is None else edges, size=size).q
+    elif not isinstance(quality, str):
+        quality = (quality if isinstance(quality, torch.Tensor) else torch.as_tensor(np.asarray(quality, dtype=np.float64))).to(dev)
+    g = layer.fuse_group(Xd, Ud, quality=quality, **fuse_kw)
+    sm = layer.smooth_ema(g.fused, target_ids=ids if len(ids) == X.shape[2] else None, **ema_kw)
+    pairs, fused, smoothed = g.pairs.cpu().numpy(), g.fused.cpu().numpy(), sm.X.cpu().numpy()
+    paths = save_group(out_dir, names, pairs, smoothed, fused if save_raw_fused else None)
+    return dict(names=names, pairs=pairs, fused=fused, smoothed=smoothed, paths=paths)
+
+
+def fuse_camera_group(inputs, out_dir, *, names=None, sigma_px=12.0, sigma_3d=0.08, alpha=0.7, adaptive_smooth=True,
+                      smooth_alpha_min=0.45, smooth_alpha_max=0.92, smooth_speed_gain=0.25, save_raw_fused=False,
+                      quality="confidence", target_ids=None, root_idx=14, left_hip_idx=11, right_hip_idx=12, left_shoulder_idx=5,
+                      right_shoulder_idx=6, scale_mode="hip", min_points=8, align=False, size=None, edges=None):
+    """fuse/main_unity.py's run_batch for one camera group: `inputs` are V .npz paths (the reference's layout, see
+    load_camera_sequence) or V (p2d, p3d) array pairs; every pair of cameras is fused (one geometry.fuse_group call), every
+    fused clip smoothed (one batched geometry.smooth_ema call) and written as fuse/save.py does, <a>__<b>_smoothed.npy and,
+    with save_raw_fused, <a>__<b>_fused.npy -> dict(names, pairs, fused, smoothed (host arrays [P, T, J, 3]), paths).
+    The five key joints default to the reference's 14, 11, 12, 5, 6: these are POSITIONS in the 15-joint array (what the
+    reference's dict-to-array conversion makes of its IDX_* constants), not MHR-70 ids.  quality: "confidence" (the
+    reference), "nogt" (geometry.joint_quality on `edges`, default skeleton.MHR70_15_EDGES, with the image `size`) or a [V, T,
+    J] array of qualities.  target_ids: the joint rows taken from a file and the ids the EMA's per-joint factors go by."""
+    fuse_kw = dict(root_idx=root_idx, left_hip_idx=left_hip_idx, right_hip_idx=right_hip_idx, left_shoulder_idx=left_shoulder_idx,
+                   right_shoulder_idx=right_shoulder_idx, sigma_px=sigma_px, sigma_3d=sigma_3d, scale_mode=scale_mode,
+                   min_points=min_points, align=align)
+    ema_kw = dict(alpha=alpha, adaptive=adaptive_smooth, alpha_min=smooth_alpha_min, alpha_max=smooth_alpha_max,
+                  speed_gain=smooth_speed_gain)
+    return _fuse_camera_group(geometry, torch.device("cuda", torch.cuda.current_device()), inputs, out_dir, names, target_ids,
+                              fuse_kw, ema_kw, quality, size, edges, save_raw_fused)

@@ -1007,6 +1007,71 @@ def gen_calibrate():
 GENERATORS["calibrate"] = gen_calibrate
 
 
+def gen_fuse_group():
+    """DESIGN §2 "Joint quality", "Group fusion", "Skeleton conversion": the reference's OWN fuse/fuse.py (no-GT quality:
+    estimate_bone_median_lengths, q_from_bone_deviation, q_from_temporal, q_2d_sanity, compute_q_nogt_frame,
+    body_side_bias), fuse/main_unity.py (_fuse_pair, then temporal_smooth_ema and fuse/save.py's array form, for every pair
+    of three views) and VideoPose3D/coco_hm36.py on seeded synthetic clips.  Inputs and results only."""
+    import itertools
+    import warnings
+    sys.path.insert(0, str(ROOT / "tests"))
+    import fuse_group_cases as gc
+    from fuse import fuse as rf
+    from fuse.main_unity import _fuse_pair, TARGET_IDS, UNITY_MHR70_MAPPING
+    from fuse.save import _seq_dicts_to_array
+    from metrics.true_data_compare import BONE_EDGES
+    from VideoPose3D import coco_hm36 as rc
+
+    out = {"target_ids": np.array(TARGET_IDS, np.int64), "bone_edge_ids": np.array(BONE_EDGES, np.int64)}
+    ids = list(TARGET_IDS)
+    # --- quality: one view's clip, dicts without the missing joints
+    c = gc.quality_golden_case()
+    X, U, W, H = c["X"], c["U"], c["width"], c["height"]
+    edge_ids = [(gc.id_of(a), gc.id_of(b)) for a, b in c["edges"]]
+    T, J = X.shape[:2]
+    seq3 = [{jid: X[t, j] for j, jid in enumerate(ids) if np.isfinite(X[t, j]).all()} for t in range(T)]
+    seq2 = [{jid: U[t, j] for j, jid in enumerate(ids) if j not in c["u_absent"]} for t in range(T)]
+    assert all(seq3)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                      # nanmedian of the edge that is never seen
+        med = rf.estimate_bone_median_lengths(seq3, ids, edge_ids)
+    qb = np.stack([rf.q_from_bone_deviation(seq3[t], ids, edge_ids, med) for t in range(T)])
+    qt = np.stack([rf.q_from_temporal(seq3[t - 1] if t else None, seq3[t], ids, beta=c["beta_temp"]) for t in range(T)])
+    qs = np.stack([rf.q_2d_sanity(seq2[t], ids, W, H) for t in range(T)])
+    kw = dict(beta_temp=c["beta_temp"], w_bone=c["w_bone"], w_temp=c["w_temp"], w_san=c["w_san"])
+    q = np.stack([rf.compute_q_nogt_frame(seq3[t], seq3[t - 1] if t else None, seq2[t], ids, edge_ids, med, W, H, **kw) for t in range(T)])
+    q_noU = np.stack([rf.compute_q_nogt_frame(seq3[t], seq3[t - 1] if t else None, None, ids, edge_ids, med, W, H, **kw) for t in range(T)])
+    out |= {"q_med": med, "q_bone": qb, "q_temp": qt, "q_san": qs, "q": q, "q_noU": q_noU,
+            "side_bias": rf.body_side_bias(ids, UNITY_MHR70_MAPPING, 0.75)}
+    # --- group: three views, every pair by main_unity._fuse_pair, then the EMA and save.py's array
+    g = gc.group_golden_case()
+    P3, P2 = g["X"], g["U"]
+    seqs = [[{"p2d": {jid: P2[v, t, j] for j, jid in enumerate(ids)}, "p3d": {jid: P3[v, t, j] for j, jid in enumerate(ids)}}
+             for t in range(P3.shape[1])] for v in range(P3.shape[0])]
+    fused, smoothed = [], []
+    for a, b in itertools.combinations(range(P3.shape[0]), 2):
+        fs = _fuse_pair(seqs[a], seqs[b], sigma_px=g["sigma_px"], sigma_3d=g["sigma_3d"])
+        fused.append(_seq_dicts_to_array(fs, ids))
+        smoothed.append(_seq_dicts_to_array(rf.temporal_smooth_ema(fs, ids, **g["ema"]), ids))
+    out |= {"g_fused": np.stack(fused), "g_smoothed": np.stack(smoothed), "g_X": P3, "g_U": P2, "q_X": X, "q_U": U,
+            "q_edges": np.array(c["edges"], np.int64)}
+    # --- skeleton conversion
+    for name, arr in gc.skeleton_golden_inputs().items():
+        out[f"sk_{name}"] = arr
+        if name.startswith("coco"):
+            out[f"sk_{name}_h36m"] = rc.coco_to_h36m(arr)
+            out[f"sk_{name}_h36m_nohead"] = rc.coco_to_h36m(arr, synthesize_head=False)
+        else:
+            out[f"sk_{name}_coco"] = rc.h36m_to_coco(arr)
+            out[f"sk_{name}_coco_face"] = rc.h36m_to_coco(arr, synthesize_face=True)
+    path = GOLD / "fuse_group.npz"
+    np.savez_compressed(path, **out)
+    print("wrote", path.name, path.stat().st_size, "bytes")
+
+
+GENERATORS["fuse_group"] = gen_fuse_group
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GENERATORS)
     for w in which:
