@@ -305,7 +305,7 @@ int skimi_attention(const void* qkv, void* out, int32_t dtype, int32_t batch, in
 int skimi_attention_out(const void* qkv, void* out, int32_t dtype, int32_t out_dtype, int32_t batch, int32_t seq,
                         int32_t heads, int32_t head_dim, void* stream);
 
-/* The attention and qk-norm launches exactly as the VGGT block forward makes them (vggt.hip), for the tests:
+/* The attention and qk-norm launches exactly as the VGGT block forward makes them (vggt_block.hip), for the tests:
  *
  * skimi_qknorm_rope_scaled: skimi_qknorm_rope, and where it takes the fast bf16 kernel (bf16 qkv 16-byte aligned,
  * qn_w, kn_w and pos given) q is multiplied by q_scale before its one rounding to bf16; *q_scaled (host) says whether
@@ -332,8 +332,8 @@ int skimi_attention_ex(const void* qkv, void* out, int32_t dtype, int32_t out_dt
 /* bytes of x3_scratch the bf16x3 attention kernel needs for `tokens` packed qkv rows of `row_elems` f32 each */
 uint64_t skimi_attention_x3_scratch_bytes(int64_t tokens, int64_t row_elems);
 
-/* The LayerNorm and fp32 attention launches with every argument the forward gives them (vggt.hip's DPT heads, the track
- * head's run_mha), for kernel-level tests.
+/* The LayerNorm and fp32 attention launches with every argument the forward gives them (vggt_dpt.hip's DPT heads,
+ * vggt_track.hip's run_mha), for kernel-level tests.
  *
  * skimi_layernorm_ex: skimi_layernorm plus
  *   grp_rows, grp_stride, grp_off   input row gather: output row r reads input row

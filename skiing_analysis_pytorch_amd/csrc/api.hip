@@ -229,7 +229,7 @@ int skimi_attention_out(const void* qkv, void* out, int32_t dtype, int32_t out_d
                             out_dtype == SKIMI_F16 && dtype == SKIMI_BF16);
 }
 
-// the two calls of the block forward (vggt.hip), with its arguments, for kernel-level tests
+// the two calls of the block forward (vggt_block.hip), with its arguments, for kernel-level tests
 int skimi_qknorm_rope_scaled(void* qkv, int32_t dtype, int64_t tokens, int32_t heads, const float* qn_w,
                              const float* qn_b, const float* kn_w, const float* kn_b, float eps,
                              const int32_t* pos, const float* rope_cos, const float* rope_sin,
@@ -262,7 +262,7 @@ uint64_t skimi_attention_x3_scratch_bytes(int64_t tokens, int64_t row_elems) {
 static inline bool is_elem_dtype(int32_t d) { return d == SKIMI_F32 || d == SKIMI_BF16 || d == SKIMI_F16; }
 static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-// the LayerNorm launch of the DPT heads (vggt.hip) and the attention launch of the track head (track_impl.inc's
+// the LayerNorm launch of the DPT heads (vggt_dpt.hip) and the attention launch of the track head (vggt_track.hip's
 // run_mha), with their arguments, for kernel-level tests.  The forward derives the gather and the strides itself; here
 // what the kernels cannot notice is checked first.
 int skimi_layernorm_ex(const float* x, const float* x2, int64_t ldx, int64_t in_rows, int64_t rows, int32_t C,

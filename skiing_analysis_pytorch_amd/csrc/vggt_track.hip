@@ -1,30 +1,19 @@
-// Track head of the VGGT forward, textually included by vggt.hip (twice: TRACK_PART 1 = weight
-// structs before `struct skimi_vggt`, TRACK_PART 2 = packer + forward after run_dpt).
+// Track head of the VGGT forward: its weight packing and its forward.
 // Reference: vggt/vggt/heads/track_head.py:72-104, track_modules/base_track_predictor.py:82-209,
 // track_modules/blocks.py:90-236, track_modules/modules.py:133-204.
 // Token streams are kept in (b, n, s) row order (the update-former's native order): all point tokens
 // [B, N, S] first, then all virtual tokens [B, V, S], so that every stage of the update-former is ONE set of
 // launches for the whole batch; the space attention reads them through strides (two-level batch (b, s))
 // instead of permuting them.
+#include <math.h>
 
-#if TRACK_PART == 1
+#include "env.h"
+#include "kernels.h"
+#include "track_kernels.h"
+#include "vggt_model.h"
 
-struct MhaW {           // AttnBlock / CrossAttnBlock (modules.py:133-204)
-    LNw n1, n2, nctx;
-    Lin in_proj;        // self: [3H, H]
-    Lin q_proj, kv_proj;  // cross: rows [0:H] and [H:3H] of in_proj_weight
-    Lin out_proj, fc1, fc2;
-    bool cross = false;
-};
-struct TrackW {
-    float* qrt = nullptr;    // query_ref_token [2, 3L+4]
-    float* virt = nullptr;   // virual_tracks [V, Hh]
-    Lin corr_fc1, corr_fc2, input_transform, flow_head, ffeat_updater, vis, conf;
-    LNw input_norm, output_norm, fmap_norm, ffeat_norm;
-    std::vector<MhaW> time, space_virtual, p2v, v2p;
-};
-
-#elif TRACK_PART == 2
+namespace skimi {
+namespace vggt {
 
 // MFMA mode of the track head's contractions.  The reference runs the track head INSIDE its bf16 autocast region
 // (models/vggt.py:85-91, unlike the camera / depth / point heads of vggt.py:65): under the 16-bit aggregator modes
@@ -36,7 +25,7 @@ static int track_prec(const skimi_vggt_config& cfg) {
     return cfg.prec == SKIMI_PREC_F16 ? SKIMI_PREC_F16 : SKIMI_PREC_BF16;
 }
 
-MhaW pack_mha(Packer& pk, const std::string& p, int H, bool cross) {
+static MhaW pack_mha(Packer& pk, const std::string& p, int H, bool cross) {
     const int X3 = track_prec(pk.h->cfg);
     MhaW w;
     w.cross = cross;
@@ -105,14 +94,12 @@ void pack_track(Packer& pk, skimi_vggt* h) {
     t.conf = pk.linear(K + ".conf_predictor.0", 1, L, X3);
 }
 
-struct MhaBufs { float *xn, *cn, *q, *kv, *ao, *hid; };
-
 // One AttnBlock / CrossAttnBlock.  xq: rq contiguous rows of Hh (in/out).  The attention sees
 // `outer` x `batch` sequences; token t of sequence (go, bi) sits at row
 // go*q_outer_rows + bi*q_batch_rows + t*q_tok_rows  of the q stream (and likewise k_* in the context stream).
-void run_mha(Ctx& c, const MhaW& w, float* xq, long rq, const float* ctx, long rk, int batch, int seq_q, int seq_k,
-             long q_tok_rows, long q_batch_rows, long k_tok_rows, long k_batch_rows, int heads, int Hh, const MhaBufs& b,
-             const float* resid2, int outer = 1, long q_outer_rows = 0, long k_outer_rows = 0) {
+static void run_mha(Ctx& c, const MhaW& w, float* xq, long rq, const float* ctx, long rk, int batch, int seq_q, int seq_k,
+                    long q_tok_rows, long q_batch_rows, long k_tok_rows, long k_batch_rows, int heads, int Hh, const MhaBufs& b,
+                    const float* resid2, int outer = 1, long q_outer_rows = 0, long k_outer_rows = 0) {
     const int hd = Hh / heads;
     // x = norm1(x): the block's residual is taken from the NORMED tensor (modules.py:160-168)
     c.ln(xq, nullptr, Hh, rq, Hh, w.n1, 1e-5f, b.xn, SKIMI_F32);
@@ -142,7 +129,7 @@ void run_mha(Ctx& c, const MhaW& w, float* xq, long rq, const float* ctx, long r
         a.k_row = a.v_row = k_tok_rows * 2 * Hh; a.k_batch = a.v_batch = k_batch_rows * 2 * Hh;
         a.k_batch2 = a.v_batch2 = k_outer_rows * 2 * Hh;
     }
-    if (!c.rc && !c.dry()) c.rc = attention_f32_launch(a, c.st);
+    c.run([&] { return attention_f32_launch(a, c.st); });
     {
         auto d = c.desc(w.out_proj, b.ao, SKIMI_F32, Hh, (int)rq, xq, SKIMI_F32, Hh);
         d.resid = b.xn; d.ldr = Hh;
@@ -193,7 +180,7 @@ void run_track(Ctx& c, float* const* sf, float* const* sg, int B, int S, int P, 
             return;
         }
         pyr[l] = (float*)c.ar.alloc((size_t)F * lh[l] * lw[l] * L * 4);
-        if (!c.rc && !c.dry()) c.rc = avgpool2_launch(pyr[l - 1], pyr[l], F, lh[l - 1], lw[l - 1], L, c.st);
+        c.run([&] { return avgpool2_launch(pyr[l - 1], pyr[l], F, lh[l - 1], lw[l - 1], L, c.st); });
     }
     const long BN = (long)B * N, rows = BN * S;
     float* coords = (float*)c.ar.alloc((size_t)rows * 2 * 4);
@@ -220,18 +207,18 @@ void run_track(Ctx& c, float* const* sf, float* const* sg, int B, int S, int P, 
     mb.kv = (float*)c.ar.alloc((size_t)R2 * 2 * Hh * 4);
     mb.ao = (float*)c.ar.alloc((size_t)R2 * Hh * 4);
     mb.hid = (float*)c.ar.alloc((size_t)R2 * 4 * Hh * 4);
-    if (!c.rc && !c.dry()) {
-        c.rc = track_init_launch(query, coords, qs, BN, S, stride, c.st);
-        // query features from frame 0 of every batch element (base_track_predictor.py:113-116)
-        if (!c.rc) c.rc = sample_border_launch(pyr[0], (long)S * HH * WW * L, qs, 2, qfeat, B, N, HH, WW, L, c.st);
-        if (!c.rc) c.rc = repeat_rows_launch(qfeat, tfeat, BN, S, L, c.st);
-        if (!c.rc) c.rc = pos_embed_sample_launch(qs, 2, pos, (int)BN, HH, WW, tdim, c.st);
-        if (!c.rc && hipMemsetAsync(fcorr, 0, (size_t)rows * ldc * 4, c.st) != hipSuccess) c.rc = SKIMI_ERR_HIP;
-        if (!c.rc && hipMemsetAsync(xinn, 0, (size_t)rows * ldx * 4, c.st) != hipSuccess) c.rc = SKIMI_ERR_HIP;
-    }
+    c.run([&] { return track_init_launch(query, coords, qs, BN, S, stride, c.st); });
+    // query features from frame 0 of every batch element (base_track_predictor.py:113-116)
+    c.run([&] { return sample_border_launch(pyr[0], (long)S * HH * WW * L, qs, 2, qfeat, B, N, HH, WW, L, c.st); });
+    c.run([&] { return repeat_rows_launch(qfeat, tfeat, BN, S, L, c.st); });
+    c.run([&] { return pos_embed_sample_launch(qs, 2, pos, (int)BN, HH, WW, tdim, c.st); });
+    c.zero(fcorr, (size_t)rows * ldc * 4);
+    c.zero(xinn, (size_t)rows * ldx * 4);
     for (int it = 0; it < cfg.track_iters && !c.rc; ++it) {
-        for (int l = 0; l < levels && !c.rc && !c.dry(); ++l)
-            c.rc = corr_sample_launch(tfeat, pyr[l], coords, fcorr, rows, N, S, lh[l], lw[l], L, r, l, ldc, l * ns, c.st);
+        for (int l = 0; l < levels; ++l)
+            c.run([&] {
+                return corr_sample_launch(tfeat, pyr[l], coords, fcorr, rows, N, S, lh[l], lw[l], L, r, l, ldc, l * ns, c.st);
+            });
         {
             auto d = c.desc(w.corr_fc1, fcorr, SKIMI_F32, ldc, (int)rows, ch, SKIMI_F32, Hh);
             d.act = SKIMI_ACT_GELU;
@@ -239,11 +226,12 @@ void run_track(Ctx& c, float* const* sf, float* const* sg, int B, int S, int P, 
             auto d2 = c.desc(w.corr_fc2, ch, SKIMI_F32, Hh, (int)rows, fc, SKIMI_F32, L);
             c.gemm(d2);
         }
-        if (!c.rc && !c.dry()) c.rc = track_input_launch(coords, fc, tfeat, pos, w.qrt, xin, rows, S, L, ldx, max_scale, c.st);
+        c.run([&] { return track_input_launch(coords, fc, tfeat, pos, w.qrt, xin, rows, S, L, ldx, max_scale, c.st); });
         // ---- EfficientUpdateFormer (blocks.py:90-134) ----
-        if (!c.rc && !c.dry())
-            c.rc = layernorm_launch(xin, nullptr, ldx, rows, tdim, w.input_norm.g, w.input_norm.b, 1e-5f, xinn, SKIMI_F32,
+        c.run([&] {   // not c.ln: the output rows keep the padded stride ldx
+            return layernorm_launch(xin, nullptr, ldx, rows, tdim, w.input_norm.g, w.input_norm.b, 1e-5f, xinn, SKIMI_F32,
                                     ldx, c.st);
+        });
         {
             auto d = c.desc(w.input_transform, xinn, SKIMI_F32, ldx, (int)rows, init, SKIMI_F32, Hh);
             c.gemm(d);
@@ -251,8 +239,8 @@ void run_track(Ctx& c, float* const* sf, float* const* sg, int B, int S, int P, 
         }
         float* Pt = X;                                  // [B, N, S, Hh]
         float* Vt = X + rows * Hh;                      // [B, V, S, Hh]
-        for (int b = 0; b < B && !c.rc && !c.dry(); ++b)
-            c.rc = repeat_rows_launch(w.virt, Vt + (long)b * V * S * Hh, V, S, Hh, c.st);
+        for (int b = 0; b < B; ++b)
+            c.run([&] { return repeat_rows_launch(w.virt, Vt + (long)b * V * S * Hh, V, S, Hh, c.st); });
         for (int i = 0; i < cfg.track_depth && !c.rc; ++i) {
             // time attention: every track (points + virtual) attends over its S frames
             run_mha(c, w.time[i], X, R2, nullptr, 0, B * (N + V), S, S, 1, S, 1, S, heads, Hh, mb, nullptr);
@@ -268,17 +256,13 @@ void run_track(Ctx& c, float* const* sf, float* const* sg, int B, int S, int P, 
                     (long)N * S, (long)V * S);
         }
         // output_norm + flow_head on the point tokens (the first B*N*S rows of X)
-        if (!c.rc && !c.dry())
-            c.rc = layernorm_launch(X, nullptr, Hh, rows, Hh, w.output_norm.g, w.output_norm.b, 1e-5f, fin, SKIMI_F32, Hh,
-                                    c.st);
+        c.ln(X, nullptr, Hh, rows, Hh, w.output_norm, 1e-5f, fin, SKIMI_F32);
         {
             auto d = c.desc(w.flow_head, fin, SKIMI_F32, Hh, (int)rows, delta, SKIMI_F32, L + 2);
             c.gemm(d);
         }
         // track_feats = ffeat_updater(ffeat_norm(delta_feats)) + track_feats (base_track_predictor.py:176-180)
-        if (!c.rc && !c.dry())
-            c.rc = layernorm_launch(delta + 2, nullptr, L + 2, rows, L, w.ffeat_norm.g, w.ffeat_norm.b, 1e-5f, gn, SKIMI_F32, L,
-                                    c.st);
+        c.ln(delta + 2, nullptr, L + 2, rows, L, w.ffeat_norm, 1e-5f, gn, SKIMI_F32);
         {
             auto d = c.desc(w.ffeat_updater, gn, SKIMI_F32, L, (int)rows, tfeat, SKIMI_F32, L);
             d.act = SKIMI_ACT_GELU;
@@ -286,7 +270,7 @@ void run_track(Ctx& c, float* const* sf, float* const* sg, int B, int S, int P, 
             c.gemm(d);
         }
         float* pred = (it == cfg.track_iters - 1) ? out_track : nullptr;
-        if (!c.rc && !c.dry()) c.rc = track_coord_update_launch(coords, delta, L + 2, qs, pred, rows, N, S, stride, c.st);
+        c.run([&] { return track_coord_update_launch(coords, delta, L + 2, qs, pred, rows, N, S, stride, c.st); });
     }
     // visibility / confidence: sigmoid(Linear(track_feats)) (base_track_predictor.py:196-205)
     for (int k = 0; k < 2; ++k) {
@@ -295,9 +279,10 @@ void run_track(Ctx& c, float* const* sf, float* const* sg, int B, int S, int P, 
         auto d = c.desc(k == 0 ? w.vis : w.conf, tfeat, SKIMI_F32, L, (int)rows, sc, SKIMI_F32, 1);
         d.act = SKIMI_ACT_SIGMOID;
         c.gemm(d);
-        if (!c.rc && !c.dry()) c.rc = bns_to_bsn_launch(sc, dst, B, N, S, c.st);
+        c.run([&] { return bns_to_bsn_launch(sc, dst, B, N, S, c.st); });
     }
     c.ar.release(mk);
 }
 
-#endif
+}  // namespace vggt
+}  // namespace skimi

@@ -1,4 +1,4 @@
-"""GPU: attention as the VGGT block forward launches it (vggt.hip: skimi_qknorm_rope_scaled + skimi_attention_ex),
+"""GPU: attention as the VGGT block forward launches it (vggt_block.hip: skimi_qknorm_rope_scaled + skimi_attention_ex),
 not only as skimi_attention does -- the parity mode's bf16x3 kernel (hi + lo operands, three MFMAs per product) with
 its scratch rule and its bf16x3 record output, and the prescaled-q chain of the bf16 / fp16 / fp8 modes (qk-norm folds
 1/sqrt(64) * log2(e) into q before q's one rounding, the attention kernel then skips its own scale fold).

@@ -35,7 +35,7 @@ def _reference(x, wT, bT, wrn, s):
 
 
 def _unfolded(x, wT, bT, wrn, s, act):
-    """the launches of SKIMI_DPT_FOLD=0 (Packer::convT + Packer::conv, run_dpt in vggt.hip)"""
+    """the launches of SKIMI_DPT_FOLD=0 (Packer::convT + Packer::conv in vggt_pack.hip, run_dpt in vggt_dpt.hip)"""
     Fr, h, w, C = x.shape
     Co = wrn.shape[0]
     wps = wT.permute(2, 3, 1, 0).reshape(s * s * C, C).contiguous()               # [(a, b, co), ci]

@@ -679,7 +679,7 @@ def test_conv_win_random_data(monkeypatch):
 @gpu
 @pytest.mark.parametrize("dt", ["bf16", "f16"])
 def test_replay_patch_embed(dt, monkeypatch):
-    """vggt.hip patch embed at VGGT-1B size, 8 frames of 518^2: patches of each frame land behind its 5 special
+    """vggt.hip (forward_impl) patch embed at VGGT-1B size, 8 frames of 518^2: patches of each frame land behind its 5 special
     tokens (out_row_off 5, frame stride P = 1374), + the DINO pos_embed broadcast over frames (batch stride 0,
     row offset 1).  K = 3*14*14 padded to 592 (not a multiple of 64): the generic 128x128 kernel, not gemm256."""
     prec, h = (PREC_BF16, torch.bfloat16) if dt == "bf16" else (PREC_F16, torch.float16)
@@ -692,7 +692,7 @@ def test_replay_patch_embed(dt, monkeypatch):
 @gpu
 @pytest.mark.parametrize("mode", ["x3_records", "bf16"])
 def test_replay_dpt_rcu1(mode, monkeypatch):
-    """vggt.hip DPT fusion RCU1 conv2: 3x3 conv feat -> feat, + relu(x) (resid, the mode's activation dtype)
+    """vggt_dpt.hip DPT fusion RCU1 conv2: 3x3 conv feat -> feat, + relu(x) (resid, the mode's activation dtype)
     + prev (resid2) then ReLU; fp32-accurate mode with its records output on the LDS-DMA kernel"""
     conv = dict(N=8, H=74, W=74, C=256, KH=3, KW=3, stride=1, pad=1)   # 43808 rows: 172 tiles of 256
     if mode == "x3_records":
@@ -717,18 +717,18 @@ def test_replay_vp3d_block(route, monkeypatch):
 
 @gpu
 def test_replay_track_fc2(monkeypatch):
-    """track_impl.inc transformer fc2: + x (resid) + the other stream's tokens (resid2), hidden 384"""
+    """vggt_track.hip transformer fc2: + x (resid) + the other stream's tokens (resid2), hidden 384"""
     run_case(monkeypatch, M=8 * 256, N=384, K=4 * 384, bias=True, resid=torch.float32, resid2=True,
              expect=dict(family="generic"))
 
 
 @gpu
 def test_replay_track_vis_conf(monkeypatch):
-    """track_impl.inc visibility / confidence: sigmoid(Linear(128 -> 1)) over B*N*S rows"""
+    """vggt_track.hip visibility / confidence: sigmoid(Linear(128 -> 1)) over B*N*S rows"""
     run_case(monkeypatch, M=2 * 256 * 8, N=1, K=128, bias=True, act=ACT_SIGMOID, expect=dict(family="generic"))
 
 
 @gpu
 def test_replay_camera_embed_pose(monkeypatch):
-    """vggt.hip camera head: poseLN_modulation embed, SiLU(Linear(16 -> 2048)) of 8 frames' pose codes"""
+    """vggt_camera.hip camera head: poseLN_modulation embed, SiLU(Linear(16 -> 2048)) of 8 frames' pose codes"""
     run_case(monkeypatch, M=8, N=2048, K=16, bias=True, act=ACT_SILU, expect=dict(family="generic", tile="64x64"))

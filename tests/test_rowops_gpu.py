@@ -215,7 +215,7 @@ def test_layernorm_gather(rows, C, family):
 
 @pytest.mark.parametrize("family", R.LN_FAMILIES)
 def test_layernorm_gather_concat_records(family):
-    """the launch of the DPT heads in parity mode (vggt.hip): gather + [frame | global] concat + records, C = 512"""
+    """the launch of the DPT heads in parity mode (vggt_dpt.hip): gather + [frame | global] concat + records, C = 512"""
     xa, xb = _dpt_rows(256, family), _dpt_rows(256, family) * np.float32(0.5) + np.float32(0.75)
     for rows in (18, 14):
         _ln("ln gather+concat records", xa, x2=xb, rows=rows, grp=(6, 11, 5), out="records")
@@ -334,7 +334,7 @@ def _randn(seed, *shape):
 
 
 def test_attention_track_time():
-    """run_mha's time attention: packed rows of 3 Hh, batch B (N + V), sequence S"""
+    """run_mha's (vggt_track.hip) time attention: packed rows of 3 Hh, batch B (N + V), sequence S"""
     rows = B_ * (N_ + V_) * S_
     x = _randn(61, rows * 3 * Hh)
     s = (3 * Hh, HD48, S_ * 3 * Hh, 0)
