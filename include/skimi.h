@@ -1267,6 +1267,53 @@ int skimi_calibrate_camera(const double* obj, const double* img, const uint8_t* 
                            double* cost0, double* cost, double* std, int32_t* n_evals, int32_t* n_views, int32_t* n_corners,
                            int32_t* success, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- chessboard corners from whole frames: candidates and sub-pixel refinement (csrc/chessboard.hip) ----
+ * camera_calibration/main.py:80-90 (find_chessboard_corners = cv2.findChessboardCorners + cv2.cornerSubPix), under the
+ * project's own rules: OpenCV's quad-based detector (adaptive threshold, fast_check, its board-orientation heuristic) is
+ * not restated.  frames [N, H, W, ch] u8 (dev), ch 1, 3 or 4, the layout of skimi_undistort_u8 with C F = N; 1 <= N <= 65535,
+ * sides 1 .. SKIMI_LENS_MAX_SIDE, H W <= SKIMI_CHESS_MAX_PIXELS.  Integer stages are exact, the only atomics are integer
+ * (order-independent), no host synchronisation, no allocation: results are bitwise reproducible and a frame's results are
+ * the same bits alone and inside a batch.  The frames are only read.  Bad arguments: SKIMI_ERR_ARG before any launch.
+ * Rules (DESIGN §2 "Chessboard corners"; tests/chessboard_restated.py):
+ *  1. Gray.  ch 1: the byte.  ch 3 or 4: the channels in the order given are taken as B, G, R (the reference reads its
+ *     frames with cv2), gray = (3735 B + 19235 G + 9798 R + 16384) >> 15; a fourth channel is ignored.
+ *  2. Blur.  b = [1 2 1]^T [1 2 1] * gray, unnormalised (16 x the mean), int32.
+ *  3. Response (ChESS, Bennett & Lasenby).  Ring offsets (dx, dy) = (rint(5 cos(k pi / 8)), rint(5 sin(k pi / 8))), k = 0 .. 15:
+ *     (5,0) (5,2) (4,4) (2,5) (0,5) (-2,5) (-4,4) (-5,2) (-5,0) (-5,-2) (-4,-4) (-2,-5) (0,-5) (2,-5) (4,-4) (5,-2); I_k = b
+ *     there.  SR = sum_{n<4} |I_n + I_{n+8} - I_{n+4} - I_{n+12}|, DR = sum_{n<8} |I_n - I_{n+8}|, MR = |5 sum_k I_k - 16 (b(0,0) +
+ *     b(-1,0) + b(1,0) + b(0,-1) + b(0,1))|, R = 5 (SR - DR) - MR in int32.  R = 0 where x < 6, x >= W - 6, y < 6 or y >= H - 6.
+ *     rmax [N] = the frame's maximum of R (>= 0: the border is part of the frame).
+ *  4. Candidates.  A pixel is one iff R > 0, 256 R > threshold rmax in int64 (threshold in 1/256 units, 0 .. 256) and R is the
+ *     maximum of its (2 nms_radius + 1)^2 window clipped to the frame (0 <= nms_radius <= SKIMI_CHESS_MAX_NMS): R > R' for
+ *     every earlier pixel of the window in raster order, R >= R' for every later one.  A frame's candidates are written in
+ *     ascending pixel order: xy [N, M, 2] i32 = (x, y), response [N, M] i32 = R, the first M = max_candidates of them; the
+ *     rows behind them are (-1, -1) and 0.  count [N] i32 is the uncapped number.
+ *  5. skimi_corner_subpix = cv2.cornerSubPix's iteration in float64 on any points [N, M, 2] f64 (dev) of those frames ->
+ *     out [N, M, 2] f64, ok [N, M] u8.  count [N] i32 (dev, or NULL): only the first count[f] points of frame f are refined.
+ *     Half window (wx, wy), 1 .. SKIMI_SUBPIX_MAX_WIN each; mask m(i, j) = exp(-((j - wx) / wx)^2) exp(-((i - wy) / wy)^2) for
+ *     0 <= j <= 2 wx, 0 <= i <= 2 wy.  A round at (x, y): a = x - floor(x), b = y - floor(y); the patch p(r, c), 0 <= r < 2 wy + 3,
+ *     0 <= c < 2 wx + 3, is the gray value (rule 1) at (floor(x) - wx - 1 + c + a, floor(y) - wy - 1 + r + b) = (1 - b) ((1 - a) g00
+ *     + a g01) + b ((1 - a) g10 + a g11) with pixel coordinates clamped to the frame (replicated border); gx = p(i + 1, j + 2) -
+ *     p(i + 1, j), gy = p(i + 2, j + 1) - p(i, j + 1) (no 1/2); gxx = (gx gx) m, gxy = (gx gy) m, gyy = (gy gy) m; A = sum gxx,
+ *     B = sum gxy, C = sum gyy, bb1 = sum (gxx (j - wx) + gxy (i - wy)), bb2 = sum (gxy (j - wx) + gyy (i - wy)); lane l of the
+ *     point's wave adds the window elements l, l + 64, .. (row-major) in order, then reduce.h's wave_sum.  det = A C - B B; zero
+ *     or non-finite: the point stays where it is for good.  Else x += (C bb1 - B bb2) / det, y += (A bb2 - B bb1) / det; a point
+ *     that is then not in [0, W) x [0, H) (a NaN fails) stops there, as cv2 stops.  Exactly `iters` rounds (0 ..
+ *     SKIMI_SUBPIX_MAX_ITERS) and no epsilon stop, unlike cv2: an early stop would make two evaluations of the rule differ by a
+ *     round near the threshold.  ok = the point was refined (inside its count, start finite and in [0, W) x [0, H)) and ended
+ *     within (wx, wy) of its start, |dx| <= wx and |dy| <= wy; otherwise out = the start, as cv2 reverts it, and ok = 0.
+ * Ordering the candidates into a board is host work on small arrays: calibration.order_chessboard. */
+#define SKIMI_CHESS_MAX_PIXELS (1 << 28)
+#define SKIMI_CHESS_MAX_NMS 15
+#define SKIMI_SUBPIX_MAX_WIN 15
+#define SKIMI_SUBPIX_MAX_ITERS 1000
+size_t skimi_chess_workspace_bytes(int64_t N, int32_t H, int32_t W);
+int skimi_chess_candidates(const uint8_t* frames, int64_t N, int32_t H, int32_t W, int32_t ch, int32_t threshold, int32_t nms_radius,
+                           int32_t max_candidates, int32_t* xy, int32_t* response, int32_t* count, int32_t* rmax, void* ws,
+                           size_t ws_bytes, void* stream);
+int skimi_corner_subpix(const uint8_t* frames, int64_t N, int32_t H, int32_t W, int32_t ch, const double* points, const int32_t* count,
+                        int32_t M, int32_t win_x, int32_t win_y, int32_t iters, double* out, uint8_t* ok, void* stream);
+
 /* ---- VGGT head and track-head helper kernels, one launch each ----
  * The kernels skimi_vggt_forward runs between its GEMMs, exposed singly so that each can be tested against a float64
  * restatement.  All maps are channels-last and dense; dtype / out_dtype are SKIMI_F32, SKIMI_BF16 or SKIMI_F16.  Every

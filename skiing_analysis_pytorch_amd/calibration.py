@@ -4,9 +4,13 @@ device solver and the device lens model.
 The solver (cv2.calibrateCamera in the reference) is `geometry.calibrate_camera` on the device: Zhang's start and a
 Levenberg-Marquardt over the intrinsics and every board's pose, many view subsets in one call.  This module is the rest of
 the reference's script without its pictures and files: the object points, the prune step, the reprojection and coverage
-statistics, and the leave-one-out spread that a batch makes cheap.  Corners arrive as arrays: detecting them
-(findChessboardCorners / cornerSubPix), sampling videos, getOptimalNewCameraMatrix / valid_roi_fraction and stereo
-calibration are outside this build.  `formats.save_calibration` / `formats.load_calibration` write and read the files.
+statistics, and the leave-one-out spread that a batch makes cheap.  Corners arrive as arrays, or are found in the frames:
+`find_chessboard_corners` (the reference's findChessboardCorners + cornerSubPix step) runs `geometry.chessboard_candidates` and
+`geometry.corner_subpix` on the device for all frames and orders each frame's points into the board with `order_chessboard`,
+and `calibrate_from_frames` is the reference's flow from the pictures on.  The detector follows the project's own rules
+(DESIGN §2 "Chessboard corners"), not OpenCV's quad-based one.  Sampling videos, reading pictures, getOptimalNewCameraMatrix /
+valid_roi_fraction and stereo calibration are outside this build.  `formats.save_calibration` / `formats.load_calibration`
+write and read the files.
 Host module: small arrays, NumPy; the heavy steps run on the device.
 """
 from __future__ import annotations
@@ -226,6 +230,177 @@ def calibrate_camera(corners, cfg: CalibConfig, image_size: Optional[Tuple[int, 
             **line_straightness(img[used & np.isfinite(img).all(axis=(1, 2))], cfg.board_size, K, dist, undistort=undistort),
             "rvecs": r["rvec"][0][used], "tvecs": r["t"][0][used], "per_image": per_img, "std_intrinsics": r["std"][0],
             "rms_before_prune": rms_first, "n_evals": int(r["n_evals"][0]), "converged": bool(r["success"][0])}
+
+
+# ---- chessboard corners from frames: the device detector's candidates ordered into a board (DESIGN §2 "Chessboard corners") ----
+_GRID_STEPS = ((1, 0), (-1, 0), (0, 1), (0, -1))
+
+
+def _grow_grid(pts: np.ndarray, D: np.ndarray, seed: int, limit: int) -> Optional[dict]:
+    """rule 6's growth from one seed -> {(i, j): point index}, or None when the seed has no two usable first steps or the grid
+    outgrows `limit` cells a side"""
+    j1 = int(np.argmin(D[seed]))
+    l1 = D[seed, j1]
+    if not np.isfinite(l1) or l1 <= 0:
+        return None
+    e1 = pts[j1] - pts[seed]
+    j2 = None
+    for j in np.argsort(D[seed], kind="stable"):
+        lj = D[seed, j]
+        if not np.isfinite(lj) or lj > 2.0 * l1:
+            break
+        if j == j1 or lj < 0.5 * l1:
+            continue
+        if abs(float(np.dot(pts[j] - pts[seed], e1))) / (lj * l1) < 0.6:
+            j2 = int(j)
+            break
+    if j2 is None:
+        return None
+    cells = {(0, 0): seed, (1, 0): j1, (0, 1): j2}
+    free = np.ones(len(pts), bool)
+    free[[seed, j1, j2]] = False
+    queue = [(0, 0), (1, 0), (0, 1)]
+    head = 0
+    while head < len(queue):                      # breadth-first; a filled cell sends its filled neighbours round again
+        c = queue[head]
+        head += 1
+        P = pts[cells[c]]
+        for d in _GRID_STEPS:
+            t = (c[0] + d[0], c[1] + d[1])
+            if t in cells:
+                continue
+            back = (c[0] - d[0], c[1] - d[1])
+            step = None
+            if back in cells:
+                step = P - pts[cells[back]]
+            else:                                 # no cell behind: the parallel edge of an adjacent row
+                for e in ((d[1], d[0]), (-d[1], -d[0])):
+                    a, b = (c[0] + e[0], c[1] + e[1]), (t[0] + e[0], t[1] + e[1])
+                    if a in cells and b in cells:
+                        step = pts[cells[b]] - pts[cells[a]]
+                        break
+            if step is None:
+                continue
+            dist = np.hypot(*(pts - (P + step)).T)
+            dist[~free] = np.inf
+            k = int(np.argmin(dist))
+            if not dist[k] <= 0.35 * float(np.hypot(*step)):
+                continue
+            cells[t] = k
+            free[k] = False
+            ii, jj = [q[0] for q in cells], [q[1] for q in cells]
+            if max(ii) - min(ii) >= limit or max(jj) - min(jj) >= limit:
+                return None
+            queue.append(t)
+            queue.extend(q for q in ((t[0] + s[0], t[1] + s[1]) for s in _GRID_STEPS) if q in cells)
+    return cells
+
+
+def _normalise_grid(pts: np.ndarray, cells: dict, cols: int, rows: int) -> Optional[np.ndarray]:
+    """a grown grid -> [rows, cols, 2] under rule 6's normalisation, or None unless it is complete and exactly the board"""
+    i0, j0 = min(q[0] for q in cells), min(q[1] for q in cells)
+    ni, nj = max(q[0] for q in cells) - i0 + 1, max(q[1] for q in cells) - j0 + 1
+    if len(cells) != cols * rows or ni * nj != len(cells):
+        return None
+    if (ni, nj) == (cols, rows):
+        arr = np.array([[pts[cells[(i0 + c, j0 + r)]] for c in range(cols)] for r in range(rows)])
+    elif (ni, nj) == (rows, cols):
+        arr = np.array([[pts[cells[(i0 + r, j0 + c)]] for c in range(cols)] for r in range(rows)])
+    else:
+        return None
+    col, row = arr[0, 1] - arr[0, 0], arr[1, 0] - arr[0, 0]
+    if col[0] * row[1] - col[1] * row[0] <= 0:    # a mirrored board: the columns run the other way
+        arr = arr[:, ::-1]
+    other = arr[::-1, ::-1]                       # the same board turned by 180 degrees
+    if (other[0, 0, 1], other[0, 0, 0]) < (arr[0, 0, 1], arr[0, 0, 0]):
+        arr = other
+    return np.ascontiguousarray(arr)
+
+
+def order_chessboard(points, board_size: Tuple[int, int], strength=None) -> Optional[np.ndarray]:
+    """The refined candidates of one frame -> the board's corners [cols * rows, 2], row-major like prepare_object_points, or
+    None.  points [m, 2] pixels (non-finite rows are skipped), board_size = (cols, rows) with both >= 2, strength [m]
+    (default: the input order, strongest first).  A point within 1 px of a stronger one is dropped.  Seeds are tried in
+    descending strength: the first step goes to the seed's nearest neighbour, the second to the nearest neighbour whose
+    length is within [0.5, 2] x the first and whose |cos| against it is < 0.6; the grid then grows breadth-first, a cell
+    predicted as 2 P - P_back (or P + the parallel edge of the adjacent row when there is no cell behind) taking the
+    nearest unused point within 0.35 x the predicted step.  A grid is accepted only if it is complete and exactly cols x
+    rows (or its transpose): distractors beside the board are left out, a missing corner or a point that continues the
+    grid gives None.  The columns run along `cols`, cross(column step, row step) > 0 in image coordinates (no mirrored
+    board), and of the two remaining boards, 180 degrees apart, the first corner is the one with the smaller (y, x)."""
+    cols, rows = (int(v) for v in board_size)
+    if cols < 2 or rows < 2:
+        raise ValueError(f"order_chessboard: the board needs at least 2 x 2 inner corners, got {cols} x {rows}")
+    pts = np.asarray(points, np.float64).reshape(-1, 2)
+    s = -np.arange(len(pts), dtype=np.float64) if strength is None else np.asarray(strength, np.float64).reshape(-1)
+    if len(s) != len(pts):
+        raise ValueError(f"order_chessboard: {len(s)} strengths for {len(pts)} points")
+    good = np.isfinite(pts).all(axis=1) & ~np.isnan(s)
+    pts, s = pts[good], s[good]
+    pts = pts[np.argsort(-s, kind="stable")]
+    keep = []
+    for i, p in enumerate(pts):
+        if not keep or np.hypot(*(pts[keep] - p).T).min() > 1.0:
+            keep.append(i)
+    pts = pts[keep]
+    if len(pts) < cols * rows:
+        return None
+    D = np.hypot(pts[:, None, 0] - pts[None, :, 0], pts[:, None, 1] - pts[None, :, 1])
+    np.fill_diagonal(D, np.inf)
+    for seed in range(len(pts)):
+        cells = _grow_grid(pts, D, seed, max(cols, rows))
+        arr = None if cells is None else _normalise_grid(pts, cells, cols, rows)
+        if arr is not None:
+            return arr.reshape(cols * rows, 2)
+    return None
+
+
+def find_chessboard_corners(frames, board_size: Tuple[int, int], win: Tuple[int, int] = (11, 11), threshold: int = 38,
+                            nms_radius: int = 4, max_candidates: int = 1024, iters: int = 30) -> Tuple[np.ndarray, np.ndarray]:
+    """find_chessboard_corners (main.py:80-90) for every frame at once: frames uint8 [F, H, W, ch] or [C, F, H, W, ch] on the
+    device (colour channels in cv2's B, G, R order) -> corners float64 [..., cols * rows, 2] (NaN rows where no board was
+    found) and found bool [...].  geometry.chessboard_candidates and geometry.corner_subpix run on the device for all frames,
+    one read-back brings the candidates over, order_chessboard orders each frame's on the host.  win is cornerSubPix's half
+    window: the reference's (11, 11) suits boards whose squares are wider than the window; take (5, 5) for small boards."""
+    import torch
+
+    from . import geometry
+    cols, rows = (int(v) for v in board_size)
+    cand = geometry.chessboard_candidates(frames, threshold=threshold, nms_radius=nms_radius, max_candidates=max_candidates)
+    ref = geometry.corner_subpix(frames, cand.xy, cand.count, win=win, iters=iters)
+    lead, M = tuple(cand.count.shape), int(cand.xy.shape[-2])
+    N = int(np.prod(lead, dtype=np.int64))
+    back = torch.cat([ref.points.reshape(N, 2 * M), ref.ok.reshape(N, M).double(), cand.response.reshape(N, M).double(),
+                      cand.count.reshape(N, 1).double()], dim=1).cpu().numpy()           # the one read-back
+    pts, ok, resp, count = back[:, :2 * M].reshape(N, M, 2), back[:, 2 * M:3 * M] != 0, back[:, 3 * M:4 * M], back[:, 4 * M]
+    corners, found = np.full((N, cols * rows, 2), np.nan), np.zeros(N, bool)
+    for f in range(N):
+        sel = ok[f] & (np.arange(M) < count[f])
+        board = order_chessboard(pts[f][sel], (cols, rows), strength=resp[f][sel])
+        if board is not None:
+            corners[f], found[f] = board, True
+    return corners.reshape(lead + (cols * rows, 2)), found.reshape(lead)
+
+
+def calibrate_from_frames(frames, cfg: CalibConfig, names: Optional[Sequence[str]] = None, win: Tuple[int, int] = (11, 11),
+                          undistort: Optional[Callable] = None) -> dict:
+    """calibrate_camera (main.py:250-323) from the pictures themselves: frames uint8 [F, H, W, ch] (or [C, F, H, W, ch], taken as
+    C F pictures of one camera) on the device; names: one per frame (default view_0000 ..).  The boards are detected
+    (find_chessboard_corners), frames without one are dropped, and calibrate_camera runs on the rest with the frames' own
+    (width, height) -> its result plus num_detected; used_names are the names of the frames that went into the result.  No
+    board in any frame: the reference's {"status": "Failed", "reason": "No corners detected", "num_images": 0}."""
+    corners, found = find_chessboard_corners(frames, cfg.board_size, win=win)
+    corners, found = corners.reshape(-1, corners.shape[-2], 2), found.reshape(-1)
+    names = [f"view_{i:04d}" for i in range(len(found))] if names is None else list(names)
+    if len(names) != len(found):
+        raise ValueError(f"{len(names)} names for {len(found)} frames")
+    if not found.any():
+        return {"status": "Failed", "reason": "No corners detected", "num_images": 0}
+    size = (int(frames.shape[-2]), int(frames.shape[-3]))
+    result = calibrate_camera(corners[found], cfg, image_size=size, names=[names[i] for i in np.flatnonzero(found)],
+                              undistort=undistort)
+    result["num_detected"] = int(found.sum())
+    return result
 
 
 def leave_one_out(corners, cfg: CalibConfig, image_size: Optional[Tuple[int, int]] = None) -> dict:

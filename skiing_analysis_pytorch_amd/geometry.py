@@ -38,6 +38,8 @@ from .device.lens import (LENS_MAX_CAMERAS, LENS_MAX_ITERS, LENS_COEFF_COUNTS, U
 from .device.bev import (HOMOGRAPHY_STAT_FIELDS, TRACK_FIELDS, HomographyResult, BevSkeletonResult, GroundTrackResult,
                          homography_fit, homography_points, bev_skeleton, ground_track)
 from .device.calibrate import (CALIB_PARAMS, CalibrationResult, calib_free_mask, calibrate_camera)
+from .device.chessboard import (CHESS_MAX_NMS, SUBPIX_MAX_WIN, SUBPIX_MAX_ITERS, ChessCandidates, SubpixResult,
+                                chessboard_candidates, corner_subpix)
 from .device.lens import _undistorted_f32
 
 # ---- host helpers of the wrapper (small arrays, NumPy as in the reference) -----------------
