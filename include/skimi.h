@@ -1314,6 +1314,68 @@ int skimi_chess_candidates(const uint8_t* frames, int64_t N, int32_t H, int32_t 
 int skimi_corner_subpix(const uint8_t* frames, int64_t N, int32_t H, int32_t W, int32_t ch, const double* points, const int32_t* count,
                         int32_t M, int32_t win_x, int32_t win_y, int32_t iters, double* out, uint8_t* ok, void* stream);
 
+/* ---- ORB-style image features and Hamming matching (csrc/features.hip) ----
+ * triangulation/camera_position/camera_position.py:181-226 (estimate_camera_pose_from_ORB = cv2.ORB_create +
+ * cv2.BFMatcher(NORM_HAMMING, crossCheck)), under the project's own rules: OpenCV's keypoints, its learned BRIEF pattern and
+ * its float orientation are not restated.  frames [N, H, W, ch] u8 (dev) as skimi_chess_candidates takes them.  Every stage is
+ * integer arithmetic, the only atomics are integer, no host synchronisation, no allocation: results are bitwise reproducible
+ * and a frame's (a set pair's) results are the same bits alone and inside a batch.  Bad arguments: SKIMI_ERR_ARG before any
+ * launch.  Rules (DESIGN §2 "Image features"; tests/features_restated.py):
+ *  1. Pyramid.  Level 0 = gray (rule 1 of the chessboard block).  L = levels, 1 .. SKIMI_ORB_MAX_LEVELS; level l has W_l =
+ *     (2 W 5^l + 6^l) / (2 6^l), H_l likewise (integer division).  Level l from the unblurred level l - 1, per axis: n =
+ *     (2 x + 1) W_{l-1} - W_l, den = 2 W_l, x0 = floor(n / den), a = ((n - x0 den) 256) / den, x0 and x0 + 1 clamped to the source;
+ *     value = ((256 - ay) ((256 - ax) p00 + ax p01) + ay ((256 - ax) p10 + ax p11) + 2^15) >> 16.  Each level's blur: [1 4 6 4 1]^T
+ *     [1 4 6 4 1] with replicated borders, (v + 128) >> 8.
+ *  2. FAST score on the unblurred level.  Ring (dx, dy), k = 0 .. 15: (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3)
+ *     (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3); d_k = ring_k - p.  s = max over the 16 arcs of 9 contiguous ring
+ *     pixels of max(min_arc d, min_arc -d), 0 where that is negative and outside the candidate region: SKIMI_ORB_BORDER <= x <
+ *     W_l - SKIMI_ORB_BORDER, the same for y.  A corner has s > threshold (0 .. 254).
+ *  3. Keypoint candidates: corners whose s is the maximum of the 3 x 3 window, s > s' for the earlier pixels in raster order
+ *     and s >= s' for the later ones; with roi [N, 4] f64 (x1, y1, x2, y2; or NULL) only those with x1 <= X < x2 and y1 <= Y < y2
+ *     for the level-0 position (X, Y) of rule 7 (a NaN in the box fails).  level_count [N, L] = their number, uncapped.
+ *  4. Harris on the unblurred level: Sobel Ix = (p(x+1,y-1) + 2 p(x+1,y) + p(x+1,y+1)) - (the same at x-1), Iy likewise; a, b, c
+ *     = sum Ix^2, sum Iy^2, sum Ix Iy over the 7 x 7 block; h = 25 (a b - c^2) - (a + b)^2 in int64.
+ *  5. Quota: w_l = 5^l 6^(L-1-l), q_l = floor(M w_l / sum w) for l >= 1, q_0 = M - sum of the others (M = max_features, 1 ..
+ *     SKIMI_ORB_MAX_FEATURES).  Level l keeps its min(level_count, q_l) candidates of largest h, ties to the smaller pixel
+ *     index.  Rows: levels in order, pixel order inside a level; count [N] = the kept number; the rows behind it hold -1 in
+ *     xy_level, xy, level, direction and 0 in score, harris, desc.
+ *  6. Orientation on the unblurred level: m10 = sum u I, m01 = sum v I over u^2 + v^2 <= 225; direction = the k in 0 .. 31 with
+ *     the largest m10 C[k] + m01 S[k] (int64), ties to the smaller k; C = SKIMI_ORB_COS, S[k] = C[(k + 24) % 32].
+ *  7. Descriptor, 256 bits: bit i = blur(p + a_i^k) < blur(p + b_i^k), in word i / 32 at position i % 32 of desc [N, M, 8] i32.
+ *     pattern [32, 256, 4] i8 (dev) = (ax, ay, bx, by) for every direction: the base pattern is drawn with rule 3's splitmix64
+ *     from s = SKIMI_ORB_PATTERN_SEED (no output discarded): four outputs give ax, ay, bx, by = (output mod 27) - 13; the draw
+ *     is rejected unless ax^2 + ay^2 <= 169, bx^2 + by^2 <= 169, a != b and (a, b) was not drawn before; direction k holds
+ *     ((x C[k] - y S[k] + 8192) >> 14, (x S[k] + y C[k] + 8192) >> 14) of both points.  The caller builds and uploads it.
+ *     Outputs per row: xy_level [N, M, 2] i32; xy [N, M, 2] f64 = ((x + 0.5) W) / W_l - 0.5 (y with H); level, direction, score
+ *     [N, M] i32; harris [N, M] i64.
+ *  8. skimi_match_hamming: B pairs of descriptor sets d1 [B, M1, 8], d2 [B, M2, 8] i32 with n1, n2 [B] i32 (dev; clamped to 0
+ *     .. M), M1, M2 <= SKIMI_ORB_MAX_FEATURES.  distance = popcount of the xor; for query i the nearest train j (ties: smaller
+ *     j) and the second-nearest; for train j the nearest query (ties: smaller i).  Query i is kept iff n2 >= 1 and (cross_check
+ *     == 0 or j's nearest query is i) and (ratio < 0 or (n2 >= 2 and (double)d_best < ratio (double)d_second)) and
+ *     (max_distance < 0 or d_best <= max_distance).  The kept (i, j) ordered by (distance, i) (a stable counting sort); the
+ *     first max_matches (1 .. SKIMI_ORB_MAX_FEATURES) go to pairs [B, max_matches, 2], dist [B, max_matches]; the rows behind
+ *     hold -1; count [B] = the rows written. */
+#define SKIMI_ORB_MAX_LEVELS 8
+#define SKIMI_ORB_MAX_FEATURES 4096
+#define SKIMI_ORB_BORDER 16
+#define SKIMI_ORB_PATTERN_SEED 0x534B494D494F5242ULL
+/* round(2^14 cos(2 pi k / 32)), k = 0 .. 31 */
+#define SKIMI_ORB_COS                                                                                                          \
+    {16384, 16069, 15137, 13623, 11585, 9102, 6270, 3196, 0, -3196, -6270, -9102, -11585, -13623, -15137, -16069, -16384, -16069, \
+     -15137, -13623, -11585, -9102, -6270, -3196, 0, 3196, 6270, 9102, 11585, 13623, 15137, 16069}
+/* round(2^14 sin(2 pi k / 32)), k = 0 .. 31 */
+#define SKIMI_ORB_SIN                                                                                                          \
+    {0, 3196, 6270, 9102, 11585, 13623, 15137, 16069, 16384, 16069, 15137, 13623, 11585, 9102, 6270, 3196, 0, -3196, -6270, -9102, \
+     -11585, -13623, -15137, -16069, -16384, -16069, -15137, -13623, -11585, -9102, -6270, -3196}
+size_t skimi_orb_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t levels);
+int skimi_orb_features(const uint8_t* frames, int64_t N, int32_t H, int32_t W, int32_t ch, int32_t levels, int32_t threshold,
+                       int32_t max_features, const double* roi, const int8_t* pattern, int32_t* xy_level, double* xy,
+                       int32_t* level, int32_t* direction, int32_t* score, int64_t* harris, int32_t* desc, int32_t* count,
+                       int32_t* level_count, void* ws, size_t ws_bytes, void* stream);
+int skimi_match_hamming(const int32_t* d1, const int32_t* n1, int32_t M1, const int32_t* d2, const int32_t* n2, int32_t M2,
+                        int64_t B, int32_t cross_check, double ratio, int32_t max_distance, int32_t max_matches, int32_t* pairs,
+                        int32_t* dist, int32_t* count, void* stream);
+
 /* ---- VGGT head and track-head helper kernels, one launch each ----
  * The kernels skimi_vggt_forward runs between its GEMMs, exposed singly so that each can be tested against a float64
  * restatement.  All maps are channels-last and dense; dtype / out_dtype are SKIMI_F32, SKIMI_BF16 or SKIMI_F16.  Every

@@ -1,12 +1,16 @@
-"""Counterpart of triangulation/camera_position/camera_position.py's keypoint path with the reference's signature:
+"""Counterpart of triangulation/camera_position/camera_position.py's keypoint and ORB paths with the reference's signatures:
 
     estimate_camera_pose_from_kpt(pts1, pts2, K, baseline_m) -> (R, T (3, 1), mask_pose)        (camera_position.py:88-117)
+    estimate_camera_pose_from_ORB(img1, img2, K, baseline_m, max_matches=1000) -> (R, T (3, 1), pose_mask)     (:181-226)
 
 cv2.findEssentialMat(RANSAC, prob 0.999, threshold 1.0) + cv2.recoverPose there; geometry.essential_ransac on the device
 here (DESIGN §2 "Essential matrix": 1024 five-point hypotheses, all scored, no early termination).  The reference's callers
 (triangulation/view_process/two_view.py, triangulation/estimate_camera_position.py) loop over the frames and call it once
-per frame on the 17 keypoints; `estimate_camera_poses_from_kpts` takes all frames as per-frame groups of one call.  Left
-out: the SIFT / ORB front ends of that module (they need cv2's detectors)."""
+per frame on the 17 keypoints; `estimate_camera_poses_from_kpts` takes all frames as per-frame groups of one call.  The ORB
+path (cv2.ORB_create(3000) + cv2.BFMatcher(NORM_HAMMING, crossCheck=True) there) is geometry.orb_features and
+geometry.match_hamming here, the project's own detector and descriptor and not OpenCV's (DESIGN §2 "Image features");
+`estimate_camera_poses_from_ORB` takes two clips and reads nothing back before the result.  Left out: the SIFT front end
+of that module (it needs cv2's detector)."""
 from __future__ import annotations
 
 import numpy as np
@@ -46,3 +50,60 @@ def estimate_camera_poses_from_kpts(pts1, pts2, K, baseline_m, hypotheses: int =
     r = _run(pts1, pts2, K, baseline_m, J, hypotheses, seed)
     ok = r.success.cpu().numpy()
     return r.R.cpu().numpy(), r.t.cpu().numpy().reshape(T_, 3, 1), r.pose_mask.cpu().numpy().reshape(T_, J), ok
+
+
+def _bgr_u8(img, dev):
+    """to_gray_cv_image's inputs, a frame or a clip of them: float in [0, 1] or uint8, [..., H, W, 3] in R, G, B order (or
+    [..., H, W] gray), host array or tensor -> uint8 device frames [..., H, W, ch] in B, G, R order"""
+    t = (img if isinstance(img, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(img))).to(dev)
+    if t.is_floating_point():
+        t = t.clamp(0, 1).mul(255).to(torch.uint8)      # the reference's .byte(): truncation
+    elif t.dtype != torch.uint8:
+        raise TypeError(f"frames must be floating point in [0, 1] or uint8, got {t.dtype}")
+    if t.shape[-1] != 3:
+        return t[..., None].contiguous()
+    return t.flip(-1).contiguous()
+
+
+def estimate_camera_poses_from_ORB(frames1, frames2, K, baseline_m, max_matches: int = 1000, max_features: int = 3000,
+                                   levels: int = 8, threshold: int = 20, hypotheses: int = 1024, seed: int = 0,
+                                   group_offset: int = 0):
+    """Every frame pair of two clips in one pass on the device: frames1, frames2 (T, H, W, 3) RGB (float in [0, 1] or
+    uint8; or (T, H, W) gray), K (3, 3) shared -> (R (T, 3, 3), T (T, 3, 1), pose_mask (T, max_matches) uint8, success (T,)
+    bool) as host arrays.  Features of both clips, cross-checked Hamming matches by (distance, query), the first
+    max_matches of them gathered into NaN-padded correspondences, one essential_ransac with a group per frame; pose_mask
+    marks the matches (in that order) that are inliers in front of both cameras.  A frame without a pose has NaN in R and T.
+    Frame f is bitwise what estimate_camera_pose_from_ORB gives for it with the same seed and group_offset = f."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    a, b = _bgr_u8(frames1, dev), _bgr_u8(frames2, dev)
+    if a.dim() != 4 or b.dim() != 4 or a.shape[0] != b.shape[0]:
+        raise ValueError(f"estimate_camera_poses_from_ORB: need two clips of T frames, got {list(a.shape)}, {list(b.shape)}")
+    T_, mm = int(a.shape[0]), int(max_matches)
+    fa = geometry.orb_features(a, max_features, levels, threshold)
+    fb = geometry.orb_features(b, max_features, levels, threshold)
+    m = geometry.match_hamming(fa.desc, fa.count, fb.desc, fb.count, cross_check=True, max_matches=mm)
+    valid = (m.pairs[..., 0] >= 0)[..., None]
+    idx = m.pairs.clamp(min=0).long()
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    pick = lambda xy, col: torch.where(valid, torch.gather(xy, 1, idx[..., col, None].expand(-1, -1, 2)), nan)   # noqa: E731
+    x2d = torch.stack([pick(fa.xy, 0).reshape(-1, 2), pick(fb.xy, 1).reshape(-1, 2)])
+    Kd = (K if isinstance(K, torch.Tensor) else torch.from_numpy(np.asarray(K))).to(dev, torch.float64).reshape(3, 3)
+    r = geometry.essential_ransac(x2d, torch.stack([Kd, Kd]), group_size=mm, hypotheses=hypotheses, seed=seed,
+                                  group_offset=group_offset, baseline=float(baseline_m))
+    return (r.R.cpu().numpy(), r.t.cpu().numpy().reshape(T_, 3, 1), r.pose_mask.cpu().numpy().reshape(T_, mm),
+            r.success.cpu().numpy())
+
+
+def estimate_camera_pose_from_ORB(img1, img2, K, baseline_m, max_matches: int = 1000, max_features: int = 3000, levels: int = 8,
+                                  threshold: int = 20, hypotheses: int = 1024, seed: int = 0, group_offset: int = 0):
+    """img1, img2 (H, W, 3) RGB, float in [0, 1] or uint8 (the reference's to_gray_cv_image inputs; (H, W) gray too), K
+    (3, 3) -> (R (3, 3), T (3, 1), pose_mask (max_matches,) uint8) as host arrays with X2 = R X1 + T and ||T|| = baseline_m,
+    or three None when no essential matrix is found (fewer than 5 matches).  pose_mask marks the matches, ordered by
+    (distance, query), that are inliers in front of both cameras.  group_offset = f draws the samples of frame f of
+    estimate_camera_poses_from_ORB."""
+    one = lambda im: (im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im)))[None]   # noqa: E731
+    R, T, mask, ok = estimate_camera_poses_from_ORB(one(img1), one(img2), K, baseline_m, max_matches, max_features, levels, threshold,
+                                                    hypotheses, seed, group_offset)
+    if not bool(ok[0]):
+        return None, None, None
+    return R[0], T[0], mask[0]

@@ -40,6 +40,8 @@ from .device.bev import (HOMOGRAPHY_STAT_FIELDS, TRACK_FIELDS, HomographyResult,
 from .device.calibrate import (CALIB_PARAMS, CalibrationResult, calib_free_mask, calibrate_camera)
 from .device.chessboard import (CHESS_MAX_NMS, SUBPIX_MAX_WIN, SUBPIX_MAX_ITERS, ChessCandidates, SubpixResult,
                                 chessboard_candidates, corner_subpix)
+from .device.features import (ORB_MAX_LEVELS, ORB_MAX_FEATURES, ORB_BORDER, OrbFeatures, HammingMatches, orb_pattern,
+                              orb_features, match_hamming)
 from .device.lens import _undistorted_f32
 
 # ---- host helpers of the wrapper (small arrays, NumPy as in the reference) -----------------
