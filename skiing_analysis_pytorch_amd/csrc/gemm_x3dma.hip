@@ -1145,6 +1145,15 @@ bool gemm_x3dma_eligible(const skimi_gemm_desc* d) {
     const long kp = ((long)d->K + 31) / 32 * 32;
     const long bias = d->a_mode == 0 ? 0 : ((long)x3_pad(d) * d->cW + x3_pad(d)) * x3_cp(d) * 4;
     if ((long)gemm_x3dma_scratch_bytes(d) + bias >= (1ll << 32) || (long)d->N * kp * 4 >= (1ll << 32)) return false;
+    if (d->a_mode == 1 || d->a_mode == 2) {
+        // a padding-tap lane reaches the zero page as an UNSIGNED offset from its K-tile's base (A + tap offset - bias), so
+        // every base must lie in front of the zero page.  A tap that starts behind the whole input (pad > cH with a
+        // dilated window: all its lanes are padding) would put the base behind it: the generic kernel takes those
+        const long rec_bytes = (long)gemm_x3dma_scratch_bytes(d) - 256;
+        const long zero_off = d->a_dtype == SKIMI_BF16X3_REC ? (long)((const char*)d->x3_scratch - (const char*)d->A) : rec_bytes;
+        const long last_base = ((long)(d->KH - 1) * d->dil * d->cW + (long)(d->KW - 1) * d->dil) * x3_cp(d) * 4 + x3_cp(d) * 4 - 128 - bias;
+        if (last_base >= zero_off) return false;
+    }
     if (fold) {
         // the 256-column loop only (a tile is one phase's channels), its epilogue's forms only
         if (d->ps_s < 2 || d->ps_C <= 128 || d->ps_C % 32 != 0 || d->N != d->ps_C || d->cW < 2 || d->bias == nullptr ||

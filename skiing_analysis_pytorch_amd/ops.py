@@ -69,7 +69,7 @@ def gemm(a, w, *, prec=PREC_BF16X3, bias=None, gamma=None, resid=None, act=ACT_N
         d.cN, d.cH, d.cW, d.cC = conv["N"], conv["H"], conv["W"], conv["C"]
         d.KH, d.KW, d.stride, d.pad, d.dil = conv["KH"], conv["KW"], conv["stride"], conv["pad"], conv["dil"]
         d.OH, d.OW = conv["OH"], conv["OW"]
-        d.M = d.cN * d.OH * d.OW
+        d.M = M if M is not None else d.cN * d.OH * d.OW   # an M of its own: only to test the library's refusal
     else:
         d.M = M if M is not None else a.shape[0]
     if records_only:
