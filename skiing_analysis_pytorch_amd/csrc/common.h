@@ -47,6 +47,15 @@ enum ProfKind { PROF_NONE = 0, PROF_ATTN_BF16 = 1, PROF_GEMM = 2 };
 bool prof_armed(int kind, long size_key);
 void prof_before(hipStream_t st);
 void prof_after(hipStream_t st, double flops, double bytes);
+// one launch inside the timer's event pair when `armed`; `launch` returns the launch's rc, which is passed on
+// (the closing event is recorded whatever rc is)
+template <typename Launch>
+static inline int prof_bracket(bool armed, hipStream_t st, double flops, double bytes, Launch&& launch) {
+    if (armed) prof_before(st);
+    const int rc = launch();
+    if (armed) prof_after(st, flops, bytes);
+    return rc;
+}
 
 // Opt a kernel in to more than 64 KiB of dynamic LDS, once per (kernel, device): `done` is that kernel's own static
 // mask (bit = device ordinal).  Thread-safe: two racing first calls both set the attribute, which is idempotent.

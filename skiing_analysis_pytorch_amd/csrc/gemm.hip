@@ -421,10 +421,8 @@ void set_gemm_path(int family, int tile, int mfma, int epi, int splitk) {
 }
 int gemm_last_path() { return tl_gemm_path; }
 
-// scratch: caller-owned fp32 slab [M, N] for split-K partials (NULL => split-K is not used)
-int gemm_dispatch(const skimi_gemm_desc* d, hipStream_t st, void* scratch, size_t scratch_bytes,
-                  int force_splitk) {
-    tl_gemm_path = 0;
+// the descriptor checks of skimi_gemm; their order decides which message a bad descriptor gets
+static int check_desc(const skimi_gemm_desc* d) {
     SKIMI_CHECK_ARG(d != nullptr, "skimi_gemm: null descriptor");
     SKIMI_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, "skimi_gemm: empty shape M=%d N=%d K=%d", d->M, d->N, d->K);
     SKIMI_CHECK_ARG(d->K % 8 == 0, "skimi_gemm: K=%d must be a multiple of 8", d->K);
@@ -475,8 +473,13 @@ int gemm_dispatch(const skimi_gemm_desc* d, hipStream_t st, void* scratch, size_
     }
     if (d->resid) SKIMI_CHECK_ARG(d->ldr >= d->N, "skimi_gemm: ldr < N");
     if (d->resid2) SKIMI_CHECK_ARG(d->ldr2 >= d->N, "skimi_gemm: ldr2 < N");
+    return SKIMI_OK;
+}
 
-    GemmArgs a;
+// the kernels' argument block: the descriptor's fields, all of K in one split, and whether the epilogue may use 16-byte
+// accesses (vec4); tile counts and split-K are the planner's
+static GemmArgs args_from_desc(const skimi_gemm_desc* d) {
+    GemmArgs a{};
     a.M = d->M; a.N = d->N; a.K = d->K;
     a.A = d->A; a.W = d->W; a.lda = d->lda; a.ldw = d->ldw;
     a.a_mode = d->a_mode;
@@ -492,9 +495,8 @@ int gemm_dispatch(const skimi_gemm_desc* d, hipStream_t st, void* scratch, size_
     a.store_mode = d->store_mode; a.ps_s = d->ps_s; a.ps_C = d->ps_C;
     a.out_rec = (unsigned short*)d->out_records;
     a.rec_row = (long)(d->N / 32) * 64;
-    a.partial = nullptr;
     a.f16 = d->prec == SKIMI_PREC_F16;
-    a.splitk_ordered = 0;
+    a.k_per_split = d->K;
     {
         auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
         const bool out_ok = d->out_dtype == SKIMI_F32 ? al16(d->out) : (((uintptr_t)d->out & 7) == 0);
@@ -504,13 +506,113 @@ int gemm_dispatch(const skimi_gemm_desc* d, hipStream_t st, void* scratch, size_
                  (!d->resid || ((((uintptr_t)d->resid) & 7) == 0 && (d->resid_dtype != SKIMI_F32 || al16(d->resid)) && d->ldr % 4 == 0)) &&
                  (!d->resid2 || ((((uintptr_t)d->resid2) & 7) == 0 && (d->resid_dtype != SKIMI_F32 || al16(d->resid2)) && d->ldr2 % 4 == 0)) && (d->store_mode == 0 || d->ps_C % 4 == 0);
     }
+    return a;
+}
+
+// what the in-library timer counts for a launch: 2 M N K, and A (a_cols elements per output row), W and the result once
+static double desc_flops(const skimi_gemm_desc* d) { return 2.0 * d->M * (double)d->N * d->K; }
+static double desc_bytes(const skimi_gemm_desc* d, int a_cols) {
+    const double ea = d->a_dtype == SKIMI_F32 ? 4.0 : 2.0, ew = d->w_dtype == SKIMI_F32 ? 4.0 : 2.0,
+                 eo = d->out_dtype == SKIMI_F32 ? 4.0 : 2.0;
+    return ea * d->M * (double)a_cols + ew * d->N * (double)d->K + eo * d->M * (double)d->N;
+}
+
+// tile and split-K of the generic kernel: fill >= ~256 CUs
+struct GenericPlan {
+    int BM, BN;
+    int ntm, ntn;
+    int splitk, k_per_split;   // k_per_split: a multiple of BK
+    bool ordered;              // splitk > 1 with one slab plane per split, added in split order by the epilogue (else atomics)
+    size_t scratch_need;       // bytes of split-K scratch (0: no split)
+    int tile_code;             // the tile field of skimi_gemm_last_path
+};
+
+// A pure function of its arguments.  atomic: SKIMI_SPLITK_ATOMIC (A/B timing).  Every mode otherwise: a fixed summation
+// order over the K splits (one slab plane per split, added in order by the epilogue) instead of global float atomics, whose
+// arrival order changes the last bits from run to run -- and, through the track head's iterations, its tracks by up to a
+// fifth of a pixel.
+static GenericPlan plan_generic(const skimi_gemm_desc* d, const void* scratch, size_t scratch_bytes, int force_splitk, bool atomic) {
+    GenericPlan p;
+    const int BK = d->prec == SKIMI_PREC_BF16X3 ? 32 : 64;
+    const bool small = cdiv(d->M, 128) * cdiv(d->N, 128) < 128;
+    p.BM = small ? 64 : 128;
+    // narrow outputs (e.g. the DPT 128 -> 32 conv): a 128 x 64 tile halves the wasted N columns
+    p.BN = (p.BM == 128 && d->N <= 64) ? 64 : p.BM;
+    p.ntm = (int)cdiv(d->M, p.BM);
+    p.ntn = (int)cdiv(d->N, p.BN);
+    const long tiles = (long)p.ntm * p.ntn;
+    int splitk = 1;
+    const int nkt = (int)cdiv(d->K, BK);
+    bool ordered = !atomic;
+    const size_t plane = (size_t)d->M * d->N * sizeof(float);
+    if (force_splitk > 0) {
+        splitk = force_splitk;
+        if (ordered && plane * (size_t)splitk > scratch_bytes) ordered = false;   // a pinned split count (tests) on a one-plane slab
+    } else if (tiles < 192 && nkt >= 8 && scratch != nullptr && plane <= scratch_bytes) {
+        splitk = (int)std::min<long>(cdiv(512, tiles), nkt / 4);
+        // one plane per split: as many splits as the slab holds (fewer than two: no split at all, never atomics)
+        if (ordered) splitk = (int)std::min<size_t>((size_t)splitk, scratch_bytes / plane);
+        if (splitk < 1) splitk = 1;
+    }
+    p.k_per_split = (int)cdiv(nkt, splitk) * BK;
+    p.splitk = (int)cdiv(d->K, p.k_per_split);
+    p.ordered = ordered && p.splitk > 1;
+    p.scratch_need = p.splitk > 1 ? plane * (p.ordered ? (size_t)p.splitk : 1) : 0;
+    p.tile_code = p.BM == 64 ? 1 : p.BN == 64 ? 2 : 3;
+    return p;
+}
+
+// One row of launch_generic's table: if the plan's tile and the descriptor's mode are this row's, launches the kernel
+// built for the operands' element types (rc) and returns true.
+template <int PREC, int BM, int BN>
+static bool launch_row(const GenericPlan& pl, const skimi_gemm_desc* d, const GemmArgs& a, hipStream_t st, int& rc) {
+    if (d->prec != PREC || pl.BM != BM || pl.BN != BN) return false;
+    constexpr bool F16 = PREC == SKIMI_PREC_F16;
+    const bool af = d->a_dtype == SKIMI_F32, wf = d->w_dtype == SKIMI_F32;
+    if constexpr (PREC == SKIMI_PREC_BF16X3) {   // fp32 weights (checked by launch_generic)
+        if (af) rc = launch_cfg<BM, BN, 32, 3, float, float>(a, st);
+        else rc = launch_cfg<BM, BN, 32, 3, unsigned short, float>(a, st);
+    } else {
+        if (af && wf) rc = launch_cfg<BM, BN, 64, 1, float, float, F16>(a, st);
+        else if (af) rc = launch_cfg<BM, BN, 64, 1, float, unsigned short, F16>(a, st);
+        else if (wf) rc = launch_cfg<BM, BN, 64, 1, unsigned short, float, F16>(a, st);
+        else rc = launch_cfg<BM, BN, 64, 1, unsigned short, unsigned short, F16>(a, st);
+    }
+    return true;
+}
+
+static int launch_generic(const GenericPlan& pl, const GemmArgs& a, const skimi_gemm_desc* d, hipStream_t st) {
+    SKIMI_CHECK_ARG(d->prec != SKIMI_PREC_BF16X3 || d->w_dtype == SKIMI_F32, "skimi_gemm: BF16X3 needs fp32 weights");
+    const int rc = prof_bracket(prof_armed(PROF_GEMM, (long)d->M), st, desc_flops(d), desc_bytes(d, d->K), [&] {
+        // the kernels lie in the code object in the order of these rows: a new row goes to the end
+        int r = SKIMI_ERR_ARG;
+        launch_row<SKIMI_PREC_F16, 128, 64>(pl, d, a, st, r) || launch_row<SKIMI_PREC_F16, 128, 128>(pl, d, a, st, r) ||
+            launch_row<SKIMI_PREC_F16, 64, 64>(pl, d, a, st, r) || launch_row<SKIMI_PREC_BF16, 128, 64>(pl, d, a, st, r) ||
+            launch_row<SKIMI_PREC_BF16X3, 128, 64>(pl, d, a, st, r) || launch_row<SKIMI_PREC_BF16, 128, 128>(pl, d, a, st, r) ||
+            launch_row<SKIMI_PREC_BF16, 64, 64>(pl, d, a, st, r) || launch_row<SKIMI_PREC_BF16X3, 128, 128>(pl, d, a, st, r) ||
+            launch_row<SKIMI_PREC_BF16X3, 64, 64>(pl, d, a, st, r);
+        return r;
+    });
+    if (rc != SKIMI_OK) return rc;
+    if (pl.splitk > 1) {
+        long total = (long)d->M * d->N;
+        int blocks = (int)std::min<long>(cdiv(total, 256), 2048);
+        hipLaunchKernelGGL(gemm_splitk_epilogue, dim3(blocks), dim3(256), 0, st, a);
+        SKIMI_LAUNCH_CHECK();
+    }
+    return SKIMI_OK;
+}
+
+// scratch: caller-owned fp32 slab [M, N] for split-K partials (NULL => split-K is not used)
+int gemm_dispatch(const skimi_gemm_desc* d, hipStream_t st, void* scratch, size_t scratch_bytes,
+                  int force_splitk) {
+    tl_gemm_path = 0;
+    if (const int rc = check_desc(d)) return rc;
+    GemmArgs a = args_from_desc(d);
+    const bool prof = prof_armed(PROF_GEMM, (long)d->M);
 
     // fp32-accurate path with pre-split weight records: LDS-DMA bf16x3 kernel (gemm_x3dma.hip)
-    if (force_splitk <= 0 && gemm_x3dma_eligible(d)) {
-        a.partial = nullptr;
-        a.k_per_split = d->K;
-        return gemm_x3dma_launch(a, d, st);
-    }
+    if (force_splitk <= 0 && gemm_x3dma_eligible(d)) return gemm_x3dma_launch(a, d, st);
     // the zero page behind the records (padding taps of the consumer's gather): the LDS-DMA kernels above
     // clear it themselves, the generic kernels get a memset node
     if (d->out_records &&
@@ -523,146 +625,35 @@ int gemm_dispatch(const skimi_gemm_desc* d, hipStream_t st, void* scratch, size_
                     "(M=%d N=%d: needs W_split, M >= 4096, N >= 96, most of a chip's worth of 256-row tiles (>= 160), a zero page behind A)", d->M, d->N);
 
     // large bf16 x bf16 plain-row shapes: 256x256 tiles staged by LDS-DMA (gemm256.hip)
-    if (force_splitk <= 0 && gemm256_eligible(d)) {
-        a.partial = nullptr;
-        a.k_per_split = d->K;
-        const bool prof256 = prof_armed(PROF_GEMM, (long)d->M);
-        if (prof256) prof_before(st);
-        int rc256 = gemm256_launch(a, st);
-        if (prof256)
-            prof_after(st, 2.0 * d->M * (double)d->N * d->K,
-                       2.0 * d->M * (double)d->K + 2.0 * d->N * (double)d->K +
-                           (d->out_dtype == SKIMI_F32 ? 4.0 : 2.0) * d->M * (double)d->N);
-        return rc256;
-    }
+    if (force_splitk <= 0 && gemm256_eligible(d))
+        return prof_bracket(prof, st, desc_flops(d), desc_bytes(d, d->K), [&] { return gemm256_launch(a, st); });
 
-    // 3 x 3 convolutions to 128 channels on 16-bit operands (the track head's feature extractor): halo window in LDS
+    // 3 x 3 convolutions to 128 channels on 16-bit operands (the track head's feature extractor): halo window in LDS;
+    // each of A's pixels is counted once
     if (force_splitk <= 0 && conv_win_eligible(d)) {
         set_gemm_path(SKIMI_GEMM_PATH_CONV_WIN, 0, 0, 0, 1);
-        const bool profw = prof_armed(PROF_GEMM, (long)d->M);
-        if (profw) prof_before(st);
-        const int rcw = conv_win_launch(a, st);
-        if (profw)
-            prof_after(st, 2.0 * d->M * (double)d->N * d->K,
-                       2.0 * d->M * (double)d->cC + 2.0 * d->N * (double)d->K + (d->out_dtype == SKIMI_F32 ? 4.0 : 2.0) * d->M * (double)d->N);
-        return rcw;
+        return prof_bracket(prof, st, desc_flops(d), desc_bytes(d, d->cC), [&] { return conv_win_launch(a, st); });
     }
 
-    // tile + split-K choice: fill >= ~256 CUs
-    const long t128 = cdiv(d->M, 128) * cdiv(d->N, 128);
-    const bool small = t128 < 128;
-    const int BM = small ? 64 : 128;
-    // narrow outputs (e.g. the DPT 128 -> 32 conv): a 128 x 64 tile halves the wasted N columns
-    const int BN = (BM == 128 && d->N <= 64) ? 64 : BM;
-    a.ntm = (int)cdiv(d->M, BM);
-    a.ntn = (int)cdiv(d->N, BN);
-    const long tiles = (long)a.ntm * a.ntn;
-    int splitk = 1;
-    const int nkt = (int)cdiv(d->K, BK);
-    // every mode: a fixed summation order over the K splits (one slab plane per split, added in order by the epilogue)
-    // instead of global float atomics, whose arrival order changes the last bits from run to run -- and, through the
-    // track head's iterations, its tracks by up to a fifth of a pixel.  SKIMI_SPLITK_ATOMIC=1: atomics (A/B timing).
-    bool ordered = !(int)env_once("SKIMI_SPLITK_ATOMIC", 0);
-    const size_t plane = (size_t)d->M * d->N * sizeof(float);
-    if (force_splitk > 0) {
-        splitk = force_splitk;
-        if (ordered && plane * (size_t)splitk > scratch_bytes) ordered = false;   // a pinned split count (tests) on a one-plane slab
-    } else if (tiles < 192 && nkt >= 8 && scratch != nullptr && plane <= scratch_bytes) {
-        splitk = (int)std::min<long>(cdiv(512, tiles), nkt / 4);
-        // one plane per split: as many splits as the slab holds (fewer than two: no split at all, never atomics)
-        if (ordered) splitk = (int)std::min<size_t>((size_t)splitk, scratch_bytes / plane);
-        if (splitk < 1) splitk = 1;
-    }
-    int kper = (int)cdiv(nkt, splitk) * BK;
-    splitk = (int)cdiv(d->K, kper);
-    a.splitk = splitk;
-    a.k_per_split = kper;
-    a.splitk_ordered = ordered && splitk > 1;
-    if (splitk > 1) {
-        size_t need = plane * (a.splitk_ordered ? (size_t)splitk : 1);
-        if (scratch == nullptr || need > scratch_bytes) {
-            set_error("skimi_gemm: split-K scratch too small (%zu needed, %zu given)", need, scratch_bytes);
+    const GenericPlan pl = plan_generic(d, scratch, scratch_bytes, force_splitk, (int)env_once("SKIMI_SPLITK_ATOMIC", 0) != 0);
+    a.ntm = pl.ntm;
+    a.ntn = pl.ntn;
+    a.splitk = pl.splitk;
+    a.k_per_split = pl.k_per_split;
+    a.splitk_ordered = pl.ordered;
+    if (pl.splitk > 1) {
+        if (scratch == nullptr || pl.scratch_need > scratch_bytes) {
+            set_error("skimi_gemm: split-K scratch too small (%zu needed, %zu given)", pl.scratch_need, scratch_bytes);
             return SKIMI_ERR_WORKSPACE;
         }
         a.partial = (float*)scratch;
         // the split-K epilogue re-zeroes what it reads, so a caller that zeroed the slab once
         // (splitk_scratch_zeroed) pays no memset per launch
-        if (!d->splitk_scratch_zeroed) SKIMI_HIP(hipMemsetAsync(scratch, 0, need, st));
+        if (!d->splitk_scratch_zeroed) SKIMI_HIP(hipMemsetAsync(scratch, 0, pl.scratch_need, st));
     }
-    set_gemm_path(splitk == 1 ? SKIMI_GEMM_PATH_GENERIC : a.splitk_ordered ? SKIMI_GEMM_PATH_SPLITK_ORDERED : SKIMI_GEMM_PATH_SPLITK_ATOMIC,
-                  BM == 64 ? 1 : BN == 64 ? 2 : 3, 0, 0, splitk);
-
-    int rc;
-    const bool prof = prof_armed(PROF_GEMM, (long)d->M);
-    if (prof) prof_before(st);
-    const bool af = d->a_dtype == SKIMI_F32, wf = d->w_dtype == SKIMI_F32;
-#define SKIMI_GO(BM_, BK_, NS_, TA_, TW_) rc = launch_cfg<BM_, BM_, BK_, NS_, TA_, TW_>(a, st)
-#define SKIMI_GO16(BM_, BN_, TA_, TW_) rc = launch_cfg<BM_, BN_, 64, 1, TA_, TW_, true>(a, st)
-    if (d->prec == SKIMI_PREC_F16) {
-        if (BN == 64 && BM == 128) {
-            if (af && wf) SKIMI_GO16(128, 64, float, float);
-            else if (af) SKIMI_GO16(128, 64, float, unsigned short);
-            else if (wf) SKIMI_GO16(128, 64, unsigned short, float);
-            else SKIMI_GO16(128, 64, unsigned short, unsigned short);
-        } else if (BM == 128) {
-            if (af && wf) SKIMI_GO16(128, 128, float, float);
-            else if (af) SKIMI_GO16(128, 128, float, unsigned short);
-            else if (wf) SKIMI_GO16(128, 128, unsigned short, float);
-            else SKIMI_GO16(128, 128, unsigned short, unsigned short);
-        } else {
-            if (af && wf) SKIMI_GO16(64, 64, float, float);
-            else if (af) SKIMI_GO16(64, 64, float, unsigned short);
-            else if (wf) SKIMI_GO16(64, 64, unsigned short, float);
-            else SKIMI_GO16(64, 64, unsigned short, unsigned short);
-        }
-    } else if (BN == 64 && BM == 128) {
-        if (d->prec == SKIMI_PREC_BF16) {
-            if (af && wf) rc = launch_cfg<128, 64, 64, 1, float, float>(a, st);
-            else if (af) rc = launch_cfg<128, 64, 64, 1, float, unsigned short>(a, st);
-            else if (wf) rc = launch_cfg<128, 64, 64, 1, unsigned short, float>(a, st);
-            else rc = launch_cfg<128, 64, 64, 1, unsigned short, unsigned short>(a, st);
-        } else {
-            SKIMI_CHECK_ARG(wf, "skimi_gemm: BF16X3 needs fp32 weights");
-            if (af) rc = launch_cfg<128, 64, 32, 3, float, float>(a, st);
-            else rc = launch_cfg<128, 64, 32, 3, unsigned short, float>(a, st);
-        }
-    } else if (d->prec == SKIMI_PREC_BF16) {
-        if (BM == 128) {
-            if (af && wf) SKIMI_GO(128, 64, 1, float, float);
-            else if (af) SKIMI_GO(128, 64, 1, float, unsigned short);
-            else if (wf) SKIMI_GO(128, 64, 1, unsigned short, float);
-            else SKIMI_GO(128, 64, 1, unsigned short, unsigned short);
-        } else {
-            if (af && wf) SKIMI_GO(64, 64, 1, float, float);
-            else if (af) SKIMI_GO(64, 64, 1, float, unsigned short);
-            else if (wf) SKIMI_GO(64, 64, 1, unsigned short, float);
-            else SKIMI_GO(64, 64, 1, unsigned short, unsigned short);
-        }
-    } else {
-        SKIMI_CHECK_ARG(wf, "skimi_gemm: BF16X3 needs fp32 weights");
-        if (BM == 128) {
-            if (af) SKIMI_GO(128, 32, 3, float, float);
-            else SKIMI_GO(128, 32, 3, unsigned short, float);
-        } else {
-            if (af) SKIMI_GO(64, 32, 3, float, float);
-            else SKIMI_GO(64, 32, 3, unsigned short, float);
-        }
-    }
-#undef SKIMI_GO
-#undef SKIMI_GO16
-    if (prof) {
-        const double ea = af ? 4.0 : 2.0, ew = wf ? 4.0 : 2.0, eo = d->out_dtype == SKIMI_F32 ? 4.0 : 2.0;
-        prof_after(st, 2.0 * d->M * (double)d->N * d->K,
-                   ea * d->M * (double)d->K + ew * d->N * (double)d->K + eo * d->M * (double)d->N);
-    }
-    if (rc != SKIMI_OK) return rc;
-    if (splitk > 1) {
-        long total = (long)d->M * d->N;
-        int blocks = (int)std::min<long>(cdiv(total, 256), 2048);
-        hipLaunchKernelGGL(gemm_splitk_epilogue, dim3(blocks), dim3(256), 0, st, a);
-        SKIMI_LAUNCH_CHECK();
-    }
-    return SKIMI_OK;
+    set_gemm_path(pl.splitk == 1 ? SKIMI_GEMM_PATH_GENERIC : pl.ordered ? SKIMI_GEMM_PATH_SPLITK_ORDERED : SKIMI_GEMM_PATH_SPLITK_ATOMIC,
+                  pl.tile_code, 0, 0, pl.splitk);
+    return launch_generic(pl, a, d, st);
 }
 
 }  // namespace skimi

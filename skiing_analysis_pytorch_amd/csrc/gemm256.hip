@@ -20,6 +20,8 @@
 //     random data the chip holds a higher clock on the 16x16 shape (profiles/r04_peaks.json).
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 #include "env.h"
 #include "gemm_epilogue.h"
@@ -1063,79 +1065,49 @@ bool gemm256_eligible(const skimi_gemm_desc* d) {
            d->N >= 512 && (((uintptr_t)d->A | (uintptr_t)d->W) & 15) == 0;
 }
 
-template <int MT, int EPI, bool F16 = false>
-static int launch256(GemmArgs& a, hipStream_t st) {
-    constexpr size_t lds = 2ull * (64 * MT + 256) * 128;
-    SKIMI_LDS_OPT_IN((gemm256_kernel<MT, EPI, F16>), lds, "gemm256");
-    a.ntm = (int)cdiv(a.M, 64 * MT);
-    a.ntn = (int)cdiv(a.N, 256);
-    a.splitk = 1;
-    hipLaunchKernelGGL((gemm256_kernel<MT, EPI, F16>), dim3(a.ntm * a.ntn), dim3(512), lds, st, a);
-    SKIMI_LAUNCH_CHECK();
-    return SKIMI_OK;
+// calls f with the launch's epilogue kind as a compile-time constant: f(std::integral_constant<int, EPI>)
+template <typename F>
+static int dispatch_epi(int epi, F&& f) {
+    if (epi == 1) return f(std::integral_constant<int, 1>{});
+    if (epi == 2) return f(std::integral_constant<int, 2>{});
+    if (epi == 3) return f(std::integral_constant<int, 3>{});
+    return f(std::integral_constant<int, 0>{});
 }
 
-template <int EPI, int DEEP, bool F16, bool M16>
-static int launch256pp_(GemmArgs& a, hipStream_t st) {
-    constexpr size_t lds = 2ull * (256 + 256) * 128;
-    SKIMI_LDS_OPT_IN((gemm256pp_kernel<EPI, DEEP, F16, M16>), lds, "gemm256pp");
-    a.ntm = (int)cdiv(a.M, 256);
-    a.ntn = (int)cdiv(a.N, 256);
-    a.splitk = 1;
-    hipLaunchKernelGGL((gemm256pp_kernel<EPI, DEEP, F16, M16>), dim3(a.ntm * a.ntn), dim3(512), lds, st, a);
-    SKIMI_LAUNCH_CHECK();
-    return SKIMI_OK;
+// the two-phase loop on tiles of 64 * MT rows
+template <int MT, bool F16>
+static int launch256(GemmArgs& a, hipStream_t st, int epi) {
+    return dispatch_epi(epi, [&](auto e) {
+        return launch_tiles<gemm256_kernel<MT, decltype(e)::value, F16>>(a, st, 2ull * (64 * MT + 256) * 128, 512, cdiv(a.M, 64 * MT),
+                                                                         cdiv(a.N, 256), "gemm256");
+    });
 }
 
-template <int EPI, bool F16, bool M16>
-static int launch256pp(GemmArgs& a, hipStream_t st) {
-    if constexpr (F16) return launch256pp_<EPI, 1, true, M16>(a, st);
-    const int deep = (int)env_switch("SKIMI_GEMM256_DEEP", 1);
-    return deep ? launch256pp_<EPI, 1, false, M16>(a, st) : launch256pp_<EPI, 0, false, M16>(a, st);
-}
-
-template <int EPI, bool F16, bool M16>
-static int launch256w4(GemmArgs& a, hipStream_t st) {
-    constexpr size_t lds = 10ull * 128 * 128;
-    SKIMI_LDS_OPT_IN((gemm256w4_kernel<EPI, F16, M16>), lds, "gemm256w4");
-    a.ntm = (int)cdiv(a.M, 256);
-    a.ntn = (int)cdiv(a.N, 256);
-    a.splitk = 1;
-    hipLaunchKernelGGL((gemm256w4_kernel<EPI, F16, M16>), dim3(a.ntm * a.ntn), dim3(256), lds, st, a);
-    SKIMI_LAUNCH_CHECK();
-    return SKIMI_OK;
-}
-
+// the single-stream (w4) or the ping-pong loop on 256-row tiles
 template <bool F16, bool M16>
 static int gemm256_pick_loop(GemmArgs& a, hipStream_t st, int epi, bool w4) {
+    const int64_t ntm = cdiv(a.M, 256), ntn = cdiv(a.N, 256);
     if (w4) {
-        if (epi == 1) return launch256w4<1, F16, M16>(a, st);
-        if (epi == 2) return launch256w4<2, F16, M16>(a, st);
-        if (epi == 3) return launch256w4<3, F16, M16>(a, st);
-        return launch256w4<0, F16, M16>(a, st);
+        return dispatch_epi(epi, [&](auto e) {
+            return launch_tiles<gemm256w4_kernel<decltype(e)::value, F16, M16>>(a, st, 10ull * 128 * 128, 256, ntm, ntn, "gemm256w4");
+        });
     }
-    if (epi == 1) return launch256pp<1, F16, M16>(a, st);
-    if (epi == 2) return launch256pp<2, F16, M16>(a, st);
-    if (epi == 3) return launch256pp<3, F16, M16>(a, st);
-    return launch256pp<0, F16, M16>(a, st);
+    return dispatch_epi(epi, [&](auto e) {
+        constexpr int EPI = decltype(e)::value;
+        constexpr size_t lds = 2ull * (256 + 256) * 128;
+        if constexpr (F16) return launch_tiles<gemm256pp_kernel<EPI, 1, true, M16>>(a, st, lds, 512, ntm, ntn, "gemm256pp");
+        const int deep = (int)env_switch("SKIMI_GEMM256_DEEP", 1);
+        return deep ? launch_tiles<gemm256pp_kernel<EPI, 1, false, M16>>(a, st, lds, 512, ntm, ntn, "gemm256pp")
+                    : launch_tiles<gemm256pp_kernel<EPI, 0, false, M16>>(a, st, lds, 512, ntm, ntn, "gemm256pp");
+    });
 }
 
 template <bool F16>
 static int gemm256_pick(GemmArgs& a, hipStream_t st, int epi, bool mt3, bool w4, int use_pp, bool m16) {
-    if (mt3) {
-        if (epi == 1) return launch256<3, 1, F16>(a, st);
-        if (epi == 2) return launch256<3, 2, F16>(a, st);
-        if (epi == 3) return launch256<3, 3, F16>(a, st);
-        return launch256<3, 0, F16>(a, st);
-    }
+    if (mt3) return launch256<3, F16>(a, st, epi);
     // the fp16 build carries the two loops the dispatch picks (single-stream, ping-pong) + the 192-row one
     if (w4 || use_pp || F16) return m16 ? gemm256_pick_loop<F16, true>(a, st, epi, w4) : gemm256_pick_loop<F16, false>(a, st, epi, w4);
-    if constexpr (!F16) {
-        if (epi == 1) return launch256<4, 1>(a, st);
-        if (epi == 2) return launch256<4, 2>(a, st);
-        if (epi == 3) return launch256<4, 3>(a, st);
-        return launch256<4, 0>(a, st);
-    }
+    if constexpr (!F16) return launch256<4, false>(a, st, epi);
     return SKIMI_ERR_ARG;
 }
 
@@ -1173,28 +1145,19 @@ int gemm256_launch(GemmArgs& a, hipStream_t st) {
     return a.f16 ? gemm256_pick<true>(a, st, epi, mt3, w4, use_pp, m16) : gemm256_pick<false>(a, st, epi, mt3, w4, use_pp, m16);
 }
 
-template <int EPI>
-static int launch256w4_fp8(GemmArgs& a, hipStream_t st) {
-    constexpr size_t lds = 10ull * 128 * 128;
-    SKIMI_LDS_OPT_IN(gemm256w4_fp8_kernel<EPI>, lds, "gemm256w4_fp8");
-    a.ntm = (int)cdiv(a.M, 256);
-    a.ntn = (int)cdiv(a.N, 256);
-    a.splitk = 1;
-    hipLaunchKernelGGL((gemm256w4_fp8_kernel<EPI>), dim3(a.ntm * a.ntn), dim3(256), lds, st, a);
-    SKIMI_LAUNCH_CHECK();
-    return SKIMI_OK;
-}
-
 // MXFP8 operands on the single-stream 256 x 256 loop.  The caller (gemm_fp8_launch) has checked the shape: K = Kp
 // (bytes per row, a multiple of 128), 16-byte aligned operands, one of the three compile-time epilogues.
 int gemm256_fp8_launch(GemmArgs& a, hipStream_t st) {
     a.dbg = 0;
-    const int epi = epi_kind(a);
-    if (epi == 1) return launch256w4_fp8<1>(a, st);
-    if (epi == 2) return launch256w4_fp8<2>(a, st);
-    if (epi == 3) return launch256w4_fp8<3>(a, st);
-    set_error("gemm256_fp8: epilogue not supported");
-    return SKIMI_ERR_ARG;
+    return dispatch_epi(epi_kind(a), [&](auto e) {
+        if constexpr (decltype(e)::value == 0) {
+            set_error("gemm256_fp8: epilogue not supported");
+            return SKIMI_ERR_ARG;
+        } else {
+            return launch_tiles<gemm256w4_fp8_kernel<decltype(e)::value>>(a, st, 10ull * 128 * 128, 256, cdiv(a.M, 256), cdiv(a.N, 256),
+                                                                          "gemm256w4_fp8");
+        }
+    });
 }
 
 }  // namespace skimi

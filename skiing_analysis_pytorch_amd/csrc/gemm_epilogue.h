@@ -264,6 +264,21 @@ __device__ __forceinline__ void store_four(const GemmArgs& p, const RowMap& rm, 
 void set_gemm_path(int family, int tile, int mfma, int epi, int splitk);
 int gemm_last_path();
 
+// Host side of every kernel that takes one workgroup per output tile and all of K: opt `Kernel` in to `lds` bytes of
+// dynamic LDS (SKIMI_LDS_OPT_IN's mask is static here, so there is one per kernel instantiation), record the tile counts
+// in `a` and launch ntm * ntn workgroups of `threads`.  `extra`: kernel arguments behind the GemmArgs.
+template <auto Kernel, typename... Extra>
+static int launch_tiles(GemmArgs& a, hipStream_t st, size_t lds, int threads, int64_t ntm, int64_t ntn, const char* what,
+                        const Extra&... extra) {
+    SKIMI_LDS_OPT_IN(Kernel, lds, what);
+    a.ntm = (int)ntm;
+    a.ntn = (int)ntn;
+    a.splitk = 1;
+    hipLaunchKernelGGL(Kernel, dim3(a.ntm * a.ntn), dim3(threads), lds, st, a, extra...);
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
 bool gemm256_eligible(const skimi_gemm_desc* d);
 bool gemm_x3dma_eligible(const skimi_gemm_desc* d);
 int gemm_x3dma_launch(GemmArgs& a, const skimi_gemm_desc* d, hipStream_t st);

@@ -301,6 +301,10 @@ int gemm_fp8_launch(const void* A, const void* As, const void* W, const void* Ws
     SKIMI_CHECK_ARG(act == SKIMI_ACT_NONE || act == SKIMI_ACT_GELU, "gemm_fp8: activation must be none or GELU");
     SKIMI_CHECK_ARG(!(gamma != nullptr) || resid != nullptr, "gemm_fp8: LayerScale needs the residual");
     SKIMI_CHECK_ARG(!(act == SKIMI_ACT_GELU && gamma), "gemm_fp8: GELU and LayerScale epilogues are separate");
+    // the in-library timer's figures: one byte per operand element, the scales not counted
+    const bool prof = prof_armed(PROF_GEMM, N);
+    const double flops = 2.0 * M * (double)N * K;
+    const double bytes = (double)M * K + (double)N * K + (double)M * N * (out_dtype == SKIMI_F32 ? 4 : 2);
     Fp8Args p;
     p.A = (const unsigned char*)A; p.As = (const unsigned char*)As; p.W = (const unsigned char*)W; p.Ws = (const unsigned char*)Ws;
     p.M = M; p.N = N; p.Kp = (int)align_up((size_t)K, 128);
@@ -320,11 +324,7 @@ int gemm_fp8_launch(const void* A, const void* As, const void* W, const void* Ws
             g.bias = bias; g.gamma = gamma; g.resid = resid; g.resid_dtype = SKIMI_F32; g.ldr = ldr;
             g.act = act; g.out = out; g.out_dtype = out_dtype; g.ldo = ldo; g.vec4 = 1;
             g.out_scales = (unsigned char*)out_scales;
-            const bool prof2 = prof_armed(PROF_GEMM, N);
-            if (prof2) prof_before(st);
-            const int rc = gemm256_fp8_launch(g, st);
-            if (prof2) prof_after(st, 2.0 * M * (double)N * K, (double)M * K + (double)N * K + (double)M * N * (out_dtype == SKIMI_F32 ? 4 : 2));
-            return rc;
+            return prof_bracket(prof, st, flops, bytes, [&] { return gemm256_fp8_launch(g, st); });
         }
     }
     SKIMI_CHECK_ARG(out_dtype != SKIMI_FP8MX, "gemm_fp8: MXFP8 output is served by the single-stream 256-row loop only (M >= 2048, "
@@ -340,21 +340,22 @@ int gemm_fp8_launch(const void* A, const void* As, const void* W, const void* Ws
     SKIMI_CHECK_ARG(nblk < (1l << 31), "gemm_fp8: grid too large");
     SKIMI_CHECK_ARG((long)bt * p.Kp < (1l << 32), "gemm_fp8: K too large for 32-bit staging offsets");
     const int epi = gamma ? 2 : act == SKIMI_ACT_GELU ? 1 : 0;
-    const bool prof = prof_armed(PROF_GEMM, N);
-    if (prof) prof_before(st);
 #define SKIMI_FP8_LAUNCH(E, T)                                                                                          \
     do {                                                                                                                \
         constexpr int lds = 4 * 64 * T * 128;                                                                           \
         if (lds > 64 * 1024) SKIMI_LDS_OPT_IN((gemm_fp8_kernel<E, T>), lds, "gemm_fp8");                                \
         hipLaunchKernelGGL((gemm_fp8_kernel<E, T>), dim3((unsigned)nblk), dim3(256), lds, st, p);                       \
     } while (0)
-    if (big) {
-        if (epi == 2) SKIMI_FP8_LAUNCH(2, 4); else if (epi == 1) SKIMI_FP8_LAUNCH(1, 4); else SKIMI_FP8_LAUNCH(0, 4);
-    } else {
-        if (epi == 2) SKIMI_FP8_LAUNCH(2, 2); else if (epi == 1) SKIMI_FP8_LAUNCH(1, 2); else SKIMI_FP8_LAUNCH(0, 2);
-    }
+    const int rc = prof_bracket(prof, st, flops, bytes, [&] {
+        if (big) {
+            if (epi == 2) SKIMI_FP8_LAUNCH(2, 4); else if (epi == 1) SKIMI_FP8_LAUNCH(1, 4); else SKIMI_FP8_LAUNCH(0, 4);
+        } else {
+            if (epi == 2) SKIMI_FP8_LAUNCH(2, 2); else if (epi == 1) SKIMI_FP8_LAUNCH(1, 2); else SKIMI_FP8_LAUNCH(0, 2);
+        }
+        return SKIMI_OK;
+    });
 #undef SKIMI_FP8_LAUNCH
-    if (prof) prof_after(st, 2.0 * M * (double)N * K, (double)M * K + (double)N * K + (double)M * N * (out_dtype == SKIMI_F32 ? 4 : 2));
+    if (rc != SKIMI_OK) return rc;
     SKIMI_LAUNCH_CHECK();
     return SKIMI_OK;
 }

@@ -1171,30 +1171,6 @@ bool gemm_x3dma_eligible(const skimi_gemm_desc* d) {
     return d->M >= (min_tiles <= 1 ? 256 : 4096) && d->N >= 96 && tiles >= min_tiles;
 }
 
-template <int AMODE, int ABL = 0, bool M16 = false>
-static int launch_x3w4_(GemmArgs& a, const X3Rec& pl, hipStream_t st, int phases) {
-    constexpr size_t lds = 10ull * 128 * 128;
-    SKIMI_LDS_OPT_IN((gemm_x3w4_kernel<AMODE, ABL, M16>), lds, "gemm_x3w4");
-    a.ntm = (int)cdiv(a.M, 256);
-    a.ntn = (int)cdiv(a.N, 256) * phases;   // a_mode 3: every output phase has its own column tiles
-    a.splitk = 1;
-    hipLaunchKernelGGL((gemm_x3w4_kernel<AMODE, ABL, M16>), dim3(a.ntm * a.ntn), dim3(256), lds, st, a, pl);
-    SKIMI_LAUNCH_CHECK();
-    return SKIMI_OK;
-}
-
-template <int AMODE, bool M16 = false>
-static int launch_x3w4n_(GemmArgs& a, const X3Rec& pl, hipStream_t st) {
-    constexpr size_t lds = 9ull * 128 * 128;
-    SKIMI_LDS_OPT_IN((gemm_x3w4n_kernel<AMODE, M16>), lds, "gemm_x3w4n");
-    a.ntm = (int)cdiv(a.M, 256);
-    a.ntn = (int)cdiv(a.N, 128);
-    a.splitk = 1;
-    hipLaunchKernelGGL((gemm_x3w4n_kernel<AMODE, M16>), dim3(a.ntm * a.ntn), dim3(256), lds, st, a, pl);
-    SKIMI_LAUNCH_CHECK();
-    return SKIMI_OK;
-}
-
 // MFMA shape of both loops (SKIMI_X3_MFMA = 16 | 32): v_mfma_f32_16x16x32_bf16 by default; read once, or per launch
 // under SKIMI_ENV_DYNAMIC=1 (interleaved A/B timing in one process)
 static bool x3_m16() {
@@ -1202,14 +1178,22 @@ static bool x3_m16() {
     return shape != 32;
 }
 
+// the 256-column loop; a_mode 3: every output phase has its own column tiles
 template <int AMODE, int ABL = 0>
 static int launch_x3w4(GemmArgs& a, const X3Rec& pl, hipStream_t st, int phases = 1) {
-    return x3_m16() ? launch_x3w4_<AMODE, ABL, true>(a, pl, st, phases) : launch_x3w4_<AMODE, ABL, false>(a, pl, st, phases);
+    constexpr size_t lds = 10ull * 128 * 128;
+    const int64_t ntm = cdiv(a.M, 256), ntn = cdiv(a.N, 256) * phases;
+    return x3_m16() ? launch_tiles<gemm_x3w4_kernel<AMODE, ABL, true>>(a, st, lds, 256, ntm, ntn, "gemm_x3w4", pl)
+                    : launch_tiles<gemm_x3w4_kernel<AMODE, ABL, false>>(a, st, lds, 256, ntm, ntn, "gemm_x3w4", pl);
 }
 
+// the 128-column loop (N <= 128)
 template <int AMODE>
 static int launch_x3w4n(GemmArgs& a, const X3Rec& pl, hipStream_t st) {
-    return x3_m16() ? launch_x3w4n_<AMODE, true>(a, pl, st) : launch_x3w4n_<AMODE, false>(a, pl, st);
+    constexpr size_t lds = 9ull * 128 * 128;
+    const int64_t ntm = cdiv(a.M, 256), ntn = cdiv(a.N, 128);
+    return x3_m16() ? launch_tiles<gemm_x3w4n_kernel<AMODE, true>>(a, st, lds, 256, ntm, ntn, "gemm_x3w4n", pl)
+                    : launch_tiles<gemm_x3w4n_kernel<AMODE, false>>(a, st, lds, 256, ntm, ntn, "gemm_x3w4n", pl);
 }
 
 // d->x3_scratch: the A records (4 bytes per element of the A buffer, rows padded to 32) + 256 zero bytes
@@ -1241,28 +1225,18 @@ int gemm_x3dma_launch(GemmArgs& a, const skimi_gemm_desc* d, hipStream_t st) {
         return launch_x3w4n<2>(a, pl, st);
     }
 #ifdef SKIMI_ABLATIONS   // timing ablations (wrong results): only in a -DSKIMI_ABLATIONS build
-    if (a.a_mode == 0) {
-        const int abl = (int)env_once("SKIMI_X3_ABL", 0);
-        switch (abl) {
-            case 1: return launch_x3w4<0, 1>(a, pl, st);
-            case 2: return launch_x3w4<0, 2>(a, pl, st);
-            case 3: return launch_x3w4<0, 3>(a, pl, st);
-            case 5: return launch_x3w4<0, 5>(a, pl, st);
-            case 6: return launch_x3w4<0, 6>(a, pl, st);
-            default: break;
-        }
+#define SKIMI_X3_ABL_GO(AMODE)                                  \
+    switch ((int)env_once("SKIMI_X3_ABL", 0)) {                 \
+        case 1: return launch_x3w4<AMODE, 1>(a, pl, st);        \
+        case 2: return launch_x3w4<AMODE, 2>(a, pl, st);        \
+        case 3: return launch_x3w4<AMODE, 3>(a, pl, st);        \
+        case 5: return launch_x3w4<AMODE, 5>(a, pl, st);        \
+        case 6: return launch_x3w4<AMODE, 6>(a, pl, st);        \
+        default: break;                                         \
     }
-    if (a.a_mode == 2) {
-        const int abl = (int)env_once("SKIMI_X3_ABL", 0);
-        switch (abl) {
-            case 1: return launch_x3w4<2, 1>(a, pl, st);
-            case 2: return launch_x3w4<2, 2>(a, pl, st);
-            case 3: return launch_x3w4<2, 3>(a, pl, st);
-            case 5: return launch_x3w4<2, 5>(a, pl, st);
-            case 6: return launch_x3w4<2, 6>(a, pl, st);
-            default: break;
-        }
-    }
+    if (a.a_mode == 0) SKIMI_X3_ABL_GO(0)
+    if (a.a_mode == 2) SKIMI_X3_ABL_GO(2)
+#undef SKIMI_X3_ABL_GO
 #endif
     if (a.a_mode == 0) return launch_x3w4<0>(a, pl, st);
     if (a.a_mode == 1) return launch_x3w4<1>(a, pl, st);
