@@ -1456,6 +1456,49 @@ int skimi_track_repeat_rows(const float* src, float* dst, int64_t BN, int32_t S,
 /* out [B, S, N] = in [B, N, S]. */
 int skimi_track_bns_to_bsn(const float* in, float* out, int32_t B, int32_t N, int32_t S, void* stream);
 
+/* ---- VideoPose3D small-batch streaming layers, one launch each (csrc/vp3d_stream.hip, csrc/vp3d_dense.hip) ----
+ * The kernels skimi_vp3d_forward runs below 2048 rows of its first layer, exposed singly so that every instantiation
+ * can be tested against a float64 restatement.  Operands are bf16 hi / lo records, x = hi + lo with hi = bf16(x) and
+ * lo = bf16(x - hi), round to nearest even, in fragment-major order:
+ *     [row tile of 16][K slice of 32][hi | lo][kg 0..3][row 0..15][8 elements]           (2 KiB per tile and slice)
+ * element (row, k) of the hi plane sits at 16-bit index ((row / 16) S + k / 32) 1024 + ((k % 32 / 8) 16 + row % 16) 8
+ * + k % 8, S = K / 32, and its lo half 512 further.  Activation rows are b * Lin + l, weight rows output channels,
+ * weight K = tap * C + channel.  Output records have the same layout with N in place of K (N % 32 == 0); rows past the
+ * last of the last tile are unspecified.  A forced choice of 0 leaves that field to the planner; R and the row tiles
+ * always follow from the planner's formulas, and a forced choice the planner could not have made feasible is refused
+ * with SKIMI_ERR_ARG before anything is launched. */
+
+/* w_host [N][K] fp32 on the host (K = taps * C, tap-major) -> dst, Npad * K * 4 bytes on the device, as weight records
+ * with rows N .. Npad - 1 zero; Npad % 16 == 0, K % 32 == 0.  The code path of skimi_vp3d_finalize. */
+int skimi_vp3d_pack_weights(const float* w_host, int32_t N, int32_t Npad, int32_t K, void* dst);
+/* out[b Lout + l][n] = resid[(b resid_L + l + resid_off) C + n] + act(bias[n] + sum_t sum_c W[n][t C + c]
+ * x[b Lin + l + t dil][c]), Lout = Lin - (taps - 1) dil, act = ReLU when relu != 0; resid may be NULL, else N == Npad ==
+ * C.  out_f32 [B Lout][ldo] and / or out_rec (N % 32 == 0).  force_family 1: vp3d_conv_kernel (taps 1 or 3; force_nw 4
+ * or 8, force_ms = row splits per clip), 2: vp3d_mm_kernel (force_ms = row splits of all B Lout rows); force_ct 16 or
+ * 32; force_family 0 (then the other three 0 too): the production plan. */
+int skimi_vp3d_stream_mm(const void* wrec, int32_t Npad, const void* xrec, const float* bias, const float* resid, int32_t resid_L,
+                         int32_t resid_off, float* out_f32, int32_t ldo, void* out_rec, int32_t B, int32_t Lin, int32_t C,
+                         int32_t taps, int32_t dil, int32_t N, int32_t relu, int32_t force_family, int32_t force_ct,
+                         int32_t force_nw, int32_t force_ms, void* stream);
+/* The window kernel of the dense model: the same sum at dilation 1, ReLU, no residual.  force_ta 1 or 2 (16 or 32
+ * channels per workgroup), force_msc = row splits per clip.  Without a forced choice a layer whose window does not fit
+ * the LDS goes to vp3d_mm_kernel, as in the forward. */
+int skimi_vp3d_stream_win(const void* wrec, int32_t Npad, const void* xrec, const float* bias, float* out_f32, int32_t ldo,
+                          void* out_rec, int32_t B, int32_t Lin, int32_t C, int32_t taps, int32_t N, int32_t force_ta,
+                          int32_t force_msc, void* stream);
+/* expand_conv: out[b Lout + l][c] = relu(bias[c] + sum_k W[c][k] x[(b Lin + l) Cin + k]), k < taps * Cin, x [B][Lin][Cin]
+ * fp32, out_f32 [B Lout][C] and out_rec both written; C % 32 == 0.  valu == 0: the MFMA kernel, w = weight records
+ * [C][ldw] with ldw = taps * Cin rounded up to 32 (zero padded), force_ms = row splits per clip.  valu != 0: the fp32
+ * FMA kernel, w = fp32 [C][ldw] on the device, force_ms = row splits of all B Lout rows. */
+int skimi_vp3d_stream_expand(const float* x, const void* w, int32_t ldw, const float* bias, float* out_f32, void* out_rec,
+                             int32_t B, int32_t Lin, int32_t Cin, int32_t taps, int32_t C, int32_t valu, int32_t force_ms,
+                             void* stream);
+/* The plan of the calling thread's last streaming launch (a forward leaves its last layer's): out[0] family (1 conv,
+ * 2 mm, 3 window, 4 MFMA expand, 5 VALU expand; 0: none yet), [1] channels per workgroup (CT, 16 TA, 32), [2] row tiles
+ * RT (conv: halo included; VALU expand: 0), [3] the kernel's TAPS (conv; MFMA expand: 1) or the layer's taps, [4] waves
+ * per workgroup, [5] row splits ms / msc, [6] rows per workgroup R, [7] workgroups.  A refused call leaves it as it was. */
+void skimi_vp3d_last_plan(int32_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,8 @@ ACT_NONE, ACT_RELU, ACT_GELU, ACT_SILU, ACT_SIGMOID = 0, 1, 2, 3, 4
 # skimi_gemm_last_path families (include/skimi.h)
 GEMM_PATH_GENERIC, GEMM_PATH_SPLITK_ORDERED, GEMM_PATH_SPLITK_ATOMIC = 1, 2, 3
 GEMM_PATH_X3DMA_WIDE, GEMM_PATH_X3DMA_NARROW, GEMM_PATH_GEMM256, GEMM_PATH_CONV_WIN = 4, 5, 6, 7
+# skimi_vp3d_last_plan families (include/skimi.h)
+VP3D_CONV, VP3D_MM, VP3D_WIN, VP3D_EXPAND_MFMA, VP3D_EXPAND_VALU = 1, 2, 3, 4, 5
 
 
 class SkimiError(RuntimeError):
@@ -111,6 +113,15 @@ _SIGNATURES = {
     "skimi_vp3d_receptive_field": (C.c_int32, [_vp]),
     "skimi_vp3d_workspace_bytes": (C.c_size_t, [_vp, C.c_int32, C.c_int32]),
     "skimi_vp3d_forward": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, _vp, C.c_size_t, _vp]),
+    "skimi_vp3d_pack_weights": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "skimi_vp3d_stream_mm": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, C.c_int32, _vp, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_int32, C.c_int32, _vp]),
+    "skimi_vp3d_stream_win": (C.c_int, [_vp, C.c_int32, _vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "skimi_vp3d_stream_expand": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "skimi_vp3d_last_plan": (None, [C.POINTER(C.c_int32)]),
     "skimi_pose_to_cameras": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "skimi_unproject_depth": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp]),
     "skimi_triangulate_dlt": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp]),

@@ -85,17 +85,45 @@ bool gemm_fp8_mx_output_ok(int M, int N);   // gemm_fp8_launch accepts out_dtype
 int layernorm_mx_launch(const float* x, int64_t ldx, int64_t rows, int C, const float* gamma, const float* beta, float eps,
                         void* payload, void* scales, hipStream_t st);
 
-// vp3d_stream.hip: the small-batch weight-streaming path of the TemporalModel (one launch per convolution)
+// vp3d_stream.hip: the small-batch weight-streaming path of the TemporalModel (one launch per convolution).
+// Every launcher is check -> plan -> launch: plan_vp3d_*() is a pure function of the layer's shape (and of the
+// SKIMI_VP3D_TAPREUSE / SKIMI_VP3D_PAIRS switches) that names the kernel instantiation and its decomposition; the
+// launch ladders take the plan.  The calling thread's last launched plan is kept for skimi_vp3d_last_plan.
+enum { VP3D_FAM_CONV = 1, VP3D_FAM_MM = 2, VP3D_FAM_WIN = 3, VP3D_FAM_EXPAND_MFMA = 4, VP3D_FAM_EXPAND_VALU = 5 };
+struct Vp3dPlan {
+    int family;   // VP3D_FAM_*; 0 from plan_vp3d_win: no window fits, the layer goes to vp3d_mm_launch
+    int ct;       // channels per workgroup: CT (conv, mm), 16 TA (win), 32 (expand)
+    int rt;       // row tiles of 16 per workgroup, the halo included for conv (0: the VALU expand has none)
+    int taps;     // the TAPS template argument (conv, MFMA expand: 1), else the layer's taps
+    int nw;       // waves per workgroup
+    int ms;       // row splits: per channel tile over all B * Lout rows (mm, VALU expand), per clip (conv, win, MFMA expand)
+    int R;        // output rows per workgroup
+    int grid;     // workgroups
+    int lds;      // bytes of LDS per workgroup
+};
+// A forced choice (tests, A/B timing): a field that is 0 is the planner's.  R and RT always come from the planner's
+// formulas, and a forced choice passes the planner's feasibility conditions or is refused with SKIMI_ERR_ARG.
+struct Vp3dForce {
+    int family;   // mm launcher: VP3D_FAM_CONV or VP3D_FAM_MM (0: plan everything, the other fields are ignored)
+    int ct;       // mm launcher: CT 16 or 32; window launcher: TA 1 or 2
+    int nw;       // conv family: 4 or 8
+    int ms;       // ms / msc
+};
+int plan_vp3d_mm(int Npad, int B, int Lin, int C, int taps, int dil, const Vp3dForce* force, Vp3dPlan* plan);
+int plan_vp3d_expand(int B, int Lin, int Cin, int taps, int C, int valu, int force_ms, Vp3dPlan* plan);
+void vp3d_set_last_plan(const Vp3dPlan& plan);
+const Vp3dPlan& vp3d_last_plan();
 int vp3d_expand_launch(const float* x, const float* w, int ldw, const float* bias, float* out_f32, void* out_rec, int B, int Lin,
-                       int Cin, int taps, int C, hipStream_t st);
+                       int Cin, int taps, int C, hipStream_t st, int force_ms = 0);
 int vp3d_expand_mfma_launch(const float* x, const void* wfrag, int Kpad, const float* bias, float* out_f32, void* out_rec, int B,
-                            int Lin, int Cin, int taps, int C, hipStream_t st);
+                            int Lin, int Cin, int taps, int C, hipStream_t st, int force_ms = 0);
 int vp3d_mm_launch(const void* wrec, int Npad, const void* xrec, const float* bias, const float* resid, int resid_L,
                    int resid_off, float* out_f32, int ldo, void* out_rec, int B, int Lin, int C, int taps, int dil, int N,
-                   int relu, hipStream_t st);
+                   int relu, hipStream_t st, const Vp3dForce* force = nullptr);
 // vp3d_dense.hip: TemporalModel(dense=True)'s wide dilation-1 convs at small batch (the tap-reuse window kernel)
 bool vp3d_window_enabled();
+int plan_vp3d_win(int Npad, int B, int Lin, int C, int taps, const Vp3dForce* force, Vp3dPlan* plan);
 int vp3d_win_launch(const void* wrec, int Npad, const void* xrec, const float* bias, float* out_f32, int ldo, void* out_rec,
-                    int B, int Lin, int C, int taps, int N, hipStream_t st);
+                    int B, int Lin, int C, int taps, int N, hipStream_t st, const Vp3dForce* force = nullptr);
 
 }  // namespace skimi

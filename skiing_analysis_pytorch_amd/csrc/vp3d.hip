@@ -83,8 +83,8 @@ skimi_vp3d* skimi_vp3d_create_ex(int32_t joints_in, int32_t in_features, int32_t
                                  const int32_t* filter_widths, int32_t n_widths, int32_t channels,
                                  int32_t causal, int32_t dense) {
     if (joints_in <= 0 || in_features <= 0 || joints_out <= 0 || !filter_widths || n_widths <= 0 ||
-        channels <= 0 || channels % 64 != 0) {
-        set_error("skimi_vp3d_create: bad arguments (channels must be a multiple of 64)");
+        channels <= 0 || channels % 32 != 0) {
+        set_error("skimi_vp3d_create: bad arguments (channels must be a multiple of 32)");
         return nullptr;
     }
     for (int i = 0; i < n_widths; ++i)
@@ -189,7 +189,8 @@ static unsigned short bf16_rne(float x) {
     const unsigned int r = u + 0x7FFFu + ((u >> 16) & 1u);
     return (unsigned short)(r >> 16);
 }
-static int upload_frag(skimi_vp3d* h, const std::vector<float>& w, int N, int Npad, int K, void** out) {
+// `d`: a device buffer of Npad * K * 4 bytes (hi and lo, bf16 each).
+static int upload_frag(const float* w, int N, int Npad, int K, void* d) {
     const size_t S = (size_t)K / 32;
     std::vector<unsigned short> buf((size_t)Npad * K * 2, 0);
     for (int n = 0; n < N; ++n)
@@ -203,12 +204,16 @@ static int upload_frag(skimi_vp3d* h, const std::vector<float>& w, int N, int Np
             buf[idx] = hi;
             buf[idx + 512] = bf16_rne(x - hf);
         }
-    void* d = nullptr;
-    SKIMI_HIP(hipMalloc(&d, buf.size() * 2));
-    h->allocs.push_back(d);
     SKIMI_HIP(hipMemcpy(d, buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
-    *out = d;
     return SKIMI_OK;
+}
+// the same into a buffer the handle owns
+static int upload_frag(skimi_vp3d* h, const std::vector<float>& w, int N, int Npad, int K, void** out) {
+    void* d = nullptr;
+    SKIMI_HIP(hipMalloc(&d, (size_t)Npad * K * 4));
+    h->allocs.push_back(d);
+    *out = d;
+    return upload_frag(w.data(), N, Npad, K, d);
 }
 
 // fp32-accurate mode: a block's weight matrix [N, K] also as bf16x3 records, for the LDS-DMA kernel that
@@ -399,6 +404,8 @@ int skimi_vp3d_forward(skimi_vp3d* h, const float* x, float* out, int32_t batch,
                                   nullptr, batch, L, C, 1, 1, h->joints_out * 3, 0, st);
         }
     }
+    // the GEMM chain below is only run at the channel counts it was written for
+    SKIMI_CHECK_ARG(C % 64 == 0, "skimi_vp3d_forward: channels %d not a multiple of 64 run on the small-batch bf16x3 path only", C);
     if ((rc = vp3d_im2col_launch(x, a0, batch, frames_in, cin0, h->fw[0], h->k0pad, st))) return rc;
 
     skimi_gemm_desc d;
@@ -516,6 +523,59 @@ int skimi_vp3d_forward(skimi_vp3d* h, const float* x, float* out, int32_t batch,
     d.out = out; d.ldo = h->joints_out * 3;
     if ((rc = gemm_dispatch(&d, st, d.splitk_scratch, d.splitk_scratch_bytes, 0))) return rc;
     return SKIMI_OK;
+}
+
+// ---- single layers of the small-batch streaming path (vp3d_stream.hip, vp3d_dense.hip), for tests ----
+
+int skimi_vp3d_pack_weights(const float* w_host, int32_t N, int32_t Npad, int32_t K, void* dst) {
+    SKIMI_CHECK_ARG(w_host && dst, "skimi_vp3d_pack_weights: null argument");
+    SKIMI_CHECK_ARG(N > 0 && Npad >= N && Npad % 16 == 0 && K > 0 && K % 32 == 0,
+                    "skimi_vp3d_pack_weights: need 0 < N <= Npad, Npad %% 16 == 0, K %% 32 == 0");
+    return upload_frag(w_host, N, Npad, K, dst);
+}
+
+int skimi_vp3d_stream_mm(const void* wrec, int32_t Npad, const void* xrec, const float* bias, const float* resid, int32_t resid_L,
+                         int32_t resid_off, float* out_f32, int32_t ldo, void* out_rec, int32_t B, int32_t Lin, int32_t C,
+                         int32_t taps, int32_t dil, int32_t N, int32_t relu, int32_t force_family, int32_t force_ct,
+                         int32_t force_nw, int32_t force_ms, void* stream) {
+    SKIMI_CHECK_ARG(wrec && xrec && bias && (out_f32 || out_rec), "skimi_vp3d_stream_mm: null argument");
+    SKIMI_CHECK_ARG(B > 0 && Lin > 0 && C > 0 && taps > 0 && dil > 0 && N > 0 && Npad > 0, "skimi_vp3d_stream_mm: sizes must be positive");
+    SKIMI_CHECK_ARG(out_f32 == nullptr || ldo >= N, "skimi_vp3d_stream_mm: ldo %d < N %d", ldo, N);
+    SKIMI_CHECK_ARG(force_family != 0 || (force_ct == 0 && force_nw == 0 && force_ms == 0),
+                    "skimi_vp3d_stream_mm: a forced CT, NW or ms needs the forced family");
+    const Vp3dForce f{force_family, force_ct, force_nw, force_ms};
+    return vp3d_mm_launch(wrec, Npad, xrec, bias, resid, resid_L, resid_off, out_f32, ldo, out_rec, B, Lin, C, taps, dil, N,
+                          relu ? 1 : 0, (hipStream_t)stream, force_family ? &f : nullptr);
+}
+
+int skimi_vp3d_stream_win(const void* wrec, int32_t Npad, const void* xrec, const float* bias, float* out_f32, int32_t ldo,
+                          void* out_rec, int32_t B, int32_t Lin, int32_t C, int32_t taps, int32_t N, int32_t force_ta,
+                          int32_t force_msc, void* stream) {
+    SKIMI_CHECK_ARG(wrec && xrec && bias && (out_f32 || out_rec), "skimi_vp3d_stream_win: null argument");
+    SKIMI_CHECK_ARG(B > 0 && Lin > 0 && C > 0 && taps > 0 && N > 0 && Npad > 0, "skimi_vp3d_stream_win: sizes must be positive");
+    SKIMI_CHECK_ARG(out_f32 == nullptr || ldo >= N, "skimi_vp3d_stream_win: ldo %d < N %d", ldo, N);
+    const Vp3dForce f{VP3D_FAM_WIN, force_ta, 0, force_msc};
+    return vp3d_win_launch(wrec, Npad, xrec, bias, out_f32, ldo, out_rec, B, Lin, C, taps, N, (hipStream_t)stream,
+                           (force_ta || force_msc) ? &f : nullptr);
+}
+
+int skimi_vp3d_stream_expand(const float* x, const void* w, int32_t ldw, const float* bias, float* out_f32, void* out_rec,
+                             int32_t B, int32_t Lin, int32_t Cin, int32_t taps, int32_t C, int32_t valu, int32_t force_ms,
+                             void* stream) {
+    SKIMI_CHECK_ARG(x && w && bias && out_f32 && out_rec, "skimi_vp3d_stream_expand: null argument");
+    SKIMI_CHECK_ARG(B > 0 && Lin > 0 && Cin > 0 && taps > 0 && C > 0, "skimi_vp3d_stream_expand: sizes must be positive");
+    SKIMI_CHECK_ARG(ldw >= taps * Cin, "skimi_vp3d_stream_expand: ldw %d < taps * Cin = %d", ldw, taps * Cin);
+    if (valu)
+        return vp3d_expand_launch(x, (const float*)w, ldw, bias, out_f32, out_rec, B, Lin, Cin, taps, C, (hipStream_t)stream,
+                                  force_ms);
+    return vp3d_expand_mfma_launch(x, w, ldw, bias, out_f32, out_rec, B, Lin, Cin, taps, C, (hipStream_t)stream, force_ms);
+}
+
+void skimi_vp3d_last_plan(int32_t out[8]) {
+    if (!out) return;
+    const Vp3dPlan& p = vp3d_last_plan();
+    out[0] = p.family; out[1] = p.ct; out[2] = p.rt; out[3] = p.taps;
+    out[4] = p.nw; out[5] = p.ms; out[6] = p.R; out[7] = p.grid;
 }
 
 }  // extern "C"

@@ -228,12 +228,28 @@ bool vp3d_window_enabled() {
     return (int)env_switch("SKIMI_VP3D_WINDOW", 1) != 0;
 }
 
-// One dense conv (dilation 1, `taps` taps) + BN (folded) + ReLU: records in, records (and optionally fp32) out.
-int vp3d_win_launch(const void* wrec, int Npad, const void* xrec, const float* bias, float* out_f32, int ldo, void* out_rec,
-                    int B, int Lin, int C, int taps, int N, hipStream_t st) {
+// The window kernel's (TA, RT, msc) for one dense conv; plan->family = 0: no window fits the LDS, the per-tap kernel
+// runs the layer.  A forced (TA = force->ct, msc = force->ms; either 0: the planner's best with the other held) passes
+// the planner's feasibility conditions or is refused.
+int plan_vp3d_win(int Npad, int B, int Lin, int C, int taps, const Vp3dForce* force, Vp3dPlan* plan) {
     const int Lout = Lin - taps + 1;
-    SKIMI_CHECK_ARG(Lout > 0 && taps >= 1 && C % 32 == 0 && Npad % 16 == 0 && Npad >= N, "vp3d_win: bad shape");
-    SKIMI_CHECK_ARG(out_rec == nullptr || N % 32 == 0, "vp3d_win: records output needs N % 32 == 0");
+    const int f_ta = force ? force->ct : 0, f_msc = force ? force->ms : 0;
+    if (f_ta != 0 || f_msc != 0) {
+        SKIMI_CHECK_ARG(f_ta == 0 || f_ta == 1 || f_ta == 2, "vp3d_win forced plan: TA %d is neither 1 nor 2", f_ta);
+        SKIMI_CHECK_ARG(f_ta == 0 || Npad % (16 * f_ta) == 0, "vp3d_win forced plan: Npad %d is not a multiple of 16 TA = %d", Npad,
+                        16 * f_ta);
+        SKIMI_CHECK_ARG(f_msc >= 0 && f_msc <= Lout, "vp3d_win forced plan: msc %d exceeds Lout %d", f_msc, Lout);
+        if (f_msc != 0) {
+            const int rt = (int)cdiv(cdiv(Lout, f_msc), 16);
+            SKIMI_CHECK_ARG(rt <= 8, "vp3d_win forced plan: msc %d needs %d row tiles, at most 8 fit", f_msc, rt);
+            SKIMI_CHECK_ARG(win_nr(rt, taps) <= VP3D_WIN_MAX_NR, "vp3d_win forced plan: a window of %d rows exceeds the %d staged rows",
+                            win_nr(rt, taps), VP3D_WIN_MAX_NR);
+            for (int ta : {1, 2})
+                if (f_ta == ta)
+                    SKIMI_CHECK_ARG(win_lds(ta, rt, taps) <= (size_t)VP3D_WIN_LDS_MAX,
+                                    "vp3d_win forced plan: %zu bytes of LDS exceed %d", win_lds(ta, rt, taps), VP3D_WIN_LDS_MAX);
+        }
+    }
     // (TA, RT, msc): clocks of one workgroup on its CU -- the larger of its MFMA issue on the busiest SIMD (two waves
     // per SIMD, taps round-robin over the eight waves), its LDS reads (ds_read_b128, 4 clk each) and its global bytes
     // (weights + window staging, ~64 B/clk per CU), plus a fixed cost -- times the rounds over the 256 CUs
@@ -243,9 +259,11 @@ int vp3d_win_launch(const void* wrec, int Npad, const void* xrec, const float* b
     double best = 1e30;
     for (int ta : {1, 2}) {
         if (Npad % (16 * ta)) continue;
+        if (f_ta != 0 && ta != f_ta) continue;
         const int nct = Npad / (16 * ta);
         for (int msc = 1; msc <= Lout; ++msc) {
             const int R = (int)cdiv(Lout, msc), rt = (int)cdiv(R, 16);
+            if (f_msc != 0 && msc != f_msc) continue;
             if (rt > 8) continue;
             if (win_nr(rt, taps) > VP3D_WIN_MAX_NR || win_lds(ta, rt, taps) > (size_t)VP3D_WIN_LDS_MAX) continue;
             const long grid = (long)nct * B * msc;
@@ -259,17 +277,39 @@ int vp3d_win_launch(const void* wrec, int Npad, const void* xrec, const float* b
             if (R <= 16) break;   // more row splits only shrink R below one tile
         }
     }
-    if (bt == 0)   // no window fits the LDS (thousands of taps): the per-tap kernel
+    if (bt == 0) {
+        SKIMI_CHECK_ARG(f_ta == 0 && f_msc == 0, "vp3d_win forced plan: no window of %d taps fits the LDS at TA %d, msc %d", taps, f_ta,
+                        f_msc);
+        *plan = Vp3dPlan{0, 0, 0, 0, 0, 0, 0, 0, 0};
+        return SKIMI_OK;
+    }
+    *plan = Vp3dPlan{VP3D_FAM_WIN, 16 * bt, br, taps, 8, bm, (int)cdiv(Lout, bm), (Npad / (16 * bt)) * B * bm,
+                     (int)win_lds(bt, br, taps)};
+    return SKIMI_OK;
+}
+
+// One dense conv (dilation 1, `taps` taps) + BN (folded) + ReLU: records in, records (and optionally fp32) out.
+int vp3d_win_launch(const void* wrec, int Npad, const void* xrec, const float* bias, float* out_f32, int ldo, void* out_rec,
+                    int B, int Lin, int C, int taps, int N, hipStream_t st, const Vp3dForce* force) {
+    const int Lout = Lin - taps + 1;
+    SKIMI_CHECK_ARG(Lout > 0 && taps >= 1 && C % 32 == 0 && Npad % 16 == 0 && Npad >= N, "vp3d_win: bad shape");
+    SKIMI_CHECK_ARG(out_rec == nullptr || N % 32 == 0, "vp3d_win: records output needs N % 32 == 0");
+    Vp3dPlan pl;
+    int rc = plan_vp3d_win(Npad, B, Lin, C, taps, force, &pl);
+    if (rc) return rc;
+    if (pl.family == 0)   // no window fits the LDS (thousands of taps): the per-tap kernel
         return vp3d_mm_launch(wrec, Npad, xrec, bias, nullptr, 0, 0, out_f32, ldo, out_rec, B, Lin, C, taps, 1, N, 1, st);
+    const int bt = pl.ct / 16, br = pl.rt, bm = pl.ms;
     Vp3dWin q;
     q.wrec = (const char*)wrec; q.xrec = (const char*)xrec; q.bias = bias;
     q.out_f32 = out_f32; q.out_rec = (char*)out_rec;
     q.B = B; q.N = N; q.C = C; q.taps = taps; q.Lin = Lin; q.Lout = Lout; q.ldo = ldo;
-    q.msc = bm; q.R = (int)cdiv(Lout, bm);
+    q.msc = bm; q.R = pl.R;
     q.NR = win_nr(br, taps);
-    const int grid = (Npad / (16 * bt)) * B * bm;
-    const size_t lds = win_lds(bt, br, taps);
-    int rc = SKIMI_ERR_ARG;
+    const int grid = pl.grid;
+    const size_t lds = (size_t)pl.lds;
+    vp3d_set_last_plan(pl);
+    rc = SKIMI_ERR_ARG;
 #define SKIMI_VP3D_WIN(TA, RT) \
     if (bt == TA && br == RT) rc = launch_win<TA, RT>(q, grid, lds, st); else
     SKIMI_VP3D_WIN(1, 1) SKIMI_VP3D_WIN(1, 2) SKIMI_VP3D_WIN(1, 3) SKIMI_VP3D_WIN(1, 4)

@@ -487,23 +487,70 @@ static int launch_conv(const Vp3dConv& p, int grid, hipStream_t st) {
 }
 
 // expand_conv on the MFMA kernel: x [B][Lin][Cin] fp32, weights fragment-major [C][Kpad] (Kpad = taps * Cin rounded up to 32)
-int vp3d_expand_mfma_launch(const float* x, const void* wfrag, int Kpad, const float* bias, float* out_f32, void* out_rec, int B,
-                            int Lin, int Cin, int taps, int C, hipStream_t st) {
-    SKIMI_CHECK_ARG(C % 32 == 0 && Kpad % 32 == 0 && Kpad >= taps * Cin, "vp3d_expand: bad shape");
+constexpr int VP3D_EXP_RB = 5;   // rows per thread of vp3d_expand_kernel
+
+static thread_local Vp3dPlan tl_vp3d_plan = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+void vp3d_set_last_plan(const Vp3dPlan& plan) { tl_vp3d_plan = plan; }
+const Vp3dPlan& vp3d_last_plan() { return tl_vp3d_plan; }
+
+// The decomposition of expand_conv.  valu = 0: vp3d_conv_kernel<32, RT, 1, 1> (row splits per clip, force_ms = msc);
+// valu = 1: vp3d_expand_kernel (row splits over all B * Lout rows, force_ms = ms).  force_ms = 0: the planner's.
+int plan_vp3d_expand(int B, int Lin, int Cin, int taps, int C, int valu, int force_ms, Vp3dPlan* plan) {
     const int Lout = Lin - taps + 1;
+    SKIMI_CHECK_ARG(B > 0 && Cin > 0 && taps > 0 && Lout > 0 && C > 0 && C % 32 == 0, "vp3d_expand: bad shape");
+    SKIMI_CHECK_ARG(force_ms >= 0, "vp3d_expand: forced row splits %d are negative", force_ms);
     const int nt = C / 32;
-    int msc = (int)std::max<long>(1, 256 / std::max<long>(1, (long)nt * B));
-    msc = std::min(msc, Lout);
-    while (cdiv(cdiv(Lout, msc), 16) > 5) ++msc;
+    if (!valu) {
+        int msc;
+        if (force_ms) {
+            msc = force_ms;
+            SKIMI_CHECK_ARG(msc <= Lout, "vp3d_expand: forced msc %d exceeds Lout %d", msc, Lout);
+            SKIMI_CHECK_ARG(cdiv(cdiv(Lout, msc), 16) <= 5, "vp3d_expand: forced msc %d needs %d row tiles, at most 5 fit", msc,
+                            (int)cdiv(cdiv(Lout, msc), 16));
+        } else {
+            msc = (int)std::max<long>(1, 256 / std::max<long>(1, (long)nt * B));
+            msc = std::min(msc, Lout);
+            while (cdiv(cdiv(Lout, msc), 16) > 5) ++msc;
+        }
+        const int R = (int)cdiv(Lout, msc), rt = (int)cdiv(R, 16);
+        *plan = Vp3dPlan{VP3D_FAM_EXPAND_MFMA, 32, rt, 1, 8, msc, R, nt * B * msc, 8 * 2 * rt * 1024};
+        return SKIMI_OK;
+    }
+    const int M = B * Lout;
+    int ms;
+    if (force_ms) {
+        ms = force_ms;
+        SKIMI_CHECK_ARG(ms <= M, "vp3d_expand: forced ms %d exceeds the %d rows", ms, M);
+        SKIMI_CHECK_ARG(cdiv(M, ms) <= 8 * VP3D_EXP_RB, "vp3d_expand: forced ms %d leaves %d rows per workgroup, at most %d fit", ms,
+                        (int)cdiv(M, ms), 8 * VP3D_EXP_RB);
+    } else {
+        // rows per workgroup <= 8 * RB (8 row groups x RB rows per thread)
+        ms = (int)std::max<long>(1, std::min<long>(cdiv(M, 8), 256 / nt));
+        ms = (int)std::max<long>(ms, cdiv(M, 8 * VP3D_EXP_RB));
+    }
+    const int R = (int)cdiv(M, ms);
+    const size_t lds = ((size_t)32 * ((taps * Cin) | 1) + (size_t)R * taps * Cin) * 4;
+    SKIMI_CHECK_ARG(lds <= 64 * 1024, "vp3d_expand: receptive window too wide");
+    *plan = Vp3dPlan{VP3D_FAM_EXPAND_VALU, 32, 0, taps, 4, ms, R, nt * ms, (int)lds};
+    return SKIMI_OK;
+}
+
+int vp3d_expand_mfma_launch(const float* x, const void* wfrag, int Kpad, const float* bias, float* out_f32, void* out_rec, int B,
+                            int Lin, int Cin, int taps, int C, hipStream_t st, int force_ms) {
+    SKIMI_CHECK_ARG(C % 32 == 0 && Kpad % 32 == 0 && Kpad >= taps * Cin, "vp3d_expand: bad shape");
+    Vp3dPlan pl;
+    int rc = plan_vp3d_expand(B, Lin, Cin, taps, C, 0, force_ms, &pl);
+    if (rc) return rc;
+    const int Lout = Lin - taps + 1;
     Vp3dConv q;
     q.wrec = (const char*)wfrag; q.xrec = (const char*)x; q.bias = bias; q.resid = nullptr;
     q.out_f32 = out_f32; q.out_rec = (char*)out_rec;
     q.B = B; q.N = C; q.C = Kpad; q.dil = 0; q.Lin = Lin; q.Lout = Lout;
     q.resid_L = 0; q.resid_off = 0; q.ldo = C; q.relu = 1;
-    q.msc = msc; q.R = (int)cdiv(Lout, msc);
+    q.msc = pl.ms; q.R = pl.R;
     q.xstride = Cin; q.kvalid = taps * Cin;
-    const int rt = (int)cdiv(q.R, 16), grid = nt * B * msc;
-    int rc;
+    const int rt = pl.rt, grid = pl.grid;
+    vp3d_set_last_plan(pl);
     if (rt == 1) rc = launch_conv<32, 1, 1, 1>(q, grid, st);
     else if (rt == 2) rc = launch_conv<32, 2, 1, 1>(q, grid, st);
     else if (rt == 3) rc = launch_conv<32, 3, 1, 1>(q, grid, st);
@@ -517,8 +564,7 @@ int vp3d_expand_mfma_launch(const float* x, const void* wfrag, int Kpad, const f
 // expand_conv: out[m][c] = relu(bias[c] + sum_k W[c][k] x[b][l .. l + taps - 1][:] (k = tap * Cin + ci)), exact fp32.
 // Workgroup = 32 channels x R rows.  The 32 weight rows (odd stride: conflict-free) and the R + taps - 1 input rows
 // of the workgroup sit in LDS; the window of output row l is `taps * Cin` consecutive floats starting at row l.
-// A thread owns one channel and up to RB rows (register blocking: one weight read feeds RB FMAs).
-constexpr int VP3D_EXP_RB = 5;
+// A thread owns one channel and up to RB = VP3D_EXP_RB rows (register blocking: one weight read feeds RB FMAs).
 __global__ __launch_bounds__(256) void vp3d_expand_kernel(const float* __restrict__ x, const float* __restrict__ w, int ldw,
                                                           const float* __restrict__ bias, float* __restrict__ out_f32,
                                                           char* __restrict__ out_rec, int M, int C, int Cin, int taps, int Lin,
@@ -576,17 +622,16 @@ __global__ __launch_bounds__(256) void vp3d_expand_kernel(const float* __restric
 }
 
 int vp3d_expand_launch(const float* x, const float* w, int ldw, const float* bias, float* out_f32, void* out_rec, int B, int Lin,
-                       int Cin, int taps, int C, hipStream_t st) {
+                       int Cin, int taps, int C, hipStream_t st, int force_ms) {
     SKIMI_CHECK_ARG(C % 32 == 0, "vp3d_expand: channels must be a multiple of 32");
+    Vp3dPlan pl;
+    const int rc = plan_vp3d_expand(B, Lin, Cin, taps, C, 1, force_ms, &pl);
+    if (rc) return rc;
     const int Lout = Lin - taps + 1, M = B * Lout;
-    const int nt = C / 32;
-    // rows per workgroup <= 8 * RB (8 row groups x RB rows per thread)
-    int ms = (int)std::max<long>(1, std::min<long>(cdiv(M, 8), 256 / nt));
-    ms = (int)std::max<long>(ms, cdiv(M, 8 * VP3D_EXP_RB));
-    const int R = (int)cdiv(M, ms);
-    const size_t lds = ((size_t)32 * ((taps * Cin) | 1) + (size_t)R * taps * Cin) * 4;
-    SKIMI_CHECK_ARG(lds <= 64 * 1024, "vp3d_expand: receptive window too wide");
-    hipLaunchKernelGGL(vp3d_expand_kernel, dim3(nt * ms), dim3(256), lds, st, x, w, ldw, bias, out_f32, (char*)out_rec, M, C, Cin,
+    const int ms = pl.ms, R = pl.R;
+    const size_t lds = (size_t)pl.lds;
+    vp3d_set_last_plan(pl);
+    hipLaunchKernelGGL(vp3d_expand_kernel, dim3(pl.grid), dim3(256), lds, st, x, w, ldw, bias, out_f32, (char*)out_rec, M, C, Cin,
                        taps, Lin, Lout, R, ms);
     SKIMI_LAUNCH_CHECK();
     return SKIMI_OK;
@@ -597,14 +642,56 @@ static void launch_mm(const Vp3dMM& p, int grid, hipStream_t st) {
     hipLaunchKernelGGL((vp3d_mm_kernel<CT, RT>), dim3(grid), dim3(512), 0, st, p);
 }
 
-// One convolution of the chain.  Npad = rows of the weight records (N rounded up to 16).
-int vp3d_mm_launch(const void* wrec, int Npad, const void* xrec, const float* bias, const float* resid, int resid_L,
-                   int resid_off, float* out_f32, int ldo, void* out_rec, int B, int Lin, int C, int taps, int dil, int N,
-                   int relu, hipStream_t st) {
+// A forced (family, CT, NW, ms / msc) of one convolution, through the feasibility conditions of the planner below and
+// of the two kernels; R and RT by the planner's formulas.  force.ms = 0: the planner's split for that (family, CT, NW).
+static int forced_vp3d_mm(int Npad, int B, int Lout, int taps, long halo, const Vp3dForce& f, Vp3dPlan* plan) {
+    const int ct = f.ct, M = B * Lout;
+    SKIMI_CHECK_ARG(f.family == VP3D_FAM_CONV || f.family == VP3D_FAM_MM, "vp3d forced plan: family %d is neither conv (%d) nor mm (%d)",
+                    f.family, VP3D_FAM_CONV, VP3D_FAM_MM);
+    SKIMI_CHECK_ARG(ct == 16 || ct == 32, "vp3d forced plan: CT %d is neither 16 nor 32", ct);
+    SKIMI_CHECK_ARG(Npad % ct == 0, "vp3d forced plan: Npad %d is not a multiple of CT %d", Npad, ct);
+    SKIMI_CHECK_ARG(f.ms >= 0, "vp3d forced plan: row splits %d are negative", f.ms);
+    const int nt = Npad / ct;
+    if (f.family == VP3D_FAM_CONV) {
+        const int nw = f.nw ? f.nw : 8, rtmax = 5;
+        SKIMI_CHECK_ARG(taps == 1 || taps == 3, "vp3d forced plan: the conv family runs 1 or 3 taps, not %d", taps);
+        SKIMI_CHECK_ARG(nw == 4 || nw == 8, "vp3d forced plan: NW %d is neither 4 nor 8", nw);
+        SKIMI_CHECK_ARG(taps != 3 || ct == 16, "vp3d forced plan: 3 taps need CT 16, not %d", ct);
+        SKIMI_CHECK_ARG(halo + 1 <= 16 * rtmax, "vp3d forced plan: a halo of %ld rows does not fit %d row tiles", halo, rtmax);
+        const long cap = nw == 4 ? 512 : 256;
+        int msc = f.ms;
+        if (msc == 0) {
+            msc = (int)std::max<long>(1, cap / std::max<long>(1, (long)nt * B));
+            msc = std::min(msc, Lout);
+            while (cdiv(cdiv(Lout, msc) + halo, 16) > rtmax) ++msc;
+        }
+        SKIMI_CHECK_ARG(msc <= Lout, "vp3d forced plan: msc %d exceeds Lout %d", msc, Lout);
+        const int R = (int)cdiv(Lout, msc), rt = (int)cdiv(R + halo, 16);
+        SKIMI_CHECK_ARG(rt <= rtmax, "vp3d forced plan: msc %d needs %d row tiles (halo %ld), at most %d fit", msc, rt, halo, rtmax);
+        SKIMI_CHECK_ARG(nw != 4 || taps * (ct / 16) * rt * 4 <= 80,
+                        "vp3d forced plan: the K-partials of a 4-wave pair, 2 x %d KiB, exceed the LDS", taps * (ct / 16) * rt * 4);
+        *plan = Vp3dPlan{VP3D_FAM_CONV, ct, rt, taps, nw, msc, R, nt * B * msc, nw * taps * (ct / 16) * rt * 1024};
+        return SKIMI_OK;
+    }
+    SKIMI_CHECK_ARG(f.nw == 0 || f.nw == 8, "vp3d forced plan: the mm family has 8 waves, not %d", f.nw);
+    const int rtmax = ct == 16 ? 5 : 4;
+    int ms = f.ms;
+    if (ms == 0) {
+        ms = (int)std::max<long>(1, std::min<long>(256 / std::max(1, std::min(nt, 256)), cdiv(M, 1)));
+        while (cdiv(cdiv(M, ms), 16) > rtmax) ++ms;
+    }
+    SKIMI_CHECK_ARG(ms <= M, "vp3d forced plan: ms %d exceeds the %d rows", ms, M);
+    const int R = (int)cdiv(M, ms), rt = (int)cdiv(R, 16);
+    SKIMI_CHECK_ARG(rt <= rtmax, "vp3d forced plan: ms %d needs %d row tiles, at most %d fit at CT %d", ms, rt, rtmax, ct);
+    *plan = Vp3dPlan{VP3D_FAM_MM, ct, rt, taps, 8, ms, R, nt * ms, 8 * (ct / 16) * rt * 1024};
+    return SKIMI_OK;
+}
+
+// The kernel and decomposition of one convolution of the chain.  Npad = rows of the weight records.
+int plan_vp3d_mm(int Npad, int B, int Lin, int C, int taps, int dil, const Vp3dForce* force, Vp3dPlan* plan) {
     const int Lout = Lin - (taps - 1) * dil, M = B * Lout;
-    SKIMI_CHECK_ARG(Lout > 0 && C % 32 == 0 && Npad % 16 == 0 && Npad >= N, "vp3d_mm: bad shape");
-    SKIMI_CHECK_ARG(out_rec == nullptr || N % 32 == 0, "vp3d_mm: records output needs N % 32 == 0");
     const long K = (long)taps * C, halo = (long)(taps - 1) * dil;
+    if (force && force->family != 0) return forced_vp3d_mm(Npad, B, Lout, taps, halo, *force, plan);
     // First choice: vp3d_conv_kernel (activations loaded once for all taps).  Candidates: taps = 1 -> CT 16 or 32, up to
     // 4 row tiles; taps = 3 -> CT 16, up to 5 row tiles INCLUDING the 2 d halo.  Cost = bytes a workgroup loads x rounds.
     const int use_conv = (int)env_once("SKIMI_VP3D_TAPREUSE", 1);
@@ -657,15 +744,41 @@ int vp3d_mm_launch(const void* wrec, int Npad, const void* xrec, const float* bi
         }
     }
     if (cv_ct != 0 && cv_cost <= best) {
+        *plan = Vp3dPlan{VP3D_FAM_CONV, cv_ct, cv_rt, taps, cv_nw, cv_msc, (int)cdiv(Lout, cv_msc), (Npad / cv_ct) * B * cv_msc,
+                         cv_nw * taps * (cv_ct / 16) * cv_rt * 1024};
+        return SKIMI_OK;
+    }
+    SKIMI_CHECK_ARG(best_ct != 0, "vp3d_mm: no tiling");
+    *plan = Vp3dPlan{VP3D_FAM_MM, best_ct, best_rt, taps, 8, best_ms, (int)cdiv(M, best_ms), (Npad / best_ct) * best_ms,
+                     8 * (best_ct / 16) * best_rt * 1024};
+    return SKIMI_OK;
+}
+
+// One convolution of the chain: check, plan (or the forced choice), launch.
+int vp3d_mm_launch(const void* wrec, int Npad, const void* xrec, const float* bias, const float* resid, int resid_L,
+                   int resid_off, float* out_f32, int ldo, void* out_rec, int B, int Lin, int C, int taps, int dil, int N,
+                   int relu, hipStream_t st, const Vp3dForce* force) {
+    const int Lout = Lin - (taps - 1) * dil, M = B * Lout;
+    SKIMI_CHECK_ARG(Lout > 0 && C % 32 == 0 && Npad % 16 == 0 && Npad >= N, "vp3d_mm: bad shape");
+    SKIMI_CHECK_ARG(out_rec == nullptr || N % 32 == 0, "vp3d_mm: records output needs N % 32 == 0");
+    // the residual is read as float4 at every channel quad of a row of C floats
+    SKIMI_CHECK_ARG(resid == nullptr || (N == C && Npad == N && resid_off >= 0 && Lout + resid_off <= resid_L),
+                    "vp3d_mm: a residual needs N == Npad == C and Lout + resid_off <= resid_L");
+    Vp3dPlan pl;
+    int rc = plan_vp3d_mm(Npad, B, Lin, C, taps, dil, force, &pl);
+    if (rc) return rc;
+    if (pl.family == VP3D_FAM_CONV) {
+        const int cv_ct = pl.ct, cv_rt = pl.rt, cv_nw = pl.nw;
         Vp3dConv q;
         q.wrec = (const char*)wrec; q.xrec = (const char*)xrec; q.bias = bias; q.resid = resid;
         q.out_f32 = out_f32; q.out_rec = (char*)out_rec;
         q.B = B; q.N = N; q.C = C; q.dil = dil; q.Lin = Lin; q.Lout = Lout;
         q.resid_L = resid_L; q.resid_off = resid_off; q.ldo = ldo; q.relu = relu;
-        q.msc = cv_msc; q.R = (int)cdiv(Lout, cv_msc);
+        q.msc = pl.ms; q.R = pl.R;
         q.xstride = 0; q.kvalid = 0;
-        const int grid = (Npad / cv_ct) * B * cv_msc;
-        int rc = SKIMI_ERR_ARG;
+        const int grid = pl.grid;
+        vp3d_set_last_plan(pl);
+        rc = SKIMI_ERR_ARG;
 #define SKIMI_VP3D_CONV(CT, RT, TAPS)                                                                   \
     if (cv_ct == CT && cv_rt == RT && taps == TAPS)                                                     \
         rc = cv_nw == 4 ? launch_conv<CT, RT, TAPS, 0, 4>(q, grid, st) : launch_conv<CT, RT, TAPS>(q, grid, st); \
@@ -679,18 +792,19 @@ int vp3d_mm_launch(const void* wrec, int Npad, const void* xrec, const float* bi
         SKIMI_LAUNCH_CHECK();
         return SKIMI_OK;
     }
-    SKIMI_CHECK_ARG(best_ct != 0, "vp3d_mm: no tiling");
+    const int best_ct = pl.ct, best_rt = pl.rt;
     Vp3dMM p;
     p.wrec = (const char*)wrec; p.xrec = (const char*)xrec; p.bias = bias; p.resid = resid;
     p.out_f32 = out_f32; p.out_rec = (char*)out_rec;
     p.M = M; p.N = N; p.C = C; p.taps = taps; p.dil = dil; p.Lin = Lin; p.Lout = Lout;
     p.resid_L = resid_L; p.resid_off = resid_off; p.ldo = ldo; p.relu = relu;
-    p.ms = best_ms; p.R = (int)cdiv(M, best_ms);
+    p.ms = pl.ms; p.R = pl.R;
     p.abl = 0;
 #ifdef SKIMI_ABLATIONS
     p.abl = getenv("SKIMI_VP3D_ABL") ? atoi(getenv("SKIMI_VP3D_ABL")) : 0;
 #endif
-    const int grid = (Npad / best_ct) * best_ms;
+    const int grid = pl.grid;
+    vp3d_set_last_plan(pl);
 #define SKIMI_VP3D_CASE(CT, RT) if (best_ct == CT && best_rt == RT) { launch_mm<CT, RT>(p, grid, st); } else
     SKIMI_VP3D_CASE(16, 1) SKIMI_VP3D_CASE(16, 2) SKIMI_VP3D_CASE(16, 3) SKIMI_VP3D_CASE(16, 4) SKIMI_VP3D_CASE(16, 5)
     SKIMI_VP3D_CASE(32, 1) SKIMI_VP3D_CASE(32, 2) SKIMI_VP3D_CASE(32, 3) SKIMI_VP3D_CASE(32, 4)

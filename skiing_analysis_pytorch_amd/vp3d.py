@@ -181,3 +181,41 @@ def lift_clip(model: TemporalModel, keypoints_px: np.ndarray, w: int, h: int, au
     if augment:
         pred = merge_augmented(pred)
     return pred.squeeze(0).cpu().numpy()
+
+
+# ---- single layers of the small-batch streaming path (include/skimi.h: "VideoPose3D small-batch streaming
+# layers"): thin wrappers over the C entries; tensors are device tensors, records are uint8 / int16 buffers ------
+def pack_weights(w: torch.Tensor, npad: int, device="cuda") -> torch.Tensor:
+    """w [N, K] fp32 on the host -> weight records [npad * K * 2] int16 on the device (skimi_vp3d_pack_weights)."""
+    w = w.detach().to("cpu", torch.float32).contiguous()
+    n, k = w.shape
+    dst = torch.empty(npad * k * 2, dtype=torch.int16, device=device)
+    check(lib().skimi_vp3d_pack_weights(w.data_ptr(), n, npad, k, ptr(dst)), "skimi_vp3d_pack_weights")
+    return dst
+
+
+def stream_mm(wrec, npad, xrec, bias, out_f32, ldo, out_rec, B, Lin, C, taps, dil, N, relu=True, resid=None, resid_L=0,
+              resid_off=0, force=(0, 0, 0, 0)):
+    """skimi_vp3d_stream_mm; force = (family, CT, NW, ms), zeros: the production plan."""
+    check(lib().skimi_vp3d_stream_mm(ptr(wrec), npad, ptr(xrec), ptr(bias), ptr(resid), resid_L, resid_off, ptr(out_f32), ldo,
+                                     ptr(out_rec), B, Lin, C, taps, dil, N, int(relu), *force, _lib.current_stream()),
+          "skimi_vp3d_stream_mm")
+
+
+def stream_win(wrec, npad, xrec, bias, out_f32, ldo, out_rec, B, Lin, C, taps, N, force=(0, 0)):
+    """skimi_vp3d_stream_win; force = (TA, msc)."""
+    check(lib().skimi_vp3d_stream_win(ptr(wrec), npad, ptr(xrec), ptr(bias), ptr(out_f32), ldo, ptr(out_rec), B, Lin, C, taps,
+                                      N, *force, _lib.current_stream()), "skimi_vp3d_stream_win")
+
+
+def stream_expand(x, w, ldw, bias, out_f32, out_rec, B, Lin, Cin, taps, C, valu=False, force_ms=0):
+    """skimi_vp3d_stream_expand; w: weight records (MFMA) or fp32 [C, ldw] (valu)."""
+    check(lib().skimi_vp3d_stream_expand(ptr(x), ptr(w), ldw, ptr(bias), ptr(out_f32), ptr(out_rec), B, Lin, Cin, taps, C,
+                                         int(valu), force_ms, _lib.current_stream()), "skimi_vp3d_stream_expand")
+
+
+def last_plan() -> tuple:
+    """(family, CT | 16 TA | 32, RT, TAPS, NW, ms | msc, R, grid) of this thread's last streaming launch."""
+    out = (C.c_int32 * 8)()
+    lib().skimi_vp3d_last_plan(out)
+    return tuple(out)
