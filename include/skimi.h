@@ -293,7 +293,8 @@ int skimi_qknorm_rope(void* qkv, int32_t dtype, int64_t tokens, int32_t heads,
 /* Scaled-dot-product attention, no mask, softmax scale 1/sqrt(head_dim)
  * (F.scaled_dot_product_attention, attention.py:60-61).
  * qkv: [batch*seq, 3, heads, head_dim]; out: [batch*seq, heads*head_dim], same dtype.
- * dtype bf16 + head_dim 64 runs the MFMA flash kernel; f32 runs the exact fp32 kernel. */
+ * dtype bf16 + head_dim 64 runs the MFMA flash kernel; f32 runs the exact fp32 kernel; any other dtype is
+ * SKIMI_ERR_ARG (in all three entries; messages name `skimi_attention:` whichever entry was called). */
 int skimi_attention(const void* qkv, void* out, int32_t dtype, int32_t batch, int32_t seq,
                     int32_t heads, int32_t head_dim, void* stream);
 /* The same with the output type named: out_dtype == dtype, or SKIMI_F16 with dtype SKIMI_BF16 -- the form
@@ -331,6 +332,13 @@ int skimi_attention_ex(const void* qkv, void* out, int32_t dtype, int32_t out_dt
                        uint64_t x3_scratch_bytes, int32_t* out_records, void* stream);
 /* bytes of x3_scratch the bf16x3 attention kernel needs for `tokens` packed qkv rows of `row_elems` f32 each */
 uint64_t skimi_attention_x3_scratch_bytes(int64_t tokens, int64_t row_elems);
+/* The plan of the calling thread's last attention launch (any entry above, skimi_attention_f32_strided, or a forward,
+ * which leaves its last launch's): out[0] family (1 exact f32, 2 bf16x3, 3 bf16 32 queries per wave, 4 bf16 64 queries
+ * per wave; 0: none yet), [1] queries per workgroup (128, or 256 for family 4), [2] output form (0 rows in the input
+ * type, 1 fp16 rows, 2 MXFP8, 3 bf16x3 records), [3] q_prescaled as honoured (0 for f32 input), [4] workgroups,
+ * [5] the exact-f32 kernel's HD template argument (64 or 128; 64 for the other families), [6] bytes of dynamic LDS
+ * (SKIMI_ATTN_LDSPAD), [7] 0.  A refused call leaves it as it was. */
+void skimi_attention_last_plan(int32_t out[8]);
 
 /* The LayerNorm and fp32 attention launches with every argument the forward gives them (vggt_dpt.hip's DPT heads,
  * vggt_track.hip's run_mha), for kernel-level tests.

@@ -98,6 +98,7 @@ _SIGNATURES = {
     "skimi_attention_ex": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      _vp, C.c_uint64, C.POINTER(C.c_int32), _vp]),
     "skimi_attention_x3_scratch_bytes": (C.c_uint64, [C.c_int64, C.c_int64]),
+    "skimi_attention_last_plan": (None, [C.POINTER(C.c_int32)]),
     "skimi_layernorm_ex": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, C.c_float, _vp,
                                      C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, _vp]),
     "skimi_attention_f32_strided": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),

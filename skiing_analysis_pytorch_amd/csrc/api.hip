@@ -209,24 +209,26 @@ int skimi_qknorm_rope(void* qkv, int32_t dtype, int64_t tokens, int32_t heads, c
                               rope_sin, rope_npos, (hipStream_t)stream);
 }
 
+// skimi_attention, skimi_attention_out, skimi_attention_ex: one request (kernels.h), one body (attention.hip)
+static int attention_entry(const void* qkv, void* out, int32_t dtype, int32_t out_dtype, int32_t batch, int32_t seq, int32_t heads,
+                           int32_t head_dim, int32_t q_prescaled, void* x3_scratch, uint64_t x3_scratch_bytes,
+                           int32_t* out_records, void* stream) {
+    AttnRequest r = {};
+    r.qkv = qkv; r.out = out; r.dtype = dtype; r.out_dtype = out_dtype;
+    r.batch = batch; r.seq = seq; r.heads = heads; r.head_dim = head_dim; r.q_prescaled = q_prescaled;
+    r.x3_scratch = x3_scratch; r.x3_scratch_bytes = (size_t)x3_scratch_bytes;
+    r.want_records = out_records != nullptr && *out_records != 0;
+    return attention_launch(r, (hipStream_t)stream, out_records);
+}
+
 int skimi_attention(const void* qkv, void* out, int32_t dtype, int32_t batch, int32_t seq,
                     int32_t heads, int32_t head_dim, void* stream) {
-    return attention_launch(qkv, out, dtype, batch, seq, heads, head_dim, (hipStream_t)stream);
+    return attention_entry(qkv, out, dtype, dtype, batch, seq, heads, head_dim, 0, nullptr, 0, nullptr, stream);
 }
 
 int skimi_attention_out(const void* qkv, void* out, int32_t dtype, int32_t out_dtype, int32_t batch, int32_t seq,
                         int32_t heads, int32_t head_dim, void* stream) {
-    if (out_dtype == SKIMI_FP8MX) {   // payload [tokens][Kp], then the scales [tokens][Kp / 32], Kp = heads * head_dim up to 128
-        SKIMI_CHECK_ARG(out && batch > 0 && seq > 0 && attention_mx_output_ok(dtype, heads, head_dim),
-                        "skimi_attention_out: MXFP8 rows need bf16 q / k / v, head_dim 64 and an even number of heads");
-        const size_t Kp = align_up((size_t)heads * head_dim, 128);
-        return attention_launch(qkv, nullptr, dtype, batch, seq, heads, head_dim, (hipStream_t)stream, 0, nullptr, 0, nullptr, 0,
-                                out, (char*)out + (size_t)batch * seq * Kp);
-    }
-    SKIMI_CHECK_ARG(out_dtype == dtype || (dtype == SKIMI_BF16 && out_dtype == SKIMI_F16),
-                    "skimi_attention_out: out_dtype is dtype, SKIMI_F16 or SKIMI_FP8MX for bf16 q / k / v (got %d -> %d)", dtype, out_dtype);
-    return attention_launch(qkv, out, dtype, batch, seq, heads, head_dim, (hipStream_t)stream, 0, nullptr, 0, nullptr,
-                            out_dtype == SKIMI_F16 && dtype == SKIMI_BF16);
+    return attention_entry(qkv, out, dtype, out_dtype, batch, seq, heads, head_dim, 0, nullptr, 0, nullptr, stream);
 }
 
 // the two calls of the block forward (vggt_block.hip), with its arguments, for kernel-level tests
@@ -241,18 +243,15 @@ int skimi_qknorm_rope_scaled(void* qkv, int32_t dtype, int64_t tokens, int32_t h
 int skimi_attention_ex(const void* qkv, void* out, int32_t dtype, int32_t out_dtype, int32_t batch, int32_t seq,
                        int32_t heads, int32_t head_dim, int32_t q_prescaled, void* x3_scratch,
                        uint64_t x3_scratch_bytes, int32_t* out_records, void* stream) {
-    if (out_dtype == SKIMI_FP8MX) {   // the layout of skimi_attention_out
-        if (out_records) *out_records = 0;
-        SKIMI_CHECK_ARG(out && batch > 0 && seq > 0 && attention_mx_output_ok(dtype, heads, head_dim),
-                        "skimi_attention_ex: MXFP8 rows need bf16 q / k / v, head_dim 64 and an even number of heads");
-        const size_t Kp = align_up((size_t)heads * head_dim, 128);
-        return attention_launch(qkv, nullptr, dtype, batch, seq, heads, head_dim, (hipStream_t)stream, q_prescaled, nullptr, 0,
-                                nullptr, 0, out, (char*)out + (size_t)batch * seq * Kp);
-    }
-    SKIMI_CHECK_ARG(out_dtype == dtype || (dtype == SKIMI_BF16 && out_dtype == SKIMI_F16),
-                    "skimi_attention_ex: out_dtype is dtype, SKIMI_F16 or SKIMI_FP8MX for bf16 q / k / v (got %d -> %d)", dtype, out_dtype);
-    return attention_launch(qkv, out, dtype, batch, seq, heads, head_dim, (hipStream_t)stream, q_prescaled, x3_scratch,
-                            (size_t)x3_scratch_bytes, out_records, out_dtype == SKIMI_F16 && dtype == SKIMI_BF16);
+    return attention_entry(qkv, out, dtype, out_dtype, batch, seq, heads, head_dim, q_prescaled, x3_scratch, x3_scratch_bytes,
+                           out_records, stream);
+}
+
+void skimi_attention_last_plan(int32_t out[8]) {
+    if (!out) return;
+    const AttnPlan& p = attention_last_plan();
+    const int32_t v[8] = {p.family, p.queries, p.out_form, p.q_prescaled, (int32_t)p.grid, p.hd, p.lds_pad, 0};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
 }
 
 uint64_t skimi_attention_x3_scratch_bytes(int64_t tokens, int64_t row_elems) {

@@ -3,8 +3,8 @@
 // vggt/vggt/models/aggregator.py:260-305 via F.scaled_dot_product_attention
 // (vggt/vggt/layers/attention.py:60-61), and the 24 DINOv2 blocks.
 //
-// This file: the launcher (attention_bf16_launch picks the kernel: the 64-query-per-wave kernel of
-// attention_q64.hip by default) and the FIRST kernel, kept for A/B timing (SKIMI_ATTN_Q64=0):
+// This file: the FIRST kernel, kept for A/B timing (SKIMI_ATTN_Q64=0; the 64-query-per-wave kernel of attention_q64.hip
+// is the default), and that kernel's launcher, nothing else: what runs is decided in attention.hip (plan_attention).
 // per workgroup 4 waves x 32 queries; K/V tiles of 64 keys double-buffered in LDS by LDS-DMA, one
 // barrier per tile, row sums on the matrix pipe (ones-operand MFMAs).
 // Products are "swapped" so each softmax row is lane-local:
@@ -17,7 +17,6 @@
 
 #include "attention_tile.h"
 #include "common.h"
-#include "env.h"
 #include "kernels.h"
 
 namespace skimi {
@@ -201,110 +200,21 @@ __global__ __launch_bounds__(256, 4) void attn_bf16_kernel(const AttnArgs a, int
     }
 }
 
-static int q64_enabled() {   // SKIMI_ATTN_Q64: 1 (default) the 64-query-per-wave kernel; 0 this file's 32-query kernel
-    return (int)env_once("SKIMI_ATTN_Q64", 1);
-}
-
-// SKIMI_ATTN_MX=0: SKIMI_PREC_FP8 quantises the bf16 output rows in a separate pass instead (A/B timing, tests)
-bool attention_mx_output_ok(int dtype, int heads, int head_dim) {
-    const int use_mx = (int)env_switch("SKIMI_ATTN_MX", 1);
-    return use_mx && dtype == SKIMI_BF16 && head_dim == 64 && heads % 2 == 0 && q64_enabled() != 0;
-}
-
-int attention_bf16_launch(const AttnArgs& a, hipStream_t st) {
-    SKIMI_CHECK_ARG(a.q && a.k && a.v && (a.out || a.out_mx), "skimi_attention: null buffer");
-    SKIMI_CHECK_ARG(a.batch > 0 && a.heads > 0 && a.seq_q > 0 && a.seq_k > 0, "skimi_attention: empty shape");
-    SKIMI_CHECK_ARG(a.head_dim == 64, "skimi_attention: the bf16 MFMA kernel is head_dim 64 only (got %d)", a.head_dim);
-    SKIMI_CHECK_ARG(a.q_row % 8 == 0 && a.k_row % 8 == 0 && a.v_row % 8 == 0 && a.o_row % 4 == 0 &&
-                    a.q_head % 8 == 0 && a.k_head % 8 == 0 && a.v_head % 8 == 0 && a.o_head % 4 == 0 &&
-                    a.q_batch % 8 == 0 && a.k_batch % 8 == 0 && a.v_batch % 8 == 0 && a.o_batch % 4 == 0,
-                    "skimi_attention: bf16 strides must keep 16-B alignment");
-    SKIMI_CHECK_ARG((((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) & 15) == 0,
-                    "skimi_attention: bf16 q / k / v are loaded in 16-B pieces: the buffer must be 16-B aligned");
-    const int nqb = (int)cdiv(a.seq_q, 128);
-    const long nblk = (long)nqb * a.heads * a.batch;
-    SKIMI_CHECK_ARG(nblk < (1l << 31), "skimi_attention: grid too large");
-    const bool prof = prof_armed(PROF_ATTN_BF16, a.seq_k);
-    if (prof) prof_before(st);
+int attention_bf16_launch(const AttnArgs& a, const AttnPlan& p, hipStream_t st) {
+    const int nqb = (int)cdiv(a.seq_q, p.queries);
+    const dim3 grid((unsigned)p.grid), block(256);
     // timing ablations (wrong results) exist only in a -DSKIMI_ABLATIONS build (SKIMI_ABLATIONS=1 python -m ...build)
+    switch (p.dbg) {
+        default: hipLaunchKernelGGL(attn_bf16_kernel<0>, grid, block, 0, st, a, nqb); break;
 #ifdef SKIMI_ABLATIONS
-    const int dbg = (int)env_once("SKIMI_ATTN_ABL", 0);
-#else
-    const int dbg = 0;
-#endif
-    const int q64 = q64_enabled();
-    SKIMI_CHECK_ARG(!a.out_mx || q64 != 0, "skimi_attention: MXFP8 output rows are written by the 64-query kernel only");
-    if (q64 != 0) {
-        attention_q64_dispatch(a, st);
-    } else if (a.q_prescaled) {   // this file's kernel multiplies by scale * log2(e): make that product 1
-        AttnArgs a1 = a;
-        a1.scale = 0.69314718055994530942f;
-        hipLaunchKernelGGL(attn_bf16_kernel<0>, dim3((unsigned)nblk), dim3(256), 0, st, a1, nqb);
-    } else
-    switch (dbg) {
-#ifdef SKIMI_ABLATIONS
-#define SKIMI_ABL_CASE(D) case D: hipLaunchKernelGGL(attn_bf16_kernel<D>, dim3((unsigned)nblk), dim3(256), 0, st, a, nqb); break;
+#define SKIMI_ABL_CASE(D) case D: hipLaunchKernelGGL(attn_bf16_kernel<D>, grid, block, 0, st, a, nqb); break;
         SKIMI_ABL_CASE(1) SKIMI_ABL_CASE(2) SKIMI_ABL_CASE(3) SKIMI_ABL_CASE(4) SKIMI_ABL_CASE(8) SKIMI_ABL_CASE(12)
         SKIMI_ABL_CASE(15)
 #undef SKIMI_ABL_CASE
 #endif
-        default: hipLaunchKernelGGL(attn_bf16_kernel<0>, dim3((unsigned)nblk), dim3(256), 0, st, a, nqb);
-    }
-    if (prof) {
-        const double bh = (double)a.batch * a.heads;
-        prof_after(st, 4.0 * bh * a.seq_q * (double)a.seq_k * 64.0,
-                   2.0 * bh * 64.0 * (2.0 * a.seq_q + 2.0 * a.seq_k));
     }
     SKIMI_LAUNCH_CHECK();
     return SKIMI_OK;
-}
-
-int attention_launch(const void* qkv, void* out, int dtype, int batch, int seq, int heads, int head_dim,
-                     hipStream_t st, int q_prescaled, void* x3_scratch, size_t x3_scratch_bytes, int* out_records, int out_f16,
-                     void* out_mx, void* out_mx_scales) {
-    SKIMI_CHECK_ARG(qkv && (out || out_mx), "skimi_attention: null buffer");
-    SKIMI_CHECK_ARG(!out_mx || (out_mx_scales && attention_mx_output_ok(dtype, heads, head_dim)),
-                    "skimi_attention: MXFP8 output needs the 64-query bf16 kernel (head_dim 64, heads even) and a scale buffer");
-    const bool want_rec = out_records != nullptr && *out_records != 0;
-    if (out_records) *out_records = 0;
-    AttnArgs a;
-    const long C = (long)heads * head_dim;
-    const size_t es = dtype == SKIMI_F32 ? 4 : 2;
-    a.q = qkv;
-    a.k = (const char*)qkv + C * es;
-    a.v = (const char*)qkv + 2 * C * es;
-    a.out = out;
-    a.q_row = a.k_row = a.v_row = 3 * C;
-    a.o_row = C;
-    a.q_batch = a.k_batch = a.v_batch = (long)seq * 3 * C;
-    a.o_batch = (long)seq * C;
-    a.q_head = a.k_head = a.v_head = a.o_head = head_dim;
-    a.batch = batch;
-    a.heads = heads;
-    a.seq_q = a.seq_k = seq;
-    a.head_dim = head_dim;
-    a.scale = 1.0f / sqrtf((float)head_dim);
-    a.q_prescaled = dtype == SKIMI_F32 ? 0 : q_prescaled;
-    a.out_f16 = dtype == SKIMI_F32 ? 0 : out_f16;
-    if (out_mx) {   // [token][align128(C)] payload + [token][align128(C) / 32] scales: gemm_fp8_launch's A operand
-        a.out_mx = out_mx;
-        a.out_mx_scales = out_mx_scales;
-        a.mx_row = (long)align_up((size_t)C, 128);
-        a.mx_srow = a.mx_row / 32;
-    }
-    if (dtype == SKIMI_F32) {
-        // fp32-accurate mode: the bf16x3 kernel when the caller lends scratch for the hi / lo planes (SKIMI_ATTN_X3=0: the
-        // exact-fp32 MFMA kernel, A/B timing and a cross-check in the tests)
-        const int use_x3 = (int)env_switch("SKIMI_ATTN_X3", 1);
-        const long tokens = (long)batch * seq;
-        if (use_x3 && head_dim == 64 && x3_scratch && x3_scratch_bytes >= attention_x3_scratch_bytes(tokens, 3 * C)) {
-            const bool rec = want_rec && ((uintptr_t)out & 127) == 0;
-            if (rec) *out_records = 1;
-            return attention_x3_launch(a, tokens, 3 * C, x3_scratch, x3_scratch_bytes, st, rec);
-        }
-        return attention_f32_launch(a, st);
-    }
-    return attention_bf16_launch(a, st);
 }
 
 }  // namespace skimi

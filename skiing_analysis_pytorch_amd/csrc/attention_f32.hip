@@ -147,20 +147,32 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const AttnArgs a) {
     }
 }
 
-int attention_f32_launch(const AttnArgs& a, hipStream_t st) {
-    SKIMI_CHECK_ARG(a.q && a.k && a.v && a.out, "skimi_attention: null buffer");
-    SKIMI_CHECK_ARG(a.batch > 0 && a.heads > 0 && a.seq_q > 0 && a.seq_k > 0, "skimi_attention: empty shape");
+int check_attention_f32(const AttnArgs& a) {
+    const int rc = check_attention_shape(a);
+    if (rc) return rc;
     SKIMI_CHECK_ARG(a.head_dim % 4 == 0 && a.head_dim > 0 && a.head_dim <= 128,
                     "skimi_attention: fp32 head_dim %d unsupported (multiple of 4, <= 128)", a.head_dim);
     SKIMI_CHECK_ARG(a.q_row % 4 == 0 && a.k_row % 4 == 0 && a.v_row % 4 == 0 && a.o_row % 4 == 0 &&
                     a.q_head % 4 == 0 && a.k_head % 4 == 0 && a.v_head % 4 == 0 && a.o_head % 4 == 0,
                     "skimi_attention: strides must keep 16-B alignment");
-    dim3 grid((unsigned)cdiv(a.seq_q, 128), a.heads, a.batch), block(256);
-    // the split of d over lane halves needs head_dim <= HD with the upper half starting at HD/2
-    if (a.head_dim <= 64) hipLaunchKernelGGL(attn_f32_kernel<64>, grid, block, 0, st, a);
+    return SKIMI_OK;
+}
+
+int attention_f32_launch(const AttnArgs& a, const AttnPlan& p, hipStream_t st) {
+    dim3 grid((unsigned)cdiv(a.seq_q, p.queries), a.heads, a.batch), block(256);
+    if (p.hd == 64) hipLaunchKernelGGL(attn_f32_kernel<64>, grid, block, 0, st, a);
     else hipLaunchKernelGGL(attn_f32_kernel<128>, grid, block, 0, st, a);
     SKIMI_LAUNCH_CHECK();
     return SKIMI_OK;
+}
+
+int attention_f32_launch(const AttnArgs& a, hipStream_t st) {
+    int rc = check_attention_f32(a);
+    if (rc) return rc;
+    const AttnPlan p = plan_attention_f32(a.batch, a.heads, a.seq_q, a.head_dim);
+    rc = attention_f32_launch(a, p, st);
+    if (rc == SKIMI_OK) attention_set_last_plan(p);
+    return rc;
 }
 
 }  // namespace skimi

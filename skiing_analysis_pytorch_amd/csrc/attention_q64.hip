@@ -39,7 +39,6 @@
 
 #include "attention_tile.h"
 #include "common.h"
-#include "env.h"
 #include "kernels.h"
 
 namespace skimi {
@@ -349,33 +348,20 @@ __global__ __launch_bounds__(256, 2) void attn_q64_kernel(const AttnArgs a, int 
     }
 }
 
-void attention_q64_dispatch(const AttnArgs& a, hipStream_t st) {
-    const int nqb = (int)cdiv(a.seq_q, 256);
-    const long nblk = (long)nqb * a.heads * a.batch;
-#ifdef SKIMI_ABLATIONS   // timing ablations (wrong results): only in a -DSKIMI_ABLATIONS build
-    const int dbg = (int)env_once("SKIMI_ATTN_ABL", 0);
-#else
-    const int dbg = 0;
-#endif
-    // SKIMI_ATTN_LDSPAD (bytes of unused dynamic LDS): occupancy experiments, e.g. 65536 -> one workgroup per CU
-    const size_t pad = (size_t)env_once("SKIMI_ATTN_LDSPAD", 0);
-    if (pad) {
-        static bool once = false;
-        if (!once) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_q64_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
-            once = true;
-        }
-        hipLaunchKernelGGL(attn_q64_kernel<0>, dim3((unsigned)nblk), dim3(256), pad, st, a, nqb);
-        return;
-    }
-    switch (dbg) {
+int attention_q64_dispatch(const AttnArgs& a, const AttnPlan& p, hipStream_t st) {
+    const int nqb = (int)cdiv(a.seq_q, p.queries);
+    const dim3 grid((unsigned)p.grid), block(256);
+    if (p.lds_pad) SKIMI_LDS_OPT_IN(attn_q64_kernel<0>, p.lds_pad, "attn_q64_kernel");   // SKIMI_ATTN_LDSPAD
+    switch (p.dbg) {   // timing ablations (wrong results): only in a -DSKIMI_ABLATIONS build
+        default: hipLaunchKernelGGL(attn_q64_kernel<0>, grid, block, (size_t)p.lds_pad, st, a, nqb); break;
 #ifdef SKIMI_ABLATIONS
-        case 1: hipLaunchKernelGGL(attn_q64_kernel<1>, dim3((unsigned)nblk), dim3(256), 0, st, a, nqb); break;
-        case 2: hipLaunchKernelGGL(attn_q64_kernel<2>, dim3((unsigned)nblk), dim3(256), 0, st, a, nqb); break;
-        case 3: hipLaunchKernelGGL(attn_q64_kernel<3>, dim3((unsigned)nblk), dim3(256), 0, st, a, nqb); break;
+        case 1: hipLaunchKernelGGL(attn_q64_kernel<1>, grid, block, 0, st, a, nqb); break;
+        case 2: hipLaunchKernelGGL(attn_q64_kernel<2>, grid, block, 0, st, a, nqb); break;
+        case 3: hipLaunchKernelGGL(attn_q64_kernel<3>, grid, block, 0, st, a, nqb); break;
 #endif
-        default: hipLaunchKernelGGL(attn_q64_kernel<0>, dim3((unsigned)nblk), dim3(256), 0, st, a, nqb);
     }
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
 }
 
 }  // namespace skimi

@@ -237,44 +237,29 @@ __global__ __launch_bounds__(256, 2) void attn_x3_kernel(const AttnX3Args a, int
 
 size_t attention_x3_scratch_bytes(long tokens, long row_elems) { return (size_t)tokens * row_elems * 4 + 512; }
 
-// a: fp32 AttnArgs (q, k, v inside ONE packed buffer of `tokens` rows x `row_elems` floats starting at a.q).
-// scratch: >= attention_x3_scratch_bytes: the hi / lo planes of that buffer.
-// out_records: a.out receives bf16x3 records [tokens][heads * 64 / 32][hi 32 | lo 32] (+ 256 zero bytes behind them) instead of
-// fp32 rows -- the operand form of the proj GEMM on the LDS-DMA bf16x3 kernel (o_row = heads * 64, plain [tokens, C] output)
-int attention_x3_launch(const AttnArgs& a, long tokens, long row_elems, void* scratch, size_t scratch_bytes, hipStream_t st,
-                        bool out_records) {
-    SKIMI_CHECK_ARG(a.q && a.k && a.v && a.out && scratch, "attention_x3: null buffer");
-    SKIMI_CHECK_ARG(a.head_dim == 64, "attention_x3: head_dim 64 only");
-    SKIMI_CHECK_ARG(scratch_bytes >= attention_x3_scratch_bytes(tokens, row_elems), "attention_x3: scratch too small");
-    SKIMI_CHECK_ARG(a.q_row % 8 == 0 && a.k_row % 8 == 0 && a.v_row % 8 == 0 && a.o_row % 4 == 0 && a.q_head % 8 == 0 &&
-                    a.k_head % 8 == 0 && a.v_head % 8 == 0 && a.o_head % 4 == 0 && a.k_batch % 8 == 0 && a.v_batch % 8 == 0 &&
-                    a.q_batch % 4 == 0 && a.o_batch % 4 == 0 && row_elems % 8 == 0,
-                    "attention_x3: strides must keep 16-B alignment");
+// a: fp32 AttnArgs of ONE packed buffer (rows [q | k | v] of a.q_row floats starting at a.q); p: plan_attention's plane
+// layout -- only k and v are read as planes (q is split in registers), so the planes hold just columns c0 .. c0 + pw.
+// scratch: >= attention_x3_scratch_bytes: the hi / lo planes.
+// p.out_form ATTN_OUT_RECORDS: a.out (128-byte aligned, a plain [tokens, heads * 64] result) receives bf16x3 records
+// [tokens][heads * 64 / 32][hi 32 | lo 32] (+ 256 zero bytes behind them) instead of fp32 rows -- the operand form of the
+// proj GEMM on the LDS-DMA bf16x3 kernel
+int attention_x3_launch(const AttnArgs& a, const AttnPlan& p, void* scratch, hipStream_t st) {
+    const long tokens = (long)a.batch * a.seq_q, row_elems = a.q_row;
     const float* base = (const float*)a.q;
-    const long koff = (const float*)a.k - base, voff = (const float*)a.v - base;
-    SKIMI_CHECK_ARG(koff >= 0 && voff >= 0 && koff < row_elems && voff < row_elems, "attention_x3: q, k, v must share one packed buffer");
-    // only k and v are read as planes (q is split in registers): when they are the tail of the packed rows ([q | k | v]),
-    // the planes hold just those columns
-    const long s0 = koff < voff ? koff : voff;
-    const bool tail = a.k_row == row_elems && a.v_row == row_elems && a.k_batch % row_elems == 0 && a.v_batch % row_elems == 0 &&
-                      s0 % 8 == 0;
-    const long c0 = tail ? s0 : 0, pw = row_elems - c0;   // first column and width of the planes
     unsigned short* hi = (unsigned short*)(((uintptr_t)scratch + 255) & ~(uintptr_t)255);
-    unsigned short* lo = hi + tokens * pw;
-    int rc = split_planes_launch(base + c0, row_elems, tokens, (int)pw, hi, lo, st);
+    unsigned short* lo = hi + tokens * p.pw;
+    int rc = split_planes_launch(base + p.c0, row_elems, tokens, (int)p.pw, hi, lo, st);
     if (rc) return rc;
     AttnX3Args x;
-    x.q = base; x.khi = hi + (koff - c0); x.klo = lo + (koff - c0); x.vhi = hi + (voff - c0); x.vlo = lo + (voff - c0); x.out = (float*)a.out;
-    x.q_row = a.q_row; x.k_row = tail ? pw : a.k_row; x.v_row = tail ? pw : a.v_row; x.o_row = a.o_row;
+    x.q = base; x.khi = hi + p.koff; x.klo = lo + p.koff; x.vhi = hi + p.voff; x.vlo = lo + p.voff; x.out = (float*)a.out;
+    x.q_row = a.q_row; x.k_row = x.v_row = p.pw; x.o_row = a.o_row;
     x.q_batch = a.q_batch; x.o_batch = a.o_batch;
-    x.k_batch = tail ? a.k_batch / row_elems * pw : a.k_batch;
-    x.v_batch = tail ? a.v_batch / row_elems * pw : a.v_batch;
+    x.k_batch = a.k_batch / row_elems * p.pw;
+    x.v_batch = a.v_batch / row_elems * p.pw;
     x.q_head = a.q_head; x.k_head = a.k_head; x.v_head = a.v_head; x.o_head = a.o_head;
     x.batch = a.batch; x.heads = a.heads; x.seq_q = a.seq_q; x.seq_k = a.seq_k; x.scale = a.scale;
     x.out_rec = nullptr; x.rec_row = 0; x.rec_batch = 0;
-    if (out_records) {
-        SKIMI_CHECK_ARG(a.o_head == 64 && a.o_row == (long)a.heads * 64 && a.o_batch == (long)a.seq_q * a.o_row && ((uintptr_t)a.out & 127) == 0,
-                        "attention_x3: records output needs a plain [tokens, heads * 64] result, 128-byte aligned");
+    if (p.out_form == ATTN_OUT_RECORDS) {
         x.out_rec = (unsigned short*)a.out;
         x.rec_row = a.o_row * 2;               // 4 bytes per element: [hi 32 | lo 32] per 32-column slice
         x.rec_batch = (long)a.seq_q * x.rec_row;
@@ -283,10 +268,7 @@ int attention_x3_launch(const AttnArgs& a, long tokens, long row_elems, void* sc
             return SKIMI_ERR_HIP;
         }
     }
-    const int nqb = (int)cdiv(a.seq_q, 128);
-    const long nblk = (long)nqb * a.heads * a.batch;
-    SKIMI_CHECK_ARG(nblk < (1l << 31), "attention_x3: grid too large");
-    hipLaunchKernelGGL(attn_x3_kernel, dim3((unsigned)nblk), dim3(256), 0, st, x, nqb);
+    hipLaunchKernelGGL(attn_x3_kernel, dim3((unsigned)p.grid), dim3(256), 0, st, x, (int)cdiv(a.seq_q, p.queries));
     SKIMI_LAUNCH_CHECK();
     return SKIMI_OK;
 }

@@ -46,10 +46,60 @@ struct AttnArgs {
     void* out_mx_scales = nullptr;
     long mx_row = 0, mx_srow = 0;
 };
-// the bf16 attention launch can write its output as MXFP8 (one head = two 32-channel blocks, each inside one lane pair)
+
+// attention.hip: the attention launch of a packed [q | k | v] buffer is check_attention -> plan_attention ->
+// attention_args -> one launcher.  The calling thread's last launched plan is kept for skimi_attention_last_plan.
+enum { ATTN_FAM_F32 = 1, ATTN_FAM_X3 = 2, ATTN_FAM_BF16_Q32 = 3, ATTN_FAM_BF16_Q64 = 4 };
+enum { ATTN_OUT_ROWS = 0, ATTN_OUT_F16 = 1, ATTN_OUT_MX = 2, ATTN_OUT_RECORDS = 3 };
+struct AttnRequest {
+    const void* qkv;           // [batch * seq][3][heads][head_dim], dtype SKIMI_F32 or SKIMI_BF16
+    void* out;                 // [batch * seq][heads * head_dim] rows of out_dtype; SKIMI_FP8MX: the e4m3 payload
+                               // [batch * seq][Kp], Kp = heads * head_dim rounded up to 128 (gemm_fp8_launch's A operand)
+    int dtype, out_dtype;      // out_dtype: dtype, SKIMI_F16 (bf16 input) or SKIMI_FP8MX (attention_mx_output_ok)
+    int batch, seq, heads, head_dim;
+    int q_prescaled;           // bf16 input: q already carries scale * log2(e) (qknorm_rope_launch's q_scale)
+    void* x3_scratch;          // fp32 input, head_dim 64: >= attention_x3_scratch_bytes selects the bf16x3 kernel
+    size_t x3_scratch_bytes;
+    bool want_records;         // fp32 input: bf16x3 records (+ 256 zero bytes) in `out` where the plan allows
+    void* out_scales;          // SKIMI_FP8MX, optional: the E8M0 scales [batch * seq][Kp / 32]; null: right behind the payload
+};
+struct AttnSwitches { int x3, mx, q64; long ldspad; int abl; };   // SKIMI_ATTN_X3, _MX, _Q64, _LDSPAD, _ABL
+struct AttnPlan {
+    int family;        // ATTN_FAM_*
+    int hd;            // the exact-fp32 kernel's HD template argument (64 elsewhere)
+    int queries;       // per workgroup
+    long grid;         // workgroups
+    int out_form;      // ATTN_OUT_*
+    int q_prescaled;   // as honoured: bf16 kernels only
+    int lds_pad;       // bytes of dynamic LDS (64-query kernel)
+    int dbg;           // timing ablation (bf16 kernels, -DSKIMI_ABLATIONS builds)
+    long c0, pw, koff, voff;   // bf16x3: the hi / lo planes hold columns c0 .. c0 + pw of the packed rows; k and v start at
+                               // koff / voff inside a plane row
+};
+int check_attention(const AttnRequest& r);
+AttnPlan plan_attention(const AttnRequest& r, const AttnSwitches& s);   // pure: no HIP call, no global, no getenv
+AttnPlan plan_attention_f32(int batch, int heads, int seq_q, int head_dim);
+AttnArgs attention_args(const AttnRequest& r, const AttnPlan& p);
+// check, plan, launch; *out_records (may be null): whether bf16x3 records were written
+int attention_launch(const AttnRequest& r, hipStream_t st, int* out_records = nullptr);
+void attention_set_last_plan(const AttnPlan& plan);
+const AttnPlan& attention_last_plan();
+// the bf16 attention launch can write its output as MXFP8 (one head = two 32-channel blocks, each inside one lane pair):
+// plan_attention's answer for this input under the current switches
 bool attention_mx_output_ok(int dtype, int heads, int head_dim);
+int check_attention_shape(const AttnArgs& a);   // null buffer, empty shape
+// the launchers: (AttnArgs, AttnPlan, stream), no decision and no argument check of their own
+int attention_f32_launch(const AttnArgs& a, const AttnPlan& p, hipStream_t st);
+int attention_bf16_launch(const AttnArgs& a, const AttnPlan& p, hipStream_t st);   // attention_bf16.hip: 32 queries per wave
+int attention_q64_dispatch(const AttnArgs& a, const AttnPlan& p, hipStream_t st);  // attention_q64.hip: 64 queries per wave
+// attention_x3.hip: fp32-accurate attention (head_dim 64) on the bf16 matrix pipe, operands split hi + lo; `scratch`
+// (>= attention_x3_scratch_bytes) takes the hi / lo planes of the k and v columns of the packed qkv buffer
+size_t attention_x3_scratch_bytes(long tokens, long row_elems);
+int attention_x3_launch(const AttnArgs& a, const AttnPlan& p, void* scratch, hipStream_t st);
+// the exact-fp32 kernel on four separate streams (vggt_track.hip, skimi_attention_f32_strided; two-level batch): its own
+// checks and plan_attention_f32
+int check_attention_f32(const AttnArgs& a);
 int attention_f32_launch(const AttnArgs& a, hipStream_t st);
-int attention_bf16_launch(const AttnArgs& a, hipStream_t st);
 // preprocess.hip: Pillow-exact separable uint8 resample pass, uint8 HWC -> fp32 CHW / 255 with crop / pad
 int resample_u8_launch(const unsigned char* in, unsigned char* out, long outer, int n_in, int n_out, long inner,
                        const int* kk, const int* bounds, int ksize, hipStream_t st);
@@ -60,17 +110,6 @@ int conv_direct_pack_launch(const float* w, unsigned short* out, int Cin, hipStr
 int conv_direct_n32_launch(const unsigned short* in_hi, const unsigned short* in_lo, const unsigned short* w_packed,
                            const float* bias, float* out, int F, int H, int W, int C, int relu, hipStream_t st,
                            long px_stride = 0);   // 0: separate planes [.., C]; 2C: pixel records [hi C | lo C]
-void attention_q64_dispatch(const AttnArgs& a, hipStream_t st);    // attention_q64.hip: 64 queries per wave
-int attention_launch(const void* qkv, void* out, int dtype, int batch, int seq, int heads, int head_dim,
-                     hipStream_t st, int q_prescaled = 0, void* x3_scratch = nullptr, size_t x3_scratch_bytes = 0,
-                     int* out_records = nullptr,    // in: bf16x3 records wanted in `out` (fp32 mode); out: whether they were written
-                     int out_f16 = 0,               // bf16 q / k / v, fp16 output rows (SKIMI_PREC_F16)
-                     void* out_mx = nullptr, void* out_mx_scales = nullptr);   // attention_mx_output_ok(): MXFP8 rows instead of `out`
-// attention_x3.hip: fp32-accurate attention (head_dim 64) on the bf16 matrix pipe, operands split hi + lo; needs
-// scratch for the hi / lo planes of the packed qkv buffer (attention_launch uses it for fp32 inputs when given)
-size_t attention_x3_scratch_bytes(long tokens, long row_elems);
-int attention_x3_launch(const AttnArgs& a, long tokens, long row_elems, void* scratch, size_t scratch_bytes, hipStream_t st,
-                        bool out_records = false);
 
 // VideoPose3D expand-conv im2col: x [B, L, Cin] f32 -> A0 [B*(L-k+1), Kpad] f32 (zero padded)
 int vp3d_im2col_launch(const float* x, float* a0, int B, int L, int Cin, int k, int Kpad, hipStream_t st);

@@ -118,11 +118,18 @@ void run_block(Ctx& c, const BlockW& w, float* x, int batch, int seq, int C, int
         const auto q = Ctx::as_records(d_proj, b.ao, (size_t)M * C * 4);
         ao_rec = gemm_x3dma_eligible(&q) ? 1 : 0;
     }
-    c.run([&] {
-        return attention_launch(b.qkv, b.ao, qdt, batch, seq, heads, C / heads, c.st, q_scaled, adt == SKIMI_F32 ? b.hid : nullptr,
-                                adt == SKIMI_F32 ? (size_t)M * hidden * 4 : 0, &ao_rec, adt == SKIMI_F16,
-                                ao_mx ? b.q8 : nullptr, ao_mx ? b.q8s : nullptr);
-    });
+    AttnRequest req = {};
+    req.qkv = b.qkv; req.out = b.ao; req.dtype = qdt; req.out_dtype = adt == SKIMI_F16 ? SKIMI_F16 : qdt;
+    req.batch = batch; req.seq = seq; req.heads = heads; req.head_dim = C / heads; req.q_prescaled = q_scaled;
+    if (adt == SKIMI_F32) {
+        req.x3_scratch = b.hid;
+        req.x3_scratch_bytes = (size_t)M * hidden * 4;
+        req.want_records = ao_rec != 0;
+    }
+    if (ao_mx) {   // proj's MXFP8 operand: payload and scales are two buffers
+        req.out = b.q8; req.out_scales = b.q8s; req.out_dtype = SKIMI_FP8MX;
+    }
+    c.run([&] { return attention_launch(req, c.st, &ao_rec); });
     if (ao_rec && !c.dry()) d_proj = Ctx::as_records(d_proj, b.ao, (size_t)M * C * 4);
     if (fp8 && w.proj.wq) {
         if (!ao_mx) c.run([&] { return quant_mx_launch(b.ao, SKIMI_BF16, C, M, C, b.q8, b.q8s, c.st); });

@@ -223,6 +223,25 @@ def attention_x3_scratch_bytes(tokens, row_elems):
     return int(lib().skimi_attention_x3_scratch_bytes(tokens, row_elems))
 
 
+class AttnPlan(NamedTuple):
+    """skimi_attention_last_plan (include/skimi.h)"""
+    family: int        # 0 none yet | 1 exact f32 | 2 bf16x3 | 3 bf16, 32 queries per wave | 4 bf16, 64 queries per wave
+    queries: int       # per workgroup
+    out_form: int      # 0 rows in the input type | 1 fp16 rows | 2 MXFP8 | 3 bf16x3 records
+    q_prescaled: int   # as honoured
+    grid: int          # workgroups
+    hd: int            # the exact-f32 kernel's HD (64 elsewhere)
+    lds: int           # bytes of dynamic LDS
+    reserved: int
+
+
+def attention_last_plan() -> AttnPlan:
+    """the plan of the calling thread's last attention launch; a refused call leaves it as it was"""
+    out = (C.c_int32 * 8)()
+    lib().skimi_attention_last_plan(out)
+    return AttnPlan(*out)
+
+
 def attention(qkv, batch, seq, heads, head_dim, out_dtype=None, *, q_prescaled=0, x3_scratch=None, out_records=False,
               out=None):
     """qkv: [batch*seq, 3*heads*head_dim] -> [batch*seq, heads*head_dim] (same dtype; out_dtype=torch.float16 with

@@ -41,35 +41,35 @@ def _rows(seq, n=512):
     return torch.unique(torch.cat([fixed, torch.randperm(seq, generator=g)[:n]]))
 
 
-def _split(qkv, batch, seq, heads):
-    """packed [batch*seq, 3*heads*64] (device) -> float64 q, k, v [batch, heads, seq, 64] (CPU)"""
-    x = qkv.double().cpu().view(batch, seq, 3, heads, 64).permute(2, 0, 3, 1, 4)
+def _split(qkv, batch, seq, heads, hd=64):
+    """packed [batch*seq, 3*heads*hd] (device) -> float64 q, k, v [batch, heads, seq, hd] (CPU)"""
+    x = qkv.double().cpu().view(batch, seq, 3, heads, hd).permute(2, 0, 3, 1, 4)
     return x[0], x[1], x[2]
 
 
 def _sdpa64(q, k, v, rows, spread=False):
-    """float64 softmax(q[rows] k^T / 8) v -> [batch, heads, len(rows), 64]; spread=True: also the largest
-    sqrt(sum_j p_j^2) of a row (1 for a row on one key, ~1/sqrt(seq) for a flat one)"""
-    B, H, S, _ = k.shape
-    out = torch.empty(B, H, len(rows), 64, dtype=torch.float64)
+    """float64 softmax(q[rows] k^T / sqrt(head_dim)) v -> [batch, heads, len(rows), head_dim] (head_dim 64: / 8);
+    spread=True: also the largest sqrt(sum_j p_j^2) of a row (1 for a row on one key, ~1/sqrt(seq) for a flat one)"""
+    B, H, S, hd = k.shape
+    out = torch.empty(B, H, len(rows), hd, dtype=torch.float64)
     hc = max(1, min(H, (1 << 25) // (len(rows) * S)))   # heads per step: <= 256 MB of scores
     sp = 0.0
     for b in range(B):
         for h in range(0, H, hc):
-            p = torch.softmax(q[b, h:h + hc, rows] @ k[b, h:h + hc].transpose(-1, -2) / 8.0, -1)
+            p = torch.softmax(q[b, h:h + hc, rows] @ k[b, h:h + hc].transpose(-1, -2) / float(hd) ** 0.5, -1)
             out[b, h:h + hc] = p @ v[b, h:h + hc]
             if spread:
                 sp = max(sp, p.square().sum(-1).sqrt().max().item())
     return (out, sp) if spread else out
 
 
-def _pick(out, batch, seq, heads, rows):
-    """kernel output [batch*seq, heads*64] (device) -> float64 [batch, heads, len(rows), 64] (CPU)"""
-    return out.double().cpu().view(batch, seq, heads, 64).permute(0, 2, 1, 3)[:, :, rows]
+def _pick(out, batch, seq, heads, rows, hd=64):
+    """kernel output [batch*seq, heads*hd] (device) -> float64 [batch, heads, len(rows), hd] (CPU)"""
+    return out.double().cpu().view(batch, seq, heads, hd).permute(0, 2, 1, 3)[:, :, rows]
 
 
-def _err(out, ref, batch, seq, heads, rows):
-    return (_pick(out, batch, seq, heads, rows) - ref).abs().max().item()
+def _err(out, ref, batch, seq, heads, rows, hd=64):
+    return (_pick(out, batch, seq, heads, rows, hd) - ref).abs().max().item()
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -128,7 +128,7 @@ X3_C = 0.12
 
 
 def _x3_tol(q, k, v, spread):
-    D = (q.norm(dim=-1).amax(-1) * k.norm(dim=-1).amax(-1) / 8.0).max().item()
+    D = (q.norm(dim=-1).amax(-1) * k.norm(dim=-1).amax(-1) / float(q.shape[-1]) ** 0.5).max().item()
     return X3_C * 2.0 ** -16 * (1.0 + D) * v.abs().max().item() * spread, D
 
 
@@ -142,11 +142,16 @@ def test_attention_x3_fp32(batch, seq, heads, case, monkeypatch):
     qkv = _qkv(batch, seq, heads, case, seed=1000 + seq).to(DEV)
     nb = ops.attention_x3_scratch_bytes(tokens, 3 * C)
     sc = torch.empty(nb, dtype=torch.uint8, device=DEV)
+    fam = lambda: ops.attention_last_plan().family   # noqa: E731  (1 exact fp32, 2 bf16x3)
     x3 = ops.attention(qkv, batch, seq, heads, 64, x3_scratch=sc)
+    assert fam() == 2
     less = ops.attention(qkv, batch, seq, heads, 64, x3_scratch=sc[:nb - 1])
+    assert fam() == 1
     f32 = ops.attention(qkv, batch, seq, heads, 64)
+    assert fam() == 1
     monkeypatch.setenv("SKIMI_ATTN_X3", "0")      # re-read per launch: conftest sets SKIMI_ENV_DYNAMIC=1
     f32_env = ops.attention(qkv, batch, seq, heads, 64, x3_scratch=sc)
+    assert fam() == 1
     monkeypatch.delenv("SKIMI_ATTN_X3")
     assert torch.equal(less, f32) and torch.equal(f32_env, f32)
     if seq > 1:   # (one key: both kernels return v)
@@ -186,11 +191,13 @@ def test_attention_x3_records(batch, seq, heads, monkeypatch):
     qkv = _qkv(batch, seq, heads, "randn", seed=2000 + seq).to(DEV)
     sc = torch.empty(ops.attention_x3_scratch_bytes(tokens, 3 * C), dtype=torch.uint8, device=DEV)
     rows32 = ops.attention(qkv, batch, seq, heads, 64, x3_scratch=sc)
+    assert ops.attention_last_plan()[:3] == (2, 128, 0)   # bf16x3, fp32 rows
 
     rec = ops.records_buffer(tokens, C)
     rec.view(torch.uint8).fill_(0xFF)
     rec, written = ops.attention(qkv, batch, seq, heads, 64, x3_scratch=sc, out_records=True, out=rec)
     assert written
+    assert ops.attention_last_plan()[:3] == (2, 128, 3)   # bf16x3, records
     r = rec[:tokens * C * 2].view(tokens, C // 32, 2, 32).float()
     hi, lo = r[:, :, 0].reshape(tokens, C), r[:, :, 1].reshape(tokens, C)
     # hi + lo reconstructs the fp32 quotient to 2^-18 relative (the issue's bar: 2^-16)
@@ -217,6 +224,7 @@ def test_attention_x3_records(batch, seq, heads, monkeypatch):
     out = big[16:]
     got, written = ops.attention(qkv, batch, seq, heads, 64, x3_scratch=sc, out_records=True, out=out)
     assert not written
+    assert ops.attention_last_plan()[:3] == (2, 128, 0)
     assert torch.equal(got[:tokens * C].view(tokens, C), rows32)
 
 
@@ -276,6 +284,18 @@ def _half_ulp_f16(x):
     return torch.ldexp(torch.ones_like(x), torch.clamp(e, min=-13) - 12)   # 11 significant bits; subnormal step 2^-24
 
 
+def _assert_mx_rows(q8, s8, ref, batch, seq, rows):
+    """MXFP8 output rows (payload, scales) against ref [batch, heads, len(rows), 64]: the bounds of
+    test_fp8_gpu.py::test_attention_mx_output"""
+    C = ref.shape[1] * 64
+    sel = (torch.arange(batch)[:, None] * seq + rows[None]).reshape(-1)
+    got = mx.mx_dequantize(q8.cpu().numpy()[sel][:, :C], s8.cpu().numpy()[sel][:, :C // 32])
+    r = ref.permute(0, 2, 1, 3).reshape(-1, C).numpy()
+    scale = np.exp2(s8.cpu().numpy()[sel][:, :C // 32].astype(np.float64) - 127.0).repeat(32, axis=1)
+    tol = 2.0 ** -4 * np.abs(r) + scale * 2.0 ** -10 + 1.5e-2 * np.abs(r).max(axis=1, keepdims=True)
+    assert (np.abs(got - r) <= tol).all(), float((np.abs(got - r) - tol).max())
+
+
 CHAIN_SHAPES = [(3, 63, 2), (1, 65, 1), (2, 77, 4), (2, 257, 2), (1, 300, 6), (8, 1374, 16), (1, 10992, 16)]
 
 
@@ -332,12 +352,7 @@ def test_attention_prescaled_chain(batch, seq, heads, case):
 
     if heads % 2 == 0:   # MXFP8 rows: the bounds of test_fp8_gpu.py::test_attention_mx_output
         q8, s8 = ops.attention(buf, batch, seq, heads, 64, out_dtype="fp8mx", q_prescaled=1)
-        sel = (torch.arange(batch)[:, None] * seq + rows[None]).reshape(-1)
-        got = mx.mx_dequantize(q8.cpu().numpy()[sel], s8.cpu().numpy()[sel])
-        r = ref.permute(0, 2, 1, 3).reshape(-1, C).numpy()
-        scale = np.exp2(s8.cpu().numpy()[sel].astype(np.float64) - 127.0).repeat(32, axis=1)
-        tol = 2.0 ** -4 * np.abs(r) + scale * 2.0 ** -10 + 1.5e-2 * np.abs(r).max(axis=1, keepdims=True)
-        assert (np.abs(got - r) <= tol).all(), float((np.abs(got - r) - tol).max())
+        _assert_mx_rows(q8, s8, ref, batch, seq, rows)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -412,6 +427,8 @@ for batch, seq, heads in [(2, 77, 3), (1, 1374, 4), (2, 256, 2)]:
     ref = t._sdpa64(q / t.Q_SCALE, k, v, rows)
     for odt in (None, torch.float16):
         out = ops.attention(buf, batch, seq, heads, 64, out_dtype=odt, q_prescaled=1)
+        # the 32-query kernel, 128 queries per workgroup, bf16 / fp16 rows, q_prescaled honoured
+        assert ops.attention_last_plan()[:4] == (3, 128, 0 if odt is None else 1, 1), ops.attention_last_plan()
         worst = max(worst, t._err(out, ref, batch, seq, heads, rows))
 print("WORST", worst)
 """

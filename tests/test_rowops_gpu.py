@@ -307,6 +307,8 @@ def _attn(key, bufs, offs, strides, *, batch, batch_inner, heads, seq_q, seq_k, 
     ops.attention_f32_strided(q, k, v, out[offs[3]:], q_strides=strides[0], k_strides=strides[1], v_strides=strides[2],
                               o_strides=strides[3], batch=batch, batch_inner=batch_inner, heads=heads, seq_q=seq_q, seq_k=seq_k,
                               head_dim=hd, scale=scale)
+    plan = ops.attention_last_plan()   # the exact-fp32 kernel, HD 64 up to head_dim 64
+    assert (plan.family, plan.hd, plan.grid) == (1, 64 if hd <= 64 else 128, -(-seq_q // 128) * heads * batch), plan
     _check_guards(gb)
     idx = R.stream_index(offs[3], strides[3], seq=seq_q, **dims).reshape(-1)
     assert len(np.unique(idx)) == idx.size, "the case's output rows overlap"

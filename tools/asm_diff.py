@@ -8,7 +8,9 @@ extracted with `git archive` into a temporary directory, and in the working tree
 EXTRA_FLAGS plus `--cuda-device-only -S`, and compares the two texts, ignoring only lines that contain `__hip_cuid_`
 (a hash of the source text) and the `.file` directive.  The compiler's diagnostics are compared as well, with the two
 directory names taken out.  One line per file: assembly line count, then `identical` or the number of differing
-lines.  Exits non-zero if any file differs.  Needs hipcc and git, no GPU; nothing inside the assembly is inspected.
+lines; a file that only the working tree has is compiled and listed as `new file` with its line count (a host-only
+file is the 23-line stub).  Exits non-zero if any file differs or only the parent has it.  Needs hipcc and git, no
+GPU; nothing inside the assembly is inspected.
 `--keep DIR` leaves parent/<name>.s and tree/<name>.s there (and reuses a parent/<name>.s it finds: the parent's
 output does not change while one edits).
 """
@@ -76,6 +78,9 @@ def main() -> int:
 
         def one(name: str):
             res = []
+            if not (pcsrc / name).exists():   # new in the tree: its line count shows whether it holds device code at all
+                (tdir / (name + ".diag")).write_text(compile_asm(CSRC / name, tdir / (name + ".s")))
+                return name, len(kept_lines(tdir / (name + ".s"))), None, True
             for csrc, out in ((pcsrc, pdir), (CSRC, tdir)):
                 s, diag = out / (name + ".s"), out / (name + ".diag")
                 if not (csrc / name).exists():
@@ -92,6 +97,9 @@ def main() -> int:
                 if n is None:
                     print(f"{name:24s} only on one side")
                     bad += 1
+                    continue
+                if d is None:
+                    print(f"{name:24s} {n:7d} lines  new file", flush=True)
                     continue
                 verdict = "identical" if d == 0 else f"{d} lines differ"
                 if not same_diag:
