@@ -1384,6 +1384,85 @@ int skimi_match_hamming(const int32_t* d1, const int32_t* n1, int32_t M1, const 
                         int64_t B, int32_t cross_check, double ratio, int32_t max_distance, int32_t max_matches, int32_t* pairs,
                         int32_t* dist, int32_t* count, void* stream);
 
+/* ---- SIFT-style image features and L2 ratio-test matching (csrc/sift.hip) ----
+ * triangulation/camera_position/camera_position.py:120-178, 242-297 (estimate_camera_pose_from_SIFT, estimate_pose_from_bbox_region
+ * = cv2.SIFT_create + BFMatcher.knnMatch(k = 2) + Lowe's ratio test) under the project's own rules: parity with cv2.SIFT_create
+ * is not pinned (no doubled first octave, one orientation per keypoint, the project's own sampling windows).  frames [N, H, W,
+ * ch] u8 (dev) as skimi_orb_features takes them, the same limits on N, H, W.  A fixed number of launches for all frames (it
+ * depends on `octaves` alone), no host synchronisation, no allocation, no float atomics; a frame's (a set pair's) results are
+ * the same bits alone and inside a batch.  Bad arguments: SKIMI_ERR_ARG before any launch.  Rules (DESIGN §2 "Image features
+ * (SIFT-style)"; tests/sift_restated.py):
+ *  1. Gray = rule 1 of the chessboard block, converted to f32.
+ *  2. Scale space in f32.  S = 3 intervals, sigma0 = 1.6, assumed input blur 0.5, no doubled first octave.  Octave o has 6
+ *     Gaussian layers of size W_o x H_o, W_0 = W, W_{o+1} = (W_o + 1) / 2 (H likewise).  Layer 0 of octave 0 = gray blurred by
+ *     sqrt(sigma0^2 - 0.25); layer i = layer i - 1 blurred by sigma0 2^((i-1)/S) sqrt(2^(2/S) - 1); layer 0 of octave o + 1 =
+ *     layer S of octave o at even x and even y.  `octaves` = 0 .. SKIMI_SIFT_MAX_OCTAVES; an octave with min(W_o, H_o) < 16 is
+ *     empty (the wrapper's default is the number of octaves that are not).  taps [6, 2 SKIMI_SIFT_MAX_RADIUS + 1] f32 (dev):
+ *     row i holds the taps of layer i's blur, tap k of -r_i .. r_i at column SKIMI_SIFT_MAX_RADIUS + k, r_i = ceil(4 sigma_i)
+ *     = SKIMI_SIFT_RADII[i]; the caller makes them in f64 (exp(-k^2 / (2 sigma_i^2)) normalised to sum 1), rounds them to f32
+ *     and uploads them: no transcendental function runs on the device in this stage.  A blur = a horizontal pass, then a
+ *     vertical pass over the f32 intermediate, borders replicated; each output = the f32 sum of f32 products added in tap
+ *     order -r .. r, starting from the first product, unfused.  DoG layer i (0 .. 4) = layer i + 1 - layer i in f32.
+ *  3. Candidates: a pixel of DoG layer 1 .. S with SKIMI_SIFT_BORDER <= x < W_o - SKIMI_SIFT_BORDER (y likewise), |d| >
+ *     SKIMI_SIFT_PRETHRESH (f32) and d strictly greater than, or strictly smaller than, all 26 neighbours.  Compacted in
+ *     (octave, layer, y, x) order; every (octave, layer) holds at most min(W_o H_o, SKIMI_SIFT_MAX_CANDIDATES) of them: those
+ *     behind the capacity in (y, x) order are dropped.  octave_count [N, octaves] i32 = the candidates of an octave, uncapped.
+ *  4. Refinement in f64 with + - * / only, unfused, on the f32 DoG values D.  Up to 5 rounds at (x, y, l): g = ((D(x+1) -
+ *     D(x-1)) 0.5, the same in y, in l); dxx = D(x+1) + D(x-1) - 2 D, dyy, dss likewise; dxy = (D(x+1,y+1) - D(x-1,y+1) -
+ *     D(x+1,y-1) + D(x-1,y-1)) 0.25, dxs, dys likewise; solve [dxx dxy dxs; dxy dyy dys; dxs dys dss] X = -g by elimination
+ *     without pivoting in the order written in sift_refine (csrc/sift.hip) and tests/sift_restated.py.  A component of X
+ *     > 0.5 moves x, y or l by + 1, < -0.5 by - 1; no move: settled.  A candidate that leaves the border or the layers 1 .. S,
+ *     or has not settled in 5 rounds, is dropped.  response = D + ((g0 X0 + g1 X1) + g2 X2) 0.5; kept iff |response| >=
+ *     SKIMI_SIFT_CONTRAST and det = dxx dyy - dxy dxy > 0 and (dxx + dyy)^2 10 < 121 det.  xy = ((x + X0) 2^o, (y + X1) 2^o);
+ *     sigma = sigma0 2^o 2^(2/3) P(u ln 2), u = (l + X2) / 3 - 2/3, P = the Taylor polynomial of exp of degree 16 by
+ *     Horner's rule (2^(2/3) = SKIMI_SIFT_CBRT4, ln 2 = SKIMI_SIFT_LN2); xy_level = (x, y), layer = l after the moves.
+ *     With roi [N, 4] f64 (x1, y1, x2, y2; or NULL) only the keypoints with x1 <= xy.x < x2 and y1 <= xy.y < y2 stay.
+ *  5. Selection: the max_features (1 .. SKIMI_SIFT_MAX_FEATURES) kept candidates of largest |response| (the bits of the
+ *     f64 as an unsigned key, an exact radix selection), ties to the earlier candidate; rows in candidate order.  count [N]
+ *     = their number; the rows behind it hold -1 in xy, xy_level, octave, layer, angle and 0 in sigma, response, desc.
+ *  6. Orientation in f64 on Gaussian layer l of the octave, L: s = sigma / 2^o; samples at the integer offsets (i, j) from
+ *     (x, y) with i^2 + j^2 <= (4.5 s)^2 whose pixel has all four neighbours; gx = L(x+1) - L(x-1), gy = L(y+1) - L(y-1);
+ *     weight = sqrt(gx^2 + gy^2) exp(-(i^2 + j^2) / (2 (1.5 s)^2)); b = atan2(gy, gx) (into [0, 2 pi)) 36 / (2 pi); the vote
+ *     goes to bins floor(b) and floor(b) + 1 (mod 36) with weights 1 - frac and frac.  Votes are added as integers of unit
+ *     2^-43 (round to nearest; LDS integer adds, so the sum does not depend on the order).  Two circular [1 4 6 4 1] / 16
+ *     smoothings; the highest bin k (ties: the smaller) with neighbours l, r: angle = 2 pi (k + 0.5 (l - r) / (l - 2 c + r))
+ *     / 36 (no offset when the denominator is 0), into [0, 2 pi).  One orientation per keypoint: Lowe's secondary peaks >=
+ *     0.8 are not emitted.
+ *  7. Descriptor, 4 x 4 cells x 8 orientations, in f64: cell width h = 3 s; offsets (i, j), |i|, |j| <= R = floor(h sqrt(2) 2.5
+ *     + 0.5), pixels with all four neighbours; c = (cos(angle) j + sin(angle) i) / h, r = (-sin(angle) j + cos(angle) i) / h
+ *     (j along x, i along y); rb = r + 1.5, cb = c + 1.5, used iff -1 < rb < 4 and -1 < cb < 4; ob = (atan2(gy, gx) - angle)
+ *     8 / (2 pi) into [0, 8); value = sqrt(gx^2 + gy^2) exp(-(r^2 + c^2) / 8); trilinear votes to the two nearest rows,
+ *     columns (outside 0 .. 3: discarded) and orientations (mod 8), added as integers of unit 2^-43 as in rule 6.  v / |v|,
+ *     min(., 0.2), / the new norm; desc [N, M, 128] u8, entry (row 4 + column) 8 + orientation = min(255, round half even
+ *     (512 v)).
+ *  8. skimi_match_l2: B pairs of descriptor sets d1 [B, M1, 128], d2 [B, M2, 128] u8 with n1, n2 [B] i32 (dev; clamped to 0 ..
+ *     M), M1, M2 <= SKIMI_SIFT_MAX_FEATURES.  Exact i32 squared distances |a|^2 + |b|^2 - 2 a.b; for query i the nearest train j
+ *     and the second-nearest by (distance, index): s1, s2 (s2 = -1 without a second train row); for train j the nearest query.
+ *     Query i is kept iff n2 >= 1 and (cross_check == 0 or j's nearest query is i) and (ratio < 0 or (n2 >= 2 and (double)s1 <
+ *     (ratio ratio) (double)s2)) and (max_distance2 < 0 or s1 <= max_distance2).  The kept (i, j) ordered by (s1, i) (a stable
+ *     radix sort); the first max_matches (1 .. SKIMI_SIFT_MAX_FEATURES) go to pairs [B, max_matches, 2], dist2, second2 [B,
+ *     max_matches] i32; the rows behind hold -1; count [B] = the rows written.  ws: 16-byte aligned, ws_bytes >= 8 B (M1 + M2)
+ *     + 4 B M1. */
+#define SKIMI_SIFT_MAX_OCTAVES 8
+#define SKIMI_SIFT_MAX_FEATURES 4096
+#define SKIMI_SIFT_MAX_CANDIDATES 32768
+#define SKIMI_SIFT_BORDER 5
+#define SKIMI_SIFT_MIN_SIDE 16
+#define SKIMI_SIFT_MAX_RADIUS 13
+#define SKIMI_SIFT_RADII {7, 5, 7, 8, 10, 13}
+#define SKIMI_SIFT_PRETHRESH 1.7f
+#define SKIMI_SIFT_CONTRAST 3.4
+#define SKIMI_SIFT_CBRT4 1.5874010519681994
+#define SKIMI_SIFT_LN2 0.6931471805599453
+size_t skimi_sift_workspace_bytes(int64_t N, int32_t H, int32_t W, int32_t octaves);
+int skimi_sift_features(const uint8_t* frames, int64_t N, int32_t H, int32_t W, int32_t ch, int32_t octaves, int32_t max_features,
+                        const double* roi, const float* taps, double* xy, int32_t* xy_level, int32_t* octave, int32_t* layer,
+                        double* sigma, double* response, double* angle, uint8_t* desc, int32_t* count, int32_t* octave_count,
+                        void* ws, size_t ws_bytes, void* stream);
+int skimi_match_l2(const uint8_t* d1, const int32_t* n1, int32_t M1, const uint8_t* d2, const int32_t* n2, int32_t M2, int64_t B,
+                   int32_t cross_check, double ratio, int32_t max_distance2, int32_t max_matches, int32_t* pairs, int32_t* dist2,
+                   int32_t* second2, int32_t* count, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- VGGT head and track-head helper kernels, one launch each ----
  * The kernels skimi_vggt_forward runs between its GEMMs, exposed singly so that each can be tested against a float64
  * restatement.  All maps are channels-last and dense; dtype / out_dtype are SKIMI_F32, SKIMI_BF16 or SKIMI_F16.  Every

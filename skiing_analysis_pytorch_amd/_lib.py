@@ -215,6 +215,11 @@ _SIGNATURES = {
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "skimi_match_hamming": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32,
                                       C.c_int32, _vp, _vp, _vp, _vp]),
+    "skimi_sift_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "skimi_sift_features": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "skimi_match_l2": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                                 _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "skimi_resize_bilinear": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_float, _vp]),
     "skimi_resize_bilinear_planes": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
     "skimi_add_uv_pos": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),

@@ -13,6 +13,7 @@
 //                        (distance << 16 | index) key; cross check, ratio, a stable counting sort over the 257 distances
 // Every stage is integer: the results are bitwise reproducible and a frame's do not depend on the batch around it.
 #include "common.h"
+#include "gray.h"
 #include "reduce.h"
 
 namespace skimi {
@@ -44,13 +45,6 @@ struct OrbWs {
     unsigned* block_count;                    // [N, G]
     unsigned char *gray, *blur, *score;       // [N, P] each
 };
-
-// chessboard.hip's gray (rule 1 of its block)
-template <int CH>
-__device__ __forceinline__ int orb_gray(const unsigned char* p) {
-    if (CH == 1) return p[0];
-    return (3735 * (int)p[0] + 19235 * (int)p[1] + 9798 * (int)p[2] + 16384) >> 15;
-}
 
 // ---- the pyramid ----
 template <int CH>

@@ -42,6 +42,8 @@ from .device.chessboard import (CHESS_MAX_NMS, SUBPIX_MAX_WIN, SUBPIX_MAX_ITERS,
                                 chessboard_candidates, corner_subpix)
 from .device.features import (ORB_MAX_LEVELS, ORB_MAX_FEATURES, ORB_BORDER, OrbFeatures, HammingMatches, orb_pattern,
                               orb_features, match_hamming)
+from .device.sift import (SIFT_MAX_OCTAVES, SIFT_MAX_FEATURES, SIFT_MAX_CANDIDATES, SIFT_BORDER, SiftFeatures, L2Matches, sift_taps,
+                          sift_octaves, sift_features, match_l2)
 from .device.lens import _undistorted_f32
 
 # ---- host helpers of the wrapper (small arrays, NumPy as in the reference) -----------------
