@@ -252,6 +252,12 @@ int skimi_gemm_fp8(const void* A, const void* A_scales, const void* W, const voi
 int skimi_conv3x3_n32_pack(const float* w, void* packed, int32_t C, void* stream);
 int skimi_conv3x3_n32(const void* in_hi, const void* in_lo, const void* packed_w, const float* bias, float* out,
                       int32_t F, int32_t H, int32_t W, int32_t C, int32_t relu, void* stream);
+/* The same conv on planes whose consecutive pixels lie px_stride elements apart (px_stride >= C, px_stride % 8 == 0:
+ * every 16-byte chunk of every pixel is 16-byte aligned); skimi_conv3x3_n32 is px_stride = C.  The DPT heads launch it
+ * on the pixel records [pixel][hi C | lo C] of skimi_resize_bilinear_planes (slice_records == 0):
+ * in_lo = in_hi + C, px_stride = 2 * C. */
+int skimi_conv3x3_n32_strided(const void* in_hi, const void* in_lo, const void* packed_w, const float* bias, float* out,
+                              int32_t F, int32_t H, int32_t W, int32_t C, int32_t relu, int64_t px_stride, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Image preprocessing on the device (vggt/load.py:38-183)                    */

@@ -153,6 +153,14 @@ int skimi_conv3x3_n32(const void* in_hi, const void* in_lo, const void* packed_w
                                   (const unsigned short*)packed_w, bias, out, F, H, W, C, relu, (hipStream_t)stream);
 }
 
+int skimi_conv3x3_n32_strided(const void* in_hi, const void* in_lo, const void* packed_w, const float* bias, float* out,
+                              int32_t F, int32_t H, int32_t W, int32_t C, int32_t relu, int64_t px_stride, void* stream) {
+    SKIMI_CHECK_ARG(px_stride > 0, "skimi_conv3x3_n32_strided: px_stride must be positive");
+    return conv_direct_n32_launch((const unsigned short*)in_hi, (const unsigned short*)in_lo,
+                                  (const unsigned short*)packed_w, bias, out, F, H, W, C, relu, (hipStream_t)stream,
+                                  (long)px_stride);
+}
+
 int skimi_split_planes(const float* x, int64_t ld, int64_t rows, int32_t C, void* hi, void* lo, void* stream) {
     SKIMI_CHECK_ARG(x && hi && lo && rows > 0 && C > 0, "skimi_split_planes: bad arguments");
     return split_planes_launch(x, (long)ld, (long)rows, C, hi, lo, (hipStream_t)stream);

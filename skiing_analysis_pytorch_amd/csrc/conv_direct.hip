@@ -216,12 +216,16 @@ int conv_direct_n32_launch(const unsigned short* in_hi, const unsigned short* in
     SKIMI_CHECK_ARG(in_hi && in_lo && w_packed && out, "conv_direct: null buffer");
     SKIMI_CHECK_ARG(C % 32 == 0 && C >= 32 && F > 0 && H > 0 && W > 0, "conv_direct: bad shape");
     SKIMI_CHECK_ARG((((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)w_packed) & 15) == 0, "conv_direct: 16-B alignment");
+    if (px_stride <= 0) px_stride = C;
+    // every pixel holds C / 8 DMA chunks of 16 B: they must not reach into the next pixel, and each must be 16-B aligned
+    SKIMI_CHECK_ARG(px_stride >= C, "conv_direct: px_stride < C");
+    SKIMI_CHECK_ARG(px_stride % 8 == 0, "conv_direct: px_stride %% 8 != 0 (16-B aligned pixels)");
     constexpr size_t lds = 2ull * CD_BUF;
     SKIMI_LDS_OPT_IN(conv_direct_n32_kernel, lds, "conv_direct");
     ConvDirectArgs a;
     a.in_hi = in_hi; a.in_lo = in_lo; a.w = w_packed; a.bias = bias; a.out = out;
     a.F = F; a.H = H; a.W = W; a.C = C; a.relu = relu;
-    a.px_stride = px_stride > 0 ? px_stride : C;
+    a.px_stride = px_stride;
     a.tiles_x = (int)cdiv(W, 16);
     a.tiles_y = (int)cdiv(H, 16);
     const long nblk = (long)F * a.tiles_x * a.tiles_y;

@@ -324,19 +324,47 @@ def _attention_ex(qkv, batch, seq, heads, head_dim, out_dtype, q_prescaled, x3_s
     return (out, bool(flag.value)) if out_records else out
 
 
-def conv3x3_n32(x, w, bias=None, relu=False):
+def conv3x3_n32_pack(w):
+    """the reference's [32, C, 3, 3] fp32 weight -> the packed bf16 tensor [C/32, 2 (hi | lo), 9 (ky * 3 + kx), 32 (cout),
+    32 (cin % 32)] that `conv3x3_n32(packed=...)` reads (skimi_conv3x3_n32_pack)"""
+    _require_cuda(w)
+    Cc = w.shape[1]
+    assert w.shape == (32, Cc, 3, 3) and w.dtype == torch.float32
+    packed = torch.empty(((Cc + 31) // 32, 2, 9, 32, 32), dtype=torch.bfloat16, device=w.device)
+    check(lib().skimi_conv3x3_n32_pack(ptr(w.contiguous()), ptr(packed), Cc, _lib.current_stream()), "skimi_conv3x3_n32_pack")
+    return packed
+
+
+def conv3x3_n32(x, w, bias=None, relu=False, *, planes=None, px_stride=None, packed=None, out=None):
     """Direct fp32-accurate 3x3 conv (stride 1, pad 1) to 32 channels.  x: fp32 [F, H, W, C] channels-last,
-    w: the reference's [32, C, 3, 3] fp32 weight -> fp32 [F, H, W, 32]."""
-    _require_cuda(x, w, bias)
-    F_, H, W_, Cc = x.shape
-    assert w.shape == (32, Cc, 3, 3) and Cc % 32 == 0
-    planes = split_planes(x.reshape(-1, Cc).contiguous())
-    packed = torch.empty(2 * 32 * Cc * 9, dtype=torch.bfloat16, device=x.device)
+    w: the reference's [32, C, 3, 3] fp32 weight -> fp32 [F, H, W, 32].
+
+    The keyword arguments make the launches of the DPT heads (skimi_conv3x3_n32_strided); nothing is copied or checked
+    here.  planes = (hi, lo): the bf16 planes of the input as they lie in memory (x is then its shape (F, H, W, C)), pixel
+    p of a plane px_stride elements behind its first (default C; the heads' records [pixel][hi C | lo C]:
+    planes = (rec, rec[C:]), px_stride = 2 C); packed: the weight from `conv3x3_n32_pack` (w is not read);
+    out: the fp32 destination, F * H * W * 32 dense elements from its first."""
+    _require_cuda(bias, packed, out)
+    F_, H, W_, Cc = x if planes is not None else x.shape
     st = _lib.current_stream()
-    check(lib().skimi_conv3x3_n32_pack(ptr(w.contiguous()), ptr(packed), Cc, st), "skimi_conv3x3_n32_pack")
-    out = torch.empty((F_, H, W_, 32), dtype=torch.float32, device=x.device)
-    check(lib().skimi_conv3x3_n32(ptr(planes[0]), ptr(planes[1]), ptr(packed), ptr(bias), ptr(out), F_, H, W_, Cc,
-                                  1 if relu else 0, st), "skimi_conv3x3_n32")
+    if planes is None:
+        _require_cuda(x)
+        planes = split_planes(x.reshape(-1, Cc).contiguous())
+        dev = x.device
+    else:
+        _require_cuda(*planes)
+        dev = next((t.device for t in planes if t is not None), "cuda")
+    if packed is None:
+        assert w.shape == (32, Cc, 3, 3) and Cc % 32 == 0
+        packed = conv3x3_n32_pack(w)
+    if out is None:
+        out = torch.empty((F_, H, W_, 32), dtype=torch.float32, device=dev)
+    if px_stride is None:
+        check(lib().skimi_conv3x3_n32(ptr(planes[0]), ptr(planes[1]), ptr(packed), ptr(bias), ptr(out), F_, H, W_, Cc,
+                                      1 if relu else 0, st), "skimi_conv3x3_n32")
+    else:
+        check(lib().skimi_conv3x3_n32_strided(ptr(planes[0]), ptr(planes[1]), ptr(packed), ptr(bias), ptr(out), F_, H, W_,
+                                              Cc, 1 if relu else 0, int(px_stride), st), "skimi_conv3x3_n32_strided")
     return out
 
 
