@@ -201,3 +201,39 @@ def frame_out(fn, fr, five, ow, oh, out):
     if not out.is_cuda or out.device != fr.device or out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous():
         raise ValueError(f"{fn}: out must be a contiguous uint8 device tensor {list(shape)}")
     return out
+
+
+# ---- image features and their matchers (device/features.py, device/sift.py) ------------------------------------------
+def feature_frames(fn, frames, roi):
+    """The frames and boxes of a feature extractor (device/features.py, device/sift.py) -> (frame_clip's [C, F, H, W, ch], the
+    number of frames, their leading axes, roi [..., 4] under those axes as float64 on the frames' device or None)"""
+    fr, five = frame_clip(fn, frames)
+    on_device(fn, roi=roi)
+    C, F = int(fr.shape[0]), int(fr.shape[1])
+    if C * F < 1:
+        raise ValueError(f"{fn}: need at least one frame, got {C * F}")
+    lead = (C, F) if five else (F,)
+    if roi is not None and tuple(roi.shape) != (*lead, 4):
+        raise ValueError(f"{fn}: roi must be {list(lead)} + [4], got {list(roi.shape)}")
+    return fr, C * F, lead, to_dev(roi, dev=fr.device)
+
+
+def descriptor_sets(fn, d1, n1, d2, n2, width, dtype, convert):
+    """The sets of a brute-force matcher: d1 [..., M1, width], d2 [..., M2, width] under common leading axes, n1, n2 [...]
+    -> (the leading axes, the number of pairs of sets, d1, n1, d2, n2 contiguous on d1's device, descriptors as `dtype`
+    and counts as int32).  convert=False: descriptors of another dtype are refused."""
+    on_device(fn, d1=d1, n1=n1, d2=d2, n2=n2)
+    lead = tuple(d1.shape[:-2])
+    if d1.dim() < 2 or d1.shape[-1] != width or d2.dim() != d1.dim() or d2.shape[-1] != width or tuple(d2.shape[:-2]) != lead:
+        raise ValueError(f"{fn}: need d1 [..., M1, {width}] and d2 [..., M2, {width}] under common leading axes, got {list(d1.shape)}, "
+                         f"{list(d2.shape)}")
+    if not convert and (d1.dtype != dtype or d2.dtype != dtype):
+        raise ValueError(f"{fn}: descriptors must be {str(dtype).replace('torch.', '')}, got {d1.dtype}, {d2.dtype}")
+    if tuple(n1.shape) != lead or tuple(n2.shape) != lead:
+        raise ValueError(f"{fn}: n1 and n2 must be {list(lead)}, got {list(n1.shape)}, {list(n2.shape)}")
+    B = int(np.prod(lead, dtype=np.int64))
+    if B < 1:
+        raise ValueError(f"{fn}: need at least one pair of sets, got leading axes {list(lead)}")
+    dev = d1.device
+    return lead, B, to_dev(d1, dtype, dev), to_dev(n1, torch.int32, dev), to_dev(d2, dtype, dev), to_dev(n2, torch.int32, dev)
+

@@ -71,6 +71,25 @@ def _bgr_u8(img, dev):
     return t.flip(-1).contiguous()
 
 
+def _one(im):
+    """a frame, host array or tensor -> a clip of that frame"""
+    return (im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im)))[None]
+
+
+def _poses_from_matches(xy1, xy2, pairs, K, baseline_m, hypotheses, seed, group_offset):
+    """keypoints xy1, xy2 [T, M, 2] and a matcher's pairs [T, max_matches, 2] (-1 behind the last) -> (essential_ransac's
+    result with a group per frame, x2d [2, T, max_matches, 2] NaN-padded) on the device, no read-back"""
+    valid = (pairs[..., 0] >= 0)[..., None]
+    idx = pairs.clamp(min=0).long()
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=pairs.device)
+    pick = lambda xy, col: torch.where(valid, torch.gather(xy, 1, idx[..., col, None].expand(-1, -1, 2)), nan)   # noqa: E731
+    x2d = torch.stack([pick(xy1, 0), pick(xy2, 1)])
+    Kd = (K if isinstance(K, torch.Tensor) else torch.from_numpy(np.asarray(K))).to(pairs.device, torch.float64).reshape(3, 3)
+    r = geometry.essential_ransac(x2d.reshape(2, -1, 2), torch.stack([Kd, Kd]), group_size=int(pairs.shape[1]), hypotheses=hypotheses,
+                                  seed=seed, group_offset=group_offset, baseline=float(baseline_m))
+    return r, x2d
+
+
 def estimate_camera_poses_from_ORB(frames1, frames2, K, baseline_m, max_matches: int = 1000, max_features: int = 3000,
                                    levels: int = 8, threshold: int = 20, hypotheses: int = 1024, seed: int = 0,
                                    group_offset: int = 0):
@@ -88,14 +107,7 @@ def estimate_camera_poses_from_ORB(frames1, frames2, K, baseline_m, max_matches:
     fa = geometry.orb_features(a, max_features, levels, threshold)
     fb = geometry.orb_features(b, max_features, levels, threshold)
     m = geometry.match_hamming(fa.desc, fa.count, fb.desc, fb.count, cross_check=True, max_matches=mm)
-    valid = (m.pairs[..., 0] >= 0)[..., None]
-    idx = m.pairs.clamp(min=0).long()
-    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
-    pick = lambda xy, col: torch.where(valid, torch.gather(xy, 1, idx[..., col, None].expand(-1, -1, 2)), nan)   # noqa: E731
-    x2d = torch.stack([pick(fa.xy, 0).reshape(-1, 2), pick(fb.xy, 1).reshape(-1, 2)])
-    Kd = (K if isinstance(K, torch.Tensor) else torch.from_numpy(np.asarray(K))).to(dev, torch.float64).reshape(3, 3)
-    r = geometry.essential_ransac(x2d, torch.stack([Kd, Kd]), group_size=mm, hypotheses=hypotheses, seed=seed,
-                                  group_offset=group_offset, baseline=float(baseline_m))
+    r, _ = _poses_from_matches(fa.xy, fb.xy, m.pairs, K, baseline_m, hypotheses, seed, group_offset)
     return (r.R.cpu().numpy(), r.t.cpu().numpy().reshape(T_, 3, 1), r.pose_mask.cpu().numpy().reshape(T_, mm),
             r.success.cpu().numpy())
 
@@ -107,8 +119,7 @@ def estimate_camera_pose_from_ORB(img1, img2, K, baseline_m, max_matches: int = 
     or three None when no essential matrix is found (fewer than 5 matches).  pose_mask marks the matches, ordered by
     (distance, query), that are inliers in front of both cameras.  group_offset = f draws the samples of frame f of
     estimate_camera_poses_from_ORB."""
-    one = lambda im: (im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im)))[None]   # noqa: E731
-    R, T, mask, ok = estimate_camera_poses_from_ORB(one(img1), one(img2), K, baseline_m, max_matches, max_features, levels, threshold,
+    R, T, mask, ok = estimate_camera_poses_from_ORB(_one(img1), _one(img2), K, baseline_m, max_matches, max_features, levels, threshold,
                                                     hypotheses, seed, group_offset)
     if not bool(ok[0]):
         return None, None, None
@@ -127,14 +138,7 @@ def _sift_chain(frames1, frames2, K, baseline_m, ratio_thresh, max_features, max
     fa = geometry.sift_features(a, max_features, roi=box(roi1))
     fb = geometry.sift_features(b, max_features, roi=box(roi2))
     m = geometry.match_l2(fa.desc, fa.count, fb.desc, fb.count, ratio=ratio_thresh, max_matches=mm)
-    valid = (m.pairs[..., 0] >= 0)[..., None]
-    idx = m.pairs.clamp(min=0).long()
-    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
-    pick = lambda xy, col: torch.where(valid, torch.gather(xy, 1, idx[..., col, None].expand(-1, -1, 2)), nan)   # noqa: E731
-    x2d = torch.stack([pick(fa.xy, 0), pick(fb.xy, 1)])
-    Kd = (K if isinstance(K, torch.Tensor) else torch.from_numpy(np.asarray(K))).to(dev, torch.float64).reshape(3, 3)
-    r = geometry.essential_ransac(x2d.reshape(2, -1, 2), torch.stack([Kd, Kd]), group_size=mm, hypotheses=hypotheses, seed=seed,
-                                  group_offset=group_offset, baseline=float(baseline_m))
+    r, x2d = _poses_from_matches(fa.xy, fb.xy, m.pairs, K, baseline_m, hypotheses, seed, group_offset)
     return r, x2d, m.count
 
 
@@ -150,9 +154,6 @@ def estimate_camera_poses_from_SIFT(frames1, frames2, K, baseline_m, ratio_thres
     T_, mm = int(x2d.shape[1]), int(x2d.shape[2])
     return (r.R.cpu().numpy(), r.t.cpu().numpy().reshape(T_, 3, 1), r.pose_mask.cpu().numpy().reshape(T_, mm),
             r.success.cpu().numpy())
-
-
-_one = lambda im: (im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im)))[None]   # noqa: E731
 
 
 def estimate_camera_pose_from_SIFT(img1, img2, K, baseline_m, ratio_thresh: float = 0.75, max_features: int = 3000,

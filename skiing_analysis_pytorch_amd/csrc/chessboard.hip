@@ -3,7 +3,7 @@
 // include/skimi.h; tests/chessboard_restated.py evaluates the same expressions.
 //   response    one launch: gray (cv2's 8-bit BGR weights), 3 x 3 binomial blur, the ChESS response on the radius-5 ring
 //               (Bennett & Lasenby) in int32, the frame's maximum by an integer atomic
-//   candidates  count / write launches in scene.hip's style: threshold against the frame's maximum, non-maximum suppression
+//   candidates  compact.h's count / write launches: threshold against the frame's maximum, non-maximum suppression
 //               with a raster-order tie rule, compaction in pixel order
 //   subpix      cv2.cornerSubPix's iteration in float64, a fixed number of rounds, one wave a point, the patch in LDS
 // Integer stages are exact and order-independent; the refinement's sums are reduce.h's wave_sum over a fixed lane
@@ -11,6 +11,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "compact.h"
 #include "fp64_util.h"
 #include "reduce.h"
 
@@ -146,20 +147,13 @@ __device__ inline bool chess_candidate(const int* __restrict__ R, int H, int W, 
 __global__ __launch_bounds__(kChessThreads) void chess_count_kernel(const int* __restrict__ resp, const int* __restrict__ rmax, int H,
                                                                     int W, int r, int t, unsigned* __restrict__ block_count) {
     __shared__ unsigned s_cnt;
-    const int tid = threadIdx.x;
     const long f = blockIdx.y, g = blockIdx.x;
     const int n = H * W;
     const int* R = resp + f * n;
     const int top = rmax[f];
-    if (tid == 0) s_cnt = 0;
-    __syncthreads();
     const long beg = g * kChessTile, end = min(beg + kChessTile, (long)n);
-    unsigned cnt = 0;
-    for (long i = beg + tid; i < end; i += kChessThreads) cnt += chess_candidate(R, H, W, (int)i, r, t, top) ? 1u : 0u;
-    cnt = wave_sum(cnt);
-    if ((tid & 63) == 0 && cnt) atomicAdd(&s_cnt, cnt);
-    __syncthreads();
-    if (tid == 0) block_count[f * gridDim.x + g] = s_cnt;
+    const unsigned cnt = tile_count<kChessThreads>(beg, end, s_cnt, [&](long i) { return chess_candidate(R, H, W, (int)i, r, t, top); });
+    if (threadIdx.x == 0) block_count[f * gridDim.x + g] = cnt;
 }
 
 // ---- launch 3: the counts become offsets; candidates are written in pixel order, the rest of the rows is padded ----
@@ -169,30 +163,13 @@ __global__ __launch_bounds__(kChessThreads) void chess_write_kernel(const int* _
                                                                     int* __restrict__ count) {
     __shared__ unsigned s_total, s_offset;
     __shared__ unsigned s_wtot[2][kChessWaves];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const long f = blockIdx.y, g = blockIdx.x;
     const int n = H * W;
     const int* R = resp + f * n;
     const int top = rmax[f];
     const unsigned* bc = block_count + f * gridDim.x;
-    if (tid == 0) {
-        s_total = 0;
-        s_offset = 0;
-    }
-    __syncthreads();
-    unsigned tot = 0, off = 0;
-    for (int i = tid; i < (int)gridDim.x; i += kChessThreads) {
-        const unsigned v = bc[i];
-        tot += v;
-        if (i < g) off += v;
-    }
-    tot = wave_sum(tot);
-    off = wave_sum(off);
-    if (lane == 0) {
-        atomicAdd(&s_total, tot);
-        atomicAdd(&s_offset, off);
-    }
-    __syncthreads();
+    group_offsets<kChessThreads>(bc, (int)gridDim.x, g, s_total, s_offset);
     const unsigned total = s_total;
     int* oxy = xy + f * cap * 2;
     int* ore = response + f * cap;
@@ -206,33 +183,16 @@ __global__ __launch_bounds__(kChessThreads) void chess_write_kernel(const int* _
     }
     if (bc[g] == 0) return;   // uniform: nothing of this workgroup's to write
     const long beg = g * kChessTile, end = min(beg + kChessTile, (long)n);
-    long row0 = (long)s_offset;
-    int buf = 0;
-    for (long i0 = beg; i0 < end; i0 += kChessThreads) {   // uniform trip count: every thread reaches the barrier
-        const long i = i0 + tid;
-        const bool kept = i < end && chess_candidate(R, H, W, (int)i, r, t, top);
-        const unsigned long long m = __ballot(kept);
-        if (lane == 0) s_wtot[buf][wave] = (unsigned)__popcll(m);
-        __syncthreads();
-        unsigned ahead = 0, chunk = 0;
-#pragma unroll
-        for (int k = 0; k < kChessWaves; ++k) {
-            const unsigned c = s_wtot[buf][k];
-            if (k < wave) ahead += c;
-            chunk += c;
-        }
-        if (kept) {
-            const long row = row0 + ahead + (long)__popcll(m & ((1ull << lane) - 1ull));
+    ordered_write<kChessThreads>(
+        beg, end, (long)s_offset, s_wtot, [&](long i) { return chess_candidate(R, H, W, (int)i, r, t, top); },
+        [&](long i, long row) {
             if (row < cap) {
                 const int y = (int)i / W;
                 oxy[2 * row] = (int)i - y * W;
                 oxy[2 * row + 1] = y;
                 ore[row] = R[i];
             }
-        }
-        row0 += chunk;
-        buf ^= 1;   // the next chunk writes the other totals: one barrier per chunk
-    }
+        });
 }
 
 // ---- the refinement: one wave a point, four points a workgroup ----

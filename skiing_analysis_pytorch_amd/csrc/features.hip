@@ -3,16 +3,17 @@
 // block in include/skimi.h; tests/features_restated.py evaluates the same expressions.
 //   gray, shrink, blur   the pyramid of a frame: bytes in the workspace, level after level
 //   fast                 the segment-test score of every level in one launch: a tile with its radius-3 halo in LDS
-//   count / write        chessboard.hip's exact compaction in pixel order: 3 x 3 non-maximum suppression and the box
+//   count / write        compact.h's exact compaction in pixel order: 3 x 3 non-maximum suppression and the box
 //   harris               the Harris response of every candidate, a candidate a lane
-//   select               one workgroup a (frame, level): an exact radix selection of the q_l largest responses (scene.hip's
-//                        style, ties to the smaller pixel), written in pixel order behind the levels before it
+//   select               one workgroup a (frame, level): compact.h's exact radix selection of the q_l largest responses
+//                        (ties to the smaller pixel), written in pixel order behind the levels before it
 //   describe             one wave a keypoint: the two moments by reduce.h's wave_sum, the direction as an integer argmax, the
 //                        256 bits as four 64-lane ballots
 //   match                one workgroup a pair of sets: train descriptors staged in LDS, a query a lane, the minimum of a packed
 //                        (distance << 16 | index) key; cross check, ratio, a stable counting sort over the 257 distances
 // Every stage is integer: the results are bitwise reproducible and a frame's do not depend on the batch around it.
 #include "common.h"
+#include "compact.h"
 #include "gray.h"
 #include "reduce.h"
 
@@ -218,20 +219,15 @@ __device__ inline long long orb_harris(const unsigned char* __restrict__ g, int 
 __global__ __launch_bounds__(kOrbThreads) void orb_count_kernel(OrbPyr py, const unsigned char* __restrict__ score,
                                                                 const double* __restrict__ roi, unsigned* __restrict__ block_count) {
     __shared__ unsigned s_cnt;
-    const int l = blockIdx.y, W = py.W[l], H = py.H[l], tid = threadIdx.x;
+    const int l = blockIdx.y, W = py.W[l], H = py.H[l];
     const long n = (long)W * H, g = blockIdx.x, f = blockIdx.z;
     if (g * kOrbTile >= n) return;
     const unsigned char* S = score + f * py.P + py.poff[l];
     const double* box = roi ? roi + 4 * f : nullptr;
-    if (tid == 0) s_cnt = 0;
-    __syncthreads();
     const long beg = g * kOrbTile, end = min(beg + kOrbTile, n);
-    unsigned cnt = 0;
-    for (long i = beg + tid; i < end; i += kOrbThreads) cnt += orb_candidate(S, W, H, py.W[0], py.H[0], (int)i, py.threshold, box) ? 1u : 0u;
-    cnt = wave_sum(cnt);
-    if ((tid & 63) == 0 && cnt) atomicAdd(&s_cnt, cnt);
-    __syncthreads();
-    if (tid == 0) block_count[f * py.G + py.goff[l] + g] = s_cnt;
+    const unsigned cnt = tile_count<kOrbThreads>(
+        beg, end, s_cnt, [&](long i) { return orb_candidate(S, W, H, py.W[0], py.H[0], (int)i, py.threshold, box); });
+    if (threadIdx.x == 0) block_count[f * py.G + py.goff[l] + g] = cnt;
 }
 
 __global__ __launch_bounds__(kOrbThreads) void orb_write_kernel(OrbPyr py, const unsigned char* __restrict__ score,
@@ -239,58 +235,24 @@ __global__ __launch_bounds__(kOrbThreads) void orb_write_kernel(OrbPyr py, const
                                                                 int* __restrict__ cand, int* __restrict__ level_count) {
     __shared__ unsigned s_total, s_offset;
     __shared__ unsigned s_wtot[2][kOrbWaves];
-    const int l = blockIdx.y, W = py.W[l], H = py.H[l], tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l = blockIdx.y, W = py.W[l], H = py.H[l];
     const long n = (long)W * H, g = blockIdx.x, f = blockIdx.z;
     if (g * kOrbTile >= n) return;
     const int groups = (int)((n + kOrbTile - 1) / kOrbTile);
     const unsigned char* S = score + f * py.P + py.poff[l];
     const double* box = roi ? roi + 4 * f : nullptr;
     const unsigned* bc = block_count + f * py.G + py.goff[l];
-    if (tid == 0) {
-        s_total = 0;
-        s_offset = 0;
-    }
-    __syncthreads();
-    unsigned tot = 0, off = 0;
-    for (int i = tid; i < groups; i += kOrbThreads) {
-        const unsigned v = bc[i];
-        tot += v;
-        if (i < g) off += v;
-    }
-    tot = wave_sum(tot);
-    off = wave_sum(off);
-    if (lane == 0) {
-        atomicAdd(&s_total, tot);
-        atomicAdd(&s_offset, off);
-    }
-    __syncthreads();
-    if (g == 0 && tid == 0) level_count[f * py.L + l] = (int)s_total;
+    group_offsets<kOrbThreads>(bc, groups, g, s_total, s_offset);
+    if (g == 0 && threadIdx.x == 0) level_count[f * py.L + l] = (int)s_total;
     if (bc[g] == 0) return;                   // uniform
     int* oc = cand + f * py.C + py.coff[l];
     const long cap = py.cap[l];
     const long beg = g * kOrbTile, end = min(beg + kOrbTile, n);
-    long row0 = (long)s_offset;
-    int buf = 0;
-    for (long i0 = beg; i0 < end; i0 += kOrbThreads) {   // uniform trip count
-        const long i = i0 + tid;
-        const bool kept = i < end && orb_candidate(S, W, H, py.W[0], py.H[0], (int)i, py.threshold, box);
-        const unsigned long long m = __ballot(kept);
-        if (lane == 0) s_wtot[buf][wave] = (unsigned)__popcll(m);
-        __syncthreads();
-        unsigned ahead = 0, chunk = 0;
-#pragma unroll
-        for (int k = 0; k < kOrbWaves; ++k) {
-            const unsigned c = s_wtot[buf][k];
-            if (k < wave) ahead += c;
-            chunk += c;
-        }
-        if (kept) {
-            const long row = row0 + ahead + (long)__popcll(m & ((1ull << lane) - 1ull));
+    ordered_write<kOrbThreads>(
+        beg, end, (long)s_offset, s_wtot, [&](long i) { return orb_candidate(S, W, H, py.W[0], py.H[0], (int)i, py.threshold, box); },
+        [&](long i, long row) {
             if (row < cap) oc[row] = (int)i;
-        }
-        row0 += chunk;
-        buf ^= 1;
-    }
+        });
 }
 
 // ---- the response of every candidate: grid (rows of level 0's capacity / threads, L, frames) ----
@@ -315,7 +277,7 @@ __global__ __launch_bounds__(kOrbThreads) void orb_select_kernel(OrbPyr py, cons
     __shared__ unsigned s_hist[256];
     __shared__ unsigned s_digit, s_need;
     __shared__ unsigned s_wtot[2][2][kOrbWaves];
-    const int l = blockIdx.x, W = py.W[l], H = py.H[l], M = py.M, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int l = blockIdx.x, W = py.W[l], H = py.H[l], M = py.M, tid = threadIdx.x;
     const long f = blockIdx.y;
     const int* lc = level_count + f * py.L;
     int base = 0, total = 0;
@@ -344,31 +306,13 @@ __global__ __launch_bounds__(kOrbThreads) void orb_select_kernel(OrbPyr py, cons
     // the key T of descending rank q - 1 and how many of the keys equal to it are kept; n <= q keeps everything
     unsigned long long T = 0;
     unsigned need = (unsigned)q;
-    if (n > q) {
-        for (int pass = 7; pass >= 0; --pass) {
-            s_hist[tid] = 0;
-            __syncthreads();
-            for (int i = tid; i < n; i += kOrbThreads) {
-                const unsigned long long key = orb_key(ch[i]);
-                if (pass == 7 || (key >> (8 * (pass + 1))) == (T >> (8 * (pass + 1)))) atomicAdd(&s_hist[(unsigned)(key >> (8 * pass)) & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                unsigned left = need;
-                int d = 255;
-                for (; d > 0; --d) {
-                    if (s_hist[d] >= left) break;
-                    left -= s_hist[d];
-                }
-                s_digit = (unsigned)d;
-                s_need = left;
-            }
-            __syncthreads();
-            T |= (unsigned long long)s_digit << (8 * pass);
-            need = s_need;
-            __syncthreads();                  // s_hist and s_need are rewritten by the next pass
-        }
-    }
+    if (n > q)
+        select_threshold<kOrbThreads>(
+            (unsigned)q,
+            [&](auto&& add) {
+                for (int i = tid; i < n; i += kOrbThreads) add(orb_key(ch[i]));
+            },
+            s_hist, s_digit, s_need, T, need);
     const unsigned char* S = score + f * py.P + py.poff[l];
     long row0 = base;
     unsigned eq0 = 0;
@@ -377,31 +321,9 @@ __global__ __launch_bounds__(kOrbThreads) void orb_select_kernel(OrbPyr py, cons
         const int i = i0 + tid;
         const bool live = i < n;
         const unsigned long long key = live ? orb_key(ch[i]) : 0;
-        const bool eq = live && n > q && key == T;
-        const unsigned long long me = __ballot(eq);
-        if (lane == 0) s_wtot[buf][0][wave] = (unsigned)__popcll(me);
-        __syncthreads();
-        unsigned eq_ahead = eq0, eq_chunk = 0;
-#pragma unroll
-        for (int k = 0; k < kOrbWaves; ++k) {
-            const unsigned c = s_wtot[buf][0][k];
-            if (k < wave) eq_ahead += c;
-            eq_chunk += c;
-        }
-        const unsigned eq_rank = eq_ahead + (unsigned)__popcll(me & ((1ull << lane) - 1ull));
-        const bool kept = live && (n <= q || key > T || (eq && eq_rank < need));
-        const unsigned long long mk = __ballot(kept);
-        if (lane == 0) s_wtot[buf][1][wave] = (unsigned)__popcll(mk);
-        __syncthreads();
-        unsigned ahead = 0, chunk = 0;
-#pragma unroll
-        for (int k = 0; k < kOrbWaves; ++k) {
-            const unsigned c = s_wtot[buf][1][k];
-            if (k < wave) ahead += c;
-            chunk += c;
-        }
-        if (kept) {
-            const long r = row0 + ahead + (long)__popcll(mk & ((1ull << lane) - 1ull));
+        unsigned rank, chunk;
+        if (select_rank<kOrbWaves>(key, live, n > q, T, need, eq0, s_wtot[buf], rank, chunk)) {
+            const long r = row0 + rank;
             if (r < M) {
                 const long o = f * M + r;
                 const int p = ci[i], y = p / W, x = p - y * W;
@@ -417,7 +339,6 @@ __global__ __launch_bounds__(kOrbThreads) void orb_select_kernel(OrbPyr py, cons
             }
         }
         row0 += chunk;
-        eq0 += eq_chunk;
         buf ^= 1;
     }
 }

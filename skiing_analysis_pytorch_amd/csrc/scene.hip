@@ -14,12 +14,13 @@
 // itself and gets the same digit), so there is no launch between passes.  Both order statistics of a percentile (ranks
 // i and i + 1) and, for the scale, both percentiles of an axis are selected in the same passes: selections of one key
 // stream that still share their prefix share one histogram.  The mask pass counts the kept pixels per workgroup; the
-// first vertex pass turns the counts into offsets and writes the cloud in pixel order.  Ten launches whatever the data;
-// no floating-point sum anywhere, only integer atomics (order-independent): results are bitwise reproducible and a
-// scene's results do not depend on the batch around it.
+// first vertex pass turns the counts into offsets and writes the cloud in pixel order (compact.h).  Ten launches
+// whatever the data; no floating-point sum anywhere, only integer atomics (order-independent): results are bitwise
+// reproducible and a scene's results do not depend on the batch around it.
 #include <math.h>
 
 #include "common.h"
+#include "compact.h"
 #include "fp64_util.h"
 #include "reduce.h"
 
@@ -310,31 +311,14 @@ __global__ __launch_bounds__(kSceneThreads) void scene_xyz_pass_kernel(const flo
     __shared__ unsigned s_prefix[kXyzSel], s_rank[kXyzSel], s_leader[kXyzSel];
     __shared__ unsigned s_total, s_offset;
     __shared__ unsigned s_wtot[2][kSceneWaves];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const long b = blockIdx.y, g = blockIdx.x;
     SceneWs* w = reinterpret_cast<SceneWs*>(ws + b * ws_stride);
     const unsigned* block_count = reinterpret_cast<const unsigned*>(w + 1);
     const double thr = w->thr[0];
     if (P == 1) {
         // the scene's kept count and the rows ahead of this workgroup's; integer sums, any order
-        if (tid == 0) {
-            s_total = 0;
-            s_offset = 0;
-        }
-        __syncthreads();
-        unsigned tot = 0, off = 0;
-        for (int i = tid; i < (int)gridDim.x; i += kSceneThreads) {
-            const unsigned v = block_count[i];
-            tot += v;
-            if (i < g) off += v;
-        }
-        tot = wave_sum(tot);
-        off = wave_sum(off);
-        if (lane == 0) {
-            atomicAdd(&s_total, tot);
-            atomicAdd(&s_offset, off);
-        }
-        __syncthreads();
+        group_offsets<kSceneThreads>(block_count, (int)gridDim.x, g, s_total, s_offset);
         const unsigned count = s_total;
         if (g == 0 && tid == 0) w->count = count;
         if (tid < kXyzSel) {
@@ -369,18 +353,10 @@ __global__ __launch_bounds__(kSceneThreads) void scene_xyz_pass_kernel(const flo
             }
         }
         if (P == 1) {
-            const unsigned long long m = __ballot(kept);
-            if (lane == 0) s_wtot[buf][wave] = (unsigned)__popcll(m);
-            __syncthreads();
-            unsigned ahead = 0, chunk = 0;
-#pragma unroll
-            for (int k = 0; k < kSceneWaves; ++k) {
-                const unsigned t = s_wtot[buf][k];
-                if (k < wave) ahead += t;
-                chunk += t;
-            }
+            unsigned chunk;
+            const unsigned rank = ordered_rank<kSceneWaves>(kept, s_wtot[buf], chunk);
             if (kept) {
-                const long row = row0 + ahead + (long)__popcll(m & ((1ull << lane) - 1ull));
+                const long row = row0 + rank;
                 if (row < cap) {
                     float* o = xyz + (b * cap + row) * 3;
                     if (align) {

@@ -5,11 +5,11 @@
 //   blur, half           the Gaussian scale space in float32: one launch a (octave, layer) for all frames; a 64 x 32 tile with
 //                        its halo in LDS, the horizontal pass into a second LDS tile, the vertical pass out of it.  The first
 //                        launch reads the frame's bytes through features.hip's gray.  Taps come from the host.
-//   count / write        features.hip's exact compaction in (octave, layer, y, x) order of the 26-neighbour extrema of the
+//   count / write        compact.h's exact compaction in (octave, layer, y, x) order of the 26-neighbour extrema of the
 //                        difference of neighbouring layers (computed where it is read, never stored)
 //   refine               a candidate a lane: the quadratic fit in float64 with + - * / only, contrast and edge tests, the box
-//   select               one workgroup a frame: an exact radix selection of the M largest |response|, ties to the earlier
-//                        candidate, rows in candidate order
+//   select               one workgroup a frame: compact.h's exact radix selection of the M largest |response|, ties to
+//                        the earlier candidate, rows in candidate order
 //   describe             one wave a keypoint: the orientation histogram and the 4 x 4 x 8 descriptor in float64, votes added
 //                        in LDS as integers of unit 2^-43, so the sums do not depend on the order of the lanes
 //   l2_nn, l2_keep       the matcher: nearest and second-nearest train rows on a grid of (64 queries, pair of sets, direction)
@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "compact.h"
 #include "gray.h"
 #include "reduce.h"
 
@@ -143,19 +144,13 @@ __device__ inline bool sift_candidate(const float* __restrict__ G, int W, int H,
 __global__ __launch_bounds__(kSiftThreads) void sift_count_kernel(SiftPyr py, const float* __restrict__ gauss,
                                                                   unsigned* __restrict__ block_count) {
     __shared__ unsigned s_cnt;
-    const int s = blockIdx.y, o = s / kSiftS, l = s - o * kSiftS + 1, W = py.W[o], H = py.H[o], tid = threadIdx.x;
+    const int s = blockIdx.y, o = s / kSiftS, l = s - o * kSiftS + 1, W = py.W[o], H = py.H[o];
     const long n = (long)W * H, g = blockIdx.x, f = blockIdx.z;
     if (g * kSiftTile >= n) return;
     const float* G = gauss + f * py.P + py.poff[o];
-    if (tid == 0) s_cnt = 0;
-    __syncthreads();
     const long beg = g * kSiftTile, end = min(beg + kSiftTile, n);
-    unsigned cnt = 0;
-    for (long i = beg + tid; i < end; i += kSiftThreads) cnt += sift_candidate(G, W, H, l, (int)i) ? 1u : 0u;
-    cnt = wave_sum(cnt);
-    if ((tid & 63) == 0 && cnt) atomicAdd(&s_cnt, cnt);
-    __syncthreads();
-    if (tid == 0) block_count[f * py.G + py.goff[s] + g] = s_cnt;
+    const unsigned cnt = tile_count<kSiftThreads>(beg, end, s_cnt, [&](long i) { return sift_candidate(G, W, H, l, (int)i); });
+    if (threadIdx.x == 0) block_count[f * py.G + py.goff[s] + g] = cnt;
 }
 
 __global__ __launch_bounds__(kSiftThreads) void sift_write_kernel(SiftPyr py, const float* __restrict__ gauss,
@@ -164,57 +159,22 @@ __global__ __launch_bounds__(kSiftThreads) void sift_write_kernel(SiftPyr py, co
     __shared__ unsigned s_total, s_offset;
     __shared__ unsigned s_wtot[2][kSiftWaves];
     const int s = blockIdx.y, o = s / kSiftS, l = s - o * kSiftS + 1, W = py.W[o], H = py.H[o];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const long n = (long)W * H, g = blockIdx.x, f = blockIdx.z;
     if (g * kSiftTile >= n) return;
     const int groups = (int)((n + kSiftTile - 1) / kSiftTile);
     const float* G = gauss + f * py.P + py.poff[o];
     const unsigned* bc = block_count + f * py.G + py.goff[s];
-    if (tid == 0) {
-        s_total = 0;
-        s_offset = 0;
-    }
-    __syncthreads();
-    unsigned tot = 0, off = 0;
-    for (int i = tid; i < groups; i += kSiftThreads) {
-        const unsigned v = bc[i];
-        tot += v;
-        if (i < g) off += v;
-    }
-    tot = wave_sum(tot);
-    off = wave_sum(off);
-    if (lane == 0) {
-        atomicAdd(&s_total, tot);
-        atomicAdd(&s_offset, off);
-    }
-    __syncthreads();
-    if (g == 0 && tid == 0) seg_count[f * kSiftSegs + s] = (int)s_total;
+    group_offsets<kSiftThreads>(bc, groups, g, s_total, s_offset);
+    if (g == 0 && threadIdx.x == 0) seg_count[f * kSiftSegs + s] = (int)s_total;
     if (bc[g] == 0) return;                   // uniform
     int* oc = cand + f * py.C + py.coff[s];
     const long cap = py.cap[o];
     const long beg = g * kSiftTile, end = min(beg + kSiftTile, n);
-    long row0 = (long)s_offset;
-    int buf = 0;
-    for (long i0 = beg; i0 < end; i0 += kSiftThreads) {   // uniform trip count
-        const long i = i0 + tid;
-        const bool kept = i < end && sift_candidate(G, W, H, l, (int)i);
-        const unsigned long long m = __ballot(kept);
-        if (lane == 0) s_wtot[buf][wave] = (unsigned)__popcll(m);
-        __syncthreads();
-        unsigned ahead = 0, chunk = 0;
-#pragma unroll
-        for (int k = 0; k < kSiftWaves; ++k) {
-            const unsigned c = s_wtot[buf][k];
-            if (k < wave) ahead += c;
-            chunk += c;
-        }
-        if (kept) {
-            const long row = row0 + ahead + (long)__popcll(m & ((1ull << lane) - 1ull));
+    ordered_write<kSiftThreads>(
+        beg, end, (long)s_offset, s_wtot, [&](long i) { return sift_candidate(G, W, H, l, (int)i); },
+        [&](long i, long row) {
             if (row < cap) oc[row] = (int)i;
-        }
-        row0 += chunk;
-        buf ^= 1;
-    }
+        });
 }
 
 // ---- refinement (rule 4): f64, + - * / only ----
@@ -320,7 +280,7 @@ __global__ __launch_bounds__(kSiftThreads) void sift_select_kernel(SiftPyr py, c
     __shared__ unsigned s_digit, s_need;
     __shared__ unsigned s_wtot[2][2][kSiftWaves];
     __shared__ int s_n[kSiftSegs];
-    const int M = py.M, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, segs = kSiftS * py.Oe;
+    const int M = py.M, tid = threadIdx.x, segs = kSiftS * py.Oe;
     const long f = blockIdx.x;
     if (tid < kSiftSegs) s_n[tid] = tid < segs ? min(seg_count[f * kSiftSegs + tid], py.cap[tid / kSiftS]) : 0;
     if (tid < py.O) {
@@ -336,35 +296,16 @@ __global__ __launch_bounds__(kSiftThreads) void sift_select_kernel(SiftPyr py, c
     // the key T of descending rank M - 1 and how many of the keys equal to it are kept; rows <= M keeps every key > 0
     unsigned long long T = 0;
     unsigned need = 0;
-    if (rows > M) {
-        need = (unsigned)M;
-        for (int pass = 7; pass >= 0; --pass) {
-            s_hist[tid] = 0;
-            __syncthreads();
-            for (int s = 0; s < segs; ++s) {
-                const unsigned long long* ks = kf + py.coff[s];
-                for (int i = tid; i < s_n[s]; i += kSiftThreads) {
-                    const unsigned long long k = ks[i];
-                    if (pass == 7 || (k >> (8 * (pass + 1))) == (T >> (8 * (pass + 1)))) atomicAdd(&s_hist[(unsigned)(k >> (8 * pass)) & 255u], 1u);
+    if (rows > M)
+        select_threshold<kSiftThreads>(
+            (unsigned)M,
+            [&](auto&& add) {
+                for (int s = 0; s < segs; ++s) {
+                    const unsigned long long* ks = kf + py.coff[s];
+                    for (int i = tid; i < s_n[s]; i += kSiftThreads) add(ks[i]);
                 }
-            }
-            __syncthreads();
-            if (tid == 0) {
-                unsigned left = need;
-                int d = 255;
-                for (; d > 0; --d) {
-                    if (s_hist[d] >= left) break;
-                    left -= s_hist[d];
-                }
-                s_digit = (unsigned)d;
-                s_need = left;
-            }
-            __syncthreads();
-            T |= (unsigned long long)s_digit << (8 * pass);
-            need = s_need;
-            __syncthreads();                  // s_hist and s_need are rewritten by the next pass
-        }
-    }
+            },
+            s_hist, s_digit, s_need, T, need);
     long row0 = 0;
     unsigned eq0 = 0;
     int buf = 0;
@@ -375,31 +316,9 @@ __global__ __launch_bounds__(kSiftThreads) void sift_select_kernel(SiftPyr py, c
             const int i = i0 + tid;
             const bool live = i < n;
             const unsigned long long k = live ? key[cb + i] : 0;
-            const bool eq = live && rows > M && k == T;
-            const unsigned long long me = __ballot(eq);
-            if (lane == 0) s_wtot[buf][0][wave] = (unsigned)__popcll(me);
-            __syncthreads();
-            unsigned eq_ahead = eq0, eq_chunk = 0;
-#pragma unroll
-            for (int w = 0; w < kSiftWaves; ++w) {
-                const unsigned c = s_wtot[buf][0][w];
-                if (w < wave) eq_ahead += c;
-                eq_chunk += c;
-            }
-            const unsigned eq_rank = eq_ahead + (unsigned)__popcll(me & ((1ull << lane) - 1ull));
-            const bool kept = live && k > 0 && (k > T || (eq && eq_rank < need));
-            const unsigned long long mk = __ballot(kept);
-            if (lane == 0) s_wtot[buf][1][wave] = (unsigned)__popcll(mk);
-            __syncthreads();
-            unsigned ahead = 0, chunk = 0;
-#pragma unroll
-            for (int w = 0; w < kSiftWaves; ++w) {
-                const unsigned c = s_wtot[buf][1][w];
-                if (w < wave) ahead += c;
-                chunk += c;
-            }
-            if (kept) {
-                const long r = row0 + ahead + (long)__popcll(mk & ((1ull << lane) - 1ull));
+            unsigned rank, chunk;
+            if (select_rank<kSiftWaves>(k, live && k > 0, rows > M, T, need, eq0, s_wtot[buf], rank, chunk)) {
+                const long r = row0 + rank;
                 if (r < M) {
                     const long q = f * M + r, c = cb + i;
                     xy[2 * q] = rxy[2 * c];
@@ -413,7 +332,6 @@ __global__ __launch_bounds__(kSiftThreads) void sift_select_kernel(SiftPyr py, c
                 }
             }
             row0 += chunk;
-            eq0 += eq_chunk;
             buf ^= 1;
         }
     }

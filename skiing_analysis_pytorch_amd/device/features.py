@@ -13,7 +13,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from .._args import f64, frame_clip, i32, on_device, to_dev, workspace
+from .._args import descriptor_sets, f64, feature_frames, i32, workspace
 from .._lib import check, current_stream, lib, ptr
 
 ORB_MAX_LEVELS, ORB_MAX_FEATURES, ORB_BORDER = 8, 4096, 16
@@ -95,16 +95,9 @@ def orb_features(frames: torch.Tensor, max_features: int = 500, levels: int = 8,
     as one of 32 integer angles, and the descriptor on a 5 x 5 blurred level.  roi [..., 4] (device; x1, y1, x2, y2 in level-0
     pixels, half-open) keeps only the keypoints inside a frame's box.  All integer: bitwise reproducible, and a frame gives
     the same bits alone and in a batch.  Nothing is read back."""
-    fr, five = frame_clip("orb_features", frames)
-    on_device("orb_features", roi=roi)
-    C, F, H, W, ch = (int(s) for s in fr.shape)
-    N, M, L, dev = C * F, int(max_features), int(levels), fr.device
-    if N < 1:
-        raise ValueError(f"orb_features: need at least one frame, got {N}")
-    lead = (C, F) if five else (F,)
-    if roi is not None and tuple(roi.shape) != (*lead, 4):
-        raise ValueError(f"orb_features: roi must be {list(lead)} + [4], got {list(roi.shape)}")
-    box = to_dev(roi, dev=dev)
+    fr, N, lead, box = feature_frames("orb_features", frames, roi)
+    H, W, ch = (int(s) for s in fr.shape[2:])
+    M, L, dev = int(max_features), int(levels), fr.device
     nws = int(lib().skimi_orb_workspace_bytes(N, H, W, L))
     xy, xyl = f64(dev, *lead, max(M, 0), 2), i32(dev, *lead, max(M, 0), 2)
     lvl, dirn, score = i32(dev, *lead, max(M, 0)), i32(dev, *lead, max(M, 0)), i32(dev, *lead, max(M, 0))
@@ -125,19 +118,8 @@ def match_hamming(d1: torch.Tensor, n1: torch.Tensor, d2: torch.Tensor, n2: torc
     = r keeps it iff d_best < r d_second in float64 (a lone train descriptor fails); max_distance bounds d_best.  The kept
     pairs by (distance, query), the first max_matches of them: sorted(matches, key=distance)[:max_matches] of the
     reference.  One launch, nothing is read back."""
-    on_device("match_hamming", d1=d1, n1=n1, d2=d2, n2=n2)
-    lead = tuple(d1.shape[:-2])
-    if d1.dim() < 2 or d1.shape[-1] != 8 or d2.dim() != d1.dim() or d2.shape[-1] != 8 or tuple(d2.shape[:-2]) != lead:
-        raise ValueError(f"match_hamming: need d1 [..., M1, 8] and d2 [..., M2, 8] under common leading axes, got {list(d1.shape)}, "
-                         f"{list(d2.shape)}")
-    if tuple(n1.shape) != lead or tuple(n2.shape) != lead:
-        raise ValueError(f"match_hamming: n1 and n2 must be {list(lead)}, got {list(n1.shape)}, {list(n2.shape)}")
+    lead, B, a, na, b, nb = descriptor_sets("match_hamming", d1, n1, d2, n2, 8, torch.int32, convert=True)
     dev, mm = d1.device, int(max_matches)
-    B = int(np.prod(lead, dtype=np.int64))
-    if B < 1:
-        raise ValueError(f"match_hamming: need at least one pair of sets, got leading axes {list(lead)}")
-    a, b = to_dev(d1, torch.int32, dev), to_dev(d2, torch.int32, dev)
-    na, nb = to_dev(n1, torch.int32, dev), to_dev(n2, torch.int32, dev)
     pairs, dist, count = i32(dev, *lead, max(mm, 0), 2), i32(dev, *lead, max(mm, 0)), i32(dev, *lead)
     check(lib().skimi_match_hamming(ptr(a), ptr(na), int(d1.shape[-2]), ptr(b), ptr(nb), int(d2.shape[-2]), B, int(bool(cross_check)),
                                     -1.0 if ratio is None else float(ratio), -1 if max_distance is None else int(max_distance), mm,

@@ -15,7 +15,7 @@ from typing import NamedTuple
 import numpy as np
 import torch
 
-from .._args import f64, frame_clip, i32, on_device, to_dev, u8, workspace
+from .._args import descriptor_sets, f64, feature_frames, i32, u8, workspace
 from .._lib import check, current_stream, lib, ptr
 
 SIFT_MAX_OCTAVES, SIFT_MAX_FEATURES, SIFT_MAX_CANDIDATES, SIFT_BORDER, SIFT_MIN_SIDE = 8, 4096, 32768, 5, 16
@@ -95,17 +95,10 @@ def sift_features(frames: torch.Tensor, max_features: int = 3000, octaves=None, 
     a 4 x 4 x 8 descriptor.  roi [..., 4] (device; x1, y1, x2, y2 in level-0 pixels, half-open) keeps only the keypoints
     inside a frame's box.  Bitwise reproducible, and a frame gives the same bits alone and in a batch.  Nothing is read
     back."""
-    fr, five = frame_clip("sift_features", frames)
-    on_device("sift_features", roi=roi)
-    C, F, H, W, ch = (int(s) for s in fr.shape)
-    N, M, dev = C * F, int(max_features), fr.device
+    fr, N, lead, box = feature_frames("sift_features", frames, roi)
+    H, W, ch = (int(s) for s in fr.shape[2:])
+    M, dev = int(max_features), fr.device
     O = sift_octaves(H, W) if octaves is None else int(octaves)
-    if N < 1:
-        raise ValueError(f"sift_features: need at least one frame, got {N}")
-    lead = (C, F) if five else (F,)
-    if roi is not None and tuple(roi.shape) != (*lead, 4):
-        raise ValueError(f"sift_features: roi must be {list(lead)} + [4], got {list(roi.shape)}")
-    box = to_dev(roi, dev=dev)
     nws = int(lib().skimi_sift_workspace_bytes(N, H, W, O))
     m = max(M, 0)
     xy, xyl, octv, lay = f64(dev, *lead, m, 2), i32(dev, *lead, m, 2), i32(dev, *lead, m), i32(dev, *lead, m)
@@ -127,22 +120,9 @@ def match_l2(d1: torch.Tensor, n1: torch.Tensor, d2: torch.Tensor, n2: torch.Ten
     nearest query is that query; max_distance2 bounds s1.  The kept pairs by (s1, query), the first max_matches of them:
     knnMatch(k = 2) + Lowe's ratio test + sorted(key=distance)[:max_matches] of the reference.  Two launches, nothing is read
     back."""
-    on_device("match_l2", d1=d1, n1=n1, d2=d2, n2=n2)
-    lead = tuple(d1.shape[:-2])
-    if d1.dim() < 2 or d1.shape[-1] != 128 or d2.dim() != d1.dim() or d2.shape[-1] != 128 or tuple(d2.shape[:-2]) != lead:
-        raise ValueError(f"match_l2: need d1 [..., M1, 128] and d2 [..., M2, 128] under common leading axes, got {list(d1.shape)}, "
-                         f"{list(d2.shape)}")
-    if d1.dtype != torch.uint8 or d2.dtype != torch.uint8:
-        raise ValueError(f"match_l2: descriptors must be uint8, got {d1.dtype}, {d2.dtype}")
-    if tuple(n1.shape) != lead or tuple(n2.shape) != lead:
-        raise ValueError(f"match_l2: n1 and n2 must be {list(lead)}, got {list(n1.shape)}, {list(n2.shape)}")
+    lead, B, a, na, b, nb = descriptor_sets("match_l2", d1, n1, d2, n2, 128, torch.uint8, convert=False)
     dev, mm = d1.device, int(max_matches)
-    B = int(np.prod(lead, dtype=np.int64))
-    if B < 1:
-        raise ValueError(f"match_l2: need at least one pair of sets, got leading axes {list(lead)}")
     M1, M2 = int(d1.shape[-2]), int(d2.shape[-2])
-    a, b = to_dev(d1, torch.uint8, dev), to_dev(d2, torch.uint8, dev)
-    na, nb = to_dev(n1, torch.int32, dev), to_dev(n2, torch.int32, dev)
     m = max(mm, 0)
     pairs, dist2, second2, count = i32(dev, *lead, m, 2), i32(dev, *lead, m), i32(dev, *lead, m), i32(dev, *lead)
     nws = 8 * B * (M1 + M2) + 4 * B * M1
