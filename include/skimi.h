@@ -258,6 +258,14 @@ int skimi_conv3x3_n32(const void* in_hi, const void* in_lo, const void* packed_w
  * in_lo = in_hi + C, px_stride = 2 * C. */
 int skimi_conv3x3_n32_strided(const void* in_hi, const void* in_lo, const void* packed_w, const float* bias, float* out,
                               int32_t F, int32_t H, int32_t W, int32_t C, int32_t relu, int64_t px_stride, void* stream);
+/* The tail of a DPT head: skimi_resize_bilinear_planes (slice_records == 0; src [F, h, w, C] fp32 to H x W, + the UV
+ * tables tabx [W, C/2], taby [H, C/2] or both NULL) followed by skimi_conv3x3_n32_strided on its records.  Where every
+ * 18 x 18 window of the conv touches at most 12 x 12 source samples (and SKIMI_DPT_TAIL_FUSED is not 0) one launch
+ * interpolates inside the conv and rec is not touched; otherwise the two launches run through rec (F * H * W * 2 C
+ * bf16).  The same bits either way.  *fused (may be NULL) says which ran. */
+int skimi_conv3x3_n32_upsampled(const float* src, int32_t h, int32_t w, const float* tabx, const float* taby,
+                                const void* packed_w, const float* bias, float* out, int32_t F, int32_t H, int32_t W, int32_t C,
+                                int32_t relu, void* rec, int32_t* fused, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Image preprocessing on the device (vggt/load.py:38-183)                    */

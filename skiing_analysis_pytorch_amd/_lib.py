@@ -87,6 +87,8 @@ _SIGNATURES = {
                                           C.c_float, _vp]),
     "skimi_conv3x3_n32_pack": (C.c_int, [_vp, _vp, C.c_int32, _vp]),
     "skimi_conv3x3_n32": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
+    "skimi_conv3x3_n32_upsampled": (C.c_int, [_vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "skimi_conv3x3_n32_strided": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                             C.c_int64, _vp]),
     "skimi_layernorm": (C.c_int, [_vp, _vp, C.c_int64, C.c_int64, C.c_int32, _vp, _vp, C.c_float, _vp,

@@ -161,6 +161,21 @@ int skimi_conv3x3_n32_strided(const void* in_hi, const void* in_lo, const void* 
                                   (long)px_stride);
 }
 
+int skimi_conv3x3_n32_upsampled(const float* src, int32_t h, int32_t w, const float* tabx, const float* taby,
+                                const void* packed_w, const float* bias, float* out, int32_t F, int32_t H, int32_t W, int32_t C,
+                                int32_t relu, void* rec, int32_t* fused, void* stream) {
+    const bool up = conv_direct_n32_up_eligible(h, w, H, W, C);
+    if (fused) *fused = up;
+    if (up)
+        return conv_direct_n32_up_launch(src, h, w, tabx, taby, (const unsigned short*)packed_w, bias, out, F, H, W, C, relu,
+                                         (hipStream_t)stream);
+    SKIMI_CHECK_ARG(rec != nullptr, "skimi_conv3x3_n32_upsampled: the two-launch path needs rec");
+    const int rc = bilinear_ac_planes_launch(src, (unsigned short*)rec, F, h, w, H, W, C, (hipStream_t)stream, tabx, taby);
+    if (rc != SKIMI_OK) return rc;
+    return conv_direct_n32_launch((const unsigned short*)rec, (const unsigned short*)rec + C, (const unsigned short*)packed_w, bias,
+                                  out, F, H, W, C, relu, (hipStream_t)stream, 2L * C);
+}
+
 int skimi_split_planes(const float* x, int64_t ld, int64_t rows, int32_t C, void* hi, void* lo, void* stream) {
     SKIMI_CHECK_ARG(x && hi && lo && rows > 0 && C > 0, "skimi_split_planes: bad arguments");
     return split_planes_launch(x, (long)ld, (long)rows, C, hi, lo, (hipStream_t)stream);

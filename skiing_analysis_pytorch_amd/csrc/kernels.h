@@ -110,6 +110,13 @@ int conv_direct_pack_launch(const float* w, unsigned short* out, int Cin, hipStr
 int conv_direct_n32_launch(const unsigned short* in_hi, const unsigned short* in_lo, const unsigned short* w_packed,
                            const float* bias, float* out, int F, int H, int W, int C, int relu, hipStream_t st,
                            long px_stride = 0);   // 0: separate planes [.., C]; 2C: pixel records [hi C | lo C]
+// the same conv on the align-corners bilinear resize of src [F][h][w][C] fp32 to H x W (+ the UV embedding tabx [W][C/2],
+// taby [H][C/2], or both null), interpolated in the window staging: bilinear_ac_planes_launch + conv_direct_n32_launch in
+// one launch with the same bits.  Eligible: SKIMI_DPT_TAIL_FUSED != 0 and every window's source samples fit its staging.
+bool conv_direct_n32_up_eligible(int h, int w, int H, int W, int C);
+int conv_direct_n32_up_launch(const float* src, int h, int w, const float* tabx, const float* taby,
+                              const unsigned short* w_packed, const float* bias, float* out, int F, int H, int W, int C, int relu,
+                              hipStream_t st);
 
 // VideoPose3D expand-conv im2col: x [B, L, Cin] f32 -> A0 [B*(L-k+1), Kpad] f32 (zero padded)
 int vp3d_im2col_launch(const float* x, float* a0, int B, int L, int Cin, int k, int Kpad, hipStream_t st);

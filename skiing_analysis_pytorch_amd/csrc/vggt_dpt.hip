@@ -244,17 +244,27 @@ void* run_dpt(Ctx& c, const DptW& w, float* const* sf, float* const* sg, int F, 
     void* c2 = nullptr;
     if (direct) {
         // upsample (+ UV embedding) straight into bf16 hi / lo planes, then the direct 3x3 -> 32 conv
+        // (shapes and a switch decide: the sizing pass agrees); where every window's source samples fit its staging,
+        // the conv interpolates them itself and the records never exist
+        const bool up = conv_direct_n32_up_eligible(h1, w1, Ho, Wo, f2);
         const size_t pe = (size_t)F * Ho * Wo * f2;
-        unsigned short* rec = (unsigned short*)c.ar.alloc(pe * 4);   // [pixel][hi f2 | lo f2]
+        unsigned short* rec = up ? nullptr : (unsigned short*)c.ar.alloc(pe * 4);   // [pixel][hi f2 | lo f2]
         c2 = c.ar.alloc((size_t)F * Ho * Wo * 32 * es);
-        c.run([&] {
-            return bilinear_ac_planes_launch((const float*)c1, rec, F, h1, w1, Ho, Wo, f2, c.st, uvt ? uvt->tx : nullptr,
-                                             uvt ? uvt->ty : nullptr);
-        });
-        c.run([&] {
-            return conv_direct_n32_launch(rec, rec + f2, w.oc2a_direct, w.oc2a.lin.b, (float*)c2, F, Ho, Wo, f2, 1, c.st,
-                                          2L * f2);
-        });
+        if (up) {
+            c.run([&] {
+                return conv_direct_n32_up_launch((const float*)c1, h1, w1, uvt ? uvt->tx : nullptr, uvt ? uvt->ty : nullptr,
+                                                 w.oc2a_direct, w.oc2a.lin.b, (float*)c2, F, Ho, Wo, f2, 1, c.st);
+            });
+        } else {
+            c.run([&] {
+                return bilinear_ac_planes_launch((const float*)c1, rec, F, h1, w1, Ho, Wo, f2, c.st, uvt ? uvt->tx : nullptr,
+                                                 uvt ? uvt->ty : nullptr);
+            });
+            c.run([&] {
+                return conv_direct_n32_launch(rec, rec + f2, w.oc2a_direct, w.oc2a.lin.b, (float*)c2, F, Ho, Wo, f2, 1, c.st,
+                                              2L * f2);
+            });
+        }
     } else {
         const int udt = (w.feature_only && w.out_f32) ? SKIMI_F32 : adt;   // the tracker's feature map: fp32 out of the last upsample
         void* c1u = c.ar.alloc((size_t)F * Ho * Wo * f2 * Ctx::esz(udt));

@@ -33,4 +33,34 @@ int permute_convT_launch(const float* in, float* out, int Ci, int Co, int s, hip
 int pad_cols_launch(const float* in, float* out, long rows, int K, int Kp, hipStream_t st);
 int tile_vec_launch(const float* in, float* out, int n, int reps, hipStream_t st);
 
+// The align-corners bilinear resize as bilinear_ac_planes_kernel and the fused window staging of conv_direct.hip both
+// compute it: one source of the arithmetic, its contraction switched off in the text, so that the two cannot round
+// differently.  One axis: output index I of a map resized from n source samples with scale = (n - 1) / (N - 1).
+struct BilinearTap {
+    int i0, i1;     // the two source samples
+    float l0, l1;   // their weights
+};
+inline __host__ __device__ BilinearTap bilinear_ac_tap(float scale, int I, int n) {
+#pragma clang fp contract(off)
+    const float f = scale * I;
+    BilinearTap t;
+    t.i0 = (int)f < n - 1 ? (int)f : n - 1;
+    t.i1 = t.i0 + 1 < n - 1 ? t.i0 + 1 : n - 1;
+    t.l1 = fminf(fmaxf(f - t.i0, 0.f), 1.f);
+    t.l0 = 1.f - t.l1;
+    return t;
+}
+#ifdef __HIPCC__
+// one value from its four source samples (+ e, the UV embedding, where add_e) -> the bf16 hi / lo halves of the fp32 result
+__device__ __forceinline__ void bilinear_ac_split(const BilinearTap& ty, const BilinearTap& tx, float p00, float p01, float p10,
+                                                  float p11, bool add_e, float e, short& hi, short& lo) {
+#pragma clang fp contract(off)
+    float r = ty.l0 * (tx.l0 * p00 + tx.l1 * p01) + ty.l1 * (tx.l0 * p10 + tx.l1 * p11);
+    if (add_e) r += e;
+    const unsigned short hb = f2bf(r);
+    hi = (short)hb;
+    lo = (short)f2bf(r - bf2f(hb));
+}
+#endif
+
 }  // namespace skimi

@@ -197,11 +197,8 @@ __global__ __launch_bounds__(256) void bilinear_ac_planes_kernel(const float* __
     for (int i = blockIdx.x * 256 + threadIdx.x; i < rowlen; i += gridDim.x * 256) {
         const int X = i / C8;
         const int c8 = i - X * C8;
-        const float fy = sy * Y, fx = sx * X;
-        const int y0 = min((int)fy, h - 1), x0 = min((int)fx, w - 1);
-        const int y1 = min(y0 + 1, h - 1), x1 = min(x0 + 1, w - 1);
-        const float ly1 = fminf(fmaxf(fy - y0, 0.f), 1.f), lx1 = fminf(fmaxf(fx - x0, 0.f), 1.f);
-        const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
+        const BilinearTap ty = bilinear_ac_tap(sy, Y, h), tx = bilinear_ac_tap(sx, X, w);
+        const int y0 = ty.i0, y1 = ty.i1, x0 = tx.i0, x1 = tx.i1;
         const float* base = in + n * (long)h * w * C + c8 * 8;
         float p00[8], p01[8], p10[8], p11[8];
         auto ld8 = [&](const float* q, float* d) {
@@ -212,23 +209,18 @@ __global__ __launch_bounds__(256) void bilinear_ac_planes_kernel(const float* __
         ld8(base + ((long)y0 * w + x1) * C, p01);
         ld8(base + ((long)y1 * w + x0) * C, p10);
         ld8(base + ((long)y1 * w + x1) * C, p11);
-        float r[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            r[k] = ly0 * (lx0 * p00[k] + lx1 * p01[k]) + ly1 * (lx0 * p10[k] + lx1 * p11[k]);
+        float e[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (tabx != nullptr) {
             const int half = C / 2, c = c8 * 8;
-            float e[8];
             ld8(c < half ? tabx + (long)X * half + c : taby + (long)Y * half + (c - half), e);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) r[k] += e[k];
         }
         bf16x8 hi, lo;
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-            const unsigned short hb = f2bf(r[k]);
-            hi[k] = (short)hb;
-            lo[k] = (short)f2bf(r[k] - bf2f(hb));
+            short hb, lb;
+            bilinear_ac_split(ty, tx, p00[k], p01[k], p10[k], p11[k], tabx != nullptr, e[k], hb, lb);
+            hi[k] = hb;
+            lo[k] = lb;
         }
         const long pix = ((n * H + Y) * (long)W + X) * 2 * C;
         // written once, read back much later by the conv (gigabytes in between): streaming stores

@@ -368,6 +368,23 @@ def conv3x3_n32(x, w, bias=None, relu=False, *, planes=None, px_stride=None, pac
     return out
 
 
+def conv3x3_n32_upsampled(src, H, W, packed, bias=None, relu=False, *, tabx=None, taby=None, out=None):
+    """A DPT head's tail (skimi_conv3x3_n32_upsampled): src [F, h, w, C] fp32 resized to H x W (align-corners bilinear, + the
+    UV tables) and convolved 3x3 -> 32 by `conv3x3_n32`, in one launch where the shape allows -> (fp32 [F, H, W, 32], whether
+    the one launch ran)"""
+    _require_cuda(src, packed, bias, tabx, taby, out)
+    F_, h, w, Cc = src.shape
+    assert src.dtype == torch.float32 and src.is_contiguous()
+    if out is None:
+        out = torch.empty((F_, H, W, 32), dtype=torch.float32, device=src.device)
+    rec = torch.empty((F_, H, W, 2 * Cc), dtype=torch.bfloat16, device=src.device)
+    fused = C.c_int32(-1)
+    check(lib().skimi_conv3x3_n32_upsampled(ptr(src), h, w, ptr(tabx), ptr(taby), ptr(packed), ptr(bias), ptr(out), F_, H, W, Cc,
+                                            1 if relu else 0, ptr(rec), C.byref(fused), _lib.current_stream()),
+          "skimi_conv3x3_n32_upsampled")
+    return out, bool(fused.value)
+
+
 def split_records(x):
     """fp32 [rows, C] -> bf16 [rows, ceil(C/32), 2, 32]: (hi, lo) halves of every 32-element slice in
     one 128-byte record (the `w_split` operand of `gemm`; a ragged last slice is zero-filled)."""
