@@ -1477,6 +1477,42 @@ int skimi_match_l2(const uint8_t* d1, const int32_t* n1, int32_t M1, const uint8
                    int32_t cross_check, double ratio, int32_t max_distance2, int32_t max_matches, int32_t* pairs, int32_t* dist2,
                    int32_t* second2, int32_t* count, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- drawing into uint8 frame clips: discs, rings, capsules and 5 x 7 glyphs (csrc/draw.hip) ----
+ * The last act of the reference's stages (cv2.circle / cv2.line / cv2.putText over every frame and joint), as one launch over
+ * a clip.  frames, out [C, F, H, W, ch] u8 (dev), ch 1, 3 or 4, sides 1 .. SKIMI_LENS_MAX_SIDE, 1 <= C, F, C F <= 65535; out ==
+ * frames draws in place, otherwise out receives every byte and frames is only read.  shapes (dev) i32 records of 8 words,
+ * P <= SKIMI_DRAW_MAX_SHAPES a list: shape_axes 2: [P, 8] shared by every frame, 3: [F, P, 8] (frame f of every camera
+ * reads list f), 4: [C, F, P, 8].  P = 0: out is a copy.  font (dev) u8 [96, 7]: characters 0x20 .. 0x7F, seven rows each, bit c
+ * of a row byte = column c from the left (values < 32); the kernel holds no table.  The anti-aliasing and the font are THIS
+ * PROJECT'S rules: no pixel parity with cv2's LINE_AA or Hershey fonts is claimed.  All arithmetic is integer; the result is
+ * bitwise reproducible and bitwise that of tests/draw_restated.py.
+ *  1. Record = kind, x0, y0, x1, y1, r, colour, opacity.  Positions and radii in 1/16 pixel; the centre of pixel (u, v) is
+ *     (16 u, 16 v) (cv2's convention: integer coordinates are pixel centres).  x0, y0, r, and x1, y1 of kinds 1 .. 3, are
+ *     saturated to +-2^20 on read (so no 64-bit expression below overflows); opacity is clamped to 0 .. 256; colour =
+ *     0x00c2c1c0: channel i of the frame gets byte i, a 1-channel frame byte 0, channel 3 of a 4-channel frame is never written.
+ *  2. Coverage cov in 0 .. 16 of a pixel centre p; isqrt = the exact floor square root of an int64; a = (x0, y0), b = (x1, y1).
+ *     kind 0 (and any kind outside 0 .. 4): nothing.
+ *     kind 1, disc: d = isqrt(|p - a|^2), cov = clamp(r + 8 - d, 0, 16).
+ *     kind 2, ring of radius r and half thickness h = x1: cov = clamp(h + 8 - |d - r|, 0, 16).
+ *     kind 3, capsule a -> b of half width r: a = b: the disc.  Else t = (p - a).(b - a), L2 = |b - a|^2; d = isqrt(|p - a|^2)
+ *       if t <= 0, isqrt(|p - b|^2) if t >= L2, else |cross(p - a, b - a)| / isqrt(L2) (floor division); cov as the disc.
+ *     kind 4, glyph: character x1 (outside 0x20 .. 0x7F: 0x7F), scale s = max(r, 1), cell top-left at pixel (left, top) =
+ *       (floor(x0 / 16), floor(y0 / 16)), 5 s x 7 s pixels; cov = 16 where bit (u - left) / s of font row (v - top) / s is set,
+ *       else 0: glyphs are not anti-aliased.
+ *  3. Compositing per pixel and channel, in list order (painter's algorithm): a = cov opacity (0 .. 4096), value = (value
+ *     (4096 - a) + colour_c a + 2048) >> 12; a = 0 changes nothing.  One thread owns a pixel: no atomics.
+ *  4. A workgroup owns a block of 4 x 4 tiles of 64 x 16 pixels of one frame and composites on a tile only the shapes whose
+ *     extent, grown by the radius (ring: r + h) plus one pixel, meets the tile; which shapes those are cannot change a byte
+ *     (cov = 0 outside that box).  One launch, no workspace, no host synchronisation. */
+#define SKIMI_DRAW_MAX_SHAPES 1024
+#define SKIMI_DRAW_NONE 0
+#define SKIMI_DRAW_DISC 1
+#define SKIMI_DRAW_RING 2
+#define SKIMI_DRAW_CAPSULE 3
+#define SKIMI_DRAW_GLYPH 4
+int skimi_draw_shapes_u8(const uint8_t* frames, uint8_t* out, const int32_t* shapes, int32_t shape_axes, const uint8_t* font,
+                         int32_t C, int32_t F, int32_t H, int32_t W, int32_t ch, int32_t P, void* stream);
+
 /* ---- VGGT head and track-head helper kernels, one launch each ----
  * The kernels skimi_vggt_forward runs between its GEMMs, exposed singly so that each can be tested against a float64
  * restatement.  All maps are channels-last and dense; dtype / out_dtype are SKIMI_F32, SKIMI_BF16 or SKIMI_F16.  Every

@@ -224,6 +224,8 @@ _SIGNATURES = {
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "skimi_match_l2": (C.c_int, [_vp, _vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int64, C.c_int32, C.c_double, C.c_int32, C.c_int32,
                                  _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "skimi_draw_shapes_u8": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       _vp]),
     "skimi_resize_bilinear": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, C.c_float, _vp]),
     "skimi_resize_bilinear_planes": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, C.c_int32, _vp, _vp]),
     "skimi_add_uv_pos": (C.c_int, [_vp, C.c_int32, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),

@@ -5,7 +5,8 @@ Four marked ground points give a homography onto a metric ground plane; every fr
 foot point is mapped to plan pixels and to metres, the side views' skeleton is placed on the plan, and the metric ground
 track (path length, speed, heading: merge's open TODO) is taken from the foot points.  The names and signatures follow
 front_side/front/bev_utils.py (copied as prepare_front_results/bev_utils.py), front_side/front/run.py and
-front_side/run.py, minus drawing and files: nothing here draws circles or text or writes PNGs (as angle.py).
+front_side/run.py, minus files: nothing here writes PNGs (as angle.py), and process_front_clip draws nothing; draw_points
+marks points on a clip with the device rasteriser (geometry.draw_shapes, DESIGN §2 "Drawing").
 
 The kernels are csrc/bev.hip (rules: include/skimi.h, DESIGN §2 "Bird's-eye view"), reached through geometry.homography_fit,
 geometry.homography_points, preprocess.warp_perspective, geometry.bev_skeleton and geometry.ground_track.  Box
@@ -107,6 +108,31 @@ def warp_image_to_bev(image: torch.Tensor, H: torch.Tensor, bev_size: Tuple[int,
         raise ValueError(f"H shape must be (3,3), got {list(Hd.shape)}")
     out = preprocess.warp_perspective(img if img.dim() == 4 else img[None], inverse3(Hd), bev_size)
     return out if img.dim() == 4 else out[0]
+
+
+def point_shapes(pts: torch.Tensor, color=(0, 0, 255), radius=4, labels=None) -> torch.Tensor:
+    """draw_points' shape list: pts [..., N, 2] -> int32 [..., N + characters, 8]: the N filled discs, then the labels (str(i + 1)
+    unless `labels` names them), in the points' colour at scale 2, from (+8, -8) of the point.  The reference converts the
+    points with np.asarray(dtype=int32), which truncates towards zero: so does this.  A non-finite point is left out."""
+    p = torch.as_tensor(pts).to(torch.float64)
+    if p.dim() < 2 or p.shape[-1] != 2:
+        raise ValueError(f"pts must be [..., N, 2], got {list(p.shape)}")
+    N = int(p.shape[-2])
+    names = [str(i + 1) for i in range(N)] if labels is None else [str(s) for s in labels]
+    if len(names) != N:
+        raise ValueError(f"draw_points: {len(names)} labels for {N} points")
+    q = torch.trunc(p)      # NaN stays NaN: kind 0 in both builders
+    off = torch.tensor([8.0, -8.0], dtype=torch.float64, device=p.device)
+    return geometry.cat_shapes(geometry.disc_shapes(q, radius, color), geometry.text_shapes(names, q + off, 2, color))
+
+
+def draw_points(frames: torch.Tensor, pts: torch.Tensor, color=(0, 0, 255), radius=4, labels=None) -> torch.Tensor:
+    """front_side/front/bev_utils.py: draw_points for a whole clip in one launch: frames uint8 [F, H, W, ch], pts [N, 2] (the
+    same points on every frame) or [F, N, 2], device tensors -> the drawn frames (a new tensor): a filled disc per point and
+    its number (labels: other strings).  Drawn by geometry.draw_shapes under the project's own anti-aliasing and font (DESIGN
+    §2 "Drawing"), not cv2's.  Nothing is read back."""
+    fr = device_tensor("draw_points", frames)
+    return geometry.draw_shapes(fr, point_shapes(device_tensor("draw_points", pts).to(fr.device), color, radius, labels))
 
 
 def check_homography(H) -> None:

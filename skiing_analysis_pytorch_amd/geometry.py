@@ -44,6 +44,9 @@ from .device.features import (ORB_MAX_LEVELS, ORB_MAX_FEATURES, ORB_BORDER, OrbF
                               orb_features, match_hamming)
 from .device.sift import (SIFT_MAX_OCTAVES, SIFT_MAX_FEATURES, SIFT_MAX_CANDIDATES, SIFT_BORDER, SiftFeatures, L2Matches, sift_taps,
                           sift_octaves, sift_features, match_l2)
+from .device.draw import (DRAW_MAX_SHAPES, DRAW_NONE, DRAW_DISC, DRAW_RING, DRAW_CAPSULE, DRAW_GLYPH, GLYPH_ADVANCE, GLYPH_HEIGHT,
+                          font_5x7, draw_shapes, pack_colour, disc_shapes, segment_shapes, polyline_shapes, glyph_shapes,
+                          string_codes, text_shapes, number_shapes, cat_shapes)
 from .device.lens import _undistorted_f32
 
 # ---- host helpers of the wrapper (small arrays, NumPy as in the reference) -----------------
