@@ -1513,6 +1513,53 @@ int skimi_match_l2(const uint8_t* d1, const int32_t* n1, int32_t M1, const uint8
 int skimi_draw_shapes_u8(const uint8_t* frames, uint8_t* out, const int32_t* shapes, int32_t shape_axes, const uint8_t* font,
                          int32_t C, int32_t F, int32_t H, int32_t W, int32_t ch, int32_t P, void* stream);
 
+/* ---- mask analysis: components, distance transform, boxes, IoU, greedy NMS (csrc/masks.hip) ----
+ * The mask post-processing of the reference's SAM3 (perflib/connected_components.py, perflib/nms.py, perflib/masks_ops.py,
+ * model/edt.py), on device masks.  A mask is u8 [H, W] (dev), non-zero = foreground; masks [B, H, W] with 1 <= H, W <=
+ * SKIMI_MASK_MAX_SIDE and B H W < 2^31.  All arithmetic is integer (dist and iou are one stated float operation on integers);
+ * every result is bitwise reproducible, bitwise that of tests/masks_restated.py, and for each mask what it is for that mask
+ * alone.  No call synchronises or reads back, and the number of launches of a call depends on the shapes only.
+ *  1. skimi_mask_components: connectivity 4 (the cross) or 8 (the full 3 x 3).  labels i32 [B, H, W]: 0 on background; the
+ *     components of a mask are numbered 1 .. count[b] in the raster order of their first pixels (scipy.ndimage.label's
+ *     numbering; THIS PROJECT'S rule: the reference's backends disagree with each other).  areas i32 [B, H, W]: the pixel count
+ *     of the pixel's component, 0 on background.  count i32 [B].  stats i64 [B, max_components, 7] = area, x_min, y_min, x_max,
+ *     y_max (inclusive), sum of x, sum of y of components 1 .. max_components; rows behind count[b] are zero; a component
+ *     whose label is above max_components is missing from the table only.  max_components = 0: no table (stats may be NULL).
+ *     ws (dev): skimi_mask_components_workspace_bytes.  Method: a block union-find (64 x 16 tiles in LDS, atomicMin across the
+ *     tile borders); the root of a component is its smallest linear index, which no order of execution can change.
+ *  2. skimi_mask_edt: d2 i32 [B, H, W] = the exact squared Euclidean distance from each pixel to the nearest zero pixel of its
+ *     mask (0 on zero pixels); border_zero != 0: every position outside the image counts as zero (the reference's
+ *     padding=True).  A mask without any zero (and border_zero = 0) gives d2 = SKIMI_EDT_NONE everywhere and dist = +inf (THIS
+ *     PROJECT'S rule: the reference gives sqrt(1e18), cv2 a large finite value).  dist f32 [B, H, W] or NULL =
+ *     (float)sqrt((double)d2).  Two integer passes: columns (vertical distance g), then rows (min over x' of (x - x')^2 +
+ *     g(x')^2, stopped where (x - x')^2 + the row's smallest g^2 reaches the best so far).
+ *  3. skimi_mask_argmax: of an i32 map [B, H, W] of values >= 0: xy i32 [B, 2] = (x, y) of the largest value, ties to the first
+ *     in raster order; best i32 [B] = that value.
+ *  4. skimi_mask_pack: masks [B, HW] -> words u64 [B, ceil(HW / 64)]: bit i of word k = pixel 64 k + i of the flattened mask, the
+ *     last word zero-filled.  skimi_mask_boxes on packed masks: xyxy i32 [B, 4] = inclusive x_min, y_min, x_max, y_max; an empty
+ *     mask gives (W, H, 0, 0) (the arithmetic of the reference's masks_to_boxes); area i32 [B].
+ *  5. skimi_mask_iou: a [T, N, words], b [T, M, words] packed -> inter, uni i32 [T, N, M] = popcount(a & b), popcount(a | b),
+ *     iou f32 = (float)inter / (float)max(uni, 1).  1 <= T <= 65535.
+ *  6. skimi_nms_greedy: T problems; iou f32 [T, N, N], scores f32 [T, N], valid u8 [T, N] or NULL, N <= SKIMI_NMS_MAX -> keep
+ *     u8 [T, N].  Entries are visited by score descending, ties (-0 = +0) to the lower index (THIS PROJECT'S rule: a stable
+ *     sort, as the reference's Triton path; its CPU loop leaves ties to argsort); a visited entry that no kept entry
+ *     suppressed is kept; a kept i suppresses every later j with iou[i, j] > iou_threshold (in f32; a NaN iou suppresses
+ *     nothing).  An entry with valid == 0 or a NaN score is not kept and suppresses nothing.  One workgroup a problem. */
+#define SKIMI_MASK_MAX_SIDE 4096
+#define SKIMI_EDT_NONE (1 << 30)
+#define SKIMI_NMS_MAX 1024
+size_t skimi_mask_components_workspace_bytes(int64_t B, int32_t H, int32_t W);
+int skimi_mask_components(const uint8_t* masks, int64_t B, int32_t H, int32_t W, int32_t connectivity, int32_t max_components,
+                          int32_t* labels, int32_t* areas, int32_t* count, int64_t* stats, void* ws, size_t ws_bytes, void* stream);
+int skimi_mask_edt(const uint8_t* masks, int64_t B, int32_t H, int32_t W, int32_t border_zero, int32_t* d2, float* dist, void* stream);
+int skimi_mask_argmax(const int32_t* d2, int64_t B, int32_t H, int32_t W, int32_t* xy, int32_t* best, void* stream);
+int skimi_mask_pack(const uint8_t* masks, int64_t B, int64_t HW, uint64_t* words, void* stream);
+int skimi_mask_boxes(const uint64_t* words, int64_t B, int32_t H, int32_t W, int32_t* xyxy, int32_t* area, void* stream);
+int skimi_mask_iou(const uint64_t* a, const uint64_t* b, int32_t T, int32_t N, int32_t M, int64_t words, float* iou, int32_t* inter,
+                   int32_t* uni, void* stream);
+int skimi_nms_greedy(const float* iou, const float* scores, const uint8_t* valid, int32_t T, int32_t N, float iou_threshold, uint8_t* keep,
+                     void* stream);
+
 /* ---- VGGT head and track-head helper kernels, one launch each ----
  * The kernels skimi_vggt_forward runs between its GEMMs, exposed singly so that each can be tested against a float64
  * restatement.  All maps are channels-last and dense; dtype / out_dtype are SKIMI_F32, SKIMI_BF16 or SKIMI_F16.  Every

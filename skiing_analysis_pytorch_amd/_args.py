@@ -237,3 +237,30 @@ def descriptor_sets(fn, d1, n1, d2, n2, width, dtype, convert):
     dev = d1.device
     return lead, B, to_dev(d1, dtype, dev), to_dev(n1, torch.int32, dev), to_dev(d2, dtype, dev), to_dev(n2, torch.int32, dev)
 
+
+
+# ---- masks (device/masks.py) -----------------------------------------------------------------------------------------
+MASK_MAX_SIDE = 4096
+
+
+def mask_batch(fn, masks, ndim=3, name="masks"):
+    """bool or uint8 device masks [..., H, W] with `ndim` axes, or one axis fewer (add_lead's rule) -> (contiguous uint8 of
+    `ndim` axes, whether the axis was added).  Everything that is wrong is a ValueError, a host tensor included; the leading
+    axes may be empty, the sides may not."""
+    if not isinstance(masks, torch.Tensor) or not masks.is_cuda:
+        raise ValueError(f"{fn}: {name} must be a device tensor (it is on {getattr(masks, 'device', 'the host')})")
+    if masks.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"{fn}: {name} must be bool or uint8, got {masks.dtype}")
+    if masks.dim() not in (ndim - 1, ndim):
+        raise ValueError(f"{fn}: {name} must have {ndim - 1} or {ndim} axes [..., H, W], got {list(masks.shape)}")
+    m, single = add_lead(masks.contiguous(), ndim)
+    H, W = int(m.shape[-2]), int(m.shape[-1])
+    if not (1 <= H <= MASK_MAX_SIDE and 1 <= W <= MASK_MAX_SIDE):
+        raise ValueError(f"{fn}: {name} of {W} x {H} pixels, sides must be 1 .. {MASK_MAX_SIDE}")
+    if m.numel() >= 2 ** 31:
+        raise ValueError(f"{fn}: {name} holds {m.numel()} pixels, at most 2^31 - 1")
+    return (m.view(torch.uint8) if m.dtype == torch.bool else m), single
+
+
+def i64(dev, *shape):
+    return torch.empty(shape, dtype=torch.int64, device=dev)

@@ -47,6 +47,8 @@ from .device.sift import (SIFT_MAX_OCTAVES, SIFT_MAX_FEATURES, SIFT_MAX_CANDIDAT
 from .device.draw import (DRAW_MAX_SHAPES, DRAW_NONE, DRAW_DISC, DRAW_RING, DRAW_CAPSULE, DRAW_GLYPH, GLYPH_ADVANCE, GLYPH_HEIGHT,
                           font_5x7, draw_shapes, pack_colour, disc_shapes, segment_shapes, polyline_shapes, glyph_shapes,
                           string_codes, text_shapes, number_shapes, cat_shapes)
+from .device.masks import (MASK_MAX_SIDE, EDT_NONE, NMS_MAX, STATS_FIELDS, ComponentsResult, EdtResult, MaskBoxes, MaskIoU,
+                           mask_components, distance_transform, mask_inner_point, pack_masks, mask_boxes, mask_iou, nms_greedy)
 from .device.lens import _undistorted_f32
 
 # ---- host helpers of the wrapper (small arrays, NumPy as in the reference) -----------------

@@ -1072,6 +1072,52 @@ def gen_fuse_group():
 GENERATORS["fuse_group"] = gen_fuse_group
 
 
+def gen_masks():
+    """DESIGN §2 "Masks": the reference's OWN masks_to_boxes and mask_iou (prepare_front_results/sam3/perflib/masks_ops.py) and
+    generic_nms_cpu (perflib/nms.py) on the CPU, on the inputs of tests/masks_cases.py.  The sam3 package's __init__ imports
+    iopath, which is not installed: an empty stand-in package with the real path takes its place, everything below it
+    (sam3.perflib and its modules) is the reference's own.  The NMS problems have distinct scores: the CPU loop leaves ties to
+    argsort.  Only inputs and results are stored.  (connected_components_cpu needs skimage and the _slow point sampler cv2:
+    neither is installed, so they have no golden.)"""
+    import hashlib
+    import types
+
+    sys.path.insert(0, str(ROOT / "tests"))
+    import masks_cases as mc
+
+    pkg = types.ModuleType("sam3")
+    pkg.__path__ = [os.path.join(REF, "prepare_front_results", "sam3")]
+    saved = sys.modules.get("sam3")
+    sys.modules["sam3"] = pkg
+    try:
+        from sam3.perflib import masks_ops, nms
+    finally:
+        if saved is None:
+            sys.modules.pop("sam3", None)
+        else:
+            sys.modules["sam3"] = saved
+    out = {}
+    H, W = mc.SIZES[0]
+    for k, (n, m) in enumerate(mc.IOU_SHAPES):
+        a, b = mc.iou_masks(n, H, W, seed=100 + k), mc.iou_masks(m, H, W, seed=200 + k)
+        out[f"iou{k}_a"], out[f"iou{k}_b"] = a, b
+        out[f"iou{k}_iou"] = masks_ops.mask_iou(torch.from_numpy(a != 0), torch.from_numpy(b != 0)).numpy()
+        out[f"iou{k}_boxes"] = masks_ops.masks_to_boxes(torch.from_numpy(a), list(range(n))).numpy()
+    for n in mc.NMS_COUNTS:
+        io, scores, _ = mc.nms_problem(n, seed=300 + n)
+        assert len(np.unique(scores)) == n
+        # the inputs are seeded: stored as their digest
+        out[f"nms{n}_digest"] = np.array(hashlib.sha256(io.tobytes() + scores.tobytes()).hexdigest())
+        for thr in mc.NMS_THRESHOLDS:
+            out[f"nms{n}_kept_{thr}"] = nms.generic_nms_cpu(torch.from_numpy(io), torch.from_numpy(scores), thr).numpy()
+    path = GOLD / "masks.npz"
+    np.savez_compressed(path, **out)
+    print("wrote", path.name, path.stat().st_size, "bytes")
+
+
+GENERATORS["masks"] = gen_masks
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GENERATORS)
     for w in which:
