@@ -1560,6 +1560,54 @@ int skimi_mask_iou(const uint64_t* a, const uint64_t* b, int32_t T, int32_t N, i
 int skimi_nms_greedy(const float* iou, const float* scores, const uint8_t* valid, int32_t T, int32_t N, float iou_threshold, uint8_t* keep,
                      void* stream);
 
+/* ---- association and tracking: linear assignment, box tracker (csrc/assign.hip, csrc/lsap.h) ----
+ * What the reference does on the host between frames (SAM3's perflib/associate_det_trk.py and model/sam3_video_base.py:
+ * iou.cpu() + scipy.optimize.linear_sum_assignment; the same solver per time step in eval/hota_eval_toolkit) and what its
+ * YOLO box picker says it lacks (prepare_dataset/model/yolov11_bbox.py: "no id-keeping mechanism").  One wave a problem / a
+ * clip, no atomics, nothing read back, the launches of a call depend on the shapes only; every result is bitwise
+ * reproducible, bitwise that of tests/assign_restated.py, and for each problem / clip what it is alone.
+ *
+ * skimi_linear_assignment: B problems; cost f64 [B, N, M] (dev), 1 <= N, M <= SKIMI_ASSIGN_MAX; n_rows, n_cols i32 [B] (dev)
+ * or NULL (= N, M): problem b is the top-left n_rows[b] x n_cols[b] block (a count is clipped to 0 .. N, 0 .. M; 0 is an empty
+ * problem).  -> row_to_col i32 [B, N], col_to_row i32 [B, M] (-1: unassigned; exactly min(n_rows, n_cols) pairs), total f64
+ * [B], status i32 [B].  The minimum of the sum of the assigned costs; no forbidden edges.
+ *  1. status = 1 iff the block holds a NaN or an infinity (or, with finite entries near the largest double, a step of the
+ *     search finds no column at a finite distance): the maps are then all -1 and total is NaN.  Else status = 0.
+ *  2. Method: shortest augmenting paths with dual variables u (rows), v (columns) in f64, all zero at the start (Crouse 2016,
+ *     the method of scipy.optimize.linear_sum_assignment).  If n_rows > n_cols the transpose is solved.  Rows are inserted in
+ *     ascending order.  For the row `cur` being inserted: min = 0, i = cur, every column unvisited with distance sp = +inf.
+ *  3. A Dijkstra step: for every unvisited column j, r = ((min + cost[i, j]) - u[i]) - v[j]; if r < sp[j] then sp[j] = r and
+ *     pred[j] = i.  The next column is the unvisited one with the smallest sp; TIES GO TO THE LOWEST COLUMN INDEX, with no
+ *     preference for free columns.  min = its sp; it becomes visited; if it is free it is the sink, else i = its row.
+ *  4. The duals after a path: u[cur] += min, and for every visited column j other than the sink u[row4col[j]] += min - sp[j]
+ *     and v[j] -= min - sp[j] (row4col as it was before the path is flipped).  Then the path is flipped from the sink back
+ *     along pred to cur.
+ *  5. total = 0 + the assigned costs in ascending row order (of the block, not of the transpose), one f64 addition each.
+ *  6. NOT PROMISED: scipy's assignment when the optimum is not unique.  scipy prefers a free column among equal distances and
+ *     visits the columns in another order; where several assignments share the minimum the two may pick different ones (the
+ *     totals agree to rounding).  With a unique optimum the assignment is scipy's.
+ *
+ * skimi_link_boxes: persistent ids for the boxes of B clips; boxes f64 [B, T, N, 4] (dev) x1, y1, x2, y2 in pixels, a box with
+ * a non-finite coordinate is "no detection"; scores f64 [B, T, N] (dev) or NULL; 1 <= N, K <= SKIMI_LINK_MAX, K = the most
+ * tracks a clip may have; max_age >= 0.  -> ids i32 [B, T, N] (-1: none), n_tracks i32 [B], table i32 [B, K, 3] = first frame,
+ * last frame, hits of track k (-1, -1, 0 behind n_tracks), overflow i32 [B].  Frame by frame:
+ *  1. The live tracks are those whose age is at most max_age, in ascending id order (age: the frames since the track was
+ *     last matched; a track matched in frame t has age 0 at frame t + 1).  The detections are the valid boxes in index order.
+ *  2. cost[d, k] = 1 - IoU(box d, the last box of live track k) in f64: iw = min(x2) - max(x1), ih = min(y2) - max(y1), inter =
+ *     iw ih if both are > 0 else 0, union = (area_d + area_k) - inter, IoU = inter / union, 0 when union <= 0.  The rules of
+ *     skimi_linear_assignment solve detections x live tracks (a failed solve assigns nothing).
+ *  3. An assigned pair with IoU >= iou_threshold gives the detection the track's id, replaces the track's box and resets its
+ *     age.  Every other valid detection with score >= new_score (no scores: every one) starts a track with the next id, in
+ *     detection-index order.
+ *  4. Ids are never reused.  When K tracks exist, further such detections get id -1 and overflow counts them.
+ *  5. A track that was not matched in the frame ages by one. */
+#define SKIMI_ASSIGN_MAX 1024
+#define SKIMI_LINK_MAX 64
+int skimi_linear_assignment(const double* cost, const int32_t* n_rows, const int32_t* n_cols, int64_t B, int32_t N, int32_t M,
+                            int32_t* row_to_col, int32_t* col_to_row, double* total, int32_t* status, void* stream);
+int skimi_link_boxes(const double* boxes, const double* scores, int64_t B, int32_t T, int32_t N, int32_t K, double iou_threshold,
+                     int32_t max_age, double new_score, int32_t* ids, int32_t* n_tracks, int32_t* table, int32_t* overflow, void* stream);
+
 /* ---- VGGT head and track-head helper kernels, one launch each ----
  * The kernels skimi_vggt_forward runs between its GEMMs, exposed singly so that each can be tested against a float64
  * restatement.  All maps are channels-last and dense; dtype / out_dtype are SKIMI_F32, SKIMI_BF16 or SKIMI_F16.  Every

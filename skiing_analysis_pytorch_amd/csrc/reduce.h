@@ -1,6 +1,6 @@
 // Fixed-order reductions of the float64 solver kernels.  Two schemes, which give different bits and are not to be mixed:
 //  - wave_sum: a xor butterfly over the 64 lanes; every lane gets the same bits (a + b == b + a).  Overloads beside
-//    common.h's float one.
+//    common.h's float one.  wave_argmin: the same butterfly on a (value, index) pair (lsap.h: the next column of a path).
 //  - block_sum / total / block_max: a shuffle-down tree per wave into `red`, then the waves in order.
 #pragma once
 #include "common.h"
@@ -22,6 +22,17 @@ __device__ __forceinline__ unsigned wave_sum(unsigned v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o, 64);
     return v;
+}
+
+// The smallest (value, index) pair of the 64 lanes, ordered by value and then by index: a xor butterfly, so every lane gets
+// the same pair as long as no value is NaN (the order is then total and the minimum is one pair, or equal pairs).
+__device__ __forceinline__ void wave_argmin(double& v, int& i) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(v, o, 64);
+        const int oi = __shfl_xor(i, o, 64);
+        if (ov < v || (ov == v && oi < i)) v = ov, i = oi;
+    }
 }
 
 // Exact selection of two ranks by one wave: the keys (order-preserving, key64) are spread over the lanes, for_keys(f) calls

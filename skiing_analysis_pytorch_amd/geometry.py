@@ -49,6 +49,7 @@ from .device.draw import (DRAW_MAX_SHAPES, DRAW_NONE, DRAW_DISC, DRAW_RING, DRAW
                           string_codes, text_shapes, number_shapes, cat_shapes)
 from .device.masks import (MASK_MAX_SIDE, EDT_NONE, NMS_MAX, STATS_FIELDS, ComponentsResult, EdtResult, MaskBoxes, MaskIoU,
                            mask_components, distance_transform, mask_inner_point, pack_masks, mask_boxes, mask_iou, nms_greedy)
+from .device.assign import (ASSIGN_MAX, LINK_MAX, Assignment, LinkedBoxes, linear_assignment, link_boxes)
 from .device.lens import _undistorted_f32
 
 # ---- host helpers of the wrapper (small arrays, NumPy as in the reference) -----------------

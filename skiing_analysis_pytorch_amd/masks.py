@@ -3,8 +3,14 @@ perflib/masks_ops.py, perflib/nms.py, model/edt.py, model/sam3_tracker_utils.py)
 turns a clip's person masks into the boxes bev.process_front_clip takes.  Thin mirrors of geometry.mask_components,
 distance_transform, mask_inner_point, mask_boxes, mask_iou and nms_greedy (device/masks.py; rules: include/skimi.h, DESIGN §2
 "Masks"); the rest is torch ops on the same device.  Only generic_nms synchronises.
+
+associate_det_trk is perflib/associate_det_trk.py for a frame or a clip, on geometry.mask_iou and geometry.linear_assignment
+(device/assign.py; DESIGN §2 "Association and tracking") without a read-back; association_lists makes the reference's Python
+objects of its result, with one copy.
 """
 from __future__ import annotations
+
+from collections import namedtuple
 
 import torch
 
@@ -113,6 +119,86 @@ def sample_one_point_from_error_center(gt_masks: torch.Tensor, pred_masks, paddi
     positive = fn_d2 > fp_d2
     points = torch.where(positive[:, None], fn_xy, fp_xy).to(torch.int64)
     return points[:, None], positive.to(torch.int64)[:, None]
+
+
+Association = namedtuple("Association", "trk_to_det trk_matched trk_unmatched det_new det_trk trk_det_scores")
+
+
+def associate_det_trk(det_masks, track_masks, iou_threshold=0.5, iou_threshold_trk=0.5, det_scores=None, new_det_thresh=0.0,
+                      n_det=None, n_trk=None, iou=None, trk_nonempty=None) -> Association:
+    """perflib/associate_det_trk.py (and the matching of model/sam3_video_base.py: _associate_det_trk) for a frame or a whole
+    clip, without a read-back: det_masks [N, H, W], track_masks [M, H, W] (foreground: > 0; bool passes as it is), or both with
+    a clip axis [T, ...]; det_scores [.., N] is required (with None the reference fails at det_scores_list[d]).  n_det, n_trk
+    int32 [T] (a frame: 0-d): the frame has that many detections and tracks, the rest of its rows and columns is padding.
+    iou float32 [.., N, M]: an already computed geometry.mask_iou(...).iou; the masks may then be None.  Both mask sets must
+    have the same size: the reference's bilinear resize of unequal sizes is not reproduced.
+
+    The cost is the reference's 1 - iou in float32, widened, and geometry.linear_assignment solves it; where the optimum is not
+    unique the assignment may differ from scipy's (DESIGN §2 "Association and tracking").  -> Association of device tensors:
+    trk_to_det int32 [.., M] (-1: none); trk_matched bool: assigned and iou >= iou_threshold_trk; trk_unmatched bool: not
+    matched, and with trk_nonempty bool [.., M] given sam3_video_base's rule, non-empty and not matched; det_new bool [.., N]:
+    no track with iou >= iou_threshold and score >= new_det_thresh (a frame without tracks: every detection, as the
+    reference's early return); det_trk bool [.., N, M] = iou >= iou_threshold, the reference's det_to_matched_trk as a mask;
+    trk_det_scores float32 [.., M, 2]: score and score * iou of the assigned detection, NaN where none is assigned."""
+    fn = "associate_det_trk"
+    if det_scores is None:
+        raise ValueError(f"{fn}: det_scores is required")
+    if iou is None:
+        if det_masks.shape[-2:] != track_masks.shape[-2:]:
+            raise ValueError(f"{fn}: det_masks and track_masks must have one size, got {list(det_masks.shape)}, {list(track_masks.shape)}")
+        det, trk = (m if m.dtype in (torch.bool, torch.uint8) else m > 0 for m in (det_masks, track_masks))
+        if det.shape[-3] == 0 or trk.shape[-3] == 0:    # no pair at all
+            iou = torch.zeros((*det.shape[:-2], trk.shape[-3]), dtype=torch.float32, device=det.device)
+        else:
+            iou = geometry.mask_iou(det, trk).iou
+    if not isinstance(iou, torch.Tensor) or iou.dtype != torch.float32 or iou.dim() not in (2, 3):
+        raise ValueError(f"{fn}: iou must be float32 [N, M] or [T, N, M]")
+    if tuple(det_scores.shape) != tuple(iou.shape[:-1]):
+        raise ValueError(f"{fn}: det_scores must be {list(iou.shape[:-1])}, got {list(det_scores.shape)}")
+    dev, lead = iou.device, tuple(iou.shape[:-2])
+    N, M = int(iou.shape[-2]), int(iou.shape[-1])
+    nd = torch.full(lead, N, dtype=torch.int32, device=dev) if n_det is None else n_det.to(dev, torch.int32).reshape(lead)
+    nt = torch.full(lead, M, dtype=torch.int32, device=dev) if n_trk is None else n_trk.to(dev, torch.int32).reshape(lead)
+    det_ok = torch.arange(N, device=dev) < nd[..., None]
+    trk_ok = torch.arange(M, device=dev) < nt[..., None]
+    scores = det_scores.to(dev, torch.float32)
+
+    trk_to_det = geometry.linear_assignment(1 - iou, nd, nt).col_to_row
+    at = trk_to_det.clamp(min=0).to(torch.int64)[..., None, :]
+    assigned = trk_to_det >= 0
+    if N:
+        pair_iou = torch.gather(iou, -2, at)[..., 0, :]
+        pair_score = torch.gather(scores[..., :, None].expand(*lead, N, M), -2, at)[..., 0, :]
+    else:
+        pair_iou = pair_score = torch.zeros((*lead, M), dtype=torch.float32, device=dev)
+    trk_matched = assigned & (pair_iou >= iou_threshold_trk)
+    trk_unmatched = trk_ok & ~trk_matched
+    if trk_nonempty is not None:
+        trk_unmatched = trk_unmatched & trk_nonempty.to(dev, torch.bool)
+    det_trk = (iou >= iou_threshold) & det_ok[..., :, None] & trk_ok[..., None, :]
+    det_new = det_ok & ((~det_trk.any(dim=-1) & (scores >= new_det_thresh)) | (nt == 0)[..., None])
+    nan = torch.full((), float("nan"), dtype=torch.float32, device=dev)
+    trk_det_scores = torch.where(assigned[..., None], torch.stack([pair_score, pair_score * pair_iou], dim=-1), nan)
+    return Association(trk_to_det, trk_matched, trk_unmatched, det_new, det_trk, trk_det_scores)
+
+
+def association_lists(result: Association):
+    """One frame's Association -> the reference's four Python objects (new_det_indices, unmatched_trk_indices,
+    det_to_matched_trk, matched_det_scores), read back in one copy.  A frame without detections or without tracks gives the
+    reference's early return: every detection new and nothing else."""
+    if result.trk_to_det.dim() != 1:
+        raise ValueError("association_lists: one frame at a time (index the clip axis of every field first)")
+    N, M = int(result.det_new.shape[0]), int(result.trk_to_det.shape[0])
+    if N == 0 or M == 0:
+        return list(range(N)), [], {}, {}
+    flat = torch.cat([result.trk_to_det.to(torch.float64), result.trk_unmatched.to(torch.float64), result.det_new.to(torch.float64),
+                      result.det_trk.reshape(-1).to(torch.float64), result.trk_det_scores.reshape(-1).to(torch.float64)]).cpu().numpy()
+    t2d, unm, new, dt, sc = flat[:M], flat[M:2 * M], flat[2 * M:2 * M + N], flat[2 * M + N:2 * M + N + N * M], flat[2 * M + N + N * M:]
+    dt, sc = dt.reshape(N, M), sc.reshape(M, 2)
+    det_to_matched_trk = {d: [t for t in range(M) if dt[d, t]] for d in range(N) if dt[d].any()}
+    # in the order the reference fills its dictionary: by detection
+    matched_det_scores = {t: [float(sc[t, 0]), float(sc[t, 1])] for t in sorted((t for t in range(M) if t2d[t] >= 0), key=lambda t: t2d[t])}
+    return [d for d in range(N) if new[d]], [t for t in range(M) if unm[t]], det_to_matched_trk, matched_det_scores
 
 
 def largest_component_boxes(stats: torch.Tensor, W: int, H: int):

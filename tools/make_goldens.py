@@ -1118,6 +1118,55 @@ def gen_masks():
 GENERATORS["masks"] = gen_masks
 
 
+def gen_assign():
+    """DESIGN §2 "Association and tracking": the reference's OWN associate_det_trk (prepare_front_results/sam3/perflib/
+    associate_det_trk.py: mask_iou, scipy's linear_sum_assignment and its Python loops) on the CPU, on the mask sets of
+    tests/assign_cases.py.  The sam3 package's __init__ imports iopath, which is not installed: the empty stand-in package of
+    gen_masks takes its place, everything below it is the reference's own.  Only a digest of the seeded inputs and the four
+    results are stored: the new detections and unmatched tracks as flags, det_to_matched_trk as a [N, M] mask, and
+    matched_det_scores as [M, 2] float64 rows (NaN: the track has no entry) with the entries' order of insertion."""
+    import hashlib
+    import types
+
+    sys.path.insert(0, str(ROOT / "tests"))
+    import assign_cases as ac
+
+    pkg = types.ModuleType("sam3")
+    pkg.__path__ = [os.path.join(REF, "prepare_front_results", "sam3")]
+    saved = sys.modules.get("sam3")
+    sys.modules["sam3"] = pkg
+    try:
+        from sam3.perflib.associate_det_trk import associate_det_trk
+    finally:
+        if saved is None:
+            sys.modules.pop("sam3", None)
+        else:
+            sys.modules["sam3"] = saved
+    out = {}
+    for name in ac.ASSOC_CASES:
+        det, trk, scores = ac.assoc_case(name)
+        N, M = len(det), len(trk)
+        thr = ac.ASSOC_THRESHOLDS
+        new, unmatched, det_to_trk, det_scores = associate_det_trk(
+            torch.from_numpy(det), torch.from_numpy(trk), thr["iou_threshold"], thr["iou_threshold_trk"], torch.from_numpy(scores),
+            thr["new_det_thresh"])
+        out[f"{name}_digest"] = np.array(hashlib.sha256(det.tobytes() + trk.tobytes() + scores.tobytes()).hexdigest())
+        out[f"{name}_new"] = np.isin(np.arange(N), new)
+        out[f"{name}_unmatched"] = np.isin(np.arange(M), unmatched)
+        out[f"{name}_det_trk"] = np.array([[t in det_to_trk.get(d, []) for t in range(M)] for d in range(N)], dtype=bool)
+        rows = np.full((M, 2), np.nan)
+        for t, pair in det_scores.items():
+            rows[int(t)] = pair
+        out[f"{name}_scores"] = rows
+        out[f"{name}_score_order"] = np.array([int(t) for t in det_scores], dtype=np.int32)
+    path = GOLD / "assign.npz"
+    np.savez_compressed(path, **out)
+    print("wrote", path.name, path.stat().st_size, "bytes")
+
+
+GENERATORS["assign"] = gen_assign
+
+
 if __name__ == "__main__":
     which = sys.argv[1:] or list(GENERATORS)
     for w in which:
