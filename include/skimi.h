@@ -1513,6 +1513,58 @@ int skimi_match_l2(const uint8_t* d1, const int32_t* n1, int32_t M1, const uint8
 int skimi_draw_shapes_u8(const uint8_t* frames, uint8_t* out, const int32_t* shapes, int32_t shape_axes, const uint8_t* font,
                          int32_t C, int32_t F, int32_t H, int32_t W, int32_t ch, int32_t P, void* stream);
 
+/* ---- 3D scene views: depth-buffered point splats and primitives (csrc/scene_view.hip) ----
+ * What the reference's 3D stages end with (SceneVisualizer.draw_scene, vggt_camera_vis.py, the Open3D bird's-eye video), on
+ * the device: clouds of coloured points and a list of depth-tested primitives (bones, joints, camera frusta, axes, grid
+ * lines) seen from F cameras, one depth test per pixel.  frames u8 [F, H, W, 3] (dev), sides 1 .. SKIMI_LENS_MAX_SIDE.  THIS
+ * PROJECT'S rules: no pixel parity with matplotlib or Open3D is claimed.  Depth is one integer per fragment, so the test is
+ * exact; the result is bitwise reproducible, independent of the order of execution, and bitwise that of
+ * tests/scene_view_restated.py.  Every f64 expression below is evaluated in the written order, without contraction.
+ *  1. views f64 [F, 20] (dev): r00 r01 r02 t0, r10 r11 r12 t1, r20 r21 r22 t2 (world -> camera), fx, fy, cx, cy, near, far,
+ *     ortho (non-zero: orthographic), one pad.  A point (x, y, z) f32 of the frame's cloud, as f64: X = ((r00 x + r01 y) +
+ *     r02 z) + t0, Y and Z alike.  It is a fragment iff X, Y, Z are finite, near <= Z <= far, and (perspective) Z > 0.
+ *     Perspective: u = (fx X) / Z + cx, v = (fy Y) / Z + cy, q = floor((2^30 near) / Z).  Orthographic: u = fx X + cx, v = fy Y +
+ *     cy, q = floor((2^30 (far - Z)) / (far - near)).  w = q clamped to 1 .. 2^30 (a NaN gives 1): larger w is nearer, 0 is
+ *     "empty".  Its pixel is (floor(u), floor(v)); with point_size s (1 .. SKIMI_SCENE_MAX_POINT_SIZE) it covers the s x s
+ *     pixels from (floor(u) - (s - 1) / 2, floor(v) - (s - 1) / 2) (integer division), those inside the frame.
+ *  2. Clouds: xyz f32 [P, N, 3], rgb u8 [P, N, 3] (dev), N < 2^31; count i64 [P] (dev) or NULL: cloud p holds min(max(count[p],
+ *     0), N) points and the rows behind them are never read (a SceneCloud leaves them unwritten); the count is read by the
+ *     kernel.  cloud_of_frame i32 [F] (dev) or NULL (then P == 1: cloud 0, or P == F: the frame's index); an entry outside
+ *     0 .. P - 1 draws no cloud.  Splat pass: a thread per (frame, point) writes the key (w << 32) | point index into the
+ *     workspace [F, H, W] u64 with a 64-bit atomic max: per pixel the nearest point wins, among equal w the highest index.
+ *  3. prims i32 records of 12 words (dev), M <= SKIMI_SCENE_MAX_PRIMS a list; prim_axes 2: [M, 12] shared by every frame, 3:
+ *     [F, M, 12].  Record = kind, x0, y0, x1, y1, r, colour, w0, w1, three reserved words (not read).  kind 1: disc at a = (x0,
+ *     y0) with depth w0 (x1, y1, w1 not read); kind 2: capsule a -> b = (x1, y1) with depths w0 at a, w1 at b; any other kind:
+ *     nothing.  Positions and r in 1/16 pixel, the centre of pixel (u, v) is (16 u, 16 v), saturated to +-2^20 on read; w0, w1
+ *     clamped to 1 .. 2^30; colour 0x00c2c1c0 as skimi_draw_shapes_u8.  Coverage is hard, no anti-aliasing: the pixel centre p
+ *     is covered iff d <= r with d the integer distance of skimi_draw_shapes_u8's rule 2 (disc; capsule with a = b: the disc).
+ *     The fragment's depth: the disc's w0; the capsule's, with t = (p - a).(b - a), L2 = |b - a|^2: w0 if t <= 0, w1 if t >= L2,
+ *     else w0 + sign(w1 - w0) floor(|w1 - w0| t / L2), exact (linear in w along the segment at the clamped foot of p: linear
+ *     in inverse depth is perspective-correct).
+ *  4. Resolve pass, one owner per pixel, no atomics: the pixel starts from its splat key (or empty); the primitives that
+ *     cover it are visited in list order and one is taken iff its w >= the w held (so a primitive beats a point of equal w,
+ *     and a later primitive an earlier one of equal w).  frames gets rgb[cloud, index] for a point, the record's colour for a
+ *     primitive, else the background: background u8 [F, H, W, 3] (dev) or, when NULL, bg_colour (0x00c2c1c0).  depth f32 [F,
+ *     H, W] or NULL: (float) of Z = (2^30 near) / w (perspective), far - (w (far - near)) / 2^30 (orthographic) of the w that
+ *     won; +inf on an empty pixel.  index i32 [F, H, W] or NULL: the nearest POINT's index whatever primitives cover it, -1
+ *     where no point landed (the cloud's visibility map from that camera).  Tiles and the two-level ordered binning of the
+ *     list are skimi_draw_shapes_u8's rule 4; a tile that no primitive touches only resolves.
+ *  5. ws (dev): 8 H W bytes a frame.  skimi_scene_view_workspace_bytes(F, H, W, cap_bytes) = 8 H W min(F, max(1, cap_bytes / (8
+ *     H W))) (cap_bytes 0: no cap).  The call renders min(F, ws_bytes / (8 H W), 65535) frames at a time: per chunk one
+ *     hipMemsetAsync, the splat launch (none when N == 0) and the resolve launch, all on `stream`: the number of launches
+ *     depends on the shapes only.  ws smaller than one frame: SKIMI_ERR_WORKSPACE.  No host synchronisation. */
+#define SKIMI_SCENE_MAX_PRIMS 1024
+#define SKIMI_SCENE_MAX_POINT_SIZE 4
+#define SKIMI_SCENE_NONE 0
+#define SKIMI_SCENE_DISC 1
+#define SKIMI_SCENE_CAPSULE 2
+#define SKIMI_SCENE_W_ONE (1 << 30)
+size_t skimi_scene_view_workspace_bytes(int64_t F, int32_t H, int32_t W, size_t cap_bytes);
+int skimi_scene_view_render(const double* views, const float* xyz, const uint8_t* rgb, const int64_t* count,
+                            const int32_t* cloud_of_frame, int32_t P, int64_t N, int32_t point_size, const int32_t* prims,
+                            int32_t prim_axes, int32_t M, const uint8_t* background, uint32_t bg_colour, uint8_t* frames, float* depth,
+                            int32_t* index, int64_t F, int32_t H, int32_t W, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- mask analysis: components, distance transform, boxes, IoU, greedy NMS (csrc/masks.hip) ----
  * The mask post-processing of the reference's SAM3 (perflib/connected_components.py, perflib/nms.py, perflib/masks_ops.py,
  * model/edt.py), on device masks.  A mask is u8 [H, W] (dev), non-zero = foreground; masks [B, H, W] with 1 <= H, W <=

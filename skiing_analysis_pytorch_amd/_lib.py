@@ -226,6 +226,9 @@ _SIGNATURES = {
                                  _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "skimi_draw_shapes_u8": (C.c_int, [_vp, _vp, _vp, C.c_int32, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        _vp]),
+    "skimi_scene_view_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32, C.c_size_t]),
+    "skimi_scene_view_render": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_int32, C.c_int64, C.c_int32, _vp, C.c_int32, C.c_int32, _vp,
+                                          C.c_uint32, _vp, _vp, _vp, C.c_int64, C.c_int32, C.c_int32, _vp, C.c_size_t, _vp]),
     "skimi_mask_components_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int32, C.c_int32]),
     "skimi_mask_components": (C.c_int, [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, C.c_size_t,
                                         _vp]),

@@ -270,3 +270,47 @@ def process_front_clip(frames: torch.Tensor, boxes_xywh: torch.Tensor, img_pts=N
             raise ValueError("process_front_clip: a skeleton needs at least one box to centre it on")
         skel = geometry.bev_skeleton(skeleton, foot_px[:, -1].contiguous(), MERGE_METRES_PER_PIXEL, (0, 2), True)
     return FrontClipResult(bev, foot_uv, foot_px, foot_m, track, H_px, H_m, fit.status[0], skel, bev_size)
+
+
+# ---- the top-down skeleton video (front_side/o3d_bev_video_robust.py) --------------------------------------------------------
+COCO_EDGES = [(0, 1), (0, 2), (1, 3), (2, 4), (5, 7), (7, 9), (6, 8), (8, 10), (5, 6), (5, 11), (6, 12), (11, 12), (11, 13), (13, 15),
+              (12, 14), (14, 16)]
+
+
+@dataclass
+class BevView:
+    """The reference's BevView (the offscreen backend's fields): the camera sits eye_height above lookat on the world's +y and
+    looks down at it; `up` is the screen's up direction."""
+    up: Tuple[float, float, float] = (0.0, 0.0, -1.0)
+    lookat: Tuple[float, float, float] = (0.0, 0.0, 10.0)
+    eye_height: float = 25.0
+    fov_deg: float = 60.0                # Open3D's default vertical field of view
+
+
+def render_bev_skeleton_clip(kpts_world: torch.Tensor, edges=COCO_EDGES, view: BevView = BevView(), size=(720, 1280), line_width=3.0,
+                             grid=((15.0, 30.0), 5.0)) -> torch.Tensor:
+    """Open3DBevVideoRenderer without the video file: kpts_world [T, J, 3] device joints -> the frames uint8 [T, H, W, 3] (RGB):
+    the skeleton's edges in the reference's green, line_width pixels wide, on white, seen top-down from eye_height above
+    view.lookat (perspective, the reference's 1280 x 720 by default); the ground, a lit box in the reference, is a grey grid
+    on the plane y = 0 ((half extents in x and z around lookat, spacing); None: no grid).  One render_scene call for the
+    clip; nothing is read back."""
+    k = device_tensor("render_bev_skeleton_clip", torch.as_tensor(kpts_world))
+    if k.dim() != 3 or k.shape[-1] != 3:
+        raise ValueError(f"render_bev_skeleton_clip: kpts_world must be [T, J, 3], got {list(k.shape)}")
+    H, W = int(size[0]), int(size[1])
+    dev, T = k.device, int(k.shape[0])
+    look = torch.tensor(view.lookat, dtype=torch.float64, device=dev)
+    eye = look + torch.tensor([0.0, view.eye_height, 0.0], dtype=torch.float64, device=dev)
+    f = (H / 2.0) / float(np.tan(np.radians(view.fov_deg) / 2.0))
+    v = geometry.look_at_view(eye, look, torch.tensor(view.up, dtype=torch.float64, device=dev), f, f, W / 2.0, H / 2.0,
+                              0.01 * view.eye_height, 4.0 * view.eye_height)
+    J = int(k.shape[1])
+    ok = [(int(a), int(b)) for a, b in edges if 0 <= int(a) < J and 0 <= int(b) < J]
+    ia = torch.tensor([e[0] for e in ok], dtype=torch.int64, device=dev)
+    ib = torch.tensor([e[1] for e in ok], dtype=torch.int64, device=dev)
+    lists = []
+    if grid is not None:
+        lists.append(geometry.grid_prims("xz", grid[0], grid[1], v, (235, 235, 235), 1.0, level=0.0, origin=(view.lookat[0], view.lookat[2])))
+    lists.append(geometry.segment3d_prims(k.index_select(1, ia), k.index_select(1, ib), v, (0, 255, 0), line_width))
+    return geometry.render_scene(v[None].expand(T, -1).contiguous(), prims=geometry.cat_prims(*lists), size=(H, W),
+                                 background=(255, 255, 255)).frames

@@ -14,26 +14,19 @@
 // tile the test of 67 records cost more than the copy it guards (profiles/draw.md).
 #include "common.h"
 #include "compact.h"
+#include "exact_int.h"
+#include "raster_tiles.h"
 #include "warp_u8.h"
 
 namespace skimi {
 
 namespace {
 
-constexpr int kDrawThreads = 256;
-constexpr int kTileW = 64, kTileH = 16;           // kTileW / kPix * kTileH = kDrawThreads
-constexpr int kSpanX = kTileW / kPix;             // threads along a tile row
-constexpr int kTilesX = 4, kTilesY = 4;           // a workgroup's block of tiles
-constexpr int kBlockW = kTileW * kTilesX, kBlockH = kTileH * kTilesY;
-static_assert(kBlockW == 64 * kPix, "the copy of an empty block: a wave a row");
-constexpr int kSat = 1 << 20;                     // coordinates and radii, in 1/16 pixel
-static_assert(kSpanX * kTileH == kDrawThreads, "a thread a span");
+constexpr int kDrawThreads = kRasterThreads;
 
 struct Shape {
     int kind, x0, y0, x1, y1, r, colour, opacity;
 };
-
-__device__ __forceinline__ int sat20(int v) { return min(max(v, -kSat), kSat); }
 
 // a record as the rules read it: coordinates and radius saturated, opacity clamped, an unknown kind drawn as nothing
 __device__ __forceinline__ Shape read_shape(const int* __restrict__ rec) {
@@ -52,26 +45,6 @@ __device__ __forceinline__ Shape read_shape(const int* __restrict__ rec) {
         s.x1 = sat20(s.x1), s.y1 = sat20(s.y1);
     }
     return s;
-}
-
-// The distances are integers carried in doubles: every coordinate difference is an int32 below 2^22 in size, so every
-// product, sum and root below is an integer below 2^46, far inside the 2^53 a double holds exactly, and each operation is
-// exact (the build does not contract a b + c, and a contraction would change nothing here).  An f64 operation is one
-// instruction on gfx950, a 64-bit integer multiply or divide a sequence of 32-bit ones.
-// exact floor square root of an integer 0 <= n < 2^52: the rounded root is within one of it
-__device__ __forceinline__ double isqrt_exact(double n) {
-    double r = floor(sqrt(n));
-    if (r * r > n) r -= 1.0;
-    if ((r + 1.0) * (r + 1.0) <= n) r += 1.0;
-    return r;
-}
-
-// exact floor(c / m) of integers 0 <= c < 2^52, 1 <= m: the rounded quotient's floor is within one of it
-__device__ __forceinline__ double floor_div_exact(double c, double m) {
-    double q = floor(c / m);
-    if (q * m > c) q -= 1.0;
-    if ((q + 1.0) * m <= c) q += 1.0;
-    return q;
 }
 
 // can the shape change a pixel whose centre lies in [tx0, tx1] x [ty0, ty1] (1/16 pixel)?  Conservative: the shape's
@@ -123,35 +96,6 @@ __device__ __forceinline__ int coverage(const Shape& s, double root, const unsig
     const int di = (int)d;   // <= 2^22 sqrt(2)
     if (s.kind == SKIMI_DRAW_RING) return clamp16(s.x1 + 8 - abs(di - s.r));
     return clamp16(s.r + 8 - di);
-}
-
-// the thread's span from src = the address of pixel (u0, v): dwords where the rows allow it, else the bytes that exist
-template <int CH>
-__device__ __forceinline__ void span_load(const unsigned char* src, unsigned int (&words)[CH], int aligned, int u0, int W) {
-    if (aligned && u0 + kPix <= W) {
-        const unsigned int* dw = reinterpret_cast<const unsigned int*>(src);
-#pragma unroll
-        for (int w = 0; w < CH; ++w) words[w] = dw[w];
-    } else {
-        const int nb = min(kPix, W - u0) * CH;
-#pragma unroll
-        for (int w = 0; w < CH; ++w) words[w] = 0;
-#pragma unroll
-        for (int byte = 0; byte < kPix * CH; ++byte)
-            if (byte < nb) words[byte >> 2] |= (unsigned int)src[byte] << (8 * (byte & 3));
-    }
-}
-
-// One round of the ordered compaction: the calling thread's candidate `idx` (kept or not) against the box; the kept ones go
-// to dst in candidate order behind the n already there.  Every thread of the workgroup calls it (ordered_rank's contract);
-// buf alternates over ALL calls of the kernel, block list and tile lists alike.
-__device__ __forceinline__ void list_round(bool kept, int idx, unsigned short* dst, unsigned& n, unsigned (*s_wtot)[kDrawThreads / 64],
-                                           int& buf) {
-    unsigned chunk;
-    const unsigned rank = ordered_rank<kDrawThreads / 64>(kept, s_wtot[buf], chunk);
-    if (kept) dst[n + rank] = (unsigned short)idx;   // n + rank < P <= SKIMI_DRAW_MAX_SHAPES
-    n += chunk;
-    buf ^= 1;
 }
 
 // `in` and `out` may be the same clip (in place): no __restrict__ on either

@@ -43,6 +43,23 @@ __device__ __forceinline__ void warp_tap_pack(const unsigned char* __restrict__ 
     }
 }
 
+// the thread's span from src = the address of pixel (u0, v): dwords where the rows allow it, else the bytes that exist
+template <int CH>
+__device__ __forceinline__ void span_load(const unsigned char* src, unsigned int (&words)[CH], int aligned, int u0, int W) {
+    if (aligned && u0 + kPix <= W) {
+        const unsigned int* dw = reinterpret_cast<const unsigned int*>(src);
+#pragma unroll
+        for (int w = 0; w < CH; ++w) words[w] = dw[w];
+    } else {
+        const int nb = min(kPix, W - u0) * CH;
+#pragma unroll
+        for (int w = 0; w < CH; ++w) words[w] = 0;
+#pragma unroll
+        for (int byte = 0; byte < kPix * CH; ++byte)
+            if (byte < nb) words[byte >> 2] |= (unsigned int)src[byte] << (8 * (byte & 3));
+    }
+}
+
 // the thread's span to dst = the address of output pixel (u0, v): dwords where the rows allow it, else the bytes that exist
 template <int CH>
 __device__ __forceinline__ void warp_store(unsigned char* __restrict__ dst, const unsigned int (&words)[CH], int aligned, int u0,

@@ -173,3 +173,165 @@ def render_reprojection_panel(img1, img2, kptL, kptR, proj_L, proj_R, joint_name
         right = _title_shapes([line.format(title_right, *s[f, 1]) for f in range(F)], W1 + 20, 30, 2, dev)
         geometry.draw_shapes(panel, geometry.cat_shapes(left, right), inplace=True)
     return visL, visR, panel
+
+
+# ---- 3D scene views (geometry.render_scene, csrc/scene_view.hip) ------------------------------------------------------------
+# vis_3d_kpt/visualization/scene_visualizer.py: the fixed box of draw_scene, the four views of draw_frame_with_scene and the
+# matplotlib colours "r" (joints), "b" (links) and C0 (the origin marker), as RGB
+SCENE_BOX = ((-0.5, 0.5), (-0.5, 0.5), (0.0, 1.8))
+SCENE_PANEL_VIEWS = ((0, -90), (0, 90), (90, -90), (90, 90))
+SCENE_PANEL_TITLES = ("Left view", "Right view", "left side view", "right side view", "top left view", "top right view")
+SCENE_KPT_COLOUR, SCENE_LINK_COLOUR, SCENE_ORIGIN_COLOUR = (255, 0, 0), (0, 0, 255), (31, 119, 180)
+SCENE_ORIGIN_LABEL = "world center (0,0,0)"
+SCENE_BACKGROUND = (255, 255, 255)
+# vggt/vis/vggt_camera_vis.py: the four views, the pad around the data, the cloud's grey
+CAMERA_VIEWS = ((30, 60), (0, 90), (90, -90), (0, 0))
+CAMERA_VIEW_NAMES = ("default", "front", "top", "side")
+CAMERA_PAD = 0.05
+CAMERA_POINT_GREY = 128
+
+
+def scene_box_view(elev, azim, size, dev):
+    """The orthographic view of draw_scene's box from (elev, azim) in matplotlib's convention: float64 [20] on dev.  The box's
+    centre is the middle of the frame and its circumscribed sphere fits the frame's shorter side."""
+    H, W = int(size[0]), int(size[1])
+    centre = [sum(SCENE_BOX[0]) / 2, sum(SCENE_BOX[1]) / 2, sum(SCENE_BOX[2]) / 2]
+    rad = sum(((hi - lo) / 2) ** 2 for lo, hi in SCENE_BOX) ** 0.5
+    scale = min(H, W) / (2.1 * rad)
+    return geometry.orbit_view(torch.tensor(centre, dtype=torch.float64, device=dev), 2.0 * rad, float(elev), float(azim), scale, scale, W / 2.0,
+                               H / 2.0, 0.5 * rad, 3.5 * rad, ortho=True)
+
+
+def draw_scene(kpts_world, skeleton=COCO_SKELETON, elev=0.0, azim=-90.0, size=(480, 480), label=True) -> torch.Tensor:
+    """SceneVisualizer.draw_scene for a whole clip: kpts_world [T, J, 3] (or [J, 3]) device joints -> uint8 [T, H, W, 3] (RGB) on
+    white: the floor grid of the reference's box (x, y in +-0.5, z in 0 .. 1.8; orthographic), the links, the joints and the
+    origin marker, depth-tested, seen from (elev, azim); then, on top through the 2D rasteriser, the "world center (0,0,0)"
+    label at the projected origin.  Nothing is read back."""
+    k = torch.as_tensor(kpts_world)
+    if not k.is_cuda:
+        raise geometry._lib.SkimiError("draw_scene needs device tensors (kpts_world is on the host)")
+    if k.dim() == 2:
+        k = k[None]
+    if k.dim() != 3 or k.shape[-1] != 3:
+        raise ValueError(f"draw_scene: kpts_world must be [T, J, 3] or [J, 3], got {list(k.shape)}")
+    dev, T = k.device, int(k.shape[0])
+    view = scene_box_view(elev, azim, size, dev)
+    origin = torch.zeros((1, 3), dtype=torch.float64, device=dev)
+    prims = geometry.cat_prims(geometry.grid_prims("xy", 0.5, 0.25, view, (210, 210, 210)),
+                               geometry.skeleton_prims(k, skeleton or [], view, SCENE_LINK_COLOUR, SCENE_KPT_COLOUR, 2.0, 3.0),
+                               geometry.disc3d_prims(origin, view, SCENE_ORIGIN_COLOUR, 4.0))
+    frames = geometry.render_scene(view[None].expand(T, -1).contiguous(), prims=prims, size=size, background=SCENE_BACKGROUND).frames
+    if label and T:
+        xy, _, ok = geometry.view_project(origin, view)
+        offset = torch.tensor([6.0, -6.0], dtype=torch.float64, device=dev)
+        geometry.draw_shapes(frames, geometry.text_shapes([SCENE_ORIGIN_LABEL], xy + offset, 1, (0, 0, 0), valid=ok), inplace=True)
+    return frames
+
+
+def fit_frames(frames, pane) -> torch.Tensor:
+    """uint8 [T, H, W, 3] device frames -> [T, ph, pw, 3]: resized (preprocess.resize_bicubic_u8, aspect kept) to fit the pane and
+    centred on white"""
+    from . import preprocess
+    ph, pw = int(pane[0]), int(pane[1])
+    T, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    s = min(ph / H, pw / W)
+    nh, nw = max(min(int(round(H * s)), ph), 1), max(min(int(round(W * s)), pw), 1)
+    out = torch.full((T, ph, pw, 3), 255, dtype=torch.uint8, device=frames.device)
+    y0, x0 = (ph - nh) // 2, (pw - nw) // 2
+    for t in range(T):
+        out[t, y0:y0 + nh, x0:x0 + nw] = preprocess.resize_bicubic_u8(frames[t], nw, nh)
+    return out
+
+
+def draw_frame_with_scene(left, right, pose_3d, skeleton=COCO_SKELETON, pane=(320, 320), titles=True) -> torch.Tensor:
+    """SceneVisualizer.draw_frame_with_scene: left, right uint8 [T, H, W, 3] (or [H, W, 3]) device frames, pose_3d [T, J, 3] (or
+    [J, 3]) -> the 2 x 3 panel uint8 [T, 2 ph, 3 pw, 3] (a single frame: [2 ph, 3 pw, 3]): row 0 = the left frame, the view
+    (0, -90), the top view (90, -90); row 1 = the right frame, (0, 90), (90, 90).  The frames are fitted by fit_frames, the
+    views are draw_scene's, the panes are assembled by device copies; titles=True writes the reference's six titles over
+    the panes' top-left corners with the 2D rasteriser."""
+    single = left.dim() == 3
+    fl, fr = (left[None], right[None]) if single else (left, right)
+    k = torch.as_tensor(pose_3d)
+    k = k[None] if k.dim() == 2 else k
+    fl, _ = frame_clip("draw_frame_with_scene", fl)
+    fr, _ = frame_clip("draw_frame_with_scene", fr)
+    T = int(fl.shape[1])
+    if fl.shape[4] != 3 or fr.shape[4] != 3 or fr.shape[1] != T or k.shape[0] != T:
+        raise ValueError(f"draw_frame_with_scene: need RGB clips and poses of one length, got {list(left.shape)}, {list(right.shape)}, "
+                         f"{list(k.shape)}")
+    ph, pw = int(pane[0]), int(pane[1])
+    panel = torch.empty((T, 2 * ph, 3 * pw, 3), dtype=torch.uint8, device=fl.device)
+    panel[:, :ph, :pw], panel[:, ph:, :pw] = fit_frames(fl[0], pane), fit_frames(fr[0], pane)
+    for n, (el, az) in enumerate(SCENE_PANEL_VIEWS):
+        r, c = n % 2, 1 + n // 2
+        panel[:, r * ph:(r + 1) * ph, c * pw:(c + 1) * pw] = draw_scene(k, skeleton, el, az, pane)
+    if titles and T:
+        where = [(0, 0), (1, 0), (0, 1), (1, 1), (0, 2), (1, 2)]
+        anchors = torch.tensor([[c * pw + 6.0, r * ph + 14.0] for r, c in where], dtype=torch.float64, device=fl.device)
+        geometry.draw_shapes(panel, geometry.text_shapes(list(SCENE_PANEL_TITLES), anchors, 1, (0, 0, 0)), inplace=True)
+    return panel[0] if single else panel
+
+
+def draw_camera_poses(extrinsic, points=None, center_mode="mean", intrinsic=None, colours=None, count=None, size=(400, 400), axis_len=0.1,
+                      show_id=True) -> torch.Tensor:
+    """vggt/vis/vggt_camera_vis.py: plot_cameras_from_predictions as a picture: extrinsic [S, 3, 4] device cameras, points [N, 3]
+    (or any [..., 3]) world points or None -> uint8 [2 h, 2 w, 3] (RGB): the reference's four views (30, 60), (0, 90), (90, -90),
+    (0, 0) in a 2 x 2 grid, each with every camera's three axes (x red, y green, z blue), its frustum (intrinsic [S, 3, 3];
+    default: a unit-focal square image), its centre and its id, and the cloud splatted in grey, or in `colours` uint8 [N, 3].
+    count: a device int64 scalar, the rows of points that exist.  center_mode "mean" | "first" | "none" moves the scene as
+    the reference does.  The limits come from the camera centres and the finite points with the reference's 5 % pad,
+    computed on the device; the views are orthographic with equal axes.  Nothing is read back."""
+    E = torch.as_tensor(extrinsic)
+    if not E.is_cuda:
+        raise geometry._lib.SkimiError("draw_camera_poses needs device tensors (extrinsic is on the host)")
+    if E.dim() != 3 or E.shape[-2:] != (3, 4):
+        raise ValueError(f"draw_camera_poses: extrinsic must be [S, 3, 4], got {list(E.shape)}")
+    dev, S = E.device, int(E.shape[0])
+    E = E.to(torch.float64)
+    C = geometry.camera_centres(E)
+    if center_mode == "mean":
+        centre = C.mean(dim=0)
+    elif center_mode == "first":
+        centre = C[0]
+    elif center_mode == "none":
+        centre = torch.zeros(3, dtype=torch.float64, device=dev)
+    else:
+        raise ValueError(f"Unknown center_mode: {center_mode}")
+    lo, hi = (C - centre).amin(dim=0), (C - centre).amax(dim=0)
+    xyz = rgb = None
+    if points is not None and torch.as_tensor(points).numel():
+        p = torch.as_tensor(points).to(dev).reshape(-1, 3)
+        live = torch.isfinite(p).all(dim=-1)
+        if count is not None:
+            live = live & (torch.arange(p.shape[0], device=dev) < torch.as_tensor(count, device=dev).reshape(()))
+        moved = p.to(torch.float64) - centre
+        inf = torch.full_like(moved, float("inf"))
+        lo = torch.minimum(lo, torch.where(live[:, None], moved, inf).amin(dim=0))
+        hi = torch.maximum(hi, torch.where(live[:, None], moved, -inf).amax(dim=0))
+        xyz = torch.where(live[:, None], moved, torch.full_like(moved, float("nan"))).to(torch.float32)[None]
+        rgb = (torch.full((1, p.shape[0], 3), CAMERA_POINT_GREY, dtype=torch.uint8, device=dev) if colours is None
+               else torch.as_tensor(colours).to(dev, torch.uint8).reshape(1, -1, 3))
+    span = (hi - lo).amax().clamp(min=1e-9)
+    half = 0.5 * span + CAMERA_PAD * span + axis_len        # the cube of the limits, and the markers that stick out of it
+    mid = 0.5 * (lo + hi)
+    h, w = int(size[0]), int(size[1])
+    scale = min(h, w) / (2.0 * 3.0 ** 0.5 * half)           # the cube's circumscribed sphere fits the pane
+    el = torch.tensor([v[0] for v in CAMERA_VIEWS], dtype=torch.float64, device=dev)
+    az = torch.tensor([v[1] for v in CAMERA_VIEWS], dtype=torch.float64, device=dev)
+    views = geometry.orbit_view(mid, 4.0 * half, el, az, scale, scale, w / 2.0, h / 2.0, 0.5 * half, 8.0 * half, ortho=True)
+    K = (torch.tensor([[1.0, 0.0, 0.5], [0.0, 1.0, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64, device=dev).expand(S, 3, 3) if intrinsic is None
+         else torch.as_tensor(intrinsic).to(dev, torch.float64))
+    prims = geometry.cat_prims(geometry.camera_prims(E, K, views, axis_len, axis_len, offset=-centre),
+                               geometry.disc3d_prims(C - centre, views, SCENE_ORIGIN_COLOUR, 3.0))
+    panes = geometry.render_scene(views, xyz, rgb, prims=prims, size=(h, w), background=SCENE_BACKGROUND).frames
+    corner = torch.tensor([6.0, 14.0], dtype=torch.float64, device=dev).expand(4, 4, 2)
+    text = [geometry.text_shapes(list(CAMERA_VIEW_NAMES), corner, 1, (0, 0, 0), valid=torch.eye(4, dtype=torch.bool, device=dev))]
+    if show_id and S:
+        xy, _, ok = geometry.view_project(C - centre, views)                               # [4, S, 2]
+        offset = torch.tensor([4.0, -4.0], dtype=torch.float64, device=dev)
+        text.append(geometry.text_shapes([str(i) for i in range(S)], xy + offset, 1, (0, 0, 0), valid=ok))
+    geometry.draw_shapes(panes, geometry.cat_shapes(*text), inplace=True)
+    out = torch.empty((2 * h, 2 * w, 3), dtype=torch.uint8, device=dev)
+    for n in range(4):
+        out[(n // 2) * h:(n // 2 + 1) * h, (n % 2) * w:(n % 2 + 1) * w] = panes[n]
+    return out

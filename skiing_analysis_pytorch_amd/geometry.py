@@ -47,6 +47,10 @@ from .device.sift import (SIFT_MAX_OCTAVES, SIFT_MAX_FEATURES, SIFT_MAX_CANDIDAT
 from .device.draw import (DRAW_MAX_SHAPES, DRAW_NONE, DRAW_DISC, DRAW_RING, DRAW_CAPSULE, DRAW_GLYPH, GLYPH_ADVANCE, GLYPH_HEIGHT,
                           font_5x7, draw_shapes, pack_colour, disc_shapes, segment_shapes, polyline_shapes, glyph_shapes,
                           string_codes, text_shapes, number_shapes, cat_shapes)
+from .device.scene_view import (SCENE_MAX_PRIMS, SCENE_MAX_POINT_SIZE, SCENE_NONE, SCENE_DISC, SCENE_CAPSULE, SCENE_W_ONE,
+                                SCENE_WORKSPACE_CAP, CAMERA_AXIS_COLOURS, CAMERA_PRIMS_PER_CAMERA, SceneView, render_scene, host_const,
+                                look_at_view, orbit_view, views_from_cameras, view_project, clip_near, disc3d_prims,
+                                segment3d_prims, skeleton_prims, camera_centres, camera_prims, grid_prims, cat_prims)
 from .device.masks import (MASK_MAX_SIDE, EDT_NONE, NMS_MAX, STATS_FIELDS, ComponentsResult, EdtResult, MaskBoxes, MaskIoU,
                            mask_components, distance_transform, mask_inner_point, pack_masks, mask_boxes, mask_iou, nms_greedy)
 from .device.assign import (ASSIGN_MAX, LINK_MAX, Assignment, LinkedBoxes, linear_assignment, link_boxes)

@@ -561,3 +561,50 @@ def process_single_view_clip(model: VGGT, frames: torch.Tensor, every: int = 30)
     out = model(sel, want={"camera"})
     E, K = geometry.pose_encoding_to_extri_intri(out["pose_enc"], (H, W))
     return {"extrinsic": E[0], "intrinsic": K[0], "pose_enc": out["pose_enc"][0]}
+
+
+def render_scene_views(cloud, extrinsic, intrinsic, joints=None, links=None, scene: int = 0, size=(518, 518), image_size=None, orbit=None,
+                       point_size: int = 1, aligned: bool = True, cameras: bool = True, background=(255, 255, 255), want_index: bool = False):
+    """The scene of a VGGT step as pictures, fed directly from CameraHead.last_scene: cloud geometry.SceneCloud (its count stays
+    on the device: the renderer reads it), extrinsic [S, 3, 4], intrinsic [S, 3, 3] the step's cameras (device), joints [J, 3]
+    world joints with `links` or None -> geometry.SceneView with frames uint8 [F, H, W, 3] (RGB, as the cloud's colours).
+    orbit=None: F = S, the scene seen from its own cameras (intrinsic is for images of image_size = (H, W), default `size`).
+    orbit=(frames, elev_deg): an orbit of that many frames about the z axis through the middle of the cloud's 5 .. 95 % box,
+    at 1.2 scene scales.  cameras=True adds every camera's axes and frustum.  aligned=True: the cloud was written with
+    scene_point_cloud(align=True), so cameras and joints are moved by cloud.transform to the cloud's frame.  Everything is
+    computed on the device; nothing is read back."""
+    dev = cloud.xyz.device
+    E = torch.as_tensor(extrinsic).to(dev, torch.float64)
+    K = torch.as_tensor(intrinsic).to(dev, torch.float64)
+    if E.dim() != 3 or E.shape[-2:] != (3, 4) or tuple(K.shape) != (E.shape[0], 3, 3):
+        raise ValueError(f"render_scene_views: need extrinsic [S, 3, 4] and intrinsic [S, 3, 3], got {list(E.shape)}, {list(K.shape)}")
+    H, W = int(size[0]), int(size[1])
+    b = int(scene)
+    T = cloud.transform[b]
+    scale = cloud.scale[b]
+    mid = 0.5 * (cloud.lower[b] + cloud.upper[b])                       # in the raw world frame
+    j = None if joints is None else torch.as_tensor(joints).to(dev, torch.float64)
+    if aligned:   # x' = T x: a camera [R|t] of the raw frame is [R|t] T^-1 in the cloud's
+        # inv_ex: the inverse without linalg.inv's check of the status on the host (a singular transform gives non-finite
+        # views, which draw nothing)
+        bottom = geometry.host_const([[0.0, 0.0, 0.0, 1.0]], torch.float64, dev).expand(E.shape[0], 1, 4)
+        E = (torch.cat([E, bottom], dim=1) @ torch.linalg.inv_ex(T).inverse)[:, :3]
+        mid = T[:3, :3] @ mid + T[:3, 3]
+        j = None if j is None else j @ T[:3, :3].T + T[:3, 3]
+    if orbit is None:
+        if image_size is not None:
+            sx, sy = W / float(image_size[1]), H / float(image_size[0])
+            K = K * geometry.host_const([[sx, 1.0, sx], [1.0, sy, sy], [1.0, 1.0, 1.0]], torch.float64, dev)
+        views = geometry.views_from_cameras(E, K, near=0.01 * scale, far=100.0 * scale)
+    else:
+        n, elev = int(orbit[0]), float(orbit[1])
+        az = torch.arange(n, dtype=torch.float64, device=dev) * (360.0 / max(n, 1))
+        views = geometry.orbit_view(mid, 1.2 * scale, elev, az, 0.8 * W, 0.8 * W, W / 2.0, H / 2.0, 0.01 * scale, 4.0 * scale)
+    lists = []
+    if cameras:
+        lists.append(geometry.camera_prims(E, K, views, 0.05 * scale, 0.05 * scale))
+    if j is not None:
+        lists.append(geometry.skeleton_prims(j, links or [], views))
+    prims = geometry.cat_prims(*lists) if lists else None
+    return geometry.render_scene(views, cloud.xyz[b:b + 1], cloud.rgb[b:b + 1], count=cloud.count[b:b + 1].clamp(max=cloud.xyz.shape[1]),
+                                 point_size=point_size, prims=prims, size=(H, W), background=background, want_index=want_index)
