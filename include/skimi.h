@@ -201,6 +201,14 @@ int skimi_split_records(const float* x, int64_t ld, int64_t rows, int32_t C, voi
 int skimi_dpt_fold_pack(const float* w_T, const float* b_T, const float* w_rn, int32_t C_in, int32_t C_mid, int32_t C_out,
                         int32_t s, void* w_records, float* beta, void* stream);
 
+/* A 3x3 / padding 1 conv (C_in -> C, bias) behind an x2 align-corners bilinear upsample, its channel contraction done on
+ * the COARSE map: taps [N, h, w, 9, C] fp32 holds, per coarse pixel, the nine 1x1 products W[:, :, ty, tx] . x (tap
+ * t = 3 ty + tx: one skimi_gemm with the [9 C][C_in] stack of the taps as its weight), and
+ *   out[n, Y, X, :] = bias + sum_t [(Y + ty - 1, X + tx - 1) inside the 2h x 2w map] . resize(taps_t)(Y + ty - 1, X + tx - 1)
+ * = conv2d(interpolate(x, scale 2, bilinear, align_corners=True), W, bias, padding=1), exactly in exact arithmetic, borders
+ * included.  The sampling is skimi_resize_bilinear's.  out [N, 2h, 2w, C] fp32; all dev, 16-byte aligned; C % 32 == 0. */
+int skimi_dpt_tap_sum(const float* taps, const float* bias, float* out, int32_t N, int32_t h, int32_t w, int32_t C, void* stream);
+
 int skimi_gemm(const skimi_gemm_desc* d, void* stream);
 
 /* Which kernel the calling thread's last skimi_gemm dispatch chose (a host-side record written before the
@@ -487,8 +495,17 @@ int skimi_vggt_forward(skimi_vggt*, const float* images, const float* query_poin
                        int32_t H, int32_t W, int32_t n_query, const skimi_vggt_outputs* out,
                        void* workspace, size_t workspace_bytes, void* stream);
 
+/* The calling thread's last skimi_vggt_forward: the workspace bytes its sizing pass planned and the bytes its launches then
+ * took from the workspace (host).  The two passes run the same code and must agree. */
+int skimi_vggt_last_arena(uint64_t* planned, uint64_t* used);
+
+/* How many DPT heads, in the calling thread's forwards so far, ran scratch.output_conv1 as nine tap contractions on
+ * refinenet1's coarse map + skimi_dpt_tap_sum (the fp32-accurate depth / point heads where that GEMM fills the 256-row
+ * LDS-DMA kernel; SKIMI_DPT_OC1_COARSE=0, read by skimi_vggt_create, keeps the upsample + 3x3 conv on the fine map). */
+int32_t skimi_vggt_oc1_coarse_count(void);
+
 /* ------------------------------------------------------------------------- */
-/* Geometry post-processing on device                                         */
+/* Geometry post-processing on device                                       */
 /* ------------------------------------------------------------------------- */
 /* pose_enc [rows, 9] (T, quat XYZW, fov_h, fov_w) -> extrinsic [rows, 3, 4] (cam-from-world,
  * OpenCV) and intrinsic [rows, 3, 3] (may be NULL) for an H x W image.

@@ -268,6 +268,9 @@ _SIGNATURES = {
     "skimi_vggt_workspace_bytes": (C.c_size_t, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "skimi_vggt_forward": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp,
                                      _vp, C.c_size_t, _vp]),
+    "skimi_vggt_last_arena": (C.c_int, [_vp, _vp]),
+    "skimi_vggt_oc1_coarse_count": (C.c_int32, []),
+    "skimi_dpt_tap_sum": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp]),
 }
 
 _lib = None

@@ -200,6 +200,10 @@ int skimi_dpt_fold_pack(const float* w_T, const float* b_T, const float* w_rn, i
     return SKIMI_OK;
 }
 
+int skimi_dpt_tap_sum(const float* taps, const float* bias, float* out, int32_t N, int32_t h, int32_t w, int32_t C, void* stream) {
+    return dpt_tap_sum_launch(taps, bias, out, N, h, w, C, (hipStream_t)stream);
+}
+
 int skimi_quant_mx(const void* x, int32_t dtype, int64_t ldx, int64_t rows, int32_t K, void* payload, void* scales,
                    void* stream) {
     return quant_mx_launch(x, dtype, (long)ldx, (long)rows, K, payload, scales, (hipStream_t)stream);

@@ -249,6 +249,9 @@ static int forward_impl(skimi_vggt* h, Ctx& c, const float* images, const float*
     return c.rc;
 }
 
+// arena peaks of the calling thread's last skimi_vggt_forward: the sizing pass's and the real pass's (skimi_vggt_last_arena)
+static thread_local size_t tl_arena_planned = 0, tl_arena_used = 0;
+
 extern "C" {
 
 skimi_vggt* skimi_vggt_create(const skimi_vggt_config* cfg) {
@@ -284,6 +287,8 @@ skimi_vggt* skimi_vggt_create(const skimi_vggt_config* cfg) {
     h->cfg = *cfg;
     // SKIMI_DPT_FOLD=0: the heads' levels 0 / 1 as ConvTranspose GEMM + 3x3 conv (interleaved A/B timing, equivalence tests)
     h->dpt_fold = !(getenv("SKIMI_DPT_FOLD") && atoi(getenv("SKIMI_DPT_FOLD")) == 0);
+    // SKIMI_DPT_OC1_COARSE=0: output_conv1 as the x2 upsample into records + the 3x3 conv on the fine map (same uses)
+    h->dpt_oc1_coarse = !(getenv("SKIMI_DPT_OC1_COARSE") && atoi(getenv("SKIMI_DPT_OC1_COARSE")) == 0);
     return h;
 }
 
@@ -434,8 +439,20 @@ int skimi_vggt_forward(skimi_vggt* h, const float* images, const float* query_po
             set_error("skimi_vggt_forward: workspace %zu < %zu", workspace_bytes, dry.ar.peak);
             return SKIMI_ERR_WORKSPACE;
         }
+        tl_arena_planned = dry.ar.peak;
     }
-    return forward_impl(h, c, images, query_points, B, S, H, W, n_query, out);
+    rc = forward_impl(h, c, images, query_points, B, S, H, W, n_query, out);
+    tl_arena_used = c.ar.peak;
+    return rc;
 }
+
+int skimi_vggt_last_arena(uint64_t* planned, uint64_t* used) {
+    SKIMI_CHECK_ARG(planned && used, "skimi_vggt_last_arena: null argument");
+    *planned = tl_arena_planned;
+    *used = tl_arena_used;
+    return SKIMI_OK;
+}
+
+int32_t skimi_vggt_oc1_coarse_count(void) { return dpt_oc1_coarse_count(); }
 
 }  // extern "C"

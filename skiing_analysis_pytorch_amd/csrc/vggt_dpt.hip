@@ -22,6 +22,9 @@ bool dpt_fused_ln(const DptW& w, int f2, int udt) {
     return !off && w.feature_only && w.out_ln != nullptr && w.out_ln->g != nullptr && w.out_ln->b != nullptr && f2 == 128 && udt == SKIMI_F32;
 }
 
+static thread_local int tl_oc1_coarse = 0;
+int dpt_oc1_coarse_count() { return tl_oc1_coarse; }
+
 static int uv_missing() {
     set_error("uv table missing");
     return SKIMI_ERR_STATE;
@@ -138,6 +141,7 @@ void* run_dpt(Ctx& c, const DptW& w, float* const* sf, float* const* sg, int F, 
     // RefineNet fusion 4 -> 1 (dpt_head.py:261-291, 427-456)
     void* prev = nullptr;   // previous refinenet output at this level's resolution
     char* prev_rec = nullptr;   // ... or, after the last level, the same map as bf16x3 operand records
+    void* c1_coarse = nullptr;  // ... or output_conv1's result already, its taps contracted on the last level's coarse map
     for (int r = 3; r >= 0; --r) {
         const FusionW& f = w.ref[r];
         const int h0 = hh[r], w0 = ww[r];
@@ -190,6 +194,33 @@ void* run_dpt(Ctx& c, const DptW& w, float* const* sf, float* const* sg, int F, 
         // (space / channels) and the interpolation weights sum to 1, so they commute exactly, bias
         // included; the 1x1 conv runs here on the 4x smaller map, fp32 rounding order aside.
         const int h1 = r > 0 ? hh[r - 1] : 2 * h0, w1 = r > 0 ? ww[r - 1] : 2 * w0;
+        // refinenet1's upsample is followed directly by output_conv1 (3x3, pad 1; dpt_head.py:287): that conv's channel
+        // contraction commutes with the upsample tap by tap, so where the nine taps are packed as 1x1 matrices (oc1t) and
+        // their GEMM fills the 256-row kernel, they are contracted HERE, on the 4x smaller map (a quarter of the MFMAs),
+        // and the upsample sums the nine shifted, resized results under the conv's padding mask (dpt_tap_sum_launch).
+        // out_conv hands its result over as operand records only.
+        if (r == 0 && !w.feature_only && adt == SKIMI_F32 && w.oc1t.w_split != nullptr && feat % 32 == 0) {
+            const size_t orec_bytes = (size_t)M * feat * 4;
+            auto dt = Ctx::as_records(c.desc(w.oc1t, nullptr, adt, feat, M, fake, adt, w.oc1t.N), fake, orec_bytes);
+            if (gemm_x3dma_eligible(&dt)) {   // pointer-independent up to alignment: the sizing pass agrees
+                c1_coarse = c.ar.alloc((size_t)F * h1 * w1 * (feat / 2) * 4);   // outlives the taps: allocated below them
+                const size_t mk_t = c.ar.mark();
+                char* orec = (char*)c.ar.alloc(orec_bytes + 256);
+                float* taps = (float*)c.ar.alloc((size_t)M * w.oc1t.N * 4);   // [pixel][tap][feat / 2]
+                auto d = c.desc(f.out_conv, u, adt, feat, M, nullptr, adt, feat);
+                if (u_recs) d = Ctx::as_records(d, u_rec, rec_bytes(r) - 256);
+                d.out_records = orec;
+                c.gemm(d);
+                dt = Ctx::as_records(c.desc(w.oc1t, nullptr, adt, feat, M, taps, adt, w.oc1t.N), orec, orec_bytes);
+                c.gemm(dt);
+                c.run([&] { return dpt_tap_sum_launch(taps, w.oc1.lin.b, (float*)c1_coarse, F, h0, w0, feat / 2, c.st); });
+                if (!c.dry()) ++tl_oc1_coarse;
+                c.ar.release(mk_t);   // stream order keeps the tail's users of this memory behind the tap sum
+                prev = nullptr;
+                hh[r] = h1; ww[r] = w1;
+                continue;
+            }
+        }
         void* olow = c.ar.alloc(bytes);
         {
             auto d = c.desc(f.out_conv, u, adt, feat, M, olow, adt, feat);
@@ -226,8 +257,10 @@ void* run_dpt(Ctx& c, const DptW& w, float* const* sf, float* const* sg, int F, 
     }
     const int h1 = hh[0], w1 = ww[0];
     const int f2 = w.feature_only ? feat : feat / 2;
-    void* c1 = c.ar.alloc((size_t)F * h1 * w1 * f2 * es);
-    if (prev_rec != nullptr) {
+    void* c1 = c1_coarse ? c1_coarse : c.ar.alloc((size_t)F * h1 * w1 * f2 * es);
+    if (c1_coarse != nullptr) {
+        // output_conv1 has run
+    } else if (prev_rec != nullptr) {
         auto d = Ctx::as_records(c.desc(w.oc1.lin, nullptr, adt, feat, F * h1 * w1, c1, adt, f2), prev_rec, (size_t)F * h1 * w1 * feat * 4);
         c.conv_geom(d, w.oc1, F, h1, w1, h1, w1);
         c.gemm(d);

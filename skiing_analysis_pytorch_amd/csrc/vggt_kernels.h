@@ -22,6 +22,10 @@ int add_uv_pos_records_launch(const float* x, const float* tabx, const float* ta
 // records of the (s + 2)^2 phase taps ((s + 2)^2 * Co * Ci * 4 bytes, as many floats of scratch in tmp) and beta [9][Co]
 int dpt_fold_pack_launch(const float* wT, const float* bT, const float* wrn, int Ci, int Cm, int Co, int s, float* tmp, void* rec,
                          float* beta, hipStream_t st);
+// out [N, 2h, 2w, C] = bias + the nine taps of a 3x3 / pad 1 conv summed over T [N, h, w, 9, C], the taps' channel
+// contractions on the coarse map, each resized x2 (align-corners bilinear) and shifted by its tap; C % 32 == 0
+int dpt_tap_sum_launch(const float* T, const float* bias, float* out, int N, int h, int w, int C, hipStream_t st);
+int permute_conv_taps_launch(const float* in, float* out, int Co, int Ci, int kh, int kw, hipStream_t st);   // -> [kh, kw, Co, Ci]
 int adaln_launch(const float* xn, const float* x, const float* mod, float* out, long rows, int D, hipStream_t st);
 int pose_update_launch(const float* delta, float* pred_pad, float* act_out, long rows, int first, hipStream_t st);
 int dpt_out_launch(const void* in, int dtype, const float* W, const float* b, int n_out, float* pts, float* conf,

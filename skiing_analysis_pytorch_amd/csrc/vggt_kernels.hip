@@ -488,6 +488,153 @@ int permute_conv_launch(const float* in, float* out, int Co, int Ci, int kh, int
     return SKIMI_OK;
 }
 
+// Conv2d weight [Co, Ci, kh, kw] -> [kh, kw, Co, Ci]  (the taps as stacked 1x1 matrices)
+__global__ void permute_conv_taps_kernel(const float* __restrict__ in, float* __restrict__ out, int Co, int Ci, int kh, int kw) {
+    const long n = (long)Co * Ci * kh * kw;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const int ci = (int)(i % Ci);
+        const long r = i / Ci;              // (y*kw + x)*Co + co
+        const int co = (int)(r % Co);
+        const int t = (int)(r / Co);
+        const int y = t / kw, x = t - y * kw;
+        out[i] = in[(((long)co * Ci + ci) * kh + y) * kw + x];
+    }
+}
+int permute_conv_taps_launch(const float* in, float* out, int Co, int Ci, int kh, int kw, hipStream_t st) {
+    hipLaunchKernelGGL(permute_conv_taps_kernel, dim3(grid_for((long)Co * Ci * kh * kw)), dim3(256), 0, st, in, out, Co, Ci, kh, kw);
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Tap sum of a 3x3 / pad 1 conv that follows an x2 align-corners bilinear upsample, the conv's channel contraction
+// already done on the coarse map (dpt_head.py:447-455 then :287: refinenet1's upsample, scratch.output_conv1):
+//   T[n, y, x, t, :] = W[:, :, ty, tx] . coarse[n, y, x, :]          (t = 3 ty + tx, one GEMM of N = 9 C columns)
+//   out[n, Y, X, :]  = bias + sum_t [(Y + ty - 1, X + tx - 1) inside the fine map] . resize(T_t)(Y + ty - 1, X + tx - 1)
+// The conv contracts channels and the resize mixes pixels, so the two orders agree exactly in exact arithmetic, the zero
+// padding included; the sampling is bilinear_ac_tap's, and a sample is summed in bilinear_ac_split's order.
+//
+// A workgroup owns TS_TH x TS_TW fine pixels of one image and walks (32-channel slice, tap): the window of T_t that the
+// tile's samples touch (<= TS_WR x TS_WC coarse pixels, 128 bytes each) is staged once in LDS -- the next one is
+// already in flight in registers -- and read by all pixels.  A thread owns one fine column and 4 channels, goes down
+// the tile's rows and keeps the two horizontally interpolated source rows of the current sample: two LDS reads per
+// new source row instead of four per pixel.  HBM-bound: T is read once (+ the windows' halo), out written once.
+// ---------------------------------------------------------------------------------------
+constexpr int TS_TH = 16, TS_TW = 32;
+// a window spans i1(last) - i0(first) + 1 <= floor(s last) - floor(s first) + 2 < s (T + 1) + 3 source samples for
+// scale s < 1/2 (H = 2 h) over the T + 2 fine positions first .. last
+constexpr int TS_WR = (TS_TH + 1) / 2 + 3, TS_WC = (TS_TW + 1) / 2 + 3;
+constexpr int TS_STAGE = (TS_WR * TS_WC * 8 + 255) / 256;   // float4 per thread of one staged window
+
+__global__ __launch_bounds__(256) void dpt_tap_sum_kernel(const float* __restrict__ T, const float* __restrict__ bias,
+                                                          float* __restrict__ out, int h, int w, int C) {
+#pragma clang fp contract(off)
+    __shared__ float4 win[TS_WR * TS_WC * 8];
+    const int H = 2 * h, W = 2 * w;
+    const float sy = (float)(h - 1) / (float)(H - 1), sx = (float)(w - 1) / (float)(W - 1);
+    const int X0 = blockIdx.x * TS_TW, Y0 = blockIdx.y * TS_TH;
+    const long n = blockIdx.z;
+    const int tid = threadIdx.x, c4 = tid & 7, col = tid >> 3;
+    // the tile's source window: samples of the fine positions [Y0 - 1, Y0 + TS_TH] x [X0 - 1, X0 + TS_TW] inside the map
+    const int ry0 = bilinear_ac_tap(sy, max(Y0 - 1, 0), h).i0, ry1 = bilinear_ac_tap(sy, min(Y0 + TS_TH, H - 1), h).i1;
+    const int cx0 = bilinear_ac_tap(sx, max(X0 - 1, 0), w).i0, cx1 = bilinear_ac_tap(sx, min(X0 + TS_TW, W - 1), w).i1;
+    const int wr = min(ry1 - ry0 + 1, TS_WR), wc = min(cx1 - cx0 + 1, TS_WC);   // min: never past the LDS window
+    const int nwin = wr * wc * 8;
+    const int X = X0 + col;
+    const int nslice = C / 32, nstage = nslice * 9;
+    const long trow = 9L * C;   // floats of one coarse pixel of T
+
+    // element e of a window (8 float4 per coarse pixel) -> its offset in T from the window's first pixel; past the
+    // window: its last element again (loaded, never stored)
+    long goff[TS_STAGE];
+#pragma unroll
+    for (int k = 0; k < TS_STAGE; ++k) {
+        const int e = min(tid + k * 256, nwin - 1);
+        const int px = e >> 3, r = px / wc, cc = px - r * wc;
+        goff[k] = ((long)r * w + cc) * trow + (e & 7) * 4;
+    }
+    const float* const tbase = T + ((n * h + ry0) * (long)w + cx0) * trow;
+    // the window in flight: named registers (an array here is left in scratch memory by the compiler)
+    static_assert(TS_STAGE == 7, "TS_EACH lists the staged float4 of a thread");
+#define TS_EACH(X) X(0) X(1) X(2) X(3) X(4) X(5) X(6)
+#define TS_DECL(k) float4 pre##k = *reinterpret_cast<const float4*>(tbase + goff[k]);
+    TS_EACH(TS_DECL)
+#undef TS_DECL
+    float4 acc[TS_TH];
+    for (int stage = 0; stage < nstage; ++stage) {
+        const int slice = stage / 9, tap = stage - slice * 9;
+        const int dy = tap / 3 - 1, dx = tap - (tap / 3) * 3 - 1;
+        if (tap == 0) {
+            const float4 b = *reinterpret_cast<const float4*>(bias + slice * 32 + c4 * 4);
+#pragma unroll
+            for (int j = 0; j < TS_TH; ++j) acc[j] = b;
+        }
+        __syncthreads();   // the previous stage's reads of the window are done
+#define TS_PUT(k) if (tid + k * 256 < nwin) win[tid + k * 256] = pre##k;
+        TS_EACH(TS_PUT)
+#undef TS_PUT
+        __syncthreads();
+        {   // the next (slice, tap)'s window, in flight during this stage's sums (after the last stage: that one again)
+            const int nxt = min(stage + 1, nstage - 1), ns = nxt / 9;
+            const float* base = tbase + (long)(nxt - ns * 9) * C + ns * 32;
+#define TS_GET(k) pre##k = *reinterpret_cast<const float4*>(base + goff[k]);
+            TS_EACH(TS_GET)
+#undef TS_GET
+        }
+        // this thread's column of the sample: clamped for addressing, masked where the conv pads
+        const int Xq = X + dx;
+        const bool xin = X < W && Xq >= 0 && Xq < W;
+        const BilinearTap tx = bilinear_ac_tap(sx, min(max(Xq, 0), W - 1), w);
+        const int o0 = (tx.i0 - cx0) * 8 + c4, o1 = (tx.i1 - cx0) * 8 + c4;
+        auto hrow = [&](int i) __attribute__((always_inline)) {   // source row i interpolated along x: the inner terms of bilinear_ac_split
+#pragma clang fp contract(off)
+            const float4 a = win[(i - ry0) * wc * 8 + o0], b = win[(i - ry0) * wc * 8 + o1];
+            return make_float4(tx.l0 * a.x + tx.l1 * b.x, tx.l0 * a.y + tx.l1 * b.y, tx.l0 * a.z + tx.l1 * b.z,
+                               tx.l0 * a.w + tx.l1 * b.w);
+        };
+        int i0 = -1, i1 = -1;   // the source rows held in ha / hb
+        float4 ha = make_float4(0.f, 0.f, 0.f, 0.f), hb = ha;
+#pragma unroll
+        for (int j = 0; j < TS_TH; ++j) {
+            const int Yq = Y0 + j + dy;   // block-uniform
+            if (Y0 + j >= H || Yq < 0 || Yq >= H) continue;
+            const BilinearTap ty = bilinear_ac_tap(sy, Yq, h);
+            if (ty.i0 != i0) {
+                ha = ty.i0 == i1 ? hb : hrow(ty.i0);
+                i0 = ty.i0;
+            }
+            if (ty.i1 != i1) {
+                hb = ty.i1 == i0 ? ha : hrow(ty.i1);
+                i1 = ty.i1;
+            }
+            if (xin) {
+                acc[j].x += ty.l0 * ha.x + ty.l1 * hb.x;
+                acc[j].y += ty.l0 * ha.y + ty.l1 * hb.y;
+                acc[j].z += ty.l0 * ha.z + ty.l1 * hb.z;
+                acc[j].w += ty.l0 * ha.w + ty.l1 * hb.w;
+            }
+        }
+        if (tap == 8 && X < W) {
+#pragma unroll
+            for (int j = 0; j < TS_TH; ++j)
+                if (Y0 + j < H) *reinterpret_cast<float4*>(out + ((n * H + Y0 + j) * (long)W + X) * C + slice * 32 + c4 * 4) = acc[j];
+        }
+    }
+}
+
+#undef TS_EACH
+
+int dpt_tap_sum_launch(const float* T, const float* bias, float* out, int N, int h, int w, int C, hipStream_t st) {
+    SKIMI_CHECK_ARG(T && bias && out, "dpt_tap_sum: null buffer");
+    SKIMI_CHECK_ARG(N > 0 && N < 65536 && h > 0 && w > 0 && h < 16384 && w < 16384 && C > 0 && C % 32 == 0,
+                    "dpt_tap_sum: needs C %% 32 == 0, N < 65536 and a coarse map below 16384 x 16384");
+    SKIMI_CHECK_ARG((((uintptr_t)T | (uintptr_t)bias | (uintptr_t)out) & 15) == 0, "dpt_tap_sum: 16-byte aligned buffers");
+    hipLaunchKernelGGL(dpt_tap_sum_kernel, dim3((unsigned)cdiv(2 * w, TS_TW), (unsigned)cdiv(2 * h, TS_TH), (unsigned)N), dim3(256), 0,
+                       st, T, bias, out, h, w, C);
+    SKIMI_LAUNCH_CHECK();
+    return SKIMI_OK;
+}
+
 // ConvTranspose2d weight [Ci, Co, s, s] -> [(a, b, co), Ci]  (pixel-shuffle GEMM, kernel == stride)
 __global__ void permute_convT_kernel(const float* __restrict__ in, float* __restrict__ out, int Ci, int Co, int s) {
     const long n = (long)Ci * Co * s * s;

@@ -45,6 +45,9 @@ struct DptW {
     ConvW rn[4];
     FusionW ref[4];     // ref[0] = refinenet1 ... ref[3] = refinenet4
     ConvW oc1, oc2a;
+    Lin oc1t;           // output_conv1's nine taps as 1x1 matrices, [9 * features / 2][features] (row t * features / 2 + k =
+                        // W[k, :, ty, tx]), no bias: contracted on refinenet1's coarse map, the x2 upsample then sums the taps
+                        // (dpt_tap_sum_launch); w_split NULL = not packed (SKIMI_DPT_OC1_COARSE=0, feature_only, 16-bit heads)
     float *oc2b_w = nullptr, *oc2b_b = nullptr;
     unsigned short* oc2a_direct = nullptr;   // conv_direct.hip weight layout of oc2a (fp32-accurate heads)
     int n_out = 0, features = 0, oc[4] = {0, 0, 0, 0};
@@ -120,6 +123,7 @@ struct skimi_vggt {
     std::map<std::string, std::pair<float*, int64_t>> raw;   // staged fp32 weights (device)
     std::vector<void*> owned;                                // packed device buffers
     bool finalized = false;
+    bool dpt_oc1_coarse = true;   // SKIMI_DPT_OC1_COARSE (read at create): output_conv1 of the bf16x3 heads contracted before the x2 upsample
     bool dpt_fold = true;   // SKIMI_DPT_FOLD (read at create): fold the bf16x3 heads' ConvTranspose resizes into layer1_rn / layer2_rn
     // packed model
     skimi::vggt::Lin patch_proj;    // [C, Kp] patchify GEMM (K = 3*p*p padded to 8)
@@ -159,6 +163,7 @@ struct Packer {
     void add_records(Lin& L);
     ConvW conv(const std::string& p, int Co, int Ci, int k, int stride, int pad, int prec, bool bias);
     Lin convT(const std::string& p, int C, int s, int prec);
+    Lin conv_taps(const std::string& p, int Co, int Ci);
     Lin conv_fold(const std::string& pT, const std::string& pRn, int C, int Co, int s);
     void add_fp8(Lin& L, const std::string& p, int N, int K);
     BlockW block(const std::string& p, int C, int hidden, bool qk_norm, int hd, int prec_in);
@@ -223,6 +228,7 @@ void run_camera(Ctx& c, const CamW& w, const float* sf, const float* sg, int B, 
                 float* out_last);                                                              // vggt_camera.hip
 const UvTab* find_uv(const ShapeTabs* h, int w, int hh, int C);                                // vggt_dpt.hip
 bool dpt_fused_ln(const DptW& w, int f2, int udt);
+int dpt_oc1_coarse_count();   // heads on the calling thread whose output_conv1 ran on the coarse map so far (tests)
 void* run_dpt(Ctx& c, const DptW& w, float* const* sf, float* const* sg, int F, int P, int nsp, int ph, int pw, int C,
               int H, int W, float* pts, float* conf, int act_mode);
 void run_track(Ctx& c, float* const* sf, float* const* sg, int B, int S, int P, int nsp, int ph, int pw, int C, int H, int W,

@@ -137,6 +137,22 @@ Lin Packer::convT(const std::string& p, int C, int s, int prec) {
     if (L.b) rc = rc ? rc : tile_vec_launch(bsrc, L.b, C, s * s, st);
     return L;
 }
+// a 3x3 conv's taps as nine stacked 1x1 matrices [9 * Co][Ci] (row t * Co + k = W[k, :, ty, tx], t = 3 ty + tx), with
+// bf16x3 records and no bias: the form the DPT heads contract on the coarse map in front of a bilinear upsample
+Lin Packer::conv_taps(const std::string& p, int Co, int Ci) {
+    Lin L;
+    float* src = raw(p + ".weight", (int64_t)Co * Ci * 9);
+    if (rc) return L;
+    float* tmp = nullptr;
+    if (hipMalloc((void**)&tmp, (size_t)9 * Co * Ci * 4) != hipSuccess) { rc = SKIMI_ERR_HIP; return L; }
+    if (!(rc = permute_conv_taps_launch(src, tmp, Co, Ci, 3, 3, st))) {
+        L = pack_matrix(tmp, 9 * Co, Ci, SKIMI_PREC_BF16X3);
+        if (!rc) add_records(L);
+    }
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(tmp);
+    return L;
+}
 // resize_layers[i] (ConvTranspose2d(C, C, k = s, stride = s)) folded into layer{i+1}_rn (3x3, C -> Co, no bias): the
 // per-phase matrices as weight records + the 9 border classes of the folded bias, from the staged fp32 weights
 // (float64 sums, one rounding).  K = 4 C is the longest phase; the kernel derives each phase's own from its taps.
@@ -240,6 +256,9 @@ DptW Packer::dpt(const std::string& p, int D, int features, const int* oc, int n
         d.oc1 = conv(p + ".scratch.output_conv1", features, features, 3, 1, 1, prec, true);
     } else {
         d.oc1 = conv(p + ".scratch.output_conv1", features / 2, features, 3, 1, 1, prec, true);
+        // the 3x3 form stays packed: launches too small for the 256-row kernel take it
+        if (h->dpt_oc1_coarse && prec == SKIMI_PREC_BF16X3 && features % 32 == 0)
+            d.oc1t = conv_taps(p + ".scratch.output_conv1", features / 2, features);
         d.oc2a = conv(p + ".scratch.output_conv2.0", 32, features / 2, 3, 1, 1, prec, true);
         if (!rc && prec == SKIMI_PREC_BF16X3 && (features / 2) % 32 == 0) {
             // the full-resolution 3x3 -> 32 conv runs as a direct convolution (conv_direct.hip)

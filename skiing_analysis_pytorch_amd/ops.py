@@ -457,6 +457,25 @@ def convT_conv3x3_folded(x, w_records, beta, s, Co, *, act=ACT_NONE, out=None, o
     return out
 
 
+def conv3x3_taps_matrix(w):
+    """Conv2d weight [Co, Ci, 3, 3] -> the nine taps as stacked 1x1 matrices [9 Co, Ci] (row t Co + k = w[k, :, ty, tx],
+    t = 3 ty + tx): the weight of the coarse-map contraction in front of `dpt_tap_sum` (Packer::conv_taps)."""
+    Co, Ci = w.shape[:2]
+    return w.permute(2, 3, 0, 1).reshape(9 * Co, Ci).contiguous()
+
+
+def dpt_tap_sum(taps, bias, *, out=None):
+    """taps [F, h, w, 9, C] fp32 (the nine tap contractions of a 3x3 / padding 1 conv on the coarse map) -> the conv of the
+    x2 align-corners upsampled map, [F, 2h, 2w, C] fp32 (skimi_dpt_tap_sum in include/skimi.h)."""
+    _require_cuda(taps, bias, out)
+    F_, h, w_, nine, Cc = taps.shape
+    assert nine == 9 and taps.is_contiguous() and taps.dtype == torch.float32
+    if out is None:
+        out = torch.empty((F_, 2 * h, 2 * w_, Cc), dtype=torch.float32, device=taps.device)
+    check(lib().skimi_dpt_tap_sum(ptr(taps), ptr(bias), ptr(out), F_, h, w_, Cc, _lib.current_stream()), "skimi_dpt_tap_sum")
+    return out
+
+
 def split_planes(x):
     """fp32 [rows, C] -> bf16 [2, rows, C] (hi, lo) with hi + lo ~= x to ~2^-17 relative."""
     _require_cuda(x)
